@@ -69,10 +69,19 @@ def parse():
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--no-fp32-line", action="store_true")
     ap.add_argument("--profile-json", default="", help="also write the per-kernel table of the profiled step here")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed (output, loss, a fixed sample of the "
+                         "updated parameters) to DIR/<name>.npy, float32 / float64, at most 64 MB in all")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup < 0:
+        ap.error("--warmup must not be negative")
+    return args
 
 
-def make_step(model, trainer, noisy, clean, use_dev_scalars, moce):
+def make_step(model, trainer, noisy, clean, use_dev_scalars, moce, keep_out=False):
+    """keep_out: also hold the last step's network output (and MoCE-IR's auxiliary loss) in the returned dict (--dump-outputs)."""
     from image_restoration_amd import ops
 
     loss_buf = {}
@@ -89,6 +98,10 @@ def make_step(model, trainer, noisy, clean, use_dev_scalars, moce):
         trainer.reduce_gradients()
         trainer.optimizer_step(use_dev_scalars=use_dev_scalars)
         loss_buf["loss"] = loss
+        if keep_out:
+            loss_buf["out"] = out
+            if moce:
+                loss_buf["aux"] = aux
         return loss
     return step, loss_buf
 
@@ -164,6 +177,41 @@ def cpu_baseline():
                           "fwd_mpix_s": {str(t): round(px128 / r["fwd_s"], 6) for t, r in sweep.items()}}}
 
 
+DUMP_BUDGET = {"output": 40 << 20, "params_sample": 16 << 20}     # bytes as float32; 56 MB + the scalars < 64 MB
+
+
+def _seeded_sample(flat: torch.Tensor, max_bytes: int, seed: int) -> torch.Tensor:
+    """The whole 1-D tensor when it fits ``max_bytes`` as float32, else a fixed seeded sample of it (sorted indices)."""
+    n = max_bytes // 4
+    if flat.numel() <= n:
+        return flat
+    g = torch.Generator(device="cpu").manual_seed(seed)
+    idx = torch.randperm(flat.numel(), generator=g)[:n].sort().values
+    return flat.index_select(0, idx.to(flat.device))
+
+
+def dump_outputs(out_dir: str, loss_buf: dict, model) -> dict:
+    """What the last timed step handed back: the network output, the loss (and MoCE-IR's auxiliary loss), and the parameters
+    after its AdamW update (a seeded sample over the concatenation of model.parameters(), in registration order)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    out = loss_buf["out"].detach().float()
+    sample = _seeded_sample(out.reshape(-1), DUMP_BUDGET["output"], seed=1)
+    arrays = {"output": sample.reshape(out.shape) if sample.numel() == out.numel() else sample,
+              "loss": loss_buf["loss"].detach().double().reshape(())}
+    if "aux" in loss_buf:
+        arrays["aux_loss"] = loss_buf["aux"].detach().double().reshape(())
+    with torch.no_grad():
+        flat = torch.cat([p.detach().float().reshape(-1) for p in model.parameters()])
+        arrays["params_sample"] = _seeded_sample(flat, DUMP_BUDGET["params_sample"], seed=2)
+    written = {}
+    for name, t in arrays.items():
+        a = t.cpu().numpy()
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        written[name] = {"shape": list(a.shape), "dtype": str(a.dtype)}
+    return written
+
+
 def main():
     args = parse()
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -228,7 +276,8 @@ def main():
     noisy = noisy32.to(dev).to(act)
 
     use_graph = args.graph == 1 and world == 1 and args.model in ("restormer", "moce")
-    step, loss_buf = make_step(model, trainer, noisy, clean, use_dev_scalars=use_graph, moce=moce)
+    keep_out = bool(args.dump_outputs)
+    step, loss_buf = make_step(model, trainer, noisy, clean, use_dev_scalars=use_graph, moce=moce, keep_out=keep_out)
 
     def run_eager(n):
         for _ in range(n):
@@ -248,7 +297,7 @@ def main():
             graph = None
             use_graph = False
             torch.cuda.synchronize()
-            step, loss_buf = make_step(model, trainer, noisy, clean, use_dev_scalars=False, moce=moce)
+            step, loss_buf = make_step(model, trainer, noisy, clean, use_dev_scalars=False, moce=moce, keep_out=keep_out)
     else:
         run_eager(2)  # allocator settle: the first steps hipMalloc the activations (never timed)
 
@@ -279,6 +328,9 @@ def main():
         elapsed = float(tt.item())
     final_loss = float(loss_buf["loss"].float().item()) if "loss" in loss_buf else float("nan")
     peak_gib = round(torch.cuda.max_memory_allocated() / 2 ** 30, 2)
+    dumped = None
+    if args.dump_outputs and rank == 0:     # before the profiled pass below: its steps move the parameters again
+        dumped = dump_outputs(args.dump_outputs, loss_buf, model)
 
     pixels_per_step = world * batch * patch * patch
     ms_per_step = elapsed / args.steps * 1e3
@@ -483,6 +535,8 @@ def main():
             "fp32_line": fp32_line, **extra,
             "cpu_baseline": cpu,
         }
+        if dumped is not None:
+            line["dumped_outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
         print(json.dumps(line))
     if dist_on:
         dist.destroy_process_group()
