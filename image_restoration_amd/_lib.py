@@ -211,6 +211,10 @@ SIGNATURES = {
     "mi_mdta_fused_fwd": (C.c_int, [C.POINTER(MdtaShape), C.POINTER(MdtaParams), vp, C.c_int, vp, vp, vp, fp, fp, vp, vp]),
     "mi_adamw_step": (C.c_int, [fp, fp, fp, fp, c_i64, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int,
                                 C.c_float, fp, vp]),
+    "mi_grad_sumsq_workspace": (C.c_size_t, [c_i64]),
+    "mi_grad_sumsq": (C.c_int, [fp, c_i64, fp, vp, vp]),
+    "mi_adamw_step_ex": (C.c_int, [fp, fp, fp, fp, fp, c_i64, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int,
+                                   C.c_float, fp, fp, C.c_float, fp, C.c_float, vp]),
     "mi_rows_gather": (C.c_int, [vp, vp, vp, C.c_int, c_i64, C.c_int, vp]),
     "mi_rows_gather_scaled": (C.c_int, [fp, vp, fp, vp, C.c_int, c_i64, C.c_int, vp]),
     "mi_rows_scatter_add": (C.c_int, [vp, vp, fp, vp, C.c_int, C.c_int, c_i64, C.c_int, C.c_int, vp]),

@@ -50,7 +50,8 @@ static std::atomic<int> g_prof_on{0};
 static const char* const g_kernel_names[K_COUNT] = {
     "ln_fwd", "ln_bwd", "dwconv_fwd", "dwconv_gate_fwd", "dwconv_bwd_data", "dwconv_gate_bwd_data", "dwconv_wgrad",
     "pw_gemm", "gram", "gram_reduce", "attn_fold", "attn_bwd_small", "reduce_rows", "chan_sum", "adamw", "cast", "l1_loss",
-    "pw_pack", "gap", "im2col3x3", "col2im3x3", "gdfn_fused_fwd", "gdfn_fused_bwd", "mdta_fused_a", "fused_pack", "moe_route", "patch_circconv", "ewise", "conv3x3", "mdta_qk", "mdta_av", "bwd_tail", "bwd_tail_finish", "adair_fre"};
+    "pw_pack", "gap", "im2col3x3", "col2im3x3", "gdfn_fused_fwd", "gdfn_fused_bwd", "mdta_fused_a", "fused_pack", "moe_route", "patch_circconv", "ewise", "conv3x3", "mdta_qk", "mdta_av", "bwd_tail", "bwd_tail_finish", "adair_fre", "grad_sumsq",
+    "adamw_clip", "adamw_clip_ema"};
 
 ProfScope::ProfScope(hipStream_t stream, int kernel_id, double bytes, double flops)
     : st(stream), kid(kernel_id), on(g_prof_on.load(std::memory_order_relaxed) != 0) {
@@ -269,6 +270,95 @@ __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const
   }
 }
 
+// Sum of squares of a flat fp32 buffer (gradient-norm clipping), stage 1: a grid-stride f32x4 pass, one fp64 partial per block.
+// The grid depends on n only and both stages walk their terms in a fixed order: bitwise reproducible.  Default cache policy:
+// the AdamW pass right after it may find the gradient in the Infinity Cache.
+constexpr int SUMSQ_MAX_BLOCKS = 1024;     // 4 x 256 CUs
+__global__ __launch_bounds__(256) void sumsq_partial_kernel(const float* __restrict__ x, int64_t n,
+                                                           double* __restrict__ part) {
+  __shared__ double sm[4];
+  const int64_t n4 = n >> 2;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  double acc = 0.0;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
+    const f32x4 v = reinterpret_cast<const f32x4*>(x)[i];
+    const double a = v[0], b = v[1], c = v[2], d = v[3];
+    acc += (a * a + b * b) + (c * c + d * d);
+  }
+  if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {           // tail of n % 4 elements
+    const double t = x[(n4 << 2) + threadIdx.x];
+    acc += t * t;
+  }
+  for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off, 64);
+  if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) part[blockIdx.x] = (sm[0] + sm[1]) + (sm[2] + sm[3]);
+}
+// Stage 2: one workgroup sums the partials in a fixed order and writes the fp32 scalar.
+__global__ __launch_bounds__(256) void sumsq_final_kernel(const double* __restrict__ part, int nparts, float* __restrict__ out) {
+  __shared__ double sm[4];
+  double acc = 0.0;
+  for (int i = threadIdx.x; i < nparts; i += 256) acc += part[i];
+  for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off, 64);
+  if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) out[0] = (float)((sm[0] + sm[1]) + (sm[2] + sm[3]));
+}
+
+// adamw_kernel with the gradient multiplied by a clip coefficient computed from a device scalar (torch clip_grad_norm_,
+// error_if_nonfinite=False) and, optionally, the weight EMA updated from the new parameters (BasicSR model_ema).  A coefficient
+// of exactly 1 gives bitwise the arithmetic of adamw_kernel.
+__global__ __launch_bounds__(256) void adamw_ex_kernel(float* __restrict__ p, const float* __restrict__ g,
+                                                       float* __restrict__ m, float* __restrict__ v, float* __restrict__ ema,
+                                                       int64_t n, float lr, float b1, float b2, float eps, float wd, float bc1,
+                                                       float bc2_sqrt, float gscale, const float* __restrict__ dev_scalars,
+                                                       const float* __restrict__ sumsq, float max_norm,
+                                                       float* __restrict__ norm_out, float decay, float one_m_decay) {
+  if (dev_scalars) { lr = dev_scalars[0]; bc1 = dev_scalars[1]; bc2_sqrt = dev_scalars[2]; }
+  float coef = 1.0f;
+  if (sumsq) {
+    const float norm = sqrtf(sumsq[0]) * gscale;
+    const float c = max_norm / (norm + 1e-6f);
+    coef = c > 1.0f ? 1.0f : c;                               // a NaN coefficient propagates, as torch.clamp(max=1) does
+    if (norm_out && blockIdx.x == 0 && threadIdx.x == 0) norm_out[0] = norm;
+  }
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x * 4;
+  for (int64_t i = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * 4; i < n; i += stride) {
+    if (i + 3 < n) {
+      f32x4 pv = *reinterpret_cast<f32x4*>(p + i), gv = *reinterpret_cast<const f32x4*>(g + i);
+      f32x4 mv = *reinterpret_cast<f32x4*>(m + i), vv = *reinterpret_cast<f32x4*>(v + i);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const float gr = (gv[j] * gscale) * coef;
+        pv[j] *= 1.0f - lr * wd;
+        mv[j] = b1 * mv[j] + (1.0f - b1) * gr;
+        vv[j] = b2 * vv[j] + (1.0f - b2) * gr * gr;
+        const float denom = sqrtf(vv[j]) / bc2_sqrt + eps;
+        pv[j] -= (lr / bc1) * (mv[j] / denom);
+      }
+      *reinterpret_cast<f32x4*>(p + i) = pv;
+      *reinterpret_cast<f32x4*>(m + i) = mv;
+      *reinterpret_cast<f32x4*>(v + i) = vv;
+      if (ema) {
+        f32x4 ev = *reinterpret_cast<f32x4*>(ema + i);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) ev[j] = ev[j] * decay + pv[j] * one_m_decay;
+        *reinterpret_cast<f32x4*>(ema + i) = ev;
+      }
+    } else {
+      for (int64_t k = i; k < n; ++k) {
+        const float gr = (g[k] * gscale) * coef;
+        float pv = p[k] * (1.0f - lr * wd);
+        const float mv = b1 * m[k] + (1.0f - b1) * gr;
+        const float vv = b2 * v[k] + (1.0f - b2) * gr * gr;
+        pv -= (lr / bc1) * (mv / (sqrtf(vv) / bc2_sqrt + eps));
+        p[k] = pv; m[k] = mv; v[k] = vv;
+        if (ema) ema[k] = ema[k] * decay + pv * one_m_decay;
+      }
+    }
+  }
+}
+
 // Global average pool of the MoCE router (moce_ir.py:703-707 AdaptiveAvgPool2d(1)): one workgroup per (image, channel).
 template <typename T>
 __global__ __launch_bounds__(256) void gap_fwd_kernel(const T* __restrict__ x, float* __restrict__ out, int64_t N) {
@@ -440,6 +530,49 @@ extern "C" int mi_adamw_step(float* p, const float* g, float* m, float* v, int64
   ProfScope ps((hipStream_t)stream, K_ADAMW, 28.0 * n, 12.0 * n);
   hipLaunchKernelGGL(adamw_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, lr, beta1, beta2, eps,
                      weight_decay, bc1, bc2, grad_scale, dev_scalars);
+  MI_LAUNCH_CHECK();
+  return MI_OK;
+}
+
+static int sumsq_blocks(int64_t n) {
+  int blocks = cdiv(n, 256 * 4);
+  return blocks < 1 ? 1 : (blocks > SUMSQ_MAX_BLOCKS ? SUMSQ_MAX_BLOCKS : blocks);
+}
+extern "C" size_t mi_grad_sumsq_workspace(int64_t n) {
+  return n > 0 ? (size_t)sumsq_blocks(n) * sizeof(double) : 0;
+}
+extern "C" int mi_grad_sumsq(const float* x, int64_t n, float* out, void* workspace, void* stream) {
+  MI_CHECK_ARG(x && out && workspace && n > 0, "grad_sumsq: bad arguments");
+  MI_CHECK_ARG(aligned16(x), "grad_sumsq: buffer must be 16-byte aligned");
+  hipStream_t st = (hipStream_t)stream;
+  const int blocks = sumsq_blocks(n);
+  {
+    ProfScope ps(st, K_SUMSQ, 4.0 * n, 2.0 * n);
+    hipLaunchKernelGGL(sumsq_partial_kernel, dim3(blocks), dim3(256), 0, st, x, n, (double*)workspace);
+    hipLaunchKernelGGL(sumsq_final_kernel, dim3(1), dim3(256), 0, st, (const double*)workspace, blocks, out);
+  }
+  MI_LAUNCH_CHECK();
+  return MI_OK;
+}
+
+extern "C" int mi_adamw_step_ex(float* p, const float* g, float* m, float* v, float* ema, int64_t n, float lr, float beta1,
+                                float beta2, float eps, float weight_decay, int step, float grad_scale,
+                                const float* dev_scalars, const float* sumsq, float max_norm, float* norm_out,
+                                float ema_decay, void* stream) {
+  MI_CHECK_ARG(p && g && m && v && n > 0 && (step >= 1 || dev_scalars), "adamw_ex: bad arguments");
+  MI_CHECK_ARG(!sumsq || max_norm > 0.0f, "adamw_ex: max_norm must be > 0");
+  MI_CHECK_ARG(!ema || (ema_decay >= 0.0f && ema_decay < 1.0f), "adamw_ex: ema_decay must be in [0, 1)");
+  if (step < 1) step = 1;
+  MI_CHECK_ARG(aligned16(p) && aligned16(g) && aligned16(m) && aligned16(v) && (!ema || aligned16(ema)),
+               "adamw_ex: buffers must be 16-byte aligned");
+  const float bc1 = 1.0f - powf(beta1, (float)step);
+  const float bc2 = sqrtf(1.0f - powf(beta2, (float)step));
+  const float one_m_decay = (float)(1.0 - (double)ema_decay);
+  int blocks = cdiv(n, 256 * 4);
+  if (blocks > 2048) blocks = 2048;
+  ProfScope ps((hipStream_t)stream, ema ? K_ADAMW_EMA : K_ADAMW_CLIP, (ema ? 36.0 : 28.0) * n, (ema ? 15.0 : 13.0) * n);
+  hipLaunchKernelGGL(adamw_ex_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, p, g, m, v, ema, n, lr, beta1, beta2,
+                     eps, weight_decay, bc1, bc2, grad_scale, dev_scalars, sumsq, max_norm, norm_out, ema_decay, one_m_decay);
   MI_LAUNCH_CHECK();
   return MI_OK;
 }

@@ -994,6 +994,43 @@ def adamw_step(p: Tensor, g: Tensor, m: Tensor, v: Tensor, lr: float, step: int,
                                   grad_scale, _p(dev_scalars), _stream()), "adamw_step")
 
 
+def grad_sumsq_workspace(n: int, device) -> Tensor:
+    """Device scratch for grad_sumsq over ``n`` elements (one fp64 partial per block)."""
+    return _blob(L.lib().mi_grad_sumsq_workspace(int(n)), device)
+
+
+def grad_sumsq(x: Tensor, out: Optional[Tensor] = None, workspace: Optional[Tensor] = None) -> Tensor:
+    """Sum of squares of a flat fp32 buffer into a 1-element device tensor (bitwise reproducible, fp64 accumulation); no host
+    sync.  ``out`` / ``workspace`` may be passed to keep their addresses fixed (graph capture)."""
+    _gpu(x, out, workspace)
+    _f32(x, "grad_sumsq input")
+    if out is None:
+        out = torch.empty(1, dtype=torch.float32, device=x.device)
+    if workspace is None:
+        workspace = grad_sumsq_workspace(x.numel(), x.device)
+    if workspace.numel() * workspace.element_size() < L.lib().mi_grad_sumsq_workspace(x.numel()):
+        raise ValueError("grad_sumsq: workspace too small")
+    L.check(L.lib().mi_grad_sumsq(_p(x), x.numel(), _p(out), _p(workspace), _stream()), "grad_sumsq")
+    return out
+
+
+def adamw_step_ex(p: Tensor, g: Tensor, m: Tensor, v: Tensor, lr: float, step: int, betas=(0.9, 0.999), eps: float = 1e-8,
+                  weight_decay: float = 1e-2, grad_scale: float = 1.0, dev_scalars: Optional[Tensor] = None,
+                  sumsq: Optional[Tensor] = None, max_norm: float = 0.0, norm_out: Optional[Tensor] = None,
+                  ema: Optional[Tensor] = None, ema_decay: float = 0.0) -> None:
+    """adamw_step with the gradient clipped by total norm (``sumsq``: device scalar sum of squares of ``g``, as grad_sumsq
+    gives; the norm sqrt(sumsq) * grad_scale goes to ``norm_out``) and/or the EMA ``ema = ema*decay + p_new*(1-decay)``."""
+    _gpu(p, g, m, v, dev_scalars, sumsq, norm_out, ema)
+    for t in (p, g, m, v, ema):
+        if t is not None and t.numel() != p.numel():
+            raise ValueError("adamw_step_ex: p, g, m, v and ema must have the same number of elements")
+    if sumsq is not None and not max_norm > 0:
+        raise ValueError("adamw_step_ex: max_norm must be > 0")
+    L.check(L.lib().mi_adamw_step_ex(_p(p), _p(g), _p(m), _p(v), _p(ema), p.numel(), lr, betas[0], betas[1], eps, weight_decay,
+                                     step, grad_scale, _p(dev_scalars), _p(sumsq), max_norm, _p(norm_out), ema_decay,
+                                     _stream()), "adamw_step_ex")
+
+
 def l1_loss(a: Tensor, b: Tensor, want_grad: bool = True, scale: float = 1.0):
     """mean|a-b| and (optionally) its gradient w.r.t. a times ``scale``; loss returned as a 1-element fp32 tensor."""
     _gpu(a, b)

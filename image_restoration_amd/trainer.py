@@ -12,6 +12,7 @@ from __future__ import annotations
 
 import math
 import os
+from contextlib import contextmanager
 from typing import Dict, List, Optional, Tuple
 
 import torch
@@ -26,10 +27,24 @@ ALIGN = 64  # elements: every parameter starts on a 256-byte boundary of the fla
 class FlatTrainer:
     def __init__(self, model: nn.Module, lr: float = 2e-4, betas=(0.9, 0.999), eps: float = 1e-8,
                  weight_decay: float = 1e-2, process_group=None, overlap: bool = True, host_update=None,
-                 pack_cache: bool = True, bucket_blocks: bool = True, shard_optimizer: bool = False):
+                 pack_cache: bool = True, bucket_blocks: bool = True, shard_optimizer: bool = False,
+                 max_grad_norm: Optional[float] = None, ema_decay: float = 0.0, norm_type: float = 2.0):
         """shard_optimizer: reduce-scatter the flat gradient, run AdamW on this rank's 1/world slice of the parameters (the two
         moment buffers shrink to that slice), all-gather the updated parameters - instead of all-reduce + replicated AdamW.
-        One collective pair per step after backward (no per-stage overlap); for models whose optimizer state matters."""
+        One collective pair per step after backward (no per-stage overlap); for models whose optimizer state matters.
+
+        max_grad_norm: clip the gradient by its total 2-norm inside optimizer_step (torch.nn.utils.clip_grad_norm_ of the
+        DDP-averaged gradient; BasicSR use_grad_clip).  The pre-clip norm of the last step is ``self.grad_norm`` (a 0-dim device
+        tensor).  ema_decay > 0: keep an exponential moving average of the weights (BasicSR model_ema), updated by the same
+        fused kernel; see ema_state_dict() / ema_weights().  Both default to off, and then the step is unchanged."""
+        if norm_type != 2.0:
+            raise ValueError(f"FlatTrainer: only the 2-norm is supported for gradient clipping, got norm_type={norm_type}")
+        if max_grad_norm is not None and not (float(max_grad_norm) > 0 and math.isfinite(float(max_grad_norm))):
+            raise ValueError(f"FlatTrainer: max_grad_norm must be a positive finite number, got {max_grad_norm}")
+        if not 0.0 <= float(ema_decay) < 1.0:
+            raise ValueError(f"FlatTrainer: ema_decay must be in [0, 1), got {ema_decay}")
+        self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
+        self.ema_decay = float(ema_decay)
         self.model = model
         # host_update(trainer, scale): test hook that stands in for the fused AdamW kernel when the gradient-bucketing /
         # all-reduce bookkeeping is exercised on CPU tensors over gloo.  The product has no CPU update: without the hook,
@@ -63,6 +78,14 @@ class FlatTrainer:
         self.flat_m = torch.zeros(self.shard, dtype=torch.float32, device=dev)
         self.flat_v = torch.zeros_like(self.flat_m)
         self._g_shard = torch.zeros(self.shard, dtype=torch.float32, device=dev) if self.sharded else None
+        # clipping: the sum of squares of the gradient AdamW consumes lands in a device scalar (all-reduced over the shards when
+        # sharded) that the fused kernel reads; fixed addresses, so a captured step replays them
+        self.grad_norm = torch.zeros((), dtype=torch.float32, device=dev)
+        if self.max_grad_norm is not None:
+            self._sumsq = torch.zeros(1, dtype=torch.float32, device=dev)
+            self._sumsq_ws = ops.grad_sumsq_workspace(self.shard, dev) if dev.type == "cuda" else None
+        self.flat_ema = torch.zeros(self.shard, dtype=torch.float32, device=dev) if self.ema_decay > 0 else None
+        self._ema_saved: Optional[torch.Tensor] = None     # flat_p while ema_weights() is active
         self.offsets: Dict[int, Tuple[int, int]] = {}
         with torch.no_grad():
             for p, o in zip(params, offs):
@@ -74,6 +97,8 @@ class FlatTrainer:
                 self.offsets[id(p)] = (o, n)
         self.params = params
         self.total = total
+        if self.flat_ema is not None:
+            self._ema_reset()                              # BasicSR model_ema(0): the average starts at the weights
         # reduction units ("stages"): the top-level children that own parameters, with nn.Sequential stages split into
         # their blocks (a 256^2 stage's four blocks take ~10 ms of backward each: per-block buckets let the first reduce
         # start that much earlier and leave only the patch embedding behind the last one); flat ranges are contiguous
@@ -187,9 +212,14 @@ class FlatTrainer:
     # ------------------------------------------------------------------ checkpointing (optimizer state; the model's own
     # state_dict carries the parameters: Lightning's checkpoint holds both, MoCE-IR-main/src/train.py:107-116,137-148)
     def state_dict(self) -> dict:
-        return {"exp_avg": self.flat_m.clone(), "exp_avg_sq": self.flat_v.clone(), "step": self.step_count, "lr": self.lr,
-                "betas": tuple(self.betas), "eps": self.eps, "weight_decay": self.wd, "numel": int(self.total),
-                "shard": (self.rank, self.world) if self.sharded else None}
+        sd = {"exp_avg": self.flat_m.clone(), "exp_avg_sq": self.flat_v.clone(), "step": self.step_count, "lr": self.lr,
+              "betas": tuple(self.betas), "eps": self.eps, "weight_decay": self.wd, "numel": int(self.total),
+              "shard": (self.rank, self.world) if self.sharded else None}
+        if self.flat_ema is not None:          # this rank's shard of the EMA when sharded, like exp_avg
+            sd["ema"], sd["ema_decay"] = self.flat_ema.clone(), self.ema_decay
+        if self.max_grad_norm is not None:
+            sd["max_grad_norm"] = self.max_grad_norm
+        return sd
 
     def load_state_dict(self, sd: dict) -> None:
         if int(sd["numel"]) != int(self.total):
@@ -197,11 +227,84 @@ class FlatTrainer:
         want = (self.rank, self.world) if self.sharded else None
         if sd.get("shard") != want:
             raise ValueError(f"optimizer state was saved for shard {sd.get('shard')}, this trainer is {want}")
+        if "ema" in sd and self.flat_ema is None:
+            raise ValueError("optimizer state holds an EMA of the weights but this trainer keeps none (construct it with "
+                             "ema_decay > 0, or drop sd['ema'] on purpose)")
         self.flat_m.copy_(sd["exp_avg"])
         self.flat_v.copy_(sd["exp_avg_sq"])
         self.step_count, self.lr = int(sd["step"]), float(sd["lr"])
         self.betas, self.eps, self.wd = tuple(sd["betas"]), float(sd["eps"]), float(sd["weight_decay"])
+        if self.flat_ema is not None:
+            if "ema" in sd:
+                self.flat_ema.copy_(sd["ema"])
+                self.ema_decay = float(sd.get("ema_decay", self.ema_decay))
+            else:                              # a state saved without EMA: start the average at the current weights
+                self._ema_reset()
+        if self.max_grad_norm is not None and "max_grad_norm" in sd:
+            self.max_grad_norm = float(sd["max_grad_norm"])
         self.weights_changed()
+
+    # ------------------------------------------------------------------ weight EMA (BasicSR model_ema / params_ema)
+    def _p_local(self) -> torch.Tensor:
+        """The part of flat_p this rank updates (its shard when sharded)."""
+        if self.sharded:
+            lo = self.rank * self.shard
+            return self.flat_p[lo:lo + self.shard]
+        return self.flat_p
+
+    def _ema_reset(self) -> None:
+        with torch.no_grad():
+            self.flat_ema.copy_(self._p_local())
+
+    def _ema_full(self) -> torch.Tensor:
+        """The whole flat EMA (all-gathered from the shards when sharded: a collective)."""
+        if self.flat_ema is None:
+            raise RuntimeError("FlatTrainer: no weight EMA (construct the trainer with ema_decay > 0)")
+        if not self.sharded:
+            return self.flat_ema
+        full = torch.empty_like(self.flat_p)
+        if dist.get_backend(self.pg) == "gloo":
+            parts = [torch.empty_like(self.flat_ema) for _ in range(self.world)]
+            dist.all_gather(parts, self.flat_ema.clone(), group=self.pg)
+            for r, part in enumerate(parts):
+                full[r * self.shard:(r + 1) * self.shard].copy_(part)
+        else:
+            dist.all_gather_into_tensor(full, self.flat_ema, group=self.pg)
+        return full
+
+    def ema_state_dict(self) -> dict:
+        """``model.state_dict()`` with every trainable parameter taken from the EMA and everything else (buffers, frozen
+        parameters) from the model: what BasicSR saves under ``params_ema``.  A collective when the optimizer is sharded."""
+        full = self._ema_full()
+        out = {}
+        for k, t in self.model.state_dict(keep_vars=True).items():
+            on = self.offsets.get(id(t))
+            if on is not None:
+                o, n = on
+                out[k] = full[o:o + n].view(t.shape).clone()
+            else:
+                out[k] = t.detach().clone()
+        return out
+
+    @contextmanager
+    def ema_weights(self):
+        """``with trainer.ema_weights(): validate(model)`` runs the model on the EMA weights (BasicSR validates on
+        net_g_ema) and puts the trained weights back on exit.  The packed 1x1 weight images follow both swaps.
+        optimizer_step inside the block raises.  A collective when the optimizer is sharded."""
+        if self._ema_saved is not None:
+            raise RuntimeError("FlatTrainer.ema_weights: already active")
+        full = self._ema_full()
+        with torch.no_grad():
+            self._ema_saved = self.flat_p.clone()
+            self.flat_p.copy_(full)
+        self.weights_changed()
+        try:
+            yield self.model
+        finally:
+            with torch.no_grad():
+                self.flat_p.copy_(self._ema_saved)
+            self._ema_saved = None
+            self.weights_changed()
 
     def no_sync(self):
         """Context manager for gradient accumulation (Lightning's accumulate_grad_batches, MoCE-IR-main/src/train.py:133):
@@ -343,7 +446,8 @@ class FlatTrainer:
 
     def capture_step(self, step_fn, warmup: int = 2):
         """Capture ``step_fn`` (a whole training step ending in ``optimizer_step(use_dev_scalars=True)``) into a HIP graph and
-        return it; ``replay_step(graph)`` runs it.  The warm-up steps run on a SIDE stream: a parameter whose gradient arrives
+        return it; ``replay_step(graph)`` runs it.  Gradient clipping and the EMA are captured with the step: the norm stays on
+        the device, and max_grad_norm and ema_decay are baked into the graph (changing them needs a new capture).  The warm-up steps run on a SIDE stream: a parameter whose gradient arrives
         through autograd's AccumulateGrad (MoCE-IR's router gates, the embedding MLP) binds that node to the stream of its
         first backward, and a node bound to the legacy default stream takes hipStreamEndCapture down.  Pending deferred sums
         are flushed first; while the capture runs nothing is deferred (the library sums at once on a capturing stream)."""
@@ -362,8 +466,11 @@ class FlatTrainer:
             p.grad = None
         graph = torch.cuda.CUDAGraph()
         self.set_step_scalars(self.step_count + 1)
+        step0 = self.step_count
         with torch.cuda.graph(graph):
             step_fn()
+        # the captured optimizer_step counted a step on the host whose kernels never ran: replay_step counts each replay
+        self.step_count = step0
         return graph
 
     def replay_step(self, graph) -> None:
@@ -374,44 +481,68 @@ class FlatTrainer:
         graph.replay()
 
     def optimizer_step(self, use_dev_scalars: bool = False) -> None:
+        if self._ema_saved is not None:
+            raise RuntimeError("FlatTrainer.optimizer_step inside ema_weights(): the model holds the EMA, not the trained weights")
         self.grads_ready()            # a loop that skips reduce_gradients() (one GPU) must not step on incomplete gradients
         self.step_count += 1
         ops.bump_weights_epoch()      # the fused AdamW kernel writes the parameters without bumping any version counter
         scale = 1.0 / self.world
         if self.sharded:
-            lo = self.rank * self.shard
-            p_shard = self.flat_p[lo:lo + self.shard]
-            if self.flat_p.is_cuda:
-                ops.adamw_step(p_shard, self._g_shard, self.flat_m, self.flat_v, self.lr, self.step_count, self.betas, self.eps,
-                               self.wd, scale, self.dev_scalars if use_dev_scalars else None)
-            elif self._host_update is not None:
-                import types
-                self._host_update(types.SimpleNamespace(flat_p=p_shard, flat_g=self._g_shard, flat_m=self.flat_m,
-                                                        flat_v=self.flat_v, betas=self.betas, lr=self.lr, wd=self.wd,
-                                                        eps=self.eps, step_count=self.step_count), scale)
+            p_buf, g_buf = self._p_local(), self._g_shard
+        else:
+            p_buf, g_buf = self.flat_p, self.flat_g
+        if self.flat_p.is_cuda:
+            dsc = self.dev_scalars if use_dev_scalars else None
+            if self.max_grad_norm is None and self.flat_ema is None:
+                ops.adamw_step(p_buf, g_buf, self.flat_m, self.flat_v, self.lr, self.step_count, self.betas, self.eps, self.wd,
+                               scale, dsc)
             else:
-                raise RuntimeError("FlatTrainer.optimizer_step: parameters are not on an MI355X (no CPU optimizer path)")
+                sumsq = None
+                if self.max_grad_norm is not None:
+                    # the gradient AdamW consumes: the rank sum of the whole buffer (norm of the mean: x 1/world), or this
+                    # rank's reduced shard, whose sum of squares is summed over the ranks on the device
+                    sumsq = ops.grad_sumsq(g_buf, self._sumsq, self._sumsq_ws)
+                    if self.sharded:
+                        dist.all_reduce(sumsq, op=dist.ReduceOp.SUM, group=self.pg)
+                ops.adamw_step_ex(p_buf, g_buf, self.flat_m, self.flat_v, self.lr, self.step_count, self.betas, self.eps,
+                                  self.wd, scale, dsc, sumsq=sumsq, max_norm=self.max_grad_norm or 0.0, norm_out=self.grad_norm,
+                                  ema=self.flat_ema, ema_decay=self.ema_decay)
+        elif self._host_update is not None:
+            self._host_step(p_buf, g_buf, scale)
+        else:
+            raise RuntimeError("FlatTrainer.optimizer_step: parameters are not on an MI355X (no CPU optimizer path)")
+        if self.sharded:
             if dist.get_backend(self.pg) == "gloo":
-                parts = [torch.empty_like(p_shard) for _ in range(self.world)]
-                dist.all_gather(parts, p_shard.clone(), group=self.pg)
+                parts = [torch.empty_like(p_buf) for _ in range(self.world)]
+                dist.all_gather(parts, p_buf.clone(), group=self.pg)
                 for r, part in enumerate(parts):
                     self.flat_p[r * self.shard:(r + 1) * self.shard].copy_(part)
             else:
-                dist.all_gather_into_tensor(self.flat_p, p_shard, group=self.pg)     # in place: each rank's slice is its input
-            if self._pack_cache and self.flat_p.is_cuda:
-                ops.pw_cache_refresh()
-                self._p_version = self._weights_version()
-            return
-        if self.flat_p.is_cuda:
-            ops.adamw_step(self.flat_p, self.flat_g, self.flat_m, self.flat_v, self.lr, self.step_count, self.betas,
-                           self.eps, self.wd, scale, self.dev_scalars if use_dev_scalars else None)
-            if self._pack_cache:
-                ops.pw_cache_refresh()   # the weights just changed: re-pack every 1x1 weight image in one launch
-                self._p_version = self._weights_version()
-        elif self._host_update is not None:
-            self._host_update(self, scale)
+                dist.all_gather_into_tensor(self.flat_p, p_buf, group=self.pg)     # in place: each rank's slice is its input
+        if self._pack_cache and self.flat_p.is_cuda:
+            ops.pw_cache_refresh()   # the weights just changed: re-pack every 1x1 weight image in one launch
+            self._p_version = self._weights_version()
+
+    def _host_step(self, p_buf: torch.Tensor, g_buf: torch.Tensor, scale: float) -> None:
+        """CPU tensors with the host_update test hook: clipping and the EMA as torch ops around the injected AdamW, so the
+        collective bookkeeping of both can be tested over gloo."""
+        coef = 1.0
+        if self.max_grad_norm is not None:
+            sumsq = g_buf.double().square().sum().reshape(1)
+            if self.sharded:
+                dist.all_reduce(sumsq, op=dist.ReduceOp.SUM, group=self.pg)
+            norm = float(sumsq.sqrt()) * scale
+            self.grad_norm.fill_(norm)
+            coef = min(self.max_grad_norm / (norm + 1e-6), 1.0)
+        if self.sharded:
+            import types
+            self._host_update(types.SimpleNamespace(flat_p=p_buf, flat_g=g_buf, flat_m=self.flat_m, flat_v=self.flat_v,
+                                                    betas=self.betas, lr=self.lr, wd=self.wd, eps=self.eps,
+                                                    step_count=self.step_count), scale * coef)
         else:
-            raise RuntimeError("FlatTrainer.optimizer_step: parameters are not on an MI355X (no CPU optimizer path)")
+            self._host_update(self, scale * coef)
+        if self.flat_ema is not None:
+            self.flat_ema.mul_(self.ema_decay).add_(p_buf, alpha=1.0 - self.ema_decay)
 
 
 def cosine_warmup_lr(epoch: int, base_lr: float, warmup_epochs: int = 15, max_epochs: int = 150,

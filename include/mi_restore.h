@@ -426,6 +426,25 @@ int mi_adamw_step(float* p, const float* g, float* m, float* v, int64_t n, float
                   float beta2, float eps, float weight_decay, int step, float grad_scale,
                   const float* dev_scalars, void* stream);
 
+/* Gradient-norm clipping and weight EMA (BasicSR image_restoration_model.py: use_grad_clip ->
+ * clip_grad_norm_(params, 0.01); ema_decay -> model_ema, saved as params_ema).
+ * grad_sumsq: *out = sum x[i]^2 over [n] fp32 (x 16-byte aligned), written to device memory.
+ *   Two launches with a fixed grid per n and a fixed order (bitwise reproducible), fp64 accumulation.
+ *   workspace: caller-owned device buffer of mi_grad_sumsq_workspace(n) bytes (<= 8 KiB).
+ * adamw_step_ex: mi_adamw_step plus, when sumsq != NULL (device scalar, e.g. from mi_grad_sumsq),
+ *   norm = sqrt(*sumsq) * grad_scale, coef = min(max_norm / (norm + 1e-6), 1) (torch clip_grad_norm_,
+ *   error_if_nonfinite=False: inf / NaN propagate), gradient (g * grad_scale) * coef; norm_out (device,
+ *   may be NULL) receives norm.  When ema != NULL ([n] fp32), after the update
+ *   ema = ema * ema_decay + p * (1 - ema_decay).  Nothing is read back to the host: graph capture works.
+ *   With sumsq == NULL and ema == NULL it computes bitwise what mi_adamw_step does.
+ * ------------------------------------------------------------------------ */
+size_t mi_grad_sumsq_workspace(int64_t n);
+int mi_grad_sumsq(const float* x, int64_t n, float* out, void* workspace, void* stream);
+int mi_adamw_step_ex(float* p, const float* g, float* m, float* v, float* ema, int64_t n, float lr,
+                     float beta1, float beta2, float eps, float weight_decay, int step, float grad_scale,
+                     const float* dev_scalars, const float* sumsq, float max_norm, float* norm_out,
+                     float ema_decay, void* stream);
+
 /* ------------------------------------------------------------------------
  * MoCE SparseDispatcher data movement (moce_ir.py:71-143).  A "row" is one sample's feature map (C*H*W elements);
  * idx is the dispatcher's _batch_index (int64, device), scale its _nonzero_gates (fp32, device).
