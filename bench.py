@@ -7,11 +7,12 @@ bs 32 per GPU ("Restormer 256^2 bs=32 at 1/2/4/8 GPU"), which fits one MI355X, s
 (weak scaling; N>1 = configs[2] with the RCCL gradient all-reduce).  `--batch 8` gives configs[1] (bs 8 on one GPU);
 `--model moce` trains MoCE-IR (configs[3]: noisy top-1 router, experts, balance loss) instead.
 
-    python bench.py --gpus 1 --steps K --warmup W
+    python bench.py --gpus 1 --steps K --warmup W [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
-Rank 0 prints ONE JSON line.  Besides the contract fields it carries
+Rank 0 prints ONE JSON line.  A plain run does only what the headline needs: it sets up, warms up, times the steps, writes
+--dump-outputs if asked and prints the line, with the fields below null.  `--full` adds the passes that fill them:
   roofline         : the dominant kernel (largest share of device time in a profiled pass of the same workload): its
                      ALGORITHMIC bytes (or flops) per launch / its average launch duration, measured with HIP events
                      recorded on the kernel's own stream by the library's profiler (mi_prof_*), against the MI355X peak
@@ -25,6 +26,7 @@ Rank 0 prints ONE JSON line.  Besides the contract fields it carries
                      (q, k and qkv0 never reach HBM on that path);
   fp32_line        : a short run of the same step with fp32 activations (the exact-MFMA parity path, the reference's
                      mainline precision), reported beside the bf16 headline, never instead of it;
+  c2_bs8, c4_moce  : short legs of BASELINE configs[1] and configs[3] (present with --full only, not null without it);
   cpu_baseline     : the CPU oracle (oracle/restormer_ref.py, "port") timed on this box's host cores: warm-up + median of
                      3 of forward + L1 + backward on one 1x3x256x256 patch (SURVEY 8(d)) at the thread count a 128x128 sweep picks;
                      the whole leg stays within ~30 s (rank 0 at N=1 only).
@@ -50,7 +52,7 @@ MFMA_PEAK_TFLOPS = {"bf16": 2500.0, "fp32": 157.3}
 TRAFFIC_FILE = os.path.join("profiles", "r04_pmc_traffic.json")
 
 
-def parse():
+def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50)
@@ -65,18 +67,23 @@ def parse():
                          "the graph's private pool doubles peak memory")
     ap.add_argument("--shard-optimizer", action="store_true",
                     help="reduce-scatter + sharded AdamW + all-gather instead of the overlapped bucketed all-reduce (N > 1)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
-    ap.add_argument("--no-fp32-line", action="store_true")
-    ap.add_argument("--profile-json", default="", help="also write the per-kernel table of the profiled step here")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run the profiled pass (roofline, step_roofline, mdta_contraction), the no_grad "
+                         "forward, the fp32 line, the bs-8 and MoCE-IR legs and the CPU baseline (off: those fields are null)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-roofline", action="store_true", help="--full without the profiled pass and the no_grad forward")
+    ap.add_argument("--no-fp32-line", action="store_true", help="--full without the fp32 line and the bs-8 / MoCE-IR legs")
+    ap.add_argument("--profile-json", default="", help="also write the per-kernel table of the profiled step here (--full)")
     ap.add_argument("--dump-outputs", default="", metavar="DIR",
                     help="after the timed steps, write what the last timed step computed (output, loss, a fixed sample of the "
                          "updated parameters) to DIR/<name>.npy, float32 / float64, at most 64 MB in all")
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
     if args.steps < 1:
         ap.error("--steps must be at least 1")
     if args.warmup < 0:
         ap.error("--warmup must not be negative")
+    if args.profile_json and not (args.full and not args.no_roofline):
+        ap.error("--profile-json needs the profiled pass: --full without --no-roofline")
     return args
 
 
@@ -336,9 +343,13 @@ def main():
     ms_per_step = elapsed / args.steps * 1e3
     value = pixels_per_step * args.steps / elapsed / 1e6
 
+    # everything below the headline runs with --full only
+    do_roofline = args.full and not args.no_roofline
+    do_fp32 = args.full and not args.no_fp32_line
+    do_cpu = args.full and not args.no_cpu_baseline
     roofline = step_roofline = contraction = None
     nprof = 2
-    if not args.no_roofline:
+    if do_roofline:
         # profiled pass: same workload, eager, every kernel bracketed by HIP events on its own stream.  EVERY rank runs
         # these steps (they contain the gradient all-reduce); only rank 0 records and reports.
         step_e, _ = make_step(model, trainer, noisy, clean, use_dev_scalars=False, moce=moce)
@@ -349,7 +360,7 @@ def main():
         for _ in range(nprof):
             step_e()
         torch.cuda.synchronize()
-    if not args.no_roofline and rank == 0:
+    if do_roofline and rank == 0:
         table = ops.prof_collect()
         ops.prof_enable(False)
         tot_ms = sum(v["ms"] for v in table.values())
@@ -407,7 +418,7 @@ def main():
                 json.dump({"steps_profiled": nprof, "kernels": rows}, f, indent=1)
 
     infer = None
-    if world == 1 and rank == 0 and args.model == "restormer" and args.dtype == "bf16" and not args.no_roofline:
+    if world == 1 and rank == 0 and args.model == "restormer" and args.dtype == "bf16" and do_roofline:
         # the no_grad forward of the same model and batch: the path whose MDTA contraction is fused (pass A: LN -> qkv -> dw3x3 ->
         # q k^T partials + v in one launch, csrc/fused_mdta.hip) - q, k and qkv0 never reach HBM there
         model.eval()
@@ -444,7 +455,7 @@ def main():
                         "and one GEMM1 -> conv barrier per tile; C = 96: the round-3 form; neither roof - DESIGN.md section 7d"}
 
     fp32_line = None
-    if world == 1 and rank == 0 and args.dtype == "bf16" and not args.no_fp32_line and not moce:
+    if world == 1 and rank == 0 and args.dtype == "bf16" and do_fp32 and not moce:
         # the parity path (exact fp32 MFMA, the reference's mainline precision) timed beside the headline: bs 8, 5 steps
         trainer.close()                     # the packed-weight cache is process-global: hand it to the fp32 trainer (idempotent)
         b32 = min(batch, 8)
@@ -464,9 +475,9 @@ def main():
         tr32.close()
 
     # BASELINE configs[1] (Restormer base, bs 8 on one GPU) and configs[3] (MoCE-IR base, the reference README's per-GPU batch and
-    # patch) as short legs of the default line, so that the driver times them too: value, ms per step, library launches per step
+    # patch) as short legs of the --full line: value, ms per step, library launches per step
     extra = {}
-    if world == 1 and rank == 0 and args.dtype == "bf16" and args.model == "restormer" and not args.no_fp32_line:
+    if world == 1 and rank == 0 and args.dtype == "bf16" and args.model == "restormer" and do_fp32:
         trainer.close()
 
         def short_leg(kind, b_, p_, steps=10, warm=3):
@@ -505,7 +516,7 @@ def main():
                                                                "(L1 + 0.01 balance loss)")
 
     cpu = None
-    if world == 1 and rank == 0 and not args.no_cpu_baseline:
+    if world == 1 and rank == 0 and do_cpu:
         cpu = cpu_baseline()
 
     if rank == 0:

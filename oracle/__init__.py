@@ -2,7 +2,7 @@
 
 TEST INFRASTRUCTURE ONLY.  Nothing under ``image_restoration_amd/`` may import
 this package: only ``tests/``, ``__graft_entry__.smoke()`` and the
-``cpu_baseline`` leg of ``bench.py`` use it, and there only as the checker.
+``cpu_baseline`` leg of ``bench.py --full`` use it, and there only as the checker.
 
 The oracle is a plain-PyTorch (CPU, fp32/fp64) functional restatement of the
 reference's algorithm; every function cites the reference file:line it follows
