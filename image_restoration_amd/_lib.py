@@ -106,6 +106,34 @@ class GdfnGrads(C.Structure):
                 ("accumulate", C.c_int)]
 
 
+class TksaShape(C.Structure):
+    _fields_ = [("B", C.c_int), ("C", C.c_int), ("heads", C.c_int), ("H", C.c_int), ("W", C.c_int), ("dtype", C.c_int),
+                ("k1", C.c_int), ("k2", C.c_int), ("k3", C.c_int), ("k4", C.c_int)]
+
+
+class TksaParams(C.Structure):
+    _fields_ = [(n, fp) for n in ("attn1", "attn2", "attn3", "attn4")]
+
+
+class TksaGrads(C.Structure):
+    _fields_ = [(n, fp) for n in ("attn1", "attn2", "attn3", "attn4")]
+
+
+MSFN_PARAM_NAMES = ("in_w", "in_b", "dw3_w", "dw3_b", "dw5_w", "dw5_b", "g3_w", "g3_b", "g5_w", "g5_b", "out_w", "out_b")
+
+
+class MsfnShape(C.Structure):
+    _fields_ = [("B", C.c_int), ("C", C.c_int), ("hidden", C.c_int), ("H", C.c_int), ("W", C.c_int), ("dtype", C.c_int)]
+
+
+class MsfnParams(C.Structure):
+    _fields_ = [(n, fp) for n in MSFN_PARAM_NAMES]
+
+
+class MsfnGrads(C.Structure):
+    _fields_ = [(n, fp) for n in MSFN_PARAM_NAMES] + [("accumulate", C.c_int)]
+
+
 # symbol -> (restype, argtypes); this table is also what tests/test_cabi.py checks against the header
 SIGNATURES = {
     "mi_version": (C.c_int, []),
@@ -196,6 +224,15 @@ SIGNATURES = {
     "mi_gdfn_fwd": (C.c_int, [C.POINTER(GdfnShape), C.POINTER(GdfnParams), vp, vp, vp, vp, vp, vp]),
     "mi_gdfn_bwd": (C.c_int, [C.POINTER(GdfnShape), C.POINTER(GdfnParams), vp, vp, vp, C.POINTER(GdfnGrads), vp, vp,
                               vp]),
+    "mi_tksa_saved_bytes": (C.c_size_t, [C.POINTER(TksaShape)]),
+    "mi_tksa_workspace": (C.c_size_t, [C.POINTER(TksaShape)]),
+    "mi_tksa_fwd": (C.c_int, [C.POINTER(TksaShape), C.POINTER(MdtaParams), C.POINTER(TksaParams), vp, vp, vp, vp, vp, fp, vp]),
+    "mi_tksa_bwd": (C.c_int, [C.POINTER(TksaShape), C.POINTER(MdtaParams), C.POINTER(TksaParams), vp, vp, vp, C.POINTER(MdtaGrads),
+                              C.POINTER(TksaGrads), vp, vp, vp]),
+    "mi_msfn_saved_bytes": (C.c_size_t, [C.POINTER(MsfnShape)]),
+    "mi_msfn_workspace": (C.c_size_t, [C.POINTER(MsfnShape)]),
+    "mi_msfn_fwd": (C.c_int, [C.POINTER(MsfnShape), C.POINTER(MsfnParams), vp, vp, vp, vp, vp, vp]),
+    "mi_msfn_bwd": (C.c_int, [C.POINTER(MsfnShape), C.POINTER(MsfnParams), vp, vp, vp, C.POINTER(MsfnGrads), vp, vp, vp]),
     "mi_gdfn_fused_ok": (C.c_int, [C.POINTER(GdfnFusedShape)]),
     "mi_gdfn_fused_pack_bytes": (C.c_size_t, [C.POINTER(GdfnFusedShape)]),
     "mi_gdfn_fused_pack": (C.c_int, [C.POINTER(GdfnFusedShape), fp, fp, C.POINTER(GdfnParams), vp, vp]),

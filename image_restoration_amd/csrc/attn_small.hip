@@ -20,23 +20,6 @@ static inline int attn_ld(int c) { return c + 1; }
 static inline int attn_ct(int c) { return (c + 15) / 16; }
 static inline int attn_rchunks(int C) { return (C + ATT_RC - 1) / ATT_RC; }
 
-// All-reduce over the 16 lanes of a DPP row (xor-1, xor-2 inside the quad, half-row mirror, row mirror): every lane ends up
-// with the row's result, no LDS-pipe permutes and no readlane.
-#define MI_ROW16_STEP(OP, ctrl)                                                                                    \
-  v = OP(v, __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, v), __builtin_bit_cast(int, v), \
-                                                                  ctrl, 0xf, 0xf, true)))
-__device__ __forceinline__ float row16_sum(float v) {
-#define MI_ADDF(a, b) ((a) + (b))
-  MI_ROW16_STEP(MI_ADDF, 0xB1); MI_ROW16_STEP(MI_ADDF, 0x4E); MI_ROW16_STEP(MI_ADDF, 0x141); MI_ROW16_STEP(MI_ADDF, 0x140);
-#undef MI_ADDF
-  return v;
-}
-__device__ __forceinline__ float row16_max(float v) {
-  MI_ROW16_STEP(fmaxf, 0xB1); MI_ROW16_STEP(fmaxf, 0x4E); MI_ROW16_STEP(fmaxf, 0x141); MI_ROW16_STEP(fmaxf, 0x140);
-  return v;
-}
-#undef MI_ROW16_STEP
-
 // LDS floats of attn_fold_kernel<CT> with rpw row chunks of W_o per workgroup
 static inline size_t attn_fold_lds_floats(int ct, int rpw) {
   const size_t cp = 16 * (size_t)ct;

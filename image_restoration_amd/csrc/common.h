@@ -245,6 +245,23 @@ __device__ __forceinline__ float wave_max(float v) {   // same DPP ladder as wav
   return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 63));
 }
 
+// All-reduce over the 16 lanes of a DPP row (xor-1, xor-2 inside the quad, half-row mirror, row mirror): every lane ends up
+// with the row's result, no LDS-pipe permutes and no readlane.
+#define MI_ROW16_STEP(OP, ctrl)                                                                                    \
+  v = OP(v, __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, v), __builtin_bit_cast(int, v), \
+                                                                  ctrl, 0xf, 0xf, true)))
+__device__ __forceinline__ float row16_sum(float v) {
+#define MI_ADDF(a, b) ((a) + (b))
+  MI_ROW16_STEP(MI_ADDF, 0xB1); MI_ROW16_STEP(MI_ADDF, 0x4E); MI_ROW16_STEP(MI_ADDF, 0x141); MI_ROW16_STEP(MI_ADDF, 0x140);
+#undef MI_ADDF
+  return v;
+}
+__device__ __forceinline__ float row16_max(float v) {
+  MI_ROW16_STEP(fmaxf, 0xB1); MI_ROW16_STEP(fmaxf, 0x4E); MI_ROW16_STEP(fmaxf, 0x141); MI_ROW16_STEP(fmaxf, 0x140);
+  return v;
+}
+#undef MI_ROW16_STEP
+
 // erf-form GELU and its derivative (Restormer.py:91: F.gelu default = erf form).
 // erf is evaluated with Abramowitz-Stegun 7.1.26 (|abs error| <= 1.5e-7, i.e. fp32 round-off level): one reciprocal,
 // one exp and five FMAs instead of the ~35-instruction branchy libm erff; exp(-x^2/2) is shared with the Gaussian
@@ -286,7 +303,8 @@ __device__ __forceinline__ float gelu_erf_grad(float x) {
 enum KernelId {
   K_LN_FWD = 0, K_LN_BWD, K_DW_FWD, K_DW_GATE_FWD, K_DW_BWD_DATA, K_DW_GATE_BWD_DATA, K_DW_WGRAD, K_PW_GEMM, K_GRAM,
   K_GRAM_REDUCE, K_ATTN_FOLD, K_ATTN_BWD_SMALL, K_REDUCE_ROWS, K_CHAN_SUM, K_ADAMW, K_CAST, K_L1, K_PW_PACK, K_GAP,
-  K_IM2COL, K_COL2IM, K_GDFN_FUSED_FWD, K_GDFN_FUSED_BWD, K_MDTA_FUSED_A, K_FUSED_PACK, K_MOE_ROUTE, K_CIRCCONV, K_EWISE, K_CONV3X3, K_GRAM_QK, K_PW_AV, K_BWD_TAIL, K_BWD_TAIL_FIN, K_ADAIR, K_SUMSQ, K_ADAMW_CLIP, K_ADAMW_EMA, K_COUNT
+  K_IM2COL, K_COL2IM, K_GDFN_FUSED_FWD, K_GDFN_FUSED_BWD, K_MDTA_FUSED_A, K_FUSED_PACK, K_MOE_ROUTE, K_CIRCCONV, K_EWISE, K_CONV3X3, K_GRAM_QK, K_PW_AV, K_BWD_TAIL, K_BWD_TAIL_FIN, K_ADAIR, K_SUMSQ, K_ADAMW_CLIP, K_ADAMW_EMA,
+  K_TKSA_ATTN, K_TKSA_FOLD, K_TKSA_BWD, K_TKSA_DWO, K_MSFN_S1, K_MSFN_S2, K_MSFN_S1_BWD, K_MSFN_S2_BWD, K_COUNT
 };
 // Brackets one kernel launch with two events on ITS stream and books its algorithmic bytes / flops.
 struct ProfScope {

@@ -20,6 +20,28 @@ int launch_attn_bwd_small(const float* dM, const float* A, const float* P, const
                           const float* wo, float* dwo_part, float* dtemp_part, float* wd, float* scratch,
                           int B, int C, int heads, hipStream_t st, void* wdb = nullptr);
 size_t attn_bwd_scratch_floats(int B, int C, int heads);
+// ---- top-k sparse attention, the c x c side (tksa.hip): drop-in for launch_attn_fold / launch_attn_bwd_small ----
+struct TopkArgs { const float* w[4]; int k[4]; };   // attn1..attn4 (device scalars) and the four top-k sizes
+int tksa_check(int C, int heads, const int* k);
+int launch_tksa_fold(const float* graw, const float* ss, const float* temperature, const TopkArgs& tk, const float* wo, float* P,
+                     float* S, float* A, float* nrm, float* M, float* scores, int B, int C, int heads, hipStream_t st, void* Mb,
+                     void* Mtb);
+int launch_tksa_bwd(const float* dM, const float* A, const float* S, const float* P, const float* nrm, const float* temperature,
+                    const TopkArgs& tk, const float* wo, float* dwo_part, float* dtemp_part, float* dattn_part, float* wd, int B,
+                    int C, int heads, hipStream_t st, void* wdb);
+// ---- mixed-scale FFN stencils (msfn.hip) ----
+int msfn_splits(int H, int W);
+size_t msfn_part_floats(int B, int hd, int H, int W);
+int launch_msfn_s1_fwd(const void* h0, const float* w3, const float* b3, const float* w5, const float* b5, void* a, void* b, int B,
+                       int hd, int H, int W, int dtype, hipStream_t st);
+int launch_msfn_s2_fwd(const void* a, const void* b, const float* g3w, const float* g3b, const float* g5w, const float* g5b, void* y,
+                       int B, int hd, int H, int W, int dtype, hipStream_t st);
+int launch_msfn_s2_bwd(const void* dY, const void* y, const void* a, const void* b, const float* g3w, const float* g5w, void* dza,
+                       void* dzb, float* g_g3w, float* g_g3b, float* g_g5w, float* g_g5b, int accumulate, float* part, int B, int hd,
+                       int H, int W, int dtype, hipStream_t st);
+int launch_msfn_s1_bwd(const void* dza, const void* dzb, const void* h0, const float* w3, const float* w5, void* dh0, float* g_w3,
+                       float* g_b3, float* g_w5, float* g_b5, int accumulate, float* part, int B, int hd, int H, int W, int dtype,
+                       hipStream_t st);
 size_t chan_sum_workspace(int C, int64_t N);
 int launch_chan_sum(const void* x, float* out, int B, int C, int64_t N, int dtype, int accumulate, void* ws, hipStream_t st);
 

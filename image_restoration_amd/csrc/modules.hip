@@ -174,14 +174,22 @@ static size_t attn_pw_ws_bytes(const AttnDims& d) {
   return max2(max2(mi_pw_gemm_workspace(&b), mi_pw_gemm_workspace(&q)), mi_pw_gemm_workspace(&q2));
 }
 
+// Top-k sparse attention (TKSA, DRSformer_arch.py:101-171): the c x c kernels of tksa.hip in place of attn_fold / attn_bwd_small.
+// S: the saved scores the masks are ranked from; scores: optional copy for the caller; dattn_part / g_attn: backward only.
+struct TopkHook { TopkArgs tk; float* S; float* scores; float* dattn_part; float* g_attn[4]; };
+
 // out = (residual?) + project_out(softmax(temperature * q^ k^T) v)        Restormer.py:121-131
 static int attn_core_fwd(const AttnDims& d, const QkvView& v, const float* temperature, const float* proj_w,
                          const float* proj_b, const void* residual, void* out, const AttnSaved& sv, const AttnScratch& w,
-                         void* stream, const mi_f8_scales* f8 = nullptr) {
+                         void* stream, const mi_f8_scales* f8 = nullptr, const TopkHook* tk = nullptr) {
   hipStream_t st = (hipStream_t)stream;
   mi_gram_desc g = attn_qk_gram(d, v, w.graw, w.ss);
   MI_TRY(mi_gram(&g, w.gram_ws, stream));
-  MI_TRY(launch_attn_fold(w.graw, w.ss, temperature, proj_w, sv.P, sv.A, sv.nrm, sv.M, d.B, d.C, d.heads, st, sv.Mb, sv.Mtb));
+  if (tk)
+    MI_TRY(launch_tksa_fold(w.graw, w.ss, temperature, tk->tk, proj_w, sv.P, tk->S, sv.A, sv.nrm, sv.M, tk->scores, d.B, d.C,
+                            d.heads, st, sv.Mb, sv.Mtb));
+  else
+    MI_TRY(launch_attn_fold(w.graw, w.ss, temperature, proj_w, sv.P, sv.A, sv.nrm, sv.M, d.B, d.C, d.heads, st, sv.Mb, sv.Mtb));
   mi_pw_desc d2 = conv1x1(v.v, d.C, sv.M, false, d.C, proj_b, residual, out, d.C, d.B, d.N, d.dtype);
   d2.x1_bs = v.v_bs;
   d2.w_bs = (int64_t)d.C * d.C;
@@ -194,7 +202,7 @@ static int attn_core_fwd(const AttnDims& d, const QkvView& v, const float* tempe
 static int attn_core_bwd(const AttnDims& d, const QkvView& v, const void* dout, void* dq, int64_t dq_bs, void* dk,
                          int64_t dk_bs, void* dv, int64_t dv_bs, const AttnSaved& sv, const float* temperature,
                          const float* proj_w, float* g_temperature, float* g_proj_w, float* g_proj_b, int acc,
-                         const AttnScratch& w, void* stream) {
+                         const AttnScratch& w, void* stream, const TopkHook* tk = nullptr) {
   hipStream_t st = (hipStream_t)stream;
   const int B = d.B, C = d.C, hd = d.heads;
   if (g_proj_b) MI_TRY(launch_chan_sum(dout, g_proj_b, B, C, d.N, d.dtype, acc, w.cs_ws, st));
@@ -207,8 +215,15 @@ static int attn_core_bwd(const AttnDims& d, const QkvView& v, const void* dout, 
     float* a2 = a1 ? deferred_take((size_t)B * hd, st) : nullptr;
     if (a1 && a2) { dwo_part = a1; dtemp_part = a2; }
   }
-  MI_TRY(launch_attn_bwd_small(w.dM, sv.A, sv.P, sv.nrm, temperature, proj_w, dwo_part, dtemp_part, w.wd,
-                               w.attn_scr, B, C, hd, st, w.wdb));
+  if (tk) {
+    MI_TRY(launch_tksa_bwd(w.dM, sv.A, tk->S, sv.P, sv.nrm, temperature, tk->tk, proj_w, dwo_part, dtemp_part, tk->dattn_part, w.wd,
+                           B, C, hd, st, w.wdb));
+    for (int m = 0; m < 4; ++m)     // d attn_m: the (image, head) partials summed in a fixed order
+      MI_TRY(launch_reduce_rows(tk->dattn_part + m, tk->g_attn[m], (int64_t)B * hd, 1, 4, acc, 1.0f, st));
+  } else {
+    MI_TRY(launch_attn_bwd_small(w.dM, sv.A, sv.P, sv.nrm, temperature, proj_w, dwo_part, dtemp_part, w.wd,
+                                 w.attn_scr, B, C, hd, st, w.wdb));
+  }
   MI_TRY(launch_reduce_rows(dwo_part, g_proj_w, B, (int64_t)C * C, (int64_t)C * C, acc, 1.0f, st));
   MI_TRY(launch_reduce_rows(dtemp_part, g_temperature, B, hd, hd, acc, 1.0f, st));
   // dq = G1 k + D1 q ; dk = G1^T q + D2 k   (grouped over heads, per-image weights)
@@ -730,4 +745,212 @@ extern "C" int mi_gdfn_bwd_ln(const mi_gdfn_shape* s, const mi_gdfn_params* p, c
   MI_TRY(ln_tail_check(ln, "gdfn_bwd_ln"));
   MI_CHECK_ARG(gr && !gr->in_b && mi_gdfn_bwd_ln_ok(s, 0), "gdfn_bwd_ln: shape not covered (bf16, C 48/96, H*W %% 64 == 0, no project_in bias)");
   return gdfn_bwd_impl(s, p, x, dout, dx, gr, saved, ws, stream, ln);
+}
+
+// ------------------------------------------------------------------ TKSA (DRSformer_arch.py:101-171)
+// MDTA's layouts (qkv 1x1 -> depthwise 3x3 -> attention core) plus the saved scores S [B*heads][c][c] the top-k masks are ranked
+// from (forward and backward rank the same fp32 values), and the d attn_m partials [B*heads][4] in the workspace.
+static mi_mdta_shape tksa_mdta_shape(const mi_tksa_shape* s) { return mi_mdta_shape{s->B, s->C, s->heads, s->H, s->W, s->dtype, 3}; }
+static int tksa_shape_check(const mi_tksa_shape* s) {
+  MI_CHECK_ARG(s, "tksa: null shape");
+  const mi_mdta_shape m = tksa_mdta_shape(s);
+  MI_TRY(mdta_check(&m));
+  const int k[4] = {s->k1, s->k2, s->k3, s->k4};
+  return tksa_check(s->C, s->heads, k);
+}
+static size_t tksa_scores_bytes(const mi_tksa_shape* s) {
+  const size_t c = s->C / s->heads;
+  return fbytes((size_t)s->B * s->heads * c * c);
+}
+struct TksaWs { MdtaWs m; float* S_inf; float* dattn_part; size_t bytes; };
+static TksaWs tksa_ws_layout(const mi_tksa_shape* s, void* base) {
+  const mi_mdta_shape ms = tksa_mdta_shape(s);
+  TksaWs w;
+  w.m = mdta_ws_layout(&ms, base);
+  Carver cv(base ? (char*)base + align_up(w.m.bytes, 256) : nullptr);
+  w.S_inf = cv.take<float>(tksa_scores_bytes(s));      // (no-grad forward: nothing saved)
+  w.dattn_part = cv.take<float>(fbytes((size_t)s->B * s->heads * 4));
+  w.bytes = align_up(w.m.bytes, 256) + cv.off;
+  return w;
+}
+static TopkHook tksa_hook(const mi_tksa_shape* s, const mi_tksa_params* tp, float* S, float* scores) {
+  TopkHook hk;
+  memset(&hk, 0, sizeof(hk));
+  hk.tk.w[0] = tp->attn1; hk.tk.w[1] = tp->attn2; hk.tk.w[2] = tp->attn3; hk.tk.w[3] = tp->attn4;
+  hk.tk.k[0] = s->k1; hk.tk.k[1] = s->k2; hk.tk.k[2] = s->k3; hk.tk.k[3] = s->k4;
+  hk.S = S; hk.scores = scores;
+  return hk;
+}
+
+extern "C" size_t mi_tksa_saved_bytes(const mi_tksa_shape* s) {
+  if (tksa_shape_check(s) != MI_OK) return 0;
+  const mi_mdta_shape ms = tksa_mdta_shape(s);
+  return mdta_saved_layout(&ms, nullptr).bytes + tksa_scores_bytes(s);
+}
+extern "C" size_t mi_tksa_workspace(const mi_tksa_shape* s) {
+  if (tksa_shape_check(s) != MI_OK) return 0;
+  return tksa_ws_layout(s, nullptr).bytes;
+}
+
+extern "C" int mi_tksa_fwd(const mi_tksa_shape* s, const mi_mdta_params* p, const mi_tksa_params* tp, const void* x,
+                           const void* residual, void* out, void* saved, void* ws, float* scores, void* stream) {
+  MI_TRY(tksa_shape_check(s));
+  MI_CHECK_ARG(p && tp && x && out && ws, "tksa_fwd: null pointer");
+  MI_CHECK_ARG(p->temperature && p->qkv_w && p->dw_w && p->proj_w, "tksa_fwd: null parameter");
+  MI_CHECK_ARG(tp->attn1 && tp->attn2 && tp->attn3 && tp->attn4, "tksa_fwd: null attn1..4");
+  const mi_mdta_shape ms = tksa_mdta_shape(s);
+  const int B = s->B, C = s->C, dt = s->dtype;
+  const int64_t N = (int64_t)s->H * s->W;
+  TksaWs w = tksa_ws_layout(s, ws);
+  MdtaSaved sv = saved ? mdta_saved_layout(&ms, saved) : w.m.inf;
+  float* S = saved ? (float*)((char*)saved + sv.bytes) : w.S_inf;
+  // qkv0 = qkv(x);  qkv = qkv_dwconv(qkv0)                        DRSformer_arch.py:123
+  mi_pw_desc d1 = conv1x1(x, C, p->qkv_w, false, C, p->qkv_b, nullptr, sv.qkv0, 3 * C, B, N, dt);
+  MI_TRY(mi_pw_gemm(&d1, w.m.at.pw_ws, stream));
+  MI_TRY(mi_dwconv_fwd(sv.qkv0, p->dw_w, p->dw_b, sv.qkv, B, 3 * C, s->H, s->W, 3, dt, stream));
+  const TopkHook hk = tksa_hook(s, tp, S, scores);
+  return attn_core_fwd(mdta_dims(&ms), mdta_view(&ms, sv.qkv), p->temperature, p->proj_w, p->proj_b, residual, out, sv.at, w.m.at,
+                       stream, nullptr, &hk);
+}
+
+extern "C" int mi_tksa_bwd(const mi_tksa_shape* s, const mi_mdta_params* p, const mi_tksa_params* tp, const void* x,
+                           const void* dout, void* dx, const mi_mdta_grads* gr, const mi_tksa_grads* tg, const void* saved, void* ws,
+                           void* stream) {
+  MI_TRY(tksa_shape_check(s));
+  MI_CHECK_ARG(p && tp && x && dout && dx && gr && tg && saved && ws, "tksa_bwd: null pointer");
+  MI_CHECK_ARG(tp->attn1 && tp->attn2 && tp->attn3 && tp->attn4, "tksa_bwd: null attn1..4");
+  MI_CHECK_ARG(gr->temperature && gr->qkv_w && gr->dw_w && gr->proj_w, "tksa_bwd: null gradient buffer");
+  MI_CHECK_ARG(tg->attn1 && tg->attn2 && tg->attn3 && tg->attn4, "tksa_bwd: null attn1..4 gradient buffer");
+  hipStream_t st = (hipStream_t)stream;
+  const mi_mdta_shape ms = tksa_mdta_shape(s);
+  const int B = s->B, C = s->C, dt = s->dtype, acc = gr->accumulate;
+  const int64_t N = (int64_t)s->H * s->W, bs = 3 * (int64_t)C * N;
+  const size_t plane = (size_t)C * N * dtype_size(dt);
+  TksaWs w = tksa_ws_layout(s, ws);
+  MdtaSaved sv = mdta_saved_layout(&ms, const_cast<void*>(saved));
+  TopkHook hk = tksa_hook(s, tp, (float*)((char*)saved + sv.bytes), nullptr);
+  hk.dattn_part = w.dattn_part;
+  hk.g_attn[0] = tg->attn1; hk.g_attn[1] = tg->attn2; hk.g_attn[2] = tg->attn3; hk.g_attn[3] = tg->attn4;
+  char* dq = (char*)w.m.dqkv;
+  MI_TRY(attn_core_bwd(mdta_dims(&ms), mdta_view(&ms, sv.qkv), dout, dq, bs, dq + plane, bs, dq + 2 * plane, bs, sv.at,
+                       p->temperature, p->proj_w, gr->temperature, gr->proj_w, gr->proj_b, acc, w.m.at, stream, &hk));
+  MI_TRY(mi_dwconv_bwd(w.m.dqkv, sv.qkv0, p->dw_w, w.m.dqkv0, gr->dw_w, gr->dw_b, B, 3 * C, s->H, s->W, 3, acc, dt, w.m.dw_ws,
+                       stream));
+  hipStream_t sd = co_fork(st);
+  mi_gram_desc g2 = wgrad_gram(w.m.dqkv0, 3 * C, x, C, B, N, dt, gr->qkv_w, acc);
+  MI_TRY(mi_gram(&g2, w.m.at.gram_ws, sd));
+  if (gr->qkv_b) MI_TRY(launch_chan_sum(w.m.dqkv0, gr->qkv_b, B, 3 * C, N, dt, acc, w.m.at.cs_ws, sd));
+  mi_pw_desc dxd = conv1x1(w.m.dqkv0, 3 * C, p->qkv_w, true, C, nullptr, nullptr, dx, C, B, N, dt);
+  MI_TRY(mi_pw_gemm(&dxd, w.m.at.pw_ws, stream));
+  return co_join(sd, st);
+}
+
+// ------------------------------------------------------------------ MSFN (DRSformer_arch.py:62-98)
+// project_in (C -> 2h) -> stencil stage 1 (a, b) -> stencil stage 2 (y = cat(y1, y2)) -> project_out (2h -> C).  Saved for
+// backward: h0, a, b and y (2h planes each): y gives the project_out weight gradient and the stage-2 ReLU mask, a and b are the
+// stage-2 inputs and carry the stage-1 ReLU masks, h0 is the stage-1 input.
+struct MsfnSaved { void* h0; void* a; void* b; void* y; size_t bytes; };
+static MsfnSaved msfn_saved_layout(const mi_msfn_shape* s, void* base) {
+  const size_t n = (size_t)s->B * 2 * s->hidden * s->H * s->W;
+  Carver cv(base);
+  MsfnSaved r;
+  r.h0 = cv.take(tbytes(n, s->dtype));
+  r.a = cv.take(tbytes(n, s->dtype));
+  r.b = cv.take(tbytes(n, s->dtype));
+  r.y = cv.take(tbytes(n, s->dtype));
+  r.bytes = cv.off;
+  return r;
+}
+struct MsfnWs { void* gram_ws; void* pw_ws; void* cs_ws; float* part; MsfnSaved inf; void* dY; void* dza; void* dzb; size_t bytes; };
+static MsfnWs msfn_ws_layout(const mi_msfn_shape* s, void* base) {
+  const int B = s->B, C = s->C, h2 = 2 * s->hidden, dt = s->dtype;
+  const int64_t N = (int64_t)s->H * s->W;
+  Carver cv(base);
+  MsfnWs w;
+  mi_gram_desc g1 = wgrad_gram((void*)256, C, (void*)256, h2, B, N, dt, (float*)256, 0);
+  mi_gram_desc g2 = wgrad_gram((void*)256, h2, (void*)256, C, B, N, dt, (float*)256, 0);
+  w.gram_ws = cv.take(max2(mi_gram_workspace(&g1), mi_gram_workspace(&g2)));
+  {
+    mi_pw_desc a = conv1x1((void*)256, C, (const float*)256, false, C, nullptr, nullptr, (void*)256, h2, B, N, dt);
+    mi_pw_desc b = conv1x1((void*)256, h2, (const float*)256, false, h2, nullptr, nullptr, (void*)256, C, B, N, dt);
+    mi_pw_desc c = conv1x1((void*)256, C, (const float*)256, true, h2, nullptr, nullptr, (void*)256, h2, B, N, dt);
+    mi_pw_desc e = conv1x1((void*)256, h2, (const float*)256, true, C, nullptr, nullptr, (void*)256, C, B, N, dt);
+    w.pw_ws = cv.take(max2(max2(mi_pw_gemm_workspace(&a), mi_pw_gemm_workspace(&b)),
+                           max2(mi_pw_gemm_workspace(&c), mi_pw_gemm_workspace(&e))));
+  }
+  w.cs_ws = cv.take(chan_sum_workspace(h2 > C ? h2 : C, N));
+  w.part = cv.take<float>(fbytes(msfn_part_floats(B, s->hidden, s->H, s->W)));
+  const size_t mark = cv.off;
+  w.inf = msfn_saved_layout(s, base ? (char*)base + mark : nullptr);
+  Carver big(base ? (char*)base + mark : nullptr);
+  const size_t plane = tbytes((size_t)B * h2 * N, dt);
+  w.dY = big.take(plane);           // gradient of cat(y1, y2); then of h0
+  w.dza = big.take(plane);
+  w.dzb = big.take(plane);
+  w.bytes = mark + max2(w.inf.bytes, big.off);
+  return w;
+}
+static int msfn_check(const mi_msfn_shape* s) {
+  MI_CHECK_ARG(s, "msfn: null shape");
+  MI_CHECK_ARG(s->B > 0 && s->C > 0 && s->hidden > 0 && s->H > 0 && s->W > 0, "msfn: bad shape");
+  MI_CHECK_ARG(2 * s->hidden <= 65535, "msfn: hidden=%d too large (2*hidden <= 65535)", s->hidden);
+  MI_CHECK_ARG(s->dtype == MI_F32 || s->dtype == MI_BF16, "msfn: bad dtype %d", s->dtype);
+  return MI_OK;
+}
+
+extern "C" size_t mi_msfn_saved_bytes(const mi_msfn_shape* s) {
+  if (msfn_check(s) != MI_OK) return 0;
+  return msfn_saved_layout(s, nullptr).bytes;
+}
+extern "C" size_t mi_msfn_workspace(const mi_msfn_shape* s) {
+  if (msfn_check(s) != MI_OK) return 0;
+  return msfn_ws_layout(s, nullptr).bytes;
+}
+
+extern "C" int mi_msfn_fwd(const mi_msfn_shape* s, const mi_msfn_params* p, const void* x, const void* residual, void* out,
+                           void* saved, void* ws, void* stream) {
+  MI_TRY(msfn_check(s));
+  MI_CHECK_ARG(p && x && out && ws, "msfn_fwd: null pointer");
+  MI_CHECK_ARG(p->in_w && p->dw3_w && p->dw5_w && p->g3_w && p->g5_w && p->out_w, "msfn_fwd: null parameter");
+  hipStream_t st = (hipStream_t)stream;
+  const int B = s->B, C = s->C, hd = s->hidden, dt = s->dtype;
+  const int64_t N = (int64_t)s->H * s->W;
+  MsfnWs w = msfn_ws_layout(s, ws);
+  MsfnSaved sv = saved ? msfn_saved_layout(s, saved) : w.inf;
+  mi_pw_desc d1 = conv1x1(x, C, p->in_w, false, C, p->in_b, nullptr, sv.h0, 2 * hd, B, N, dt);     // DRSformer_arch.py:86
+  MI_TRY(mi_pw_gemm(&d1, w.pw_ws, stream));
+  MI_TRY(launch_msfn_s1_fwd(sv.h0, p->dw3_w, p->dw3_b, p->dw5_w, p->dw5_b, sv.a, sv.b, B, hd, s->H, s->W, dt, st));       // :87-88
+  MI_TRY(launch_msfn_s2_fwd(sv.a, sv.b, p->g3_w, p->g3_b, p->g5_w, p->g5_b, sv.y, B, hd, s->H, s->W, dt, st));           // :90-96
+  mi_pw_desc d2 = conv1x1(sv.y, 2 * hd, p->out_w, false, 2 * hd, p->out_b, residual, out, C, B, N, dt);                 // :98
+  return mi_pw_gemm(&d2, w.pw_ws, stream);
+}
+
+extern "C" int mi_msfn_bwd(const mi_msfn_shape* s, const mi_msfn_params* p, const void* x, const void* dout, void* dx,
+                           const mi_msfn_grads* gr, const void* saved, void* ws, void* stream) {
+  MI_TRY(msfn_check(s));
+  MI_CHECK_ARG(p && x && dout && dx && gr && saved && ws, "msfn_bwd: null pointer");
+  MI_CHECK_ARG(p->in_w && p->dw3_w && p->dw5_w && p->g3_w && p->g5_w && p->out_w, "msfn_bwd: null parameter");
+  MI_CHECK_ARG(gr->in_w && gr->dw3_w && gr->dw5_w && gr->g3_w && gr->g5_w && gr->out_w, "msfn_bwd: null gradient buffer");
+  hipStream_t st = (hipStream_t)stream;
+  const int B = s->B, C = s->C, hd = s->hidden, dt = s->dtype, acc = gr->accumulate;
+  const int64_t N = (int64_t)s->H * s->W;
+  MsfnWs w = msfn_ws_layout(s, ws);
+  MsfnSaved sv = msfn_saved_layout(s, const_cast<void*>(saved));
+  if (gr->out_b) MI_TRY(launch_chan_sum(dout, gr->out_b, B, C, N, dt, acc, w.cs_ws, st));
+  mi_gram_desc g1 = wgrad_gram(dout, C, sv.y, 2 * hd, B, N, dt, gr->out_w, acc);
+  MI_TRY(mi_gram(&g1, w.gram_ws, stream));
+  mi_pw_desc d1 = conv1x1(dout, C, p->out_w, true, 2 * hd, nullptr, nullptr, w.dY, 2 * hd, B, N, dt);
+  MI_TRY(mi_pw_gemm(&d1, w.pw_ws, stream));
+  MI_TRY(launch_msfn_s2_bwd(w.dY, sv.y, sv.a, sv.b, p->g3_w, p->g5_w, w.dza, w.dzb, gr->g3_w, gr->g3_b, gr->g5_w, gr->g5_b, acc,
+                            w.part, B, hd, s->H, s->W, dt, st));
+  void* dh0 = w.dY;                 // (dY is dead once stage 2 is through)
+  MI_TRY(launch_msfn_s1_bwd(w.dza, w.dzb, sv.h0, p->dw3_w, p->dw5_w, dh0, gr->dw3_w, gr->dw3_b, gr->dw5_w, gr->dw5_b, acc, w.part,
+                            B, hd, s->H, s->W, dt, st));
+  hipStream_t sd = co_fork(st);
+  mi_gram_desc g2 = wgrad_gram(dh0, 2 * hd, x, C, B, N, dt, gr->in_w, acc);
+  MI_TRY(mi_gram(&g2, w.gram_ws, sd));
+  if (gr->in_b) MI_TRY(launch_chan_sum(dh0, gr->in_b, B, 2 * hd, N, dt, acc, w.cs_ws, sd));
+  mi_pw_desc d2 = conv1x1(dh0, 2 * hd, p->in_w, true, C, nullptr, nullptr, dx, C, B, N, dt);
+  MI_TRY(mi_pw_gemm(&d2, w.pw_ws, stream));
+  return co_join(sd, st);
 }

@@ -531,6 +531,116 @@ def gdfn_bwd(x: Tensor, dout: Tensor, params: GdfnParamsT, saved: Tensor, grads:
     return dx
 
 
+# ----------------------------------------------------------------------------- DRSformer: TKSA / MSFN
+def tksa_topk(c: int) -> Tuple[int, int, int, int]:
+    """The four top-k sizes of DRSformer_arch.py:141-155, with the reference's own expressions."""
+    return int(c / 2), int(c * 2 / 3), int(c * 3 / 4), int(c * 4 / 5)
+
+
+def _tksa_shape(x: Tensor, heads: int, topk: Sequence[int]) -> L.TksaShape:
+    B, Cc, H, W = x.shape
+    return L.TksaShape(B, Cc, heads, H, W, _dt(x), *[int(k) for k in topk])
+
+
+def tksa_sizes(B: int, Cc: int, heads: int, H: int, W: int, dtype: torch.dtype, topk: Sequence[int]) -> Tuple[int, int]:
+    """(saved bytes, workspace bytes) of one TKSA call; (0, 0) for a shape the kernels do not cover.  No GPU needed."""
+    s = L.TksaShape(B, Cc, heads, H, W, L.MI_BF16 if dtype == torch.bfloat16 else L.MI_F32, *[int(k) for k in topk])
+    lib = L.lib()
+    return int(lib.mi_tksa_saved_bytes(C.byref(s))), int(lib.mi_tksa_workspace(C.byref(s)))
+
+
+def tksa_fwd(x: Tensor, residual: Optional[Tensor], params: Sequence[Optional[Tensor]], heads: int, topk: Sequence[int],
+             need_saved: bool, want_scores: bool = False):
+    """DRSformer Attention (TKSA).  params = (temperature, qkv.weight, qkv.bias, qkv_dwconv.weight, qkv_dwconv.bias,
+    project_out.weight, project_out.bias, attn1, attn2, attn3, attn4); topk: the four k (tksa_topk).  Returns (out, saved) or,
+    with want_scores, (out, saved, scores [B, heads, c, c] fp32: the S the top-k masks were ranked from)."""
+    _gpu(x, residual, *params)
+    for t in params:
+        _f32(t, "TKSA parameter")
+    s = _tksa_shape(x, heads, topk)
+    lib = L.lib()
+    ws_bytes = lib.mi_tksa_workspace(C.byref(s))
+    if ws_bytes == 0:
+        L.check(-1, "tksa_workspace")
+    out = torch.empty_like(x)
+    saved = _blob(lib.mi_tksa_saved_bytes(C.byref(s)), x.device) if need_saved else None
+    ws = _ws(ws_bytes, x.device)
+    c = x.shape[1] // heads
+    scores = torch.empty((x.shape[0], heads, c, c), dtype=torch.float32, device=x.device) if want_scores else None
+    pp = _mdta_params(params[:7])
+    tp = L.TksaParams(*[_p(t) for t in params[7:11]])
+    L.check(lib.mi_tksa_fwd(C.byref(s), C.byref(pp), C.byref(tp), _p(x), _p(residual), _p(out), _p(saved), _p(ws), _p(scores),
+                            _stream()), "tksa_fwd")
+    return (out, saved, scores) if want_scores else (out, saved)
+
+
+def tksa_bwd(x: Tensor, dout: Tensor, params: Sequence[Optional[Tensor]], heads: int, topk: Sequence[int], saved: Tensor,
+             grads: Sequence[Optional[Tensor]], accumulate: bool) -> Tensor:
+    """Backward of tksa_fwd: dx; the 11 parameter gradients are written (accumulate: added) into ``grads``."""
+    _gpu(x, dout, saved, *params, *grads)
+    s = _tksa_shape(x, heads, topk)
+    lib = L.lib()
+    dx = torch.empty_like(x)
+    for t in grads:
+        _f32(t, "TKSA gradient")
+    pp = _mdta_params(params[:7])
+    tp = L.TksaParams(*[_p(t) for t in params[7:11]])
+    gg = L.MdtaGrads(*[_p(t) for t in grads[:7]], int(accumulate))
+    tg = L.TksaGrads(*[_p(t) for t in grads[7:11]])
+    ws = _ws(lib.mi_tksa_workspace(C.byref(s)), x.device)
+    L.check(lib.mi_tksa_bwd(C.byref(s), C.byref(pp), C.byref(tp), _p(x), _p(dout), _p(dx), C.byref(gg), C.byref(tg), _p(saved),
+                            _p(ws), _stream()), "tksa_bwd")
+    return dx
+
+
+def _msfn_shape(x: Tensor, hidden: int) -> L.MsfnShape:
+    B, Cc, H, W = x.shape
+    return L.MsfnShape(B, Cc, hidden, H, W, _dt(x))
+
+
+def msfn_fwd(x: Tensor, residual: Optional[Tensor], params: Sequence[Optional[Tensor]], need_saved: bool):
+    """DRSformer FeedForward (MSFN).  params = (project_in.weight, .bias, dwconv3x3.weight, .bias, dwconv5x5.weight, .bias,
+    dwconv3x3_1.weight, .bias, dwconv5x5_1.weight, .bias, project_out.weight, .bias).  Returns (out, saved)."""
+    _gpu(x, residual, *params)
+    for t in params:
+        _f32(t, "MSFN parameter")
+    s = _msfn_shape(x, params[6].shape[0])
+    lib = L.lib()
+    out = torch.empty_like(x)
+    saved = _blob(lib.mi_msfn_saved_bytes(C.byref(s)), x.device) if need_saved else None
+    ws = _ws(lib.mi_msfn_workspace(C.byref(s)), x.device)
+    pp = L.MsfnParams(*[_p(t) for t in params])
+    L.check(lib.mi_msfn_fwd(C.byref(s), C.byref(pp), _p(x), _p(residual), _p(out), _p(saved), _p(ws), _stream()), "msfn_fwd")
+    return out, saved
+
+
+def msfn_saved_views(saved: Tensor, x: Tensor, hidden: int) -> dict:
+    """The planes a training forward keeps in its saved blob: h0 (project_in output), a, b (stage-1 outputs) and y
+    (cat(y1, y2)), each [B, 2h, H, W] in x's dtype - views into the blob (mi_msfn_saved_bytes' layout)."""
+    B, _, H, W = x.shape
+    n = B * 2 * hidden * H * W
+    es = x.element_size()
+    step = (n * es + 255) // 256 * 256
+    return {name: saved[i * step:i * step + n * es].view(x.dtype).view(B, 2 * hidden, H, W)
+            for i, name in enumerate(("h0", "a", "b", "y"))}
+
+
+def msfn_bwd(x: Tensor, dout: Tensor, params: Sequence[Optional[Tensor]], saved: Tensor, grads: Sequence[Optional[Tensor]],
+             accumulate: bool) -> Tensor:
+    _gpu(x, dout, saved, *params, *grads)
+    s = _msfn_shape(x, params[6].shape[0])
+    lib = L.lib()
+    dx = torch.empty_like(x)
+    for t in grads:
+        _f32(t, "MSFN gradient")
+    pp = L.MsfnParams(*[_p(t) for t in params])
+    gg = L.MsfnGrads(*[_p(t) for t in grads], int(accumulate))
+    ws = _ws(lib.mi_msfn_workspace(C.byref(s)), x.device)
+    L.check(lib.mi_msfn_bwd(C.byref(s), C.byref(pp), _p(x), _p(dout), _p(dx), C.byref(gg), _p(saved), _p(ws), _stream()),
+            "msfn_bwd")
+    return dx
+
+
 def bwd_tail_ok(M: int, Cc: int, N: int, dtype: torch.dtype) -> bool:
     return bool(L.lib().mi_bwd_tail_ok(M, Cc, N, L.MI_BF16 if dtype == torch.bfloat16 else L.MI_F32))
 

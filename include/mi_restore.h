@@ -249,6 +249,52 @@ int mi_xmdta_bwd(const mi_xmdta_shape* s, const mi_xmdta_params* p, const void* 
                  void* dx, void* dy, const mi_xmdta_grads* g, const void* saved, void* ws, void* stream);
 
 /* ------------------------------------------------------------------------
+ * TKSA — DRSformer's top-k sparse attention, Attention.forward / backward (DRSformer_arch.py:101-171).  MDTA's qkv 1x1, 3x3
+ * depthwise, L2-normalised q, k, temperature and project_out; the c x c map is A = sum_m attn_m softmax(top-k_m(S)) with
+ * S = temperature * cos(q, k): in each row of S only the k_m largest entries stay, the rest are -inf (ties: lower column index
+ * first).  c = C/heads <= 120; k1..k4 in 1..c (DRSformer: int(c/2), int(c*2/3), int(c*3/4), int(c*4/5), computed by the
+ * caller).  mi_mdta_params / mi_mdta_grads carry the MDTA parameters (the depthwise conv is 3x3); mi_tksa_params /
+ * mi_tksa_grads the four [1] mixing weights.  scores: NULL or [B, heads, c, c] fp32, receives the S the masks were ranked
+ * from.  The attn_m gradients follow mi_mdta_grads.accumulate.  Sizing entry points return 0 for a shape not covered.
+ * ------------------------------------------------------------------------ */
+typedef struct { int B, C, heads, H, W, dtype, k1, k2, k3, k4; } mi_tksa_shape;
+typedef struct { const float* attn1; const float* attn2; const float* attn3; const float* attn4; } mi_tksa_params;
+typedef struct { float* attn1; float* attn2; float* attn3; float* attn4; } mi_tksa_grads;
+size_t mi_tksa_saved_bytes(const mi_tksa_shape* s);
+size_t mi_tksa_workspace(const mi_tksa_shape* s);
+int mi_tksa_fwd(const mi_tksa_shape* s, const mi_mdta_params* p, const mi_tksa_params* tp, const void* x, const void* residual,
+                void* out, void* saved, void* ws, float* scores, void* stream);
+int mi_tksa_bwd(const mi_tksa_shape* s, const mi_mdta_params* p, const mi_tksa_params* tp, const void* x, const void* dout,
+                void* dx, const mi_mdta_grads* g, const mi_tksa_grads* tg, const void* saved, void* ws, void* stream);
+
+/* ------------------------------------------------------------------------
+ * MSFN — DRSformer's mixed-scale FeedForward.forward / backward (DRSformer_arch.py:62-98).  hidden = h:
+ *   h0 = project_in(x) [2h];  a = relu(dwconv3x3(h0)), b = relu(dwconv5x5(h0)) (depthwise, 2h each);
+ *   y1 = relu(dwconv3x3_1(cat(a[:h], b[:h]))), y2 = relu(dwconv5x5_1(cat(a[h:], b[h:]))) (groups = h, two inputs per group);
+ *   out = (residual?) + project_out(cat(y1, y2)).
+ * Any h (odd h: one group reads the last channel of a and the first of b).  NULL biases: the convs have none.
+ * ------------------------------------------------------------------------ */
+typedef struct { int B, C, hidden, H, W, dtype; } mi_msfn_shape;
+typedef struct {
+  const float* in_w;  const float* in_b;   /* [2h,C], [2h]|NULL */
+  const float* dw3_w; const float* dw3_b;  /* [2h,9], [2h]|NULL */
+  const float* dw5_w; const float* dw5_b;  /* [2h,25], [2h]|NULL */
+  const float* g3_w;  const float* g3_b;   /* [h,2,9], [h]|NULL */
+  const float* g5_w;  const float* g5_b;   /* [h,2,25], [h]|NULL */
+  const float* out_w; const float* out_b;  /* [C,2h], [C]|NULL */
+} mi_msfn_params;
+typedef struct {
+  float* in_w; float* in_b; float* dw3_w; float* dw3_b; float* dw5_w; float* dw5_b; float* g3_w; float* g3_b; float* g5_w;
+  float* g5_b; float* out_w; float* out_b; int accumulate;
+} mi_msfn_grads;
+size_t mi_msfn_saved_bytes(const mi_msfn_shape* s);
+size_t mi_msfn_workspace(const mi_msfn_shape* s);
+int mi_msfn_fwd(const mi_msfn_shape* s, const mi_msfn_params* p, const void* x, const void* residual,
+                void* out, void* saved, void* ws, void* stream);
+int mi_msfn_bwd(const mi_msfn_shape* s, const mi_msfn_params* p, const void* x, const void* dout,
+                void* dx, const mi_msfn_grads* g, const void* saved, void* ws, void* stream);
+
+/* ------------------------------------------------------------------------
  * GDFN — FeedForward.forward / backward (Restormer.py:76-93; moce_ir.py:255-276;
  * AdaIR-main/net/model.py:76-94).  hidden = h (project_in has 2h outputs).
  * ------------------------------------------------------------------------ */

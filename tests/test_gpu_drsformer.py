@@ -1,0 +1,341 @@
+"""DRSformer's transformer block on the MI355X: the native TKSA / MSFN / STB modules against the reference fixtures and against
+the fp64 restatement (tests/drs_ref.py) fed with the device's own top-k masks, determinism, no_grad, and FlatTrainer training
+(eager and captured)."""
+import importlib.util
+import os
+import subprocess
+import sys
+import textwrap
+
+import pytest
+import torch
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+ROOT = os.path.dirname(HERE)
+sys.path.insert(0, HERE)
+sys.path.insert(0, ROOT)
+
+import drs_ref as D  # noqa: E402
+from oracle.fixtures import check, load, seeded_input  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+DEV = torch.device("cuda:0")
+
+
+def N():
+    from image_restoration_amd import drsformer
+    return drsformer
+
+
+def _capture_module():
+    spec = importlib.util.spec_from_file_location("capture_golden_drs", os.path.join(ROOT, "tools", "capture_golden_drs.py"))
+    m = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(m)
+    return m
+
+
+G = _capture_module()
+
+
+def rel(a, b):
+    a, b = a.detach().double().cpu(), b.detach().double().cpu()
+    return float((a - b).abs().max() / b.abs().max().clamp_min(1e-30))
+
+
+def nrel(a, b):
+    a, b = a.detach().double().cpu(), b.detach().double().cpu()
+    return float((a - b).norm() / b.norm().clamp_min(1e-30))
+
+
+def build(kind, dim, heads, factor, bias, ln_type, seed):
+    shapes = G.case_shapes(kind, dim, heads, factor, bias, ln_type)
+    sd = D.make_state(shapes, seed)
+    if kind == "tksa":
+        mod = N().Attention(dim, heads, bias)
+    elif kind == "msfn":
+        mod = N().FeedForward(dim, factor, bias)
+    else:
+        mod = N().TransformerBlock(dim, heads, factor, bias, ln_type)
+    mod.load_state_dict(sd)
+    return mod.to(DEV), sd
+
+
+def attn_of(mod):
+    return mod if isinstance(mod, N().Attention) else getattr(mod, "attn", None)
+
+
+def ffn_of(mod):
+    return mod if isinstance(mod, N().FeedForward) else getattr(mod, "ffn", None)
+
+
+def run_native(mod, x, cot, dtype, want_relu=False):
+    mod.zero_grad(set_to_none=True)
+    a, f = attn_of(mod), ffn_of(mod)
+    if a is not None:
+        a.record_scores = True
+    if f is not None:
+        f.record_masks = want_relu
+    xg = x.to(DEV).to(dtype).requires_grad_(True)
+    y = mod(xg)
+    y.backward(cot.to(DEV).to(dtype))
+    torch.cuda.synchronize()
+    grads = {k: p.grad.detach().clone() for k, p in mod.named_parameters()}
+    scores = a.scores.detach().clone() if a is not None else None
+    if want_relu:
+        return y.detach(), xg.grad.detach(), grads, scores, (None if f is None else [m.cpu() for m in f.relu_masks])
+    return y.detach(), xg.grad.detach(), grads, scores
+
+
+def run_oracle(kind, sd, heads, x, cot, masks=None, relu_masks=None):
+    ps = {k: v.double().requires_grad_(True) for k, v in sd.items()}
+    xr = x.double().requires_grad_(True)
+    S = None
+    if kind == "tksa":
+        y, S = D.tksa(xr, ps, heads, masks)
+    elif kind == "msfn":
+        y = D.msfn(xr, ps, relu_masks)
+    else:
+        y, S = D.stb(xr, ps, heads, masks, relu_masks)
+    y.backward(cot.double())
+    return y.detach(), xr.grad, {k: v.grad for k, v in ps.items()}, S
+
+
+@pytest.mark.parametrize("name", sorted(G.CASES))
+def test_native_modules_match_reference_fixtures(name):
+    """fp32 against the fixtures captured from the reference (its own fp64 top-k), the bar of test_modules_vs_reference_golden."""
+    kind, dim, heads, factor, bias, ln_type, bhw, seed = G.CASES[name]
+    mod, _ = build(kind, dim, heads, factor, bias, ln_type, seed)
+    x, cot = G.case_io(dim, bhw, seed)
+    y, dx, grads, _ = run_native(mod, x, cot, torch.float32)
+    gold = load(name)
+    check("y", y, gold, 1e-3, what=name + " ")
+    check("dx", dx, gold, 1e-3, what=name + " ")
+    for k, g in grads.items():
+        check("g." + k, g, gold, 1e-3, what=name + " ")
+
+
+# (kind, C, heads, factor, bias, LayerNorm, (B, H, W))
+PARITY = [
+    ("stb", 48, 1, 2.66, False, "WithBias", (2, 16, 16)),
+    ("stb", 96, 2, 2.66, True, "BiasFree", (2, 16, 16)),
+    ("stb", 192, 4, 2.66, False, "WithBias", (2, 8, 8)),
+    ("stb", 384, 8, 2.66, False, "BiasFree", (1, 8, 8)),
+    ("stb", 96, 1, 2.66, False, "WithBias", (2, 20, 20)),
+    ("stb", 48, 1, 2.66, True, "WithBias", (2, 9, 11)),
+    ("tksa", 48, 1, None, False, None, (2, 9, 11)),
+    ("tksa", 96, 1, None, True, None, (2, 20, 20)),
+    ("tksa", 384, 8, None, False, None, (2, 8, 8)),
+    ("msfn", 48, 1, 2.66, True, None, (2, 9, 11)),
+    ("msfn", 32, 1, 2.0, False, None, (2, 20, 20)),
+    ("msfn", 384, 1, 2.66, False, None, (1, 8, 8)),
+]
+
+
+def _parity(kind, dim, heads, factor, bias, ln_type, bhw, dtype, seed):
+    mod, sd = build(kind, dim, heads, factor, bias, ln_type, seed)
+    B, H, W = bhw
+    x, cot = seeded_input((B, dim, H, W), 3000 + seed), seeded_input((B, dim, H, W), 4000 + seed)
+    if dtype == torch.bfloat16:           # the oracle sees the same (rounded) input and cotangent
+        x, cot = x.to(dtype).float(), cot.to(dtype).float()
+    y, dx, grads, scores, relu = run_native(mod, x, cot, dtype, want_relu=True)
+    masks = D.topk_masks(scores.cpu().double()) if scores is not None else None
+    yr, dxr, gr, _ = run_oracle(kind, sd, heads, x, cot, masks, relu)
+    tol = 5e-5 if dtype == torch.float32 else 3e-2
+    # the four [1] mixing weights are held as one tensor [4], like every other gradient (max |delta| / max |ref| per tensor):
+    # each is a sum of signed terms over every (image, head, row, column), and alone one of them can cancel to near 0
+    mix = [k for k in grads if k.split(".")[-1] in ("attn1", "attn2", "attn3", "attn4")]
+    if mix:
+        grads["attn1..4"] = torch.cat([grads.pop(k) for k in mix])
+        gr["attn1..4"] = torch.cat([gr[k] for k in mix])
+    errs = {"y": rel(y, yr), "dx": rel(dx, dxr)}
+    errs.update({"g_" + k: rel(g, gr[k]) for k, g in grads.items()})
+    nerrs = {"dx": nrel(dx, dxr)}
+    nerrs.update({"g_" + k: nrel(g, gr[k]) for k, g in grads.items()})
+    worst = max(errs, key=errs.get)
+    nworst = max(nerrs, key=nerrs.get)
+    print(f"PARITY {kind} C{dim}h{heads} {bhw} bias={bias} {ln_type} {dtype}: max-rel {worst} {errs[worst]:.2e}; "
+          f"norm-rel {nworst} {nerrs[nworst]:.2e}; y {errs['y']:.2e}")
+    assert errs[worst] < tol, (worst, errs[worst], errs)
+    return errs
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16], ids=["fp32", "bf16"])
+@pytest.mark.parametrize("case", PARITY, ids=[f"{c[0]}_C{c[1]}h{c[2]}_{c[6][1]}x{c[6][2]}_{'bias' if c[4] else 'nobias'}"
+                                              f"{'_' + c[5] if c[5] else ''}" for c in PARITY])
+def test_parity_with_device_masks(case, dtype):
+    kind, dim, heads, factor, bias, ln_type, bhw = case
+    _parity(kind, dim, heads, factor, bias, ln_type, bhw, dtype, seed=dim + heads + bhw[1])
+
+
+def test_parity_at_training_size():
+    """bs 2, C = 48 at 256^2 (DRSformer's first level), fp32."""
+    _parity("stb", 48, 1, 2.66, False, "WithBias", (2, 256, 256), torch.float32, seed=7)
+
+
+def test_device_masks_differ_from_fp64_only_at_near_ties():
+    """In every row where the device's top-k set differs from the one the fp64 restatement picks on its own, the fp64 gap at
+    that top-k boundary is below 1e-4 max|S|: a kernel that mis-ranks fails here."""
+    for dim, heads, bhw, seed in ((96, 1, (2, 16, 16), 41), (48, 1, (2, 64, 64), 42), (192, 4, (2, 16, 16), 43)):
+        mod, sd = build("tksa", dim, heads, None, False, None, seed)
+        B, H, W = bhw
+        x, cot = seeded_input((B, dim, H, W), 5000 + seed), seeded_input((B, dim, H, W), 6000 + seed)
+        _, _, _, scores = run_native(mod, x, cot, torch.float32)
+        _, _, _, S64 = run_oracle("tksa", sd, heads, x, cot)
+        S64 = S64.detach()
+        assert rel(scores, S64) < 1e-5
+        dev = D.topk_masks(scores.cpu().double())
+        ref = D.topk_masks(S64)
+        srt = torch.sort(S64, dim=-1, descending=True).values
+        smax = float(S64.abs().max())
+        for k, md, mr in zip(D.topk_sizes(dim // heads), dev, ref):
+            diff = (md != mr).any(-1)
+            gap = srt[..., k - 1] - srt[..., k]
+            assert bool((gap[diff] < 1e-4 * smax).all()), (dim, k, float(gap[diff].max()))
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16], ids=["fp32", "bf16"])
+def test_backward_is_bitwise_reproducible(dtype):
+    mod, _ = build("stb", 96, 2, 2.66, True, "WithBias", 51)
+    x, cot = seeded_input((2, 96, 24, 24), 51), seeded_input((2, 96, 24, 24), 52)
+    y1, dx1, g1, _ = run_native(mod, x, cot, dtype)
+    y2, dx2, g2, _ = run_native(mod, x, cot, dtype)
+    assert torch.equal(y1, y2) and torch.equal(dx1, dx2)
+    for k in g1:
+        assert torch.equal(g1[k], g2[k]), k
+
+
+@pytest.mark.parametrize("kind", ["stb", "tksa", "msfn"])
+def test_no_grad_output_equals_grad_mode_output(kind):
+    mod, _ = build(kind, 48, 1, 2.66, False, "WithBias", 61)
+    x = seeded_input((2, 48, 16, 16), 61).to(DEV)
+    with torch.no_grad():
+        y0 = mod(x)
+    y1 = mod(x.clone().requires_grad_(True))
+    assert torch.equal(y0, y1.detach())
+
+
+def test_cpu_tensors_are_refused():
+    for kind in ("stb", "tksa", "msfn"):
+        mod, _ = build(kind, 48, 1, 2.66, False, "WithBias", 71)
+        with pytest.raises(RuntimeError, match="MI355X only"):
+            mod(torch.zeros(1, 48, 8, 8))
+
+
+def _stack(seed):
+    net = torch.nn.Sequential(N().TransformerBlock(48, 1, 2.66, False, "WithBias"),
+                              N().TransformerBlock(48, 1, 2.66, False, "WithBias"))
+    shapes = {f"{i}.{k}": v for i in range(2) for k, v in D.stb_shapes(48, 1, 2.66, False, "WithBias").items()}
+    sd = D.make_state(shapes, seed)
+    net.load_state_dict(sd)
+    return net, sd
+
+
+def test_training_steps_follow_the_oracle_trajectory():
+    """Three FlatTrainer steps (main_grad accumulation, deferred sums, fused AdamW) of a two-STB stack against the fp64 oracle
+    plus torch.optim.AdamW, fp32.  The oracle uses each step's device top-k and ReLU masks (both are discontinuous)."""
+    from image_restoration_amd.trainer import FlatTrainer
+    net, sd0 = _stack(81)
+    x, tgt = seeded_input((2, 48, 32, 32), 81), seeded_input((2, 48, 32, 32), 82)
+    lr = 1e-3
+    net = net.to(DEV).train()
+    for blk in net:
+        blk.attn.record_scores = True
+        blk.ffn.record_masks = True
+    tr = FlatTrainer(net, lr=lr, weight_decay=0.01)
+    losses, masks = [], []
+    try:
+        xd, td = x.to(DEV), tgt.to(DEV)
+        for _ in range(3):
+            tr.zero_grad()
+            loss = (net(xd) - td).abs().mean()
+            masks.append([(D.topk_masks(blk.attn.scores.cpu().double()), [m.cpu() for m in blk.ffn.relu_masks]) for blk in net])
+            loss.backward()
+            tr.reduce_gradients()
+            tr.optimizer_step()
+            losses.append(float(loss.detach()))
+        got = {k: v.detach().cpu() for k, v in net.state_dict().items()}
+    finally:
+        tr.close()
+    ps = {k: v.double().clone().requires_grad_(True) for k, v in sd0.items()}
+    opt = torch.optim.AdamW(list(ps.values()), lr=lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.01)
+    for step in range(3):
+        opt.zero_grad()
+        h = x.double()
+        for i in range(2):
+            h, _ = D.stb(h, D.sub(ps, f"{i}."), 1, *masks[step][i])
+        loss = (h - tgt.double()).abs().mean()
+        loss.backward()
+        opt.step()
+        assert abs(losses[step] - float(loss)) < 1e-4 * float(loss), (step, losses[step], float(loss))
+    for k, v in ps.items():
+        w0 = sd0[k].double()
+        a, r = got[k].double(), v.detach()
+        d = (a - r).abs()
+        ua, ur = (a - w0).flatten(), (r - w0).flatten()
+        cos = float((ua @ ur) / (ua.norm() * ur.norm()).clamp_min(1e-30))
+        assert cos >= 0.9995, (k, cos)
+        assert float(d.mean()) <= 0.02 * lr and float(d.max()) <= 2.0 * lr, (k, float(d.mean()) / lr, float(d.max()) / lr)
+
+
+CHILD = textwrap.dedent(r'''
+    import os, sys, torch
+    sys.path.insert(0, os.getcwd())
+    sys.path.insert(0, os.path.join(os.getcwd(), "tests"))
+    import drs_ref as D
+    from image_restoration_amd import drsformer as N
+    from image_restoration_amd.trainer import FlatTrainer
+    dev = "cuda"
+    shapes = {f"{i}.{k}": v for i in range(2) for k, v in D.stb_shapes(48, 1, 2.66, False, "WithBias").items()}
+    sd = D.make_state(shapes, 91)
+    g = torch.Generator().manual_seed(91)
+    x = torch.randn(2, 48, 32, 32, generator=g).to(dev).to(torch.bfloat16)
+    t = torch.randn(2, 48, 32, 32, generator=g).to(dev).to(torch.bfloat16)
+
+    def make():
+        net = torch.nn.Sequential(N.TransformerBlock(48, 1, 2.66, False, "WithBias"),
+                                  N.TransformerBlock(48, 1, 2.66, False, "WithBias"))
+        net.load_state_dict(sd)
+        net = net.to(dev).train()
+        tr = FlatTrainer(net, lr=1e-3)
+        losses = []
+        def step():
+            tr.zero_grad()
+            loss = (net(x).float() - t.float()).abs().mean()
+            loss.backward()
+            tr.reduce_gradients()
+            tr.optimizer_step(use_dev_scalars=True)
+            losses.append(loss.detach())
+        return tr, step, losses
+
+    tr_e, step_e, loss_e = make()
+    for _ in range(5):
+        tr_e.set_step_scalars(tr_e.step_count + 1)
+        step_e()
+    torch.cuda.synchronize()
+    tr_c, step_c, loss_c = make()
+    graph = tr_c.capture_step(step_c, warmup=2)
+    for _ in range(3):
+        tr_c.replay_step(graph)
+    torch.cuda.synchronize()
+    pe, pc = tr_e.flat_p.float(), tr_c.flat_p.float()
+    err = float((pe - pc).abs().max() / pe.abs().max())
+    le = [float(v) for v in loss_e]
+    lc = [float(v) for v in loss_c]
+    print("losses", le, lc[:2] + [float(lc[2])], "param err", err)
+    assert torch.isfinite(pc).all() and err < 1e-5, err
+    assert all(abs(a - b) <= 1e-5 * abs(a) for a, b in zip(le[:2], lc[:2])), (le, lc)
+    tr_e.close(); tr_c.close()
+    print("CAPTURE_OK")
+''')
+
+
+def test_captured_training_step_replays_equal_to_eager_steps(tmp_path):
+    """Two STBs, bf16 activations: 2 warm-up steps + a captured step replayed 3 times against 5 eager steps from the same
+    weights, in a fresh child process with a timeout (a failed capture takes its process down)."""
+    script = tmp_path / "child.py"
+    script.write_text(CHILD)
+    env = dict(os.environ)
+    env.pop("MI_DEFER_MB", None)
+    res = subprocess.run([sys.executable, str(script)], cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT,
+                         text=True, timeout=600)
+    assert res.returncode == 0 and "CAPTURE_OK" in res.stdout, res.stdout[-3000:]
