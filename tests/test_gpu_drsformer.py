@@ -128,6 +128,27 @@ PARITY = [
     ("msfn", 48, 1, 2.66, True, None, (2, 9, 11)),
     ("msfn", 32, 1, 2.0, False, None, (2, 20, 20)),
     ("msfn", 384, 1, 2.66, False, None, (1, 8, 8)),
+    # MSFN / STB tile seams (32 x 8 tiles) and uneven backward walks (splits = min(ntiles, 16) workgroups per plane, each walking
+    # every splits-th tile):
+    # tiles_x 4 (last column 4 wide) x 5 rows (last 5 tall) = 20 tiles; splits 16: 4 workgroups walk 2 tiles, 12 walk 1; B = 3
+    ("msfn", 48, 1, 2.66, False, None, (3, 37, 100)),
+    # tiles_x 3 (last column 1 wide) x 9 rows = 27 tiles; splits 16: 11 walk 2, 5 walk 1
+    ("msfn", 32, 1, 2.0, True, None, (2, 72, 65)),
+    # one-pixel planes, every halo row (column) outside: tiles_x 3 (last 6 wide) x 1 row = 3 tiles; splits 3, each walks 1
+    ("msfn", 48, 1, 2.66, True, None, (2, 1, 70)),
+    # tiles_x 1 (1 wide) x 9 rows (last 6 tall) = 9 tiles; splits 9, each walks 1
+    ("msfn", 48, 1, 2.66, True, None, (2, 70, 1)),
+    # tiles_x 3 (last 6 wide) x 5 rows = 15 tiles; splits 15, each walks 1; B = 3
+    ("stb", 48, 1, 2.66, False, "WithBias", (3, 40, 70)),
+    # tiles_x 4 (last 1 wide) x 5 rows (last 1 tall) = 20 tiles; splits 16: 4 walk 2, 12 walk 1
+    ("stb", 96, 2, 2.66, True, "BiasFree", (2, 33, 97)),
+    # every TKSA head width c = C / heads (CT = ceil(c / 16) column slots per lane, compiled for 1, 2, 3, 4, 6, 8)
+    ("tksa", 16, 2, None, False, None, (2, 12, 20)),      # c 8, CT 1
+    ("tksa", 40, 2, None, True, None, (2, 12, 20)),       # c 20, CT 2
+    ("tksa", 64, 1, None, False, None, (2, 12, 20)),      # c 64, CT 4
+    ("tksa", 160, 2, None, True, None, (2, 12, 20)),      # c 80, CT 5 -> 6
+    ("tksa", 100, 1, None, False, None, (2, 12, 20)),     # c 100, CT 8: first c whose backward needs > 64 KiB of LDS (65 760 B)
+    ("tksa", 240, 2, None, True, None, (2, 12, 20)),      # c 120, CT 8: the maximum, 83 440 B of LDS in the backward
 ]
 
 
@@ -339,3 +360,218 @@ def test_captured_training_step_replays_equal_to_eager_steps(tmp_path):
     res = subprocess.run([sys.executable, str(script)], cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT,
                          text=True, timeout=600)
     assert res.returncode == 0 and "CAPTURE_OK" in res.stdout, res.stdout[-3000:]
+
+
+# ---------------------------------------------------------------- tile seams: no_grad and bf16 reproducibility
+SEAM = (3, 40, 70)     # tiles_x 3 (last column 6 wide) x 5 rows = 15 tiles per plane
+
+
+@pytest.mark.parametrize("kind", ["stb", "tksa", "msfn"])
+def test_no_grad_output_equals_grad_mode_output_at_seams(kind):
+    """The no-grad forward runs in the inference workspace (nothing saved); at a seam shape it gives the training output bitwise."""
+    mod, _ = build(kind, 48, 1, 2.66, False, "WithBias", 62)
+    x = seeded_input((SEAM[0], 48) + SEAM[1:], 62).to(DEV)
+    with torch.no_grad():
+        y0 = mod(x)
+    y1 = mod(x.clone().requires_grad_(True))
+    assert torch.equal(y0, y1.detach())
+
+
+def test_backward_is_bitwise_reproducible_at_seams_bf16():
+    mod, _ = build("stb", 48, 1, 2.66, False, "WithBias", 53)
+    x, cot = seeded_input((SEAM[0], 48) + SEAM[1:], 53), seeded_input((SEAM[0], 48) + SEAM[1:], 54)
+    y1, dx1, g1, _ = run_native(mod, x, cot, torch.bfloat16)
+    y2, dx2, g2, _ = run_native(mod, x, cot, torch.bfloat16)
+    assert torch.equal(y1, y2) and torch.equal(dx1, dx2)
+    for k in g1:
+        assert torch.equal(g1[k], g2[k]), k
+
+
+def test_unsupported_head_widths_are_refused():
+    """c = C / heads above 120, and c = 1 (top-k size k1 = int(1 / 2) = 0), fail the library's shape check before any launch."""
+    for dim, heads in ((121, 1), (2, 2)):
+        mod = N().Attention(dim, heads, False).to(DEV)
+        x = torch.zeros(1, dim, 4, 4, device=DEV)
+        with pytest.raises(RuntimeError, match=r"tksa: (channels per head 121 unsupported|top-k size k1=0)"):
+            mod(x)
+    torch.cuda.synchronize()
+
+
+# ---------------------------------------------------------------- exact ties in the top-k
+def _tied_state(sd, dim, heads, prefix=""):
+    """k channels in groups of identical copies (qkv rows dim .. 2 dim - 1, their depthwise kernels and biases): head 0 in groups
+    of 4, head 1 all c alike.  Every row of S then holds exactly equal entries, and in head 0 the boundary of k4 falls inside a
+    group (c = 48: k = 24, 32, 36, 38)."""
+    c = dim // heads
+    src = list(range(3 * dim))
+    for h, grp in ((0, 4), (1, c)):
+        for j in range(c):
+            src[dim + h * c + j] = dim + h * c + (j // grp) * grp
+    out = dict(sd)
+    for key in ("qkv.weight", "qkv.bias", "qkv_dwconv.weight", "qkv_dwconv.bias"):
+        if prefix + key in out:
+            out[prefix + key] = out[prefix + key][src].clone()
+    return out
+
+
+def _masks_higher_column_first(S):
+    """The opposite tie rule: among equal entries the higher column goes first."""
+    return [m.flip(-1) for m in D.topk_masks(S.flip(-1))]
+
+
+def _grad_errs(grads, gr):
+    """max |delta| / max |ref| per gradient, attn1..4 pooled into one tensor as in _parity."""
+    grads, gr = dict(grads), dict(gr)
+    mix = [k for k in grads if k.split(".")[-1] in ("attn1", "attn2", "attn3", "attn4")]
+    if mix:
+        grads["attn1..4"] = torch.cat([grads.pop(k) for k in mix])
+        gr["attn1..4"] = torch.cat([gr[k] for k in mix])
+    return {"g_" + k: rel(g, gr[k]) for k, g in grads.items()}
+
+
+def _errs(y, dx, grads, yr, dxr, gr):
+    return {"y": rel(y, yr), "dx": rel(dx, dxr), **_grad_errs(grads, gr)}
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16], ids=["fp32", "bf16"])
+@pytest.mark.parametrize("kind", ["tksa", "stb"])
+def test_exact_ties_go_to_the_lower_column(kind, dtype):
+    """C = 96, 2 heads (c = 48) with duplicated k channels: the device's S is bitwise equal across each group of copies, parity
+    holds with the lower-column-first masks, and the opposite rule would give a far different result (the test is not vacuous)."""
+    dim, heads, c, bhw, seed = 96, 2, 48, (2, 12, 20), 121
+    mod, sd = build(kind, dim, heads, 2.66, True, "WithBias", seed)
+    sd = _tied_state(sd, dim, heads, "" if kind == "tksa" else "attn.")
+    mod.load_state_dict(sd)
+    B, H, W = bhw
+    x, cot = seeded_input((B, dim, H, W), 3000 + seed), seeded_input((B, dim, H, W), 4000 + seed)
+    if dtype == torch.bfloat16:
+        x, cot = x.to(dtype).float(), cot.to(dtype).float()
+    y, dx, grads, scores, relu = run_native(mod, x, cot, dtype, want_relu=True)
+    scores = scores.cpu()
+    assert torch.equal(scores[:, 0], scores[:, 0][..., [(j // 4) * 4 for j in range(c)]])
+    assert torch.equal(scores[:, 1], scores[:, 1][..., [0] * c])
+    S = scores.double()
+    errs = _errs(y, dx, grads, *run_oracle(kind, sd, heads, x, cot, D.topk_masks(S), relu)[:3])
+    opp = _errs(y, dx, grads, *run_oracle(kind, sd, heads, x, cot, _masks_higher_column_first(S), relu)[:3])
+    tol = 5e-5 if dtype == torch.float32 else 3e-2
+    worst, oworst = max(errs, key=errs.get), max(opp, key=opp.get)
+    print(f"PARITY exact ties {kind} C{dim}h{heads} {bhw} {dtype}: max-rel {worst} {errs[worst]:.2e}; "
+          f"opposite rule {oworst} {opp[oworst]:.2e}")
+    assert errs[worst] < tol, (worst, errs[worst], errs)
+    assert opp[oworst] > 10 * tol, (oworst, opp[oworst])
+
+
+# ---------------------------------------------------------------- gradient accumulation
+def _ops_backward(kind, mod, x):
+    """fwd once through ops (saved blob kept); returns bwd(cot, grads, accumulate) -> dx."""
+    from image_restoration_amd import ops
+    params = mod._params()
+    if kind == "tksa":
+        heads, topk = mod.num_heads, mod.topk(x.shape[1])
+        _, saved = ops.tksa_fwd(x, None, params, heads, topk, True)
+        return params, lambda cot, grads, acc: ops.tksa_bwd(x, cot, params, heads, topk, saved, grads, acc)
+    _, saved = ops.msfn_fwd(x, None, params, True)
+    return params, lambda cot, grads, acc: ops.msfn_bwd(x, cot, params, saved, grads, acc)
+
+
+@pytest.mark.parametrize("kind", ["tksa", "msfn"])
+def test_ops_backward_accumulates_onto_existing_gradients(kind):
+    """accumulate=True adds onto what the gradient buffers hold: G0 + g_a + g_b after two calls, where g_a and g_b are the
+    accumulate=False results.  Seam shape with uneven walks (msfn: 20 tiles, splits 16), biases present."""
+    bhw = (3, 37, 100)
+    mod, _ = build(kind, 48, 1, 2.66, True, None, 131)
+    shape = (bhw[0], 48) + bhw[1:]
+    x = seeded_input(shape, 131).to(DEV)
+    ca, cb = seeded_input(shape, 132).to(DEV), seeded_input(shape, 133).to(DEV)
+    params, bwd = _ops_backward(kind, mod, x)
+    ga, gb = ([None if p is None else torch.empty_like(p) for p in params] for _ in range(2))
+    dxa = bwd(ca, ga, False)
+    dxb = bwd(cb, gb, False)
+    g = torch.Generator().manual_seed(134)
+    g0 = [None if p is None else (torch.randn(p.shape, generator=g) * float(a.abs().max())).to(DEV) for p, a in zip(params, ga)]
+    acc = [None if t is None else t.clone() for t in g0]
+    dxa2 = bwd(ca, acc, True)
+    dxb2 = bwd(cb, acc, True)
+    torch.cuda.synchronize()
+    assert torch.equal(dxa, dxa2) and torch.equal(dxb, dxb2)
+    n = 0
+    for i, t in enumerate(acc):
+        if t is None:
+            continue
+        ref = g0[i].double() + ga[i].double() + gb[i].double()
+        e = rel(t, ref)
+        assert e <= 1e-6, (kind, i, e)
+        assert rel(g0[i], ref) > 1e-3, (kind, i)      # g_a + g_b is not lost in G0's rounding
+        n += 1
+    assert n == sum(p is not None for p in params)
+
+
+def test_micro_batches_accumulate_under_no_sync(monkeypatch):
+    """Two STBs (fp32) through FlatTrainer: two micro-batches under no_sync() and one outside, into main_grad with accumulate on.
+    With the deferred sums on, two runs are bitwise equal and within 1e-5 of a run with the deferral off; the gradient is the
+    fp64 oracle's sum over the three micro-batches (each with its own device top-k and ReLU masks)."""
+    from image_restoration_amd import ops
+    from image_restoration_amd.trainer import FlatTrainer
+    shape = (SEAM[0], 48) + SEAM[1:]
+    xs = [seeded_input(shape, 141 + i) for i in range(3)]
+    cots = [seeded_input(shape, 151 + i) for i in range(3)]
+
+    def run(defer_mb):
+        monkeypatch.setenv("MI_DEFER_MB", str(defer_mb))
+        net, sd0 = _stack(141)
+        net = net.to(DEV).train()
+        for blk in net:
+            blk.attn.record_scores = True
+            blk.ffn.record_masks = True
+        tr = FlatTrainer(net, lr=1e-3)
+        masks = []
+        try:
+            tr.zero_grad()
+
+            def micro(i):
+                y = net(xs[i].to(DEV))
+                masks.append([(D.topk_masks(blk.attn.scores.cpu().double()), [m.cpu() for m in blk.ffn.relu_masks]) for blk in net])
+                y.backward(cots[i].to(DEV))
+            with tr.no_sync():
+                micro(0)
+                micro(1)
+            micro(2)
+            if defer_mb > 0:
+                assert ops.deferred_pending() > 0
+            tr.reduce_gradients()
+            assert ops.deferred_pending() == 0
+            got = {k: p.main_grad.detach().cpu().clone() for k, p in net.named_parameters()}
+            return tr.flat_g.clone(), got, masks, sd0
+        finally:
+            tr.close()
+
+    g1, got, masks, sd0 = run(256)
+    g2, _, _, _ = run(256)
+    g0, _, _, _ = run(0)
+    assert torch.equal(g1, g2)
+    assert rel(g1, g0) < 1e-5, rel(g1, g0)
+    ps = {k: v.double().requires_grad_(True) for k, v in sd0.items()}
+    for i in range(3):
+        h = xs[i].double()
+        for b in range(2):
+            h, _ = D.stb(h, D.sub(ps, f"{b}."), 1, *masks[i][b])
+        h.backward(cots[i].double())
+    gr = {k: v.grad for k, v in ps.items()}
+    errs = {}
+    for b in range(2):      # attn1..4 pooled per block
+        errs.update({f"{b}.{k}": e for k, e in _grad_errs(D.sub(got, f"{b}."), D.sub(gr, f"{b}.")).items()})
+    worst = max(errs, key=errs.get)
+    print(f"PARITY micro-batches x3 two-STB {SEAM}: max-rel {worst} {errs[worst]:.2e}")
+    assert errs[worst] < 5e-5, (worst, errs[worst], errs)
+
+
+# ---------------------------------------------------------------- the benchmarked level sizes (tools/bench_drs.py), batch 1
+LEVELS = [("L2", 96, 2, 128, torch.bfloat16), ("L3", 192, 4, 64, torch.bfloat16), ("L4", 384, 8, 32, torch.bfloat16),
+          ("dec-L1", 96, 1, 256, torch.bfloat16), ("dec-L1", 96, 1, 256, torch.float32)]
+
+
+@pytest.mark.parametrize("level", LEVELS, ids=[f"{lv[0]}_{'bf16' if lv[4] == torch.bfloat16 else 'fp32'}" for lv in LEVELS])
+def test_parity_at_benchmarked_level_sizes(level):
+    """DRSformer base's STB (factor 2.66, no bias, WithBias) at the plane sizes of the measured speed-ups, batch 1."""
+    _, dim, heads, hw, dtype = level
+    _parity("stb", dim, heads, 2.66, False, "WithBias", (1, hw, hw), dtype, seed=dim + heads + hw)
