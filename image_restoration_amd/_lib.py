@@ -134,6 +134,30 @@ class MsfnGrads(C.Structure):
     _fields_ = [(n, fp) for n in MSFN_PARAM_NAMES] + [("accumulate", C.c_int)]
 
 
+class MefcShape(C.Structure):
+    _fields_ = [("B", C.c_int), ("C", C.c_int), ("H", C.c_int), ("W", C.c_int), ("dtype", C.c_int), ("steps", C.c_int)]
+
+
+MEFC_STEP_FIELDS = (("sep_dw1", 4), ("sep_pw1", 4), ("sep_dw2", 4), ("sep_pw2", 4), ("dil_dw", 3), ("dil_pw", 3), ("out_w", 1))
+
+
+class MefcStepParams(C.Structure):
+    _fields_ = [(n, fp * k) if k > 1 else (n, fp) for n, k in MEFC_STEP_FIELDS]
+
+
+class MefcStepGrads(C.Structure):
+    _fields_ = [(n, fp * k) if k > 1 else (n, fp) for n, k in MEFC_STEP_FIELDS]
+
+
+class MefcParams(C.Structure):
+    _fields_ = [(n, fp) for n in ("fc1_w", "fc1_b", "fc2_w", "fc2_b", "pre_w")] + [("step", C.POINTER(MefcStepParams))]
+
+
+class MefcGrads(C.Structure):
+    _fields_ = [(n, fp) for n in ("fc1_w", "fc1_b", "fc2_w", "fc2_b", "pre_w")] + [("step", C.POINTER(MefcStepGrads)),
+                                                                                     ("accumulate", C.c_int)]
+
+
 # symbol -> (restype, argtypes); this table is also what tests/test_cabi.py checks against the header
 SIGNATURES = {
     "mi_version": (C.c_int, []),
@@ -233,6 +257,10 @@ SIGNATURES = {
     "mi_msfn_workspace": (C.c_size_t, [C.POINTER(MsfnShape)]),
     "mi_msfn_fwd": (C.c_int, [C.POINTER(MsfnShape), C.POINTER(MsfnParams), vp, vp, vp, vp, vp, vp]),
     "mi_msfn_bwd": (C.c_int, [C.POINTER(MsfnShape), C.POINTER(MsfnParams), vp, vp, vp, C.POINTER(MsfnGrads), vp, vp, vp]),
+    "mi_mefc_saved_bytes": (C.c_size_t, [C.POINTER(MefcShape)]),
+    "mi_mefc_workspace": (C.c_size_t, [C.POINTER(MefcShape)]),
+    "mi_mefc_fwd": (C.c_int, [C.POINTER(MefcShape), C.POINTER(MefcParams), vp, vp, vp, vp, vp]),
+    "mi_mefc_bwd": (C.c_int, [C.POINTER(MefcShape), C.POINTER(MefcParams), vp, vp, vp, vp, C.POINTER(MefcGrads), vp, vp, vp]),
     "mi_gdfn_fused_ok": (C.c_int, [C.POINTER(GdfnFusedShape)]),
     "mi_gdfn_fused_pack_bytes": (C.c_size_t, [C.POINTER(GdfnFusedShape)]),
     "mi_gdfn_fused_pack": (C.c_int, [C.POINTER(GdfnFusedShape), fp, fp, C.POINTER(GdfnParams), vp, vp]),

@@ -5,6 +5,8 @@ RESTORMER_TINY   the survey's pin of "Restormer-tiny" (configs[0]): dim 16, two 
 MOCEIR_BASE      MoCE-IR-main/src/options.py:70-84 (`--model MoCE_IR`) as PLTrainModel passes them
                  (MoCE-IR-main/src/train.py:33-47; 25.35 M parameters): configs[3]
 MOCEIR_S         options.py:55-68 (`--model MoCE_IR_S`, dim 32)
+DRSFORMER_BASE   DRSformer_arch.py:389-397 constructor defaults (the U-Net of sparse transformer blocks plus two MEFCs)
+DRSFORMER_TINY   dim 16, one block per level: tests and rehearsals
 """
 RESTORMER_BASE = dict(dim=48, num_blocks=[4, 6, 6, 8], num_refinement_blocks=4, heads=[1, 2, 4, 8], ffn_expansion_factor=2.66,
                       bias=False, LayerNorm_type="WithBias", inp_channels=3, out_channels=3)
@@ -18,6 +20,9 @@ MOCEIR_S = dict(MOCEIR_BASE, dim=32)
 MOCEIR_TINY = dict(dim=16, levels=4, heads=[1, 2, 4, 8], num_blocks=[1, 1, 1, 2], num_dec_blocks=[1, 1, 1],
                    num_refinement_blocks=1, rank=2, num_experts=4, depth_type="constant", stage_depth=[1, 1, 1],
                    rank_type="spread", topk=1, with_complexity=True, complexity_scale="max")
+DRSFORMER_BASE = dict(inp_channels=3, out_channels=3, dim=48, num_blocks=[4, 6, 6, 8], heads=[1, 2, 4, 8],
+                      ffn_expansion_factor=2.66, bias=False, LayerNorm_type="WithBias")
+DRSFORMER_TINY = dict(DRSFORMER_BASE, dim=16, num_blocks=[1, 1, 1, 1])
 # AdaIR-main/net/model.py:380-390 constructor defaults (the Restormer U-Net + three FreModules; AdaIR-main/train.py builds it bare)
 ADAIR_BASE = dict(dim=48, num_blocks=[4, 6, 6, 8], num_refinement_blocks=4, heads=[1, 2, 4, 8], ffn_expansion_factor=2.66,
                   bias=False, LayerNorm_type="WithBias", decoder=True)

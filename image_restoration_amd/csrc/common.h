@@ -304,7 +304,9 @@ enum KernelId {
   K_LN_FWD = 0, K_LN_BWD, K_DW_FWD, K_DW_GATE_FWD, K_DW_BWD_DATA, K_DW_GATE_BWD_DATA, K_DW_WGRAD, K_PW_GEMM, K_GRAM,
   K_GRAM_REDUCE, K_ATTN_FOLD, K_ATTN_BWD_SMALL, K_REDUCE_ROWS, K_CHAN_SUM, K_ADAMW, K_CAST, K_L1, K_PW_PACK, K_GAP,
   K_IM2COL, K_COL2IM, K_GDFN_FUSED_FWD, K_GDFN_FUSED_BWD, K_MDTA_FUSED_A, K_FUSED_PACK, K_MOE_ROUTE, K_CIRCCONV, K_EWISE, K_CONV3X3, K_GRAM_QK, K_PW_AV, K_BWD_TAIL, K_BWD_TAIL_FIN, K_ADAIR, K_SUMSQ, K_ADAMW_CLIP, K_ADAMW_EMA,
-  K_TKSA_ATTN, K_TKSA_FOLD, K_TKSA_BWD, K_TKSA_DWO, K_MSFN_S1, K_MSFN_S2, K_MSFN_S1_BWD, K_MSFN_S2_BWD, K_COUNT
+  K_TKSA_ATTN, K_TKSA_FOLD, K_TKSA_BWD, K_TKSA_DWO, K_MSFN_S1, K_MSFN_S2, K_MSFN_S1_BWD, K_MSFN_S2_BWD,
+  K_MEFC_STA, K_MEFC_STB, K_MEFC_STA_BWD, K_MEFC_STB_BWD, K_MEFC_WGRAD, K_MEFC_FOLD, K_MEFC_FOLD_BWD, K_MEFC_HEAD, K_MEFC_HEAD_BWD,
+  K_MEFC_EW, K_COUNT
 };
 // Brackets one kernel launch with two events on ITS stream and books its algorithmic bytes / flops.
 struct ProfScope {

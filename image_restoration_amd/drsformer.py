@@ -1,4 +1,4 @@
-"""Drop-in replacements for the transformer blocks of the reference's ``DRSformer_arch.py``.
+"""Drop-in replacements for the reference's ``DRSformer_arch.py``: its transformer blocks, its MEFC and the whole network.
 
 ``Attention`` (TKSA, top-k sparse attention, :101-171), ``FeedForward`` (MSFN, mixed-scale FFN, :62-98) and
 ``TransformerBlock`` (STB, :174-187) keep the reference's class names, constructor arguments, parameter names and shapes
@@ -12,6 +12,13 @@ masks are ranked on the device from the fp32 scores, so nothing syncs with the h
 ``Attention.record_scores = True`` keeps the last forward's scores (``Attention.scores``, [B, heads, c, c] fp32): the S the
 masks were ranked from, for tests and inspection.  Likewise ``FeedForward.record_masks = True`` keeps the last training
 forward's ReLU decisions (``FeedForward.relu_masks``: a > 0, b > 0, y > 0 of the saved planes, [B, 2h, H, W] bool).
+
+The Mixture of Experts Feature Compensator (``subnet``, :328-354, with ``OALayer``, ``GroupOLs``, ``OperationLayer``,
+``SepConv``, ``DilConv``) runs one layer pair (routing head + GroupOLs) as one autograd node on ``mi_mefc_*``; its submodules are
+parameter containers whose own ``forward`` raises (the pair is computed whole).  ``subnet.record_masks = True`` keeps the last
+training forward's ReLU decisions and routing weights (``subnet.relu_masks``: one dict per layer pair, see ``_mefc_record``).
+``DRSformer`` (:388-480) assembles the U-Net from these, the STB and Restormer's native glue (patch embed, resampling, the
+concat-free ``reduce_chan`` 1x1s, the output conv with its ``+ inp_img`` residual).
 """
 from __future__ import annotations
 
@@ -19,11 +26,13 @@ import torch
 import torch.nn as nn
 
 from . import ops
-from .restormer import LayerNorm, _apply, _fresh_grads, _grad_mode, _main_grads
+from .restormer import (Downsample, LayerNorm, OverlapPatchEmbed, Upsample, _apply, _conv1x1_module, _conv2d, _fresh_grads,
+                        _grad_mode, _main_grads, _up_cat)
 
 Tensor = torch.Tensor
 
-__all__ = ["Attention", "FeedForward", "TransformerBlock", "LayerNorm"]
+__all__ = ["Attention", "FeedForward", "TransformerBlock", "LayerNorm", "SepConv", "DilConv", "OperationLayer", "GroupOLs",
+           "OALayer", "subnet", "OverlapPatchEmbed", "Downsample", "Upsample", "DRSformer", "Operations"]
 
 
 def _unpack(ctx, rest):
@@ -203,3 +212,231 @@ class TransformerBlock(nn.Module):
     def forward(self, x):
         params = self.norm1._params() + self.attn._params() + self.norm2._params() + self.ffn._params()
         return _apply(_StbFn, x, self, *params)
+
+
+# ====================================================================================== MEFC (DRSformer_arch.py:189-354)
+Operations = ['sep_conv_1x1', 'sep_conv_3x3', 'sep_conv_5x5', 'sep_conv_7x7', 'dil_conv_3x3', 'dil_conv_5x5', 'dil_conv_7x7',
+              'avg_pool_3x3']
+
+
+def _whole_pair_only(name):
+    raise NotImplementedError(f"image_restoration_amd: {name} runs inside subnet only (one mi_mefc_* call per OALayer + GroupOLs "
+                              "pair); its modules hold the parameters")
+
+
+class SepConv(nn.Module):
+    """dw k x k -> 1x1 -> ReLU -> dw k x k -> 1x1 (:284-296); parameter container."""
+
+    def __init__(self, C_in, C_out, kernel_size, stride, padding, affine=True):
+        super().__init__()
+        self.op = nn.Sequential(
+            nn.Conv2d(C_in, C_in, kernel_size=kernel_size, stride=stride, padding=padding, groups=C_in, bias=False),
+            nn.Conv2d(C_in, C_in, kernel_size=1, padding=0, bias=False),
+            nn.ReLU(inplace=False),
+            nn.Conv2d(C_in, C_in, kernel_size=kernel_size, stride=1, padding=padding, groups=C_in, bias=False),
+            nn.Conv2d(C_in, C_out, kernel_size=1, padding=0, bias=False),)
+
+    def forward(self, x):
+        _whole_pair_only("SepConv")
+
+
+class DilConv(nn.Module):
+    """dw k x k with dilation -> 1x1 (:259-267); parameter container."""
+
+    def __init__(self, C_in, C_out, kernel_size, stride, padding, dilation, affine=True):
+        super().__init__()
+        self.op = nn.Sequential(
+            nn.Conv2d(C_in, C_in, kernel_size=kernel_size, stride=stride, padding=padding, dilation=dilation, groups=C_in,
+                      bias=False),
+            nn.Conv2d(C_in, C_out, kernel_size=1, padding=0, bias=False),)
+
+    def forward(self, x):
+        _whole_pair_only("DilConv")
+
+
+class ReLUConv(nn.Module):
+    """1x1 conv -> ReLU (:250-257): GroupOLs.preprocess."""
+
+    def __init__(self, C_in, C_out, kernel_size, stride, padding, affine=True):
+        super().__init__()
+        self.op = nn.Sequential(nn.Conv2d(C_in, C_out, kernel_size, stride=stride, padding=padding, bias=False),
+                                nn.ReLU(inplace=False))
+
+    def forward(self, x):
+        _whole_pair_only("ReLUConv")
+
+
+def _op(name, C, stride):
+    k = int(name[-1])
+    if name.startswith("sep"):
+        return SepConv(C, C, k, stride, k // 2, affine=False)
+    if name.startswith("dil"):
+        return DilConv(C, C, k, stride, k - 1, 2, affine=False)
+    return nn.AvgPool2d(3, stride=stride, padding=1, count_include_pad=False)
+
+
+class OperationLayer(nn.Module):
+    """The eight weighted operations and the 8C -> C projection (:189-204)."""
+
+    def __init__(self, C, stride):
+        super().__init__()
+        if stride != 1:
+            raise NotImplementedError("image_restoration_amd: OperationLayer is built for stride 1 (DRSformer's only use)")
+        self._ops = nn.ModuleList([_op(o, C, stride) for o in Operations])
+        self._out = nn.Sequential(nn.Conv2d(C * len(Operations), C, 1, padding=0, bias=False), nn.ReLU())
+
+    def _params(self):
+        ps = []
+        for i in range(4):
+            s = self._ops[i].op
+            ps += [s[0].weight, s[1].weight, s[3].weight, s[4].weight]
+        for i in range(4, 7):
+            d = self._ops[i].op
+            ps += [d[0].weight, d[1].weight]
+        return ps + [self._out[0].weight]
+
+    def forward(self, x, weights):
+        _whole_pair_only("OperationLayer")
+
+
+class GroupOLs(nn.Module):
+    """preprocess, then ``steps`` residual OperationLayers (:206-225)."""
+
+    def __init__(self, steps, C):
+        super().__init__()
+        self.preprocess = ReLUConv(C, C, 1, 1, 0, affine=False)
+        self._steps = steps
+        self._ops = nn.ModuleList([OperationLayer(C, 1) for _ in range(steps)])
+        self.relu = nn.ReLU()
+
+    def forward(self, s0, weights):
+        _whole_pair_only("GroupOLs")
+
+
+class OALayer(nn.Module):
+    """Routing head: global average pool, Linear -> ReLU -> Linear, viewed [B, k, num_ops] (:227-247)."""
+
+    def __init__(self, channel, k, num_ops):
+        super().__init__()
+        self.k = k
+        self.num_ops = num_ops
+        self.output = k * num_ops
+        self.avg_pool = nn.AdaptiveAvgPool2d(1)
+        self.ca_fc = nn.Sequential(nn.Linear(channel, self.output * 2), nn.ReLU(), nn.Linear(self.output * 2, self.k * self.num_ops))
+
+    def forward(self, x):
+        _whole_pair_only("OALayer")
+
+
+def _mefc_record(owner, x, saved, out, steps) -> None:
+    """ReLU decisions and routing weights of one training forward of a layer pair: pre0 (preprocess, s_0 > 0), h (routing hidden
+    layer), per step u (pw1 outputs U > 0, [B, 4C, H, W]), pre (out projection > 0) and out (residual ReLU: s_{t+1} > 0), and w
+    ([B, steps, 8] fp32)."""
+    v = ops.mefc_saved_views(saved, x, steps)
+    s_next = v["s"][1:] + [out]
+    owner.relu_masks.append({"pre0": v["s"][0] > 0, "h": v["hpre"] > 0, "u": [u > 0 for u in v["u"]],
+                             "pre": [p > 0 for p in v["pre"]], "out": [s > 0 for s in s_next], "w": v["w"].clone()})
+
+
+class _MefcFn(torch.autograd.Function):
+    """One OALayer + GroupOLs pair (DRSformer_arch.py:346-351) as one autograd node."""
+
+    @staticmethod
+    def forward(ctx, x, owner, steps, *params):
+        need = _grad_mode() and any(ctx.needs_input_grad)
+        out, saved = ops.mefc_fwd(x, params, steps, need)
+        if owner.record_masks and saved is not None:
+            _mefc_record(owner, x, saved, out, steps)
+        if need:
+            ctx.steps = steps
+            ctx.mg = _main_grads(params)
+            ctx.save_for_backward(x, out, saved, *params)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        x, out, saved, *params = ctx.saved_tensors
+        acc = ctx.mg is not None
+        grads = ctx.mg if acc else _fresh_grads(params)
+        dx = ops.mefc_bwd(x, out, dout.contiguous(), params, ctx.steps, saved, grads, acc)
+        return (dx, None, None) + tuple(None if acc else g for g in grads)
+
+
+class subnet(nn.Module):  # noqa: N801  (the reference's class name)
+    """Mixture of Experts Feature Compensator (:328-354): ``layer_num`` pairs of (OALayer, GroupOLs)."""
+
+    def __init__(self, dim, layer_num=1, steps=4):
+        super().__init__()
+        self._C = dim
+        self.num_ops = len(Operations)
+        self._layer_num = layer_num
+        self._steps = steps
+        self.layers = nn.ModuleList()
+        for _ in range(self._layer_num):
+            self.layers += [OALayer(self._C, self._steps, self.num_ops)]
+            self.layers += [GroupOLs(steps, self._C)]
+        self.record_masks = False
+        self.relu_masks = None
+
+    def pair_params(self, i):
+        oal, grp = self.layers[2 * i], self.layers[2 * i + 1]
+        ps = [oal.ca_fc[0].weight, oal.ca_fc[0].bias, oal.ca_fc[2].weight, oal.ca_fc[2].bias, grp.preprocess.op[0].weight]
+        for op in grp._ops:
+            ps += op._params()
+        return ps
+
+    def forward(self, x):
+        ops._gpu(x)
+        if self.record_masks and torch.is_grad_enabled():
+            self.relu_masks = []
+        x = x.contiguous()
+        for i in range(self._layer_num):
+            x = _apply(_MefcFn, x, self, self._steps, *self.pair_params(i))
+        return x
+
+
+# ====================================================================================== the network (DRSformer_arch.py:388-480)
+def _stage(dim, heads, n, ffn, bias, ln):
+    return nn.Sequential(*[TransformerBlock(dim=dim, num_heads=heads, ffn_expansion_factor=ffn, bias=bias, LayerNorm_type=ln)
+                           for _ in range(n)])
+
+
+class DRSformer(nn.Module):
+    """The reference U-Net over the native STB and MEFC; same constructor and state_dict."""
+
+    def __init__(self, inp_channels=3, out_channels=3, dim=48, num_blocks=[4, 6, 6, 8], heads=[1, 2, 4, 8],
+                 ffn_expansion_factor=2.66, bias=False, LayerNorm_type='WithBias'):
+        super().__init__()
+        f, b, ln = ffn_expansion_factor, bias, LayerNorm_type
+        self.patch_embed = OverlapPatchEmbed(inp_channels, dim)
+        self.encoder_level0 = subnet(dim)
+        self.encoder_level1 = _stage(dim, heads[0], num_blocks[0], f, b, ln)
+        self.down1_2 = Downsample(dim)
+        self.encoder_level2 = _stage(int(dim * 2 ** 1), heads[1], num_blocks[1], f, b, ln)
+        self.down2_3 = Downsample(int(dim * 2 ** 1))
+        self.encoder_level3 = _stage(int(dim * 2 ** 2), heads[2], num_blocks[2], f, b, ln)
+        self.down3_4 = Downsample(int(dim * 2 ** 2))
+        self.latent = _stage(int(dim * 2 ** 3), heads[3], num_blocks[3], f, b, ln)
+        self.up4_3 = Upsample(int(dim * 2 ** 3))
+        self.reduce_chan_level3 = nn.Conv2d(int(dim * 2 ** 3), int(dim * 2 ** 2), kernel_size=1, bias=bias)
+        self.decoder_level3 = _stage(int(dim * 2 ** 2), heads[2], num_blocks[2], f, b, ln)
+        self.up3_2 = Upsample(int(dim * 2 ** 2))
+        self.reduce_chan_level2 = nn.Conv2d(int(dim * 2 ** 2), int(dim * 2 ** 1), kernel_size=1, bias=bias)
+        self.decoder_level2 = _stage(int(dim * 2 ** 1), heads[1], num_blocks[1], f, b, ln)
+        self.up2_1 = Upsample(int(dim * 2 ** 1))
+        self.decoder_level1 = _stage(int(dim * 2 ** 1), heads[0], num_blocks[0], f, b, ln)
+        self.refinement = subnet(dim=int(dim * 2 ** 1))
+        self.output = nn.Conv2d(int(dim * 2 ** 1), out_channels, kernel_size=3, stride=1, padding=1, bias=bias)
+
+    def forward(self, inp_img):
+        inp_enc_level1 = self.patch_embed(inp_img)
+        out_enc_level1 = self.encoder_level1(self.encoder_level0(inp_enc_level1))
+        out_enc_level2 = self.encoder_level2(self.down1_2(out_enc_level1))
+        out_enc_level3 = self.encoder_level3(self.down2_3(out_enc_level2))
+        latent = self.latent(self.down3_4(out_enc_level3))
+        # concat-free channel reduce: two K-panels of one 1x1 GEMM (:467-473); level 1 concatenates without one (:475-477)
+        out_dec_level3 = self.decoder_level3(_conv1x1_module(self.up4_3(latent), out_enc_level3, self.reduce_chan_level3))
+        out_dec_level2 = self.decoder_level2(_conv1x1_module(self.up3_2(out_dec_level3), out_enc_level2, self.reduce_chan_level2))
+        out_dec_level1 = self.decoder_level1(_up_cat(self.up2_1, out_dec_level2, out_enc_level1))
+        out_dec_level1 = self.refinement(out_dec_level1)
+        return _conv2d(out_dec_level1, self.output, inp_img)

@@ -641,6 +641,103 @@ def msfn_bwd(x: Tensor, dout: Tensor, params: Sequence[Optional[Tensor]], saved:
     return dx
 
 
+# ----------------------------------------------------------------------------- DRSformer: MEFC (one OALayer + GroupOLs pair)
+MEFC_STEP_PARAMS = 23     # per OperationLayer: SepConv k = 1, 3, 5, 7 (op.0, op.1, op.3, op.4), DilConv k = 3, 5, 7 (op.0, op.1), _out.0
+
+
+def _mefc_shape(x: Tensor, steps: int) -> L.MefcShape:
+    B, Cc, H, W = x.shape
+    return L.MefcShape(B, Cc, H, W, _dt(x), int(steps))
+
+
+def _mefc_steps(ts: Sequence[Optional[Tensor]], steps: int, cls):
+    """Per-step structs from the flat per-step tensors in module order (see MEFC_STEP_PARAMS); a host array of ``steps``."""
+    arr = (cls * steps)()
+    for t in range(steps):
+        q = ts[t * MEFC_STEP_PARAMS:(t + 1) * MEFC_STEP_PARAMS]
+        st = arr[t]
+        for k in range(4):
+            st.sep_dw1[k], st.sep_pw1[k], st.sep_dw2[k], st.sep_pw2[k] = (_p(v) for v in q[4 * k:4 * k + 4])
+        for k in range(3):
+            st.dil_dw[k], st.dil_pw[k] = _p(q[16 + 2 * k]), _p(q[17 + 2 * k])
+        st.out_w = _p(q[22])
+    return arr
+
+
+def mefc_sizes(B: int, Cc: int, H: int, W: int, dtype: torch.dtype, steps: int) -> Tuple[int, int]:
+    """(saved bytes, workspace bytes) of one MEFC layer pair; (0, 0) for a shape the kernels do not cover.  No GPU needed."""
+    s = L.MefcShape(B, Cc, H, W, L.MI_BF16 if dtype == torch.bfloat16 else L.MI_F32, int(steps))
+    lib = L.lib()
+    return int(lib.mi_mefc_saved_bytes(C.byref(s))), int(lib.mi_mefc_workspace(C.byref(s)))
+
+
+def mefc_fwd(x: Tensor, params: Sequence[Tensor], steps: int, need_saved: bool):
+    """One MEFC layer pair (OALayer routing + GroupOLs, DRSformer_arch.py:206-247, 346-351).  params = (ca_fc.0.weight, .bias,
+    ca_fc.2.weight, .bias, preprocess.op.0.weight) + per step the 23 OperationLayer weights in module order.  -> (out, saved)."""
+    _gpu(x, *params)
+    for t in params:
+        _f32(t, "MEFC parameter")
+    if len(params) != 5 + MEFC_STEP_PARAMS * steps:
+        raise ValueError(f"mefc: expected {5 + MEFC_STEP_PARAMS * steps} parameters for {steps} steps, got {len(params)}")
+    s = _mefc_shape(x, steps)
+    lib = L.lib()
+    ws_bytes = lib.mi_mefc_workspace(C.byref(s))
+    if ws_bytes == 0:
+        L.check(-1, "mefc_workspace")
+    out = torch.empty_like(x)
+    saved = _blob(lib.mi_mefc_saved_bytes(C.byref(s)), x.device) if need_saved else None
+    ws = _ws(ws_bytes, x.device)
+    arr = _mefc_steps(params[5:], steps, L.MefcStepParams)
+    pp = L.MefcParams(*[_p(t) for t in params[:5]], C.cast(arr, C.POINTER(L.MefcStepParams)))
+    L.check(lib.mi_mefc_fwd(C.byref(s), C.byref(pp), _p(x), _p(out), _p(saved), _p(ws), _stream()), "mefc_fwd")
+    return out, saved
+
+
+def mefc_saved_views(saved: Tensor, x: Tensor, steps: int) -> dict:
+    """Views into a training forward's saved blob (mi_mefc_saved_bytes' layout): pooled [B, C], hpre [B, 16 steps] (fc1 output),
+    w [B, steps, 8] (routing weights) in fp32, and per step lists s, d1, u, z, pre of x's dtype: the step input s_t [B, C, H, W],
+    dw1 outputs [B, 4C, ..], pw1 outputs U [B, 4C, ..], Z [B, 8C, ..] and the out projection's pre-activation [B, C, ..]."""
+    B, Cc, H, W = x.shape
+    N = H * W
+    off = [0]
+
+    def take(n, dtype):
+        es = torch.empty((), dtype=dtype).element_size()
+        o = off[0]
+        off[0] += (n * es + 255) // 256 * 256
+        return saved[o:o + n * es].view(dtype)
+
+    v = {"pooled": take(B * Cc, torch.float32).view(B, Cc), "hpre": take(B * 16 * steps, torch.float32).view(B, 16 * steps),
+         "w": take(B * 8 * steps, torch.float32).view(B, steps, 8)}
+    for name in ("s", "d1", "u", "z", "pre"):
+        v[name] = []
+    for _ in range(steps):
+        for name, k in (("s", 1), ("d1", 4), ("u", 4), ("z", 8), ("pre", 1)):
+            v[name].append(take(B * k * Cc * N, x.dtype).view(B, k * Cc, H, W))
+        for _m in range(3):
+            take(B * Cc * 8 * Cc, torch.float32 if _m == 0 else torch.bfloat16)
+    return v
+
+
+def mefc_bwd(x: Tensor, out: Tensor, dout: Tensor, params: Sequence[Tensor], steps: int, saved: Tensor,
+             grads: Sequence[Tensor], accumulate: bool) -> Tensor:
+    """Backward of mefc_fwd (``out``: its output): dx; the parameter gradients are written (accumulate: added) into ``grads``."""
+    _gpu(x, out, dout, saved, *params, *grads)
+    for t in grads:
+        _f32(t, "MEFC gradient")
+    s = _mefc_shape(x, steps)
+    lib = L.lib()
+    dx = torch.empty_like(x)
+    pa = _mefc_steps(params[5:], steps, L.MefcStepParams)
+    ga = _mefc_steps(grads[5:], steps, L.MefcStepGrads)
+    pp = L.MefcParams(*[_p(t) for t in params[:5]], C.cast(pa, C.POINTER(L.MefcStepParams)))
+    gg = L.MefcGrads(*[_p(t) for t in grads[:5]], C.cast(ga, C.POINTER(L.MefcStepGrads)), int(accumulate))
+    ws = _ws(lib.mi_mefc_workspace(C.byref(s)), x.device)
+    L.check(lib.mi_mefc_bwd(C.byref(s), C.byref(pp), _p(x), _p(out), _p(dout), _p(dx), C.byref(gg), _p(saved), _p(ws), _stream()),
+            "mefc_bwd")
+    return dx
+
+
 def bwd_tail_ok(M: int, Cc: int, N: int, dtype: torch.dtype) -> bool:
     return bool(L.lib().mi_bwd_tail_ok(M, Cc, N, L.MI_BF16 if dtype == torch.bfloat16 else L.MI_F32))
 

@@ -295,6 +295,45 @@ int mi_msfn_bwd(const mi_msfn_shape* s, const mi_msfn_params* p, const void* x, 
                 void* dx, const mi_msfn_grads* g, const void* saved, void* ws, void* stream);
 
 /* ------------------------------------------------------------------------
+ * MEFC — one layer pair of DRSformer's Mixture of Experts Feature Compensator (`subnet`, DRSformer_arch.py:328-354): the
+ * OALayer routing head (:227-247) and the GroupOLs it weights (:206-225), forward / backward as one unit:
+ *   w[b, t, :] = softmax_i(fc2(relu(fc1(mean_hw x[b]))))[t]           (steps x 8 routing weights per image)
+ *   s = relu(pre_w . x);  per step t:  s = relu(relu(out_w . cat_i(w[b,t,i] op_i(s))) + s)
+ *   ops i = sep1, sep3, sep5, sep7 (SepConv: pw2 . dw2(relu(pw1 . dw1(s)))), dil3, dil5, dil7 (DilConv: pw . dw_dilation2(s)),
+ *   avg (3x3 average pool, count_include_pad=False).
+ * Any H, W >= 1; 1 <= steps <= 16; C <= 4096.  Parameters and gradients fp32; dw weights [C, k*k], 1x1 weights [C, C] (out_w
+ * [C, 8C]); `step` points to a HOST array of `steps` structs.  fwd: out [B, C, H, W]; saved (NULL: inference) receives the
+ * planes the backward reads.  bwd takes the forward's output as well (the mask of the last residual ReLU).  NULL is not
+ * accepted for any weight (the reference's convs have no bias; its Linears have one).
+ * ------------------------------------------------------------------------ */
+typedef struct { int B, C, H, W, dtype, steps; } mi_mefc_shape;
+typedef struct {
+  const float* sep_dw1[4]; const float* sep_pw1[4];  /* SepConv k = 1, 3, 5, 7: op.0 [C, k*k], op.1 [C, C] */
+  const float* sep_dw2[4]; const float* sep_pw2[4];  /*                          op.3 [C, k*k], op.4 [C, C] */
+  const float* dil_dw[3];  const float* dil_pw[3];   /* DilConv k = 3, 5, 7:     op.0 [C, k*k], op.1 [C, C] */
+  const float* out_w;                                /* _out.0 [C, 8C] */
+} mi_mefc_step_params;
+typedef struct {
+  float* sep_dw1[4]; float* sep_pw1[4]; float* sep_dw2[4]; float* sep_pw2[4]; float* dil_dw[3]; float* dil_pw[3]; float* out_w;
+} mi_mefc_step_grads;
+typedef struct {
+  const float* fc1_w; const float* fc1_b;   /* OALayer ca_fc.0: [16 steps, C], [16 steps] */
+  const float* fc2_w; const float* fc2_b;   /* ca_fc.2: [8 steps, 16 steps], [8 steps] */
+  const float* pre_w;                       /* GroupOLs.preprocess.op.0 [C, C] */
+  const mi_mefc_step_params* step;          /* host array [steps] */
+} mi_mefc_params;
+typedef struct {
+  float* fc1_w; float* fc1_b; float* fc2_w; float* fc2_b; float* pre_w;
+  const mi_mefc_step_grads* step;           /* host array [steps] */
+  int accumulate;
+} mi_mefc_grads;
+size_t mi_mefc_saved_bytes(const mi_mefc_shape* s);
+size_t mi_mefc_workspace(const mi_mefc_shape* s);
+int mi_mefc_fwd(const mi_mefc_shape* s, const mi_mefc_params* p, const void* x, void* out, void* saved, void* ws, void* stream);
+int mi_mefc_bwd(const mi_mefc_shape* s, const mi_mefc_params* p, const void* x, const void* out, const void* dout, void* dx,
+                const mi_mefc_grads* g, const void* saved, void* ws, void* stream);
+
+/* ------------------------------------------------------------------------
  * GDFN — FeedForward.forward / backward (Restormer.py:76-93; moce_ir.py:255-276;
  * AdaIR-main/net/model.py:76-94).  hidden = h (project_in has 2h outputs).
  * ------------------------------------------------------------------------ */
