@@ -706,6 +706,26 @@ static int dw_bwd_common(const void* dy_or_dg, const void* gy, const void* x, co
 
 extern "C" int mi_dwconv_gate_recompute_ok(int H, int W, int ks) { return dws_eligible(H, W, ks) ? 1 : 0; }
 
+// What the launchers above pick for 16-byte-aligned planes; op 0 fwd, 1 gate fwd, 2 bwd (every form), 3 gate bwd (stored y or
+// recomputed).  Host-side only: it calls the same dws_eligible / make_plan / dw_tiling the launches do.
+extern "C" int mi_dwconv_plan(int B, int C, int H, int W, int ks, int op, int* out) {
+  MI_CHECK_ARG(out, "dwconv_plan: null pointer");
+  MI_CHECK_ARG(op >= 0 && op <= 3, "dwconv_plan: bad op %d", op);
+  MI_TRY(check_common("dwconv_plan", B, C, H, W, ks, MI_F32));
+  const bool gate = op == 1 || op == 3;
+  MI_CHECK_ARG(!gate || C % 2 == 0, "dwconv_plan: channel count %d must be even", C);
+  if (dws_eligible(H, W, ks)) {
+    out[0] = 1;
+    dws_plan(H, W, (int64_t)B * (gate ? C / 2 : C), &out[1], &out[2], &out[3], &out[4]);
+    out[5] = out[1];  // a lane walks its whole band
+  } else {
+    // max rows per thread as the launchers pass it: the gate forms hold two tiles (2), plain 3x3 4, 5x5 / 7x7 1
+    const DwTiling t = dw_tiling(H, W, ks, ks != 3 ? 1 : (gate ? 2 : 4));
+    out[0] = 0; out[1] = t.th; out[2] = t.bands; out[3] = t.tw; out[4] = 0; out[5] = t.rpt;
+  }
+  return MI_OK;
+}
+
 extern "C" int mi_dwconv_gate_bwd_recompute(const void* dg, const void* x, const float* w, const float* bias, void* dx,
                                             float* dwg, float* dbg, int B, int C2, int H, int W, int ks, int accumulate,
                                             int dtype, void* ws, void* stream) {

@@ -632,6 +632,11 @@ bool dws_eligible(int H, int W, int ks) {
 
 int dws_partial_rows(int B, int H, int W, int64_t planes) { return make_plan(H, W, planes).nb * B; }
 
+void dws_plan(int H, int W, int64_t planes, int* band, int* nb, int* lpr, int* uni) {
+  const Plan p = make_plan(H, W, planes);
+  *band = p.band; *nb = p.nb; *lpr = W / 4; *uni = p.uni ? 1 : 0;
+}
+
 int dws_fwd(const DwArgs& a, int B, bool gate, bool flip, int dtype, hipStream_t st) {
   const int64_t planes = (int64_t)B * (gate ? a.hidden : a.Cc);
   const Plan p = make_plan(a.H, a.W, planes);

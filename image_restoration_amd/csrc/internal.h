@@ -59,6 +59,7 @@ struct DwArgs {
 // Streaming 3x3 path: usable when the row is 16..256 pixels, a power of two, and every plane base is 16-byte aligned.
 bool dws_eligible(int H, int W, int ks);
 int dws_partial_rows(int B, int H, int W, int64_t planes);  // rows of weight-gradient partials the backward kernels write
+void dws_plan(int H, int W, int64_t planes, int* band, int* nb, int* lpr, int* uni);  // the launch plan (mi_dwconv_plan)
 int dws_fwd(const DwArgs& a, int B, bool gate, bool flip, int dtype, hipStream_t st);
 int dws_bwd(const DwArgs& dya, const void* xin, float* part, int B, bool want_dx, int* rows_out, int dtype, hipStream_t st);
 int dws_gate_bwd(const DwArgs& a, const void* xin, float* part, int B, bool want_dw, int* rows_out, int dtype,

@@ -189,6 +189,18 @@ def dwconv_gate_recompute_ok(H: int, W: int, ks: int) -> bool:
     return bool(L.lib().mi_dwconv_gate_recompute_ok(H, W, ks))
 
 
+DWCONV_PLAN_OPS = {"fwd": 0, "gate_fwd": 1, "bwd": 2, "gate_bwd": 3}
+
+
+def dwconv_plan(B: int, C: int, H: int, W: int, ks: int, op: str) -> dict:
+    """The launch plan the depthwise entry point `op` takes for 16-byte-aligned planes (mi_dwconv_plan; no GPU work)."""
+    out = (L.C.c_int * 6)()   # (C is the channel count here)
+    L.check(L.lib().mi_dwconv_plan(B, C, H, W, ks, DWCONV_PLAN_OPS[op], out), "dwconv_plan")
+    if out[0] == 1:
+        return {"family": "stream", "band": out[1], "nb": out[2], "lpr": out[3], "uni": bool(out[4]), "rows": out[5]}
+    return {"family": "lds", "th": out[1], "bands": out[2], "tw": out[3], "uni": False, "rpt": out[5]}
+
+
 def dwconv_gate_bwd_recompute(dg: Tensor, x: Tensor, w: Tensor, bias: Optional[Tensor]):
     """Gate backward with the conv outputs recomputed from the conv input x (no stored y)."""
     _gpu(dg, x, w, bias)

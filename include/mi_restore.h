@@ -106,6 +106,11 @@ int mi_dwconv_gate_bwd(const void* dg, const void* y, const void* x, const float
  * y = NULL) - a third less HBM traffic over the depthwise stage and 2h fewer saved planes.  Available for the shapes
  * mi_dwconv_gate_recompute_ok() reports (3x3, rows of 16..256 pixels, power of two); same workspace as mi_dwconv_gate_bwd. */
 int mi_dwconv_gate_recompute_ok(int H, int W, int ks);
+/* The launch plan the depthwise entry points take for 16-byte-aligned planes (read-only; honours MI_DW_LDS).
+ * op: 0 fwd, 1 gate fwd, 2 bwd (every form), 3 gate bwd (stored or recomputed y); the gate ops work on B*C/2 planes.
+ * out[6] = {family (0 LDS-tiled, 1 register-streaming), band rows | tile rows, bands per plane, lanes per row | tile width,
+ *           uni (streaming: one plane per wave), rows per lane | rows per thread}. */
+int mi_dwconv_plan(int B, int C, int H, int W, int ks, int op, int* out);
 int mi_dwconv_gate_bwd_recompute(const void* dg, const void* x, const float* w, const float* bias, void* dx, float* dw,
                                  float* db, int B, int C2, int H, int W, int ks, int accumulate, int dtype, void* ws,
                                  void* stream);
