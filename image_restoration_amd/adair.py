@@ -19,8 +19,9 @@ import torch
 import torch.nn as nn
 
 from . import ops
+from ._autograd import _apply, _grad_mode, _main_grads, module_op
 from .restormer import (Attention, Downsample, FeedForward, LayerNorm, OverlapPatchEmbed, TransformerBlock, Upsample,  # noqa: F401
-                        _apply, _Conv1x1Fn, _conv2d, _CrossAttentionFn, _DwConvFn, _grad_mode, _main_grads, _stage, _up_cat)
+                        _Conv1x1Fn, _conv2d, _DwConvFn, _stage, _up_cat, _XmdtaOp)
 
 __all__ = ["Attention", "FeedForward", "LayerNorm", "TransformerBlock", "Chanel_Cross_Attention", "SpatialGate", "ChannelGate",
            "FreRefine", "FreModule", "AdaIR"]
@@ -44,7 +45,7 @@ class Chanel_Cross_Attention(nn.Module):
     def forward(self, x, y):
         # x -> q, y -> kv
         assert x.shape == y.shape, 'The shape of feature maps from image and features are not equal!'
-        return _apply(_CrossAttentionFn, x, y, self.num_head, *self._params())
+        return module_op(_XmdtaOp(self.num_head), (x, y), self._params())
 
 
 # ----------------------------------------------------------------------------------------------- autograd nodes

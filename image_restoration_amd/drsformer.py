@@ -26,18 +26,13 @@ import torch
 import torch.nn as nn
 
 from . import ops
-from .restormer import (Downsample, LayerNorm, OverlapPatchEmbed, Upsample, _apply, _conv1x1_module, _conv2d, _fresh_grads,
-                        _grad_mode, _main_grads, _up_cat)
+from ._autograd import module_op
+from .restormer import Downsample, LayerNorm, OverlapPatchEmbed, Upsample, _conv1x1_module, _conv2d, _stage, _up_cat
 
 Tensor = torch.Tensor
 
 __all__ = ["Attention", "FeedForward", "TransformerBlock", "LayerNorm", "SepConv", "DilConv", "OperationLayer", "GroupOLs",
            "OALayer", "subnet", "OverlapPatchEmbed", "Downsample", "Upsample", "DRSformer", "Operations"]
-
-
-def _unpack(ctx, rest):
-    it = iter(rest)
-    return tuple(next(it) if pr else None for pr in ctx.present)
 
 
 def _scores_to(owner, scores) -> None:
@@ -51,94 +46,78 @@ def _relu_masks_to(ffn, x, saved) -> None:
         ffn.relu_masks = (v["a"] > 0, v["b"] > 0, v["y"] > 0)
 
 
-class _TksaFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, owner, *params):
-        need = _grad_mode() and any(ctx.needs_input_grad)
-        heads, topk = owner.num_heads, owner.topk(x.shape[1])
-        res = ops.tksa_fwd(x, None, params, heads, topk, need, want_scores=owner.record_scores)
-        out, saved = res[0], res[1]
-        _scores_to(owner, res[2] if owner.record_scores else None)
-        if need:
-            ctx.heads, ctx.topk = heads, topk
-            ctx.mg = _main_grads(params)
-            ctx.present = [p is not None for p in params]
-            ctx.save_for_backward(x, saved, *[p for p in params if p is not None])
-        return out
+class _TksaOp:
+    """Attention.forward (TKSA).  params: ops.tksa_fwd; saved = [the kernels' blob].  ``dim``: the channel count of x."""
 
-    @staticmethod
-    def backward(ctx, dout):
-        x, saved, *rest = ctx.saved_tensors
-        params = _unpack(ctx, rest)
-        acc = ctx.mg is not None
-        grads = ctx.mg if acc else _fresh_grads(params)
-        dx = ops.tksa_bwd(x, dout.contiguous(), params, ctx.heads, ctx.topk, saved, grads, acc)
-        return (dx, None) + tuple(None if acc else g for g in grads)
+    def __init__(self, owner, dim):
+        self.owner, self.heads, self.topk = owner, owner.num_heads, owner.topk(dim)
+
+    def fwd(self, x, residual, params, need):
+        """-> (out, blob); keeps the scores on the owner when it records them."""
+        res = ops.tksa_fwd(x, residual, params, self.heads, self.topk, need, want_scores=self.owner.record_scores)
+        _scores_to(self.owner, res[2] if self.owner.record_scores else None)
+        return res[0], res[1]
+
+    def forward(self, acts, params, need):
+        out, blob = self.fwd(acts[0], None, params, need)
+        return out, [blob]
+
+    def backward(self, acts, saved, dout, params, grads, acc):
+        return (ops.tksa_bwd(acts[0], dout, params, self.heads, self.topk, saved[0], grads, acc),)
 
 
-class _MsfnFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, owner, *params):
-        need = _grad_mode() and any(ctx.needs_input_grad)
-        out, saved = ops.msfn_fwd(x, None, params, need)
-        _relu_masks_to(owner, x, saved)
-        if need:
-            ctx.mg = _main_grads(params)
-            ctx.present = [p is not None for p in params]
-            ctx.save_for_backward(x, saved, *[p for p in params if p is not None])
-        return out
+class _MsfnOp:
+    """FeedForward.forward (MSFN).  params: ops.msfn_fwd; saved = [the kernels' blob]."""
 
-    @staticmethod
-    def backward(ctx, dout):
-        x, saved, *rest = ctx.saved_tensors
-        params = _unpack(ctx, rest)
-        acc = ctx.mg is not None
-        grads = ctx.mg if acc else _fresh_grads(params)
-        dx = ops.msfn_bwd(x, dout.contiguous(), params, saved, grads, acc)
-        return (dx, None) + tuple(None if acc else g for g in grads)
+    def __init__(self, owner):
+        self.owner = owner
+
+    def fwd(self, x, residual, params, need):
+        """-> (out, blob); keeps the ReLU decisions on the owner when it records them."""
+        out, blob = ops.msfn_fwd(x, residual, params, need)
+        _relu_masks_to(self.owner, x, blob)
+        return out, blob
+
+    def forward(self, acts, params, need):
+        out, blob = self.fwd(acts[0], None, params, need)
+        return out, [blob]
+
+    def backward(self, acts, saved, dout, params, grads, acc):
+        return (ops.msfn_bwd(acts[0], dout, params, saved[0], grads, acc),)
 
 
-class _StbFn(torch.autograd.Function):
-    """x + attn(norm1(x)), then + ffn(norm2(.)) (DRSformer_arch.py:183-187) as one autograd node; both residual adds run in
-    the epilogue of the producing 1x1 GEMM, and their gradients enter the LayerNorm backward kernels (dres)."""
+def split_block(params):
+    """The STB's parameter (and gradient) layout: norm1 (2), TKSA (11), norm2 (2), MSFN (12)."""
+    return params[0:2], params[2:13], params[13:15], params[15:27]
 
-    N_LN, N_ATT, N_FFN = 2, 11, 12
 
-    @staticmethod
-    def forward(ctx, x, owner, *params):
-        need = _grad_mode() and any(ctx.needs_input_grad)
-        n1, att, n2, ffn = params[0:2], params[2:13], params[13:15], params[15:27]
+class _StbOp:
+    """x + attn(norm1(x)), then + ffn(norm2(.)) (DRSformer_arch.py:183-187) as one module op; both residual adds run in
+    the epilogue of the producing 1x1 GEMM, and their gradients enter the LayerNorm backward kernels (dres).
+    saved = [xn, y, yn, mean1, rstd1, mean2, rstd2, sv_a, sv_f]."""
+
+    def __init__(self, owner, dim):
+        self.attn, self.ffn = _TksaOp(owner.attn, dim), _MsfnOp(owner.ffn)
+
+    def forward(self, acts, params, need):
+        x = acts[0]
+        n1, att, n2, ffn = split_block(params)
         wb = n1[1] is not None
-        attn = owner.attn
-        heads, topk = attn.num_heads, attn.topk(x.shape[1])
         xn, mean1, rstd1 = ops.ln_fwd(x, n1[0], n1[1], wb, want_stats=need)
-        res = ops.tksa_fwd(xn, x, att, heads, topk, need, want_scores=attn.record_scores)
-        y, sv_a = res[0], res[1]
-        _scores_to(attn, res[2] if attn.record_scores else None)
+        y, sv_a = self.attn.fwd(xn, x, att, need)
         yn, mean2, rstd2 = ops.ln_fwd(y, n2[0], n2[1], wb, want_stats=need)
-        out, sv_f = ops.msfn_fwd(yn, y, ffn, need)
-        _relu_masks_to(owner.ffn, yn, sv_f)
-        if need:
-            ctx.heads, ctx.topk, ctx.wb = heads, topk, wb
-            ctx.mg = _main_grads(params)
-            ctx.present = [p is not None for p in params]
-            ctx.save_for_backward(x, xn, y, yn, mean1, rstd1, mean2, rstd2, sv_a, sv_f, *[p for p in params if p is not None])
-        return out
+        out, sv_f = self.ffn.fwd(yn, y, ffn, need)
+        return out, [xn, y, yn, mean1, rstd1, mean2, rstd2, sv_a, sv_f]
 
-    @staticmethod
-    def backward(ctx, dout):
-        x, xn, y, yn, mean1, rstd1, mean2, rstd2, sv_a, sv_f, *rest = ctx.saved_tensors
-        params = _unpack(ctx, rest)
-        acc = ctx.mg is not None
-        grads = ctx.mg if acc else _fresh_grads(params)
-        n1, att, n2, ffn = params[0:2], params[2:13], params[13:15], params[15:27]
-        g1, ga, g2, gf = grads[0:2], grads[2:13], grads[13:15], grads[15:27]
-        dout = dout.contiguous()
-        dyn = ops.msfn_bwd(yn, dout, ffn, sv_f, gf, acc)
-        dy = ops.ln_bwd(dyn, y, n2[0], mean2, rstd2, dout, ctx.wb, g2[0], g2[1], acc)
-        dxn = ops.tksa_bwd(xn, dy, att, ctx.heads, ctx.topk, sv_a, ga, acc)
-        dx = ops.ln_bwd(dxn, x, n1[0], mean1, rstd1, dy, ctx.wb, g1[0], g1[1], acc)
-        return (dx, None) + tuple(None if acc else g for g in grads)
+    def backward(self, acts, saved, dout, params, grads, acc):
+        xn, y, yn, mean1, rstd1, mean2, rstd2, sv_a, sv_f = saved
+        n1, att, n2, ffn = split_block(params)
+        g1, ga, g2, gf = split_block(grads)
+        wb = n1[1] is not None
+        dyn, = self.ffn.backward((yn,), (sv_f,), dout, ffn, gf, acc)
+        dy = ops.ln_bwd(dyn, y, n2[0], mean2, rstd2, dout, wb, g2[0], g2[1], acc)
+        dxn, = self.attn.backward((xn,), (sv_a,), dy, att, ga, acc)
+        return (ops.ln_bwd(dxn, acts[0], n1[0], mean1, rstd1, dy, wb, g1[0], g1[1], acc),)
 
 
 class FeedForward(nn.Module):
@@ -167,7 +146,7 @@ class FeedForward(nn.Module):
                 self.dwconv5x5_1.weight, self.dwconv5x5_1.bias, self.project_out.weight, self.project_out.bias)
 
     def forward(self, x):
-        return _apply(_MsfnFn, x, self, *self._params())
+        return module_op(_MsfnOp(self), (x,), self._params())
 
 
 class Attention(nn.Module):
@@ -196,7 +175,7 @@ class Attention(nn.Module):
                 self.project_out.weight, self.project_out.bias, self.attn1, self.attn2, self.attn3, self.attn4)
 
     def forward(self, x):
-        return _apply(_TksaFn, x, self, *self._params())
+        return module_op(_TksaOp(self, x.shape[1]), (x,), self._params())
 
 
 class TransformerBlock(nn.Module):
@@ -211,7 +190,7 @@ class TransformerBlock(nn.Module):
 
     def forward(self, x):
         params = self.norm1._params() + self.attn._params() + self.norm2._params() + self.ffn._params()
-        return _apply(_StbFn, x, self, *params)
+        return module_op(_StbOp(self, x.shape[1]), (x,), params)
 
 
 # ====================================================================================== MEFC (DRSformer_arch.py:189-354)
@@ -338,28 +317,21 @@ def _mefc_record(owner, x, saved, out, steps) -> None:
                              "pre": [p > 0 for p in v["pre"]], "out": [s > 0 for s in s_next], "w": v["w"].clone()})
 
 
-class _MefcFn(torch.autograd.Function):
-    """One OALayer + GroupOLs pair (DRSformer_arch.py:346-351) as one autograd node."""
+class _MefcOp:
+    """One OALayer + GroupOLs pair (DRSformer_arch.py:346-351) as one module op.  params: ops.mefc_fwd; saved = [out (the
+    backward reads the pair's own output), the kernels' blob]."""
 
-    @staticmethod
-    def forward(ctx, x, owner, steps, *params):
-        need = _grad_mode() and any(ctx.needs_input_grad)
-        out, saved = ops.mefc_fwd(x, params, steps, need)
-        if owner.record_masks and saved is not None:
-            _mefc_record(owner, x, saved, out, steps)
-        if need:
-            ctx.steps = steps
-            ctx.mg = _main_grads(params)
-            ctx.save_for_backward(x, out, saved, *params)
-        return out
+    def __init__(self, owner, steps):
+        self.owner, self.steps = owner, steps
 
-    @staticmethod
-    def backward(ctx, dout):
-        x, out, saved, *params = ctx.saved_tensors
-        acc = ctx.mg is not None
-        grads = ctx.mg if acc else _fresh_grads(params)
-        dx = ops.mefc_bwd(x, out, dout.contiguous(), params, ctx.steps, saved, grads, acc)
-        return (dx, None, None) + tuple(None if acc else g for g in grads)
+    def forward(self, acts, params, need):
+        out, blob = ops.mefc_fwd(acts[0], params, self.steps, need)
+        if self.owner.record_masks and blob is not None:
+            _mefc_record(self.owner, acts[0], blob, out, self.steps)
+        return out, [out, blob]
+
+    def backward(self, acts, saved, dout, params, grads, acc):
+        return (ops.mefc_bwd(acts[0], saved[0], dout, params, self.steps, saved[1], grads, acc),)
 
 
 class subnet(nn.Module):  # noqa: N801  (the reference's class name)
@@ -391,40 +363,38 @@ class subnet(nn.Module):  # noqa: N801  (the reference's class name)
             self.relu_masks = []
         x = x.contiguous()
         for i in range(self._layer_num):
-            x = _apply(_MefcFn, x, self, self._steps, *self.pair_params(i))
+            x = module_op(_MefcOp(self, self._steps), (x,), self.pair_params(i))
         return x
 
 
 # ====================================================================================== the network (DRSformer_arch.py:388-480)
-def _stage(dim, heads, n, ffn, bias, ln):
-    return nn.Sequential(*[TransformerBlock(dim=dim, num_heads=heads, ffn_expansion_factor=ffn, bias=bias, LayerNorm_type=ln)
-                           for _ in range(n)])
-
-
 class DRSformer(nn.Module):
     """The reference U-Net over the native STB and MEFC; same constructor and state_dict."""
 
     def __init__(self, inp_channels=3, out_channels=3, dim=48, num_blocks=[4, 6, 6, 8], heads=[1, 2, 4, 8],
                  ffn_expansion_factor=2.66, bias=False, LayerNorm_type='WithBias'):
         super().__init__()
-        f, b, ln = ffn_expansion_factor, bias, LayerNorm_type
+
+        def stage(c, h, n):
+            return _stage(c, h, n, ffn_expansion_factor, bias, LayerNorm_type, block=TransformerBlock)
+
         self.patch_embed = OverlapPatchEmbed(inp_channels, dim)
         self.encoder_level0 = subnet(dim)
-        self.encoder_level1 = _stage(dim, heads[0], num_blocks[0], f, b, ln)
+        self.encoder_level1 = stage(dim, heads[0], num_blocks[0])
         self.down1_2 = Downsample(dim)
-        self.encoder_level2 = _stage(int(dim * 2 ** 1), heads[1], num_blocks[1], f, b, ln)
+        self.encoder_level2 = stage(int(dim * 2 ** 1), heads[1], num_blocks[1])
         self.down2_3 = Downsample(int(dim * 2 ** 1))
-        self.encoder_level3 = _stage(int(dim * 2 ** 2), heads[2], num_blocks[2], f, b, ln)
+        self.encoder_level3 = stage(int(dim * 2 ** 2), heads[2], num_blocks[2])
         self.down3_4 = Downsample(int(dim * 2 ** 2))
-        self.latent = _stage(int(dim * 2 ** 3), heads[3], num_blocks[3], f, b, ln)
+        self.latent = stage(int(dim * 2 ** 3), heads[3], num_blocks[3])
         self.up4_3 = Upsample(int(dim * 2 ** 3))
         self.reduce_chan_level3 = nn.Conv2d(int(dim * 2 ** 3), int(dim * 2 ** 2), kernel_size=1, bias=bias)
-        self.decoder_level3 = _stage(int(dim * 2 ** 2), heads[2], num_blocks[2], f, b, ln)
+        self.decoder_level3 = stage(int(dim * 2 ** 2), heads[2], num_blocks[2])
         self.up3_2 = Upsample(int(dim * 2 ** 2))
         self.reduce_chan_level2 = nn.Conv2d(int(dim * 2 ** 2), int(dim * 2 ** 1), kernel_size=1, bias=bias)
-        self.decoder_level2 = _stage(int(dim * 2 ** 1), heads[1], num_blocks[1], f, b, ln)
+        self.decoder_level2 = stage(int(dim * 2 ** 1), heads[1], num_blocks[1])
         self.up2_1 = Upsample(int(dim * 2 ** 1))
-        self.decoder_level1 = _stage(int(dim * 2 ** 1), heads[0], num_blocks[0], f, b, ln)
+        self.decoder_level1 = stage(int(dim * 2 ** 1), heads[0], num_blocks[0])
         self.refinement = subnet(dim=int(dim * 2 ** 1))
         self.output = nn.Conv2d(int(dim * 2 ** 1), out_channels, kernel_size=3, stride=1, padding=1, bias=bias)
 

@@ -29,8 +29,9 @@ import torch
 import torch.nn as nn
 
 from . import ops
-from .restormer import (Attention, Downsample, FeedForward, LayerNorm, OverlapPatchEmbed, Upsample, _apply,  # noqa: F401
-                        _BlockFn, block_apply, _Conv1x1Fn, _conv1x1_module, _CrossAttentionFn, _DwConvFn, _conv2d, _grad_mode, _main_grads)
+from ._autograd import _apply, _grad_mode, _main_grads, _present, _refill, _squeeze, module_op
+from .restormer import (Attention, Downsample, FeedForward, LayerNorm, OverlapPatchEmbed, Upsample, block_apply,  # noqa: F401
+                        _Conv1x1Fn, _conv1x1_module, _conv2d, _DwConvFn, _XmdtaOp)
 
 __all__ = ["SparseDispatcher", "LayerNorm", "FeedForward", "Attention", "CrossAttention", "FFTAttention", "MySequential",
            "ModExpert", "AdapterLayer", "RoutingFunction", "EncoderBlock", "DecoderBlock", "HighPassConv2d",
@@ -322,8 +323,8 @@ class _ExpertsOutFn(torch.autograd.Function):
         if probs:
             ops.grouped_pw_gemm(probs, dev_counts, dev_offsets, R, H * W, xrows.dtype)
         ctx.counts, ctx.cap = counts, cap
-        ctx.save_for_backward(dev_counts, dev_offsets, *[t for t in ts if t is not None], *ws)
-        ctx.present = [t is not None for t in ts]
+        ctx.save_for_backward(dev_counts, dev_offsets, *_squeeze(ts), *ws)
+        ctx.present = _present(ts)
         ctx.mg = [getattr(w, "main_grad", None) for w in ws]
         return out
 
@@ -333,8 +334,7 @@ class _ExpertsOutFn(torch.autograd.Function):
         E = len(ctx.counts)
         dev_counts, dev_offsets, *saved = ctx.saved_tensors
         nt = sum(ctx.present)
-        it = iter(saved[:nt])
-        ts = [next(it) if pr else None for pr in ctx.present]
+        ts = _refill(ctx.present, saved[:nt])
         ws = saved[nt:]
         R, Cc, H, W = dout.shape
         dts = [(torch.zeros_like(t) if ctx.cap else torch.empty_like(t)) if t is not None else None for t in ts]
@@ -416,7 +416,7 @@ class CrossAttention(nn.Module):
                 self.kv.bias, self.kv_dwconv.weight, self.kv_dwconv.bias, self.project_out.weight, self.project_out.bias)
 
     def forward(self, x, y):
-        return _apply(_CrossAttentionFn, x, y, self.num_heads, *self._params())
+        return module_op(_XmdtaOp(self.num_heads), (x, y), self._params())
 
 
 class FFTAttention(nn.Module):

@@ -17,12 +17,16 @@ from . import _lib as L
 Tensor = torch.Tensor
 
 
-def _dt(t: Tensor) -> int:
-    if t.dtype == torch.float32:
+def _dtype_code(dtype: torch.dtype) -> int:
+    if dtype == torch.float32:
         return L.MI_F32
-    if t.dtype == torch.bfloat16:
+    if dtype == torch.bfloat16:
         return L.MI_BF16
-    raise TypeError(f"activations must be float32 or bfloat16, got {t.dtype}")
+    raise TypeError(f"activations must be float32 or bfloat16, got {dtype}")
+
+
+def _dt(t: Tensor) -> int:
+    return _dtype_code(t.dtype)
 
 
 def _gpu(*ts: Optional[Tensor]) -> None:
@@ -44,6 +48,13 @@ def _f32(t: Optional[Tensor], what: str) -> Optional[Tensor]:
     if t is not None and t.dtype != torch.float32:
         raise TypeError(f"{what} must be float32 (parameters and their gradients stay fp32), got {t.dtype}")
     return t
+
+
+def _f32_struct(cls, ts: Sequence[Optional[Tensor]], what: str, *tail):
+    """Struct ``cls`` of the pointers of ``ts`` (parameters or their gradients: each checked to be fp32), then ``tail``."""
+    for t in ts:
+        _f32(t, what)
+    return cls(*[_p(t) for t in ts], *tail)
 
 
 def _stream() -> int:
@@ -281,6 +292,41 @@ def gram(a: Tensor, b: Tensor, groups: int = 1, sum_batch: bool = False, want_su
     return (out, ss) if want_sumsq else out
 
 
+def conv1x1_dgrad_panel(dy: Tensor, w2: Tensor, k0: int, k: int) -> Tensor:
+    """dx[:, k0:k0+k] = W[:, k0:k0+k]^T dy  using the column block of w2 [M, K1+K2] in place (row stride stays K1+K2)."""
+    B, M, H, W = dy.shape
+    N = H * W
+    dx = torch.empty((B, k, H, W), dtype=dy.dtype, device=dy.device)
+    d = L.PwDesc()
+    d.x1, d.x1_bs, d.k1 = _p(dy), M * N, M
+    d.w = _p(w2) + 4 * k0
+    d.w_sm, d.w_sk = 1, w2.shape[1]
+    d.y, d.y_bs = _p(dx), k * N
+    d.m, d.n, d.batch, d.groups, d.dtype = k, N, B, 1, _dt(dy)
+    pw_gemm_desc(d, dy.device)
+    return dx
+
+
+def conv1x1_wgrad_panels(dy: Tensor, x1: Tensor, x2: Optional[Tensor], dw2: Tensor, accumulate: bool) -> None:
+    """dw2[:, panel] (+)= dy . x^T for the K-panels x1, x2 of a 1x1 conv: each Gram lands in its column block of dw2 [M, K1+K2]."""
+    B, M, H, W = dy.shape
+    N = H * W
+    k0 = 0
+    for xp in (x1, x2):
+        if xp is None:
+            continue
+        k = xp.shape[1]
+        d = L.GramDesc()
+        d.a, d.a_bs, d.ma = _p(dy), M * N, M
+        d.b, d.b_bs, d.mb = _p(xp), k * N, k
+        d.n, d.batch, d.groups, d.dtype = N, B, 1, _dt(dy)
+        d.sum_batch, d.accumulate = 1, int(accumulate)
+        d.out, d.out_ld, d.out_zs = _p(dw2) + 4 * k0, dw2.shape[1], 0
+        ws = _blob(L.lib().mi_gram_workspace(C.byref(d)), dy.device)
+        L.check(L.lib().mi_gram(C.byref(d), _p(ws), _stream()), "gram(wgrad panel)")
+        k0 += k
+
+
 # ----------------------------------------------------------------------------- MDTA / GDFN modules
 MdtaParamsT = Tuple[Tensor, Tensor, Optional[Tensor], Tensor, Optional[Tensor], Tensor, Optional[Tensor]]
 GdfnParamsT = Tuple[Tensor, Optional[Tensor], Tensor, Optional[Tensor], Tensor, Optional[Tensor]]
@@ -292,9 +338,12 @@ def _mdta_shape(x: Tensor, heads: int, ks: int) -> L.MdtaShape:
 
 
 def _mdta_params(p: Sequence[Optional[Tensor]]) -> L.MdtaParams:
-    for t in p:
-        _f32(t, "MDTA parameter")
-    return L.MdtaParams(*[_p(t) for t in p])
+    return _f32_struct(L.MdtaParams, p, "MDTA parameter")
+
+
+def mdta_saved_bytes(x: Tensor, heads: int, ks: int) -> int:
+    """Size of the blob mdta_fwd saves for this activation (shape and dtype only: fake tensors do)."""
+    return int(L.lib().mi_mdta_saved_bytes(C.byref(_mdta_shape(x, heads, ks))))
 
 
 LnHeadT = Tuple[Tensor, Optional[Tensor], bool]     # LayerNorm weight, bias, want_stats
@@ -394,9 +443,7 @@ def mdta_bwd(x: Tensor, dout: Tensor, params: MdtaParamsT, heads: int, saved: Te
     lib = L.lib()
     dx = torch.empty_like(x)
     pp = _mdta_params(params)
-    for t in grads:
-        _f32(t, "MDTA gradient")
-    gg = L.MdtaGrads(*[_p(t) for t in grads], int(accumulate))
+    gg = _f32_struct(L.MdtaGrads, grads, "MDTA gradient", int(accumulate))
     if ln is None:
         ws = _ws(lib.mi_mdta_workspace(C.byref(s)), x.device)
         L.check(lib.mi_mdta_bwd(C.byref(s), C.byref(pp), _p(x), _p(dout), _p(dx), C.byref(gg), _p(saved), _p(ws), _stream()),
@@ -420,14 +467,12 @@ def xmdta_fwd(x: Tensor, y: Tensor, residual: Optional[Tensor], params: Sequence
     kv_dwconv.weight, kv_dwconv.bias, project_out.weight, project_out.bias)."""
     _gpu(x, y, residual, *params)
     assert x.shape == y.shape and x.dtype == y.dtype, "cross-MDTA needs x and y of one shape and dtype"
-    for t in params:
-        _f32(t, "cross-MDTA parameter")
     s = _xmdta_shape(x, heads, params[3].shape[-1], params[7].shape[-1])
     lib = L.lib()
     out = torch.empty_like(x)
     saved = _blob(lib.mi_xmdta_saved_bytes(C.byref(s)), x.device) if need_saved else None
     ws = _ws(lib.mi_xmdta_workspace(C.byref(s)), x.device)
-    pp = L.XmdtaParams(*[_p(t) for t in params])
+    pp = _f32_struct(L.XmdtaParams, params, "cross-MDTA parameter")
     L.check(lib.mi_xmdta_fwd(C.byref(s), C.byref(pp), _p(x), _p(y), _p(residual), _p(out), _p(saved), _p(ws), _stream()),
             "xmdta_fwd")
     return out, saved
@@ -440,10 +485,8 @@ def xmdta_bwd(x: Tensor, y: Tensor, dout: Tensor, params: Sequence[Optional[Tens
     lib = L.lib()
     dx, dy = torch.empty_like(x), torch.empty_like(y)
     ws = _ws(lib.mi_xmdta_workspace(C.byref(s)), x.device)
-    pp = L.XmdtaParams(*[_p(t) for t in params])
-    for t in grads:
-        _f32(t, "cross-MDTA gradient")
-    gg = L.XmdtaGrads(*[_p(t) for t in grads], int(accumulate))
+    pp = _f32_struct(L.XmdtaParams, params, "cross-MDTA parameter")
+    gg = _f32_struct(L.XmdtaGrads, grads, "cross-MDTA gradient", int(accumulate))
     L.check(lib.mi_xmdta_bwd(C.byref(s), C.byref(pp), _p(x), _p(y), _p(dout), _p(dx), _p(dy), C.byref(gg), _p(saved), _p(ws),
                              _stream()), "xmdta_bwd")
     return dx, dy
@@ -452,6 +495,22 @@ def xmdta_bwd(x: Tensor, y: Tensor, dout: Tensor, params: Sequence[Optional[Tens
 def _gdfn_shape(x: Tensor, hidden: int, ks: int, flags: int = 0) -> L.GdfnShape:
     B, Cc, H, W = x.shape
     return L.GdfnShape(B, Cc, hidden, H, W, _dt(x), ks, flags)
+
+
+def _gdfn_train_shape(x: Tensor, hidden: int, ks: int) -> L.GdfnShape:
+    """The shape a training forward carves its blob for.  A/B switch MI_GDFN_STORE_Y: keep the conv output instead of
+    recomputing it in backward.  Read here, once per forward; backward recovers the choice from the blob's size, so toggling
+    the variable between the two cannot desynchronise them."""
+    return _gdfn_shape(x, hidden, ks, 1 if env("MI_GDFN_STORE_Y") else 0)
+
+
+def gdfn_saved_bytes(x: Tensor, hidden: int, ks: int) -> int:
+    """Size of the blob gdfn_fwd saves for this activation (shape and dtype only: fake tensors do)."""
+    return int(L.lib().mi_gdfn_saved_bytes(C.byref(_gdfn_train_shape(x, hidden, ks))))
+
+
+def _gdfn_params(p: Sequence[Optional[Tensor]]) -> L.GdfnParams:
+    return _f32_struct(L.GdfnParams, p, "GDFN parameter")
 
 
 def gdfn_fwd_ln_ok(x: Tensor, hidden: int, ks: int) -> bool:
@@ -472,9 +531,8 @@ def gdfn_fwd(x: Tensor, residual: Optional[Tensor], params: GdfnParamsT, need_sa
              f8: Optional[F8ScalesT] = None):
     """params = (project_in.weight, .bias, dwconv.weight, .bias, project_out.weight, .bias).  ln, f8: as in mdta_fwd."""
     _gpu(x, residual, *params)
-    for t in params:
-        _f32(t, "GDFN parameter")
     hidden, ks = params[4].shape[1], params[2].shape[-1]
+    pp = _gdfn_params(params)
     if f8 is not None:
         if need_saved or (ln is not None and ln[2]):
             raise ValueError("fp8 projections are an inference path: nothing can be saved")
@@ -483,18 +541,15 @@ def gdfn_fwd(x: Tensor, residual: Optional[Tensor], params: GdfnParamsT, need_sa
         out = torch.empty_like(x)
         ws = _ws(lib.mi_gdfn_workspace(C.byref(s)), x.device)
         lh = _ln_head(ln, x)[0] if ln is not None else None
-        L.check(lib.mi_gdfn_fwd_f8(C.byref(s), C.byref(L.GdfnParams(*[_p(t) for t in params])),
+        L.check(lib.mi_gdfn_fwd_f8(C.byref(s), C.byref(pp),
                                    C.byref(lh) if lh is not None else None, C.byref(L.F8Scales(*[float(v) for v in f8])),
                                    _p(x), _p(residual), _p(out), _p(ws), _stream()), "gdfn_fwd_f8")
         return out
-    # A/B switch: keep the conv output instead of recomputing it in backward.  Read here, once per forward; backward
-    # recovers the choice from the blob's size, so toggling the variable between the two cannot desynchronise them.
-    s = _gdfn_shape(x, hidden, ks, 1 if env("MI_GDFN_STORE_Y") else 0)
+    s = _gdfn_train_shape(x, hidden, ks)
     lib = L.lib()
     out = torch.empty_like(x)
     saved = _blob(lib.mi_gdfn_saved_bytes(C.byref(s)), x.device) if need_saved else None
     ws = _ws(lib.mi_gdfn_workspace(C.byref(s)), x.device)
-    pp = L.GdfnParams(*[_p(t) for t in params])
     if ln is None:
         L.check(lib.mi_gdfn_fwd(C.byref(s), C.byref(pp), _p(x), _p(residual), _p(out), _p(saved), _p(ws), _stream()),
                 "gdfn_fwd")
@@ -527,10 +582,8 @@ def gdfn_bwd(x: Tensor, dout: Tensor, params: GdfnParamsT, saved: Tensor, grads:
     if s is None:
         raise RuntimeError("gdfn_bwd: the saved blob matches neither layout of this shape")
     dx = torch.empty_like(x)
-    pp = L.GdfnParams(*[_p(t) for t in params])
-    for t in grads:
-        _f32(t, "GDFN gradient")
-    gg = L.GdfnGrads(*[_p(t) for t in grads], int(accumulate))
+    pp = _gdfn_params(params)
+    gg = _f32_struct(L.GdfnGrads, grads, "GDFN gradient", int(accumulate))
     if ln is None:
         ws = _ws(lib.mi_gdfn_workspace(C.byref(s)), x.device)
         L.check(lib.mi_gdfn_bwd(C.byref(s), C.byref(pp), _p(x), _p(dout), _p(dx), C.byref(gg), _p(saved), _p(ws), _stream()),
@@ -556,7 +609,7 @@ def _tksa_shape(x: Tensor, heads: int, topk: Sequence[int]) -> L.TksaShape:
 
 def tksa_sizes(B: int, Cc: int, heads: int, H: int, W: int, dtype: torch.dtype, topk: Sequence[int]) -> Tuple[int, int]:
     """(saved bytes, workspace bytes) of one TKSA call; (0, 0) for a shape the kernels do not cover.  No GPU needed."""
-    s = L.TksaShape(B, Cc, heads, H, W, L.MI_BF16 if dtype == torch.bfloat16 else L.MI_F32, *[int(k) for k in topk])
+    s = L.TksaShape(B, Cc, heads, H, W, _dtype_code(dtype), *[int(k) for k in topk])
     lib = L.lib()
     return int(lib.mi_tksa_saved_bytes(C.byref(s))), int(lib.mi_tksa_workspace(C.byref(s)))
 
@@ -567,8 +620,6 @@ def tksa_fwd(x: Tensor, residual: Optional[Tensor], params: Sequence[Optional[Te
     project_out.weight, project_out.bias, attn1, attn2, attn3, attn4); topk: the four k (tksa_topk).  Returns (out, saved) or,
     with want_scores, (out, saved, scores [B, heads, c, c] fp32: the S the top-k masks were ranked from)."""
     _gpu(x, residual, *params)
-    for t in params:
-        _f32(t, "TKSA parameter")
     s = _tksa_shape(x, heads, topk)
     lib = L.lib()
     ws_bytes = lib.mi_tksa_workspace(C.byref(s))
@@ -580,7 +631,7 @@ def tksa_fwd(x: Tensor, residual: Optional[Tensor], params: Sequence[Optional[Te
     c = x.shape[1] // heads
     scores = torch.empty((x.shape[0], heads, c, c), dtype=torch.float32, device=x.device) if want_scores else None
     pp = _mdta_params(params[:7])
-    tp = L.TksaParams(*[_p(t) for t in params[7:11]])
+    tp = _f32_struct(L.TksaParams, params[7:11], "TKSA parameter")
     L.check(lib.mi_tksa_fwd(C.byref(s), C.byref(pp), C.byref(tp), _p(x), _p(residual), _p(out), _p(saved), _p(ws), _p(scores),
                             _stream()), "tksa_fwd")
     return (out, saved, scores) if want_scores else (out, saved)
@@ -593,12 +644,10 @@ def tksa_bwd(x: Tensor, dout: Tensor, params: Sequence[Optional[Tensor]], heads:
     s = _tksa_shape(x, heads, topk)
     lib = L.lib()
     dx = torch.empty_like(x)
-    for t in grads:
-        _f32(t, "TKSA gradient")
     pp = _mdta_params(params[:7])
-    tp = L.TksaParams(*[_p(t) for t in params[7:11]])
-    gg = L.MdtaGrads(*[_p(t) for t in grads[:7]], int(accumulate))
-    tg = L.TksaGrads(*[_p(t) for t in grads[7:11]])
+    tp = _f32_struct(L.TksaParams, params[7:11], "TKSA parameter")
+    gg = _f32_struct(L.MdtaGrads, grads[:7], "TKSA gradient", int(accumulate))
+    tg = _f32_struct(L.TksaGrads, grads[7:11], "TKSA gradient")
     ws = _ws(lib.mi_tksa_workspace(C.byref(s)), x.device)
     L.check(lib.mi_tksa_bwd(C.byref(s), C.byref(pp), C.byref(tp), _p(x), _p(dout), _p(dx), C.byref(gg), C.byref(tg), _p(saved),
                             _p(ws), _stream()), "tksa_bwd")
@@ -614,14 +663,12 @@ def msfn_fwd(x: Tensor, residual: Optional[Tensor], params: Sequence[Optional[Te
     """DRSformer FeedForward (MSFN).  params = (project_in.weight, .bias, dwconv3x3.weight, .bias, dwconv5x5.weight, .bias,
     dwconv3x3_1.weight, .bias, dwconv5x5_1.weight, .bias, project_out.weight, .bias).  Returns (out, saved)."""
     _gpu(x, residual, *params)
-    for t in params:
-        _f32(t, "MSFN parameter")
     s = _msfn_shape(x, params[6].shape[0])
     lib = L.lib()
     out = torch.empty_like(x)
     saved = _blob(lib.mi_msfn_saved_bytes(C.byref(s)), x.device) if need_saved else None
     ws = _ws(lib.mi_msfn_workspace(C.byref(s)), x.device)
-    pp = L.MsfnParams(*[_p(t) for t in params])
+    pp = _f32_struct(L.MsfnParams, params, "MSFN parameter")
     L.check(lib.mi_msfn_fwd(C.byref(s), C.byref(pp), _p(x), _p(residual), _p(out), _p(saved), _p(ws), _stream()), "msfn_fwd")
     return out, saved
 
@@ -643,10 +690,8 @@ def msfn_bwd(x: Tensor, dout: Tensor, params: Sequence[Optional[Tensor]], saved:
     s = _msfn_shape(x, params[6].shape[0])
     lib = L.lib()
     dx = torch.empty_like(x)
-    for t in grads:
-        _f32(t, "MSFN gradient")
-    pp = L.MsfnParams(*[_p(t) for t in params])
-    gg = L.MsfnGrads(*[_p(t) for t in grads], int(accumulate))
+    pp = _f32_struct(L.MsfnParams, params, "MSFN parameter")
+    gg = _f32_struct(L.MsfnGrads, grads, "MSFN gradient", int(accumulate))
     ws = _ws(lib.mi_msfn_workspace(C.byref(s)), x.device)
     L.check(lib.mi_msfn_bwd(C.byref(s), C.byref(pp), _p(x), _p(dout), _p(dx), C.byref(gg), _p(saved), _p(ws), _stream()),
             "msfn_bwd")
@@ -678,7 +723,7 @@ def _mefc_steps(ts: Sequence[Optional[Tensor]], steps: int, cls):
 
 def mefc_sizes(B: int, Cc: int, H: int, W: int, dtype: torch.dtype, steps: int) -> Tuple[int, int]:
     """(saved bytes, workspace bytes) of one MEFC layer pair; (0, 0) for a shape the kernels do not cover.  No GPU needed."""
-    s = L.MefcShape(B, Cc, H, W, L.MI_BF16 if dtype == torch.bfloat16 else L.MI_F32, int(steps))
+    s = L.MefcShape(B, Cc, H, W, _dtype_code(dtype), int(steps))
     lib = L.lib()
     return int(lib.mi_mefc_saved_bytes(C.byref(s))), int(lib.mi_mefc_workspace(C.byref(s)))
 
@@ -687,7 +732,7 @@ def mefc_fwd(x: Tensor, params: Sequence[Tensor], steps: int, need_saved: bool):
     """One MEFC layer pair (OALayer routing + GroupOLs, DRSformer_arch.py:206-247, 346-351).  params = (ca_fc.0.weight, .bias,
     ca_fc.2.weight, .bias, preprocess.op.0.weight) + per step the 23 OperationLayer weights in module order.  -> (out, saved)."""
     _gpu(x, *params)
-    for t in params:
+    for t in params[5:]:
         _f32(t, "MEFC parameter")
     if len(params) != 5 + MEFC_STEP_PARAMS * steps:
         raise ValueError(f"mefc: expected {5 + MEFC_STEP_PARAMS * steps} parameters for {steps} steps, got {len(params)}")
@@ -700,7 +745,7 @@ def mefc_fwd(x: Tensor, params: Sequence[Tensor], steps: int, need_saved: bool):
     saved = _blob(lib.mi_mefc_saved_bytes(C.byref(s)), x.device) if need_saved else None
     ws = _ws(ws_bytes, x.device)
     arr = _mefc_steps(params[5:], steps, L.MefcStepParams)
-    pp = L.MefcParams(*[_p(t) for t in params[:5]], C.cast(arr, C.POINTER(L.MefcStepParams)))
+    pp = _f32_struct(L.MefcParams, params[:5], "MEFC parameter", C.cast(arr, C.POINTER(L.MefcStepParams)))
     L.check(lib.mi_mefc_fwd(C.byref(s), C.byref(pp), _p(x), _p(out), _p(saved), _p(ws), _stream()), "mefc_fwd")
     return out, saved
 
@@ -735,15 +780,15 @@ def mefc_bwd(x: Tensor, out: Tensor, dout: Tensor, params: Sequence[Tensor], ste
              grads: Sequence[Tensor], accumulate: bool) -> Tensor:
     """Backward of mefc_fwd (``out``: its output): dx; the parameter gradients are written (accumulate: added) into ``grads``."""
     _gpu(x, out, dout, saved, *params, *grads)
-    for t in grads:
+    for t in grads[5:]:
         _f32(t, "MEFC gradient")
     s = _mefc_shape(x, steps)
     lib = L.lib()
     dx = torch.empty_like(x)
     pa = _mefc_steps(params[5:], steps, L.MefcStepParams)
     ga = _mefc_steps(grads[5:], steps, L.MefcStepGrads)
-    pp = L.MefcParams(*[_p(t) for t in params[:5]], C.cast(pa, C.POINTER(L.MefcStepParams)))
-    gg = L.MefcGrads(*[_p(t) for t in grads[:5]], C.cast(ga, C.POINTER(L.MefcStepGrads)), int(accumulate))
+    pp = _f32_struct(L.MefcParams, params[:5], "MEFC parameter", C.cast(pa, C.POINTER(L.MefcStepParams)))
+    gg = _f32_struct(L.MefcGrads, grads[:5], "MEFC gradient", C.cast(ga, C.POINTER(L.MefcStepGrads)), int(accumulate))
     ws = _ws(lib.mi_mefc_workspace(C.byref(s)), x.device)
     L.check(lib.mi_mefc_bwd(C.byref(s), C.byref(pp), _p(x), _p(out), _p(dout), _p(dx), C.byref(gg), _p(saved), _p(ws), _stream()),
             "mefc_bwd")
@@ -751,7 +796,7 @@ def mefc_bwd(x: Tensor, out: Tensor, dout: Tensor, params: Sequence[Tensor], ste
 
 
 def bwd_tail_ok(M: int, Cc: int, N: int, dtype: torch.dtype) -> bool:
-    return bool(L.lib().mi_bwd_tail_ok(M, Cc, N, L.MI_BF16 if dtype == torch.bfloat16 else L.MI_F32))
+    return bool(L.lib().mi_bwd_tail_ok(M, Cc, N, _dtype_code(dtype)))
 
 
 def bwd_tail(dy: Tensor, x: Tensor, dres: Optional[Tensor], mean: Tensor, rstd: Tensor, w: Tensor, gamma: Tensor,
@@ -785,13 +830,12 @@ def gdfn_fused_ok(x: Tensor, hidden: int, ks: int = 3) -> bool:
 def gdfn_fused_pack(x_like: Tensor, ln_w: Tensor, ln_b: Optional[Tensor], params: "GdfnParamsT") -> Tensor:
     """LayerNorm affine + GDFN parameters -> the fused kernel's packed weight images (re-run after weight updates)."""
     _gpu(ln_w, ln_b, *params)
-    for t in (ln_w, ln_b) + tuple(params):
-        _f32(t, "fused GDFN parameter")
+    _f32(ln_w, "fused GDFN parameter"); _f32(ln_b, "fused GDFN parameter")
     hidden = params[4].shape[1]
     s = _gdfn_fused_shape(x_like, hidden, ln_b is not None)
     lib = L.lib()
     pack = _blob(lib.mi_gdfn_fused_pack_bytes(C.byref(s)), ln_w.device)
-    pp = L.GdfnParams(*[_p(t) for t in params])
+    pp = _f32_struct(L.GdfnParams, params, "fused GDFN parameter")
     L.check(lib.mi_gdfn_fused_pack(C.byref(s), _p(ln_w), _p(ln_b), C.byref(pp), _p(pack), _stream()), "gdfn_fused_pack")
     return pack
 
@@ -856,8 +900,7 @@ def mdta_fused_pays(x: Tensor, heads: int, ks: int = 3) -> bool:
 def mdta_fused_pack(x_like: Tensor, heads: int, ln_w: Tensor, ln_b: Optional[Tensor], params: "MdtaParamsT") -> Tensor:
     """LayerNorm affine + qkv / depthwise parameters -> the fused MDTA kernel's packed weight images."""
     _gpu(ln_w, ln_b, *params)
-    for t in (ln_w, ln_b) + tuple(params):
-        _f32(t, "fused MDTA parameter")
+    _f32(ln_w, "fused MDTA parameter"); _f32(ln_b, "fused MDTA parameter")
     s = _mdta_shape(x_like, heads, params[3].shape[-1])
     lib = L.lib()
     pack = _blob(lib.mi_mdta_fused_pack_bytes(C.byref(s)), ln_w.device)
@@ -903,7 +946,7 @@ def rows_gather_scaled(x_f32: Tensor, idx: Tensor, scale: Optional[Tensor], dtyp
     n = int(idx.numel())
     out = torch.empty((n,) + tuple(x_f32.shape[1:]), dtype=dtype, device=x_f32.device)
     L.check(L.lib().mi_rows_gather_scaled(_p(x_f32), _p(idx), _p(_f32(scale, "scale")), _p(out), n, x_f32[0].numel(),
-                                          L.MI_BF16 if dtype == torch.bfloat16 else L.MI_F32, _stream()), "rows_gather_scaled")
+                                          _dtype_code(dtype), _stream()), "rows_gather_scaled")
     return out
 
 
@@ -1139,7 +1182,7 @@ def grouped_pw_gemm(problems, counts: Tensor, offsets: Tensor, max_rows: int, n_
         g.m, g.k, g.expert = int(q["m"]), int(q["k"]), int(q["expert"])
         g.x_local, g.y_local, g.r_local = int(bool(q.get("x_local"))), int(bool(q.get("y_local"))), int(bool(q.get("r_local")))
     L.check(L.lib().mi_grouped_pw_gemm(arr, len(problems), _p(counts), _p(offsets), int(max_rows), int(n_pix),
-                                       L.MI_BF16 if dtype == torch.bfloat16 else L.MI_F32, _stream()), "grouped_pw_gemm")
+                                       _dtype_code(dtype), _stream()), "grouped_pw_gemm")
 
 
 def _bstride(t: Tensor) -> int:

@@ -15,57 +15,21 @@ from __future__ import annotations
 
 import math
 import numbers
-import os
-import threading
 from typing import List, Optional, Sequence
 
 import torch
 import torch.nn as nn
 
 from . import ops
+from ._autograd import _apply, _grad_mode, _main_grads, module_op
 
 Tensor = torch.Tensor
-
-
-def _main_grads(params: Sequence[Optional[Tensor]]) -> Optional[List[Optional[Tensor]]]:
-    """main_grad buffers if every present parameter has one, else None."""
-    out = []
-    for p in params:
-        if p is None:
-            out.append(None)
-            continue
-        mg = getattr(p, "main_grad", None)
-        if mg is None:
-            return None
-        out.append(mg)
-    return out
-
-
-def _fresh_grads(params: Sequence[Optional[Tensor]]) -> List[Optional[Tensor]]:
-    return [None if p is None else torch.empty_like(p) for p in params]
-
-
-# ======================================================================================
-# autograd glue
-# ======================================================================================
-# Inside Function.forward grad mode is always off and ctx.needs_input_grad ignores torch.no_grad(), so the caller's grad
-# mode is recorded right before .apply(): under no_grad nothing is saved for backward (no blobs, no LN statistics).
-_tls = threading.local()
-
-
-def _apply(fn, *args):
-    _tls.grad = torch.is_grad_enabled()
-    return fn.apply(*args)
-
-
-def _grad_mode() -> bool:
-    return getattr(_tls, "grad", True)
 
 
 def _use_torch_ops(x: Tensor) -> bool:
     """Which door the modules take to the kernels.  The torch.library custom ops (torch_ops.py: ``mi_restore::*_fwd`` / ``_bwd``
     with fake implementations) are what a tracer needs, so they are taken while torch.compile is tracing and whenever
-    MI_TORCH_OPS=1; eager execution takes the bare autograd.Function nodes - the same ``_block_forward`` / ``_block_backward``
+    MI_TORCH_OPS=1; eager execution takes the bare autograd node (_autograd.module_op) - the same function pairs
     underneath, without the dispatcher's per-call cost (MoCE-IR base, 3 500 launches per step, host-bound: 64.7 -> 51.8 ms per
     step; Restormer bs 32, GPU-bound: no difference).  MI_TORCH_OPS=0 forces the direct route."""
     if not x.is_cuda:
@@ -82,78 +46,66 @@ def _torch_ops():
 
 
 def block_apply(x: Tensor, heads: int, params) -> Tensor:
-    """One TransformerBlock / EncoderBlock with autograd: through mi_restore::transformer_block (default) or _BlockFn."""
+    """One TransformerBlock / EncoderBlock with autograd: through mi_restore::transformer_block (default) or the bare node."""
     if _use_torch_ops(x):
         return _torch_ops().transformer_block(x, heads, params)
-    return _apply(_BlockFn, x, heads, *params)
+    return module_op(_BlockOp(heads), (x,), params)
 
 
-class _LayerNormFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, weight, bias):
-        need = _grad_mode() and any(ctx.needs_input_grad)
-        y, mean, rstd = ops.ln_fwd(x, weight, bias, bias is not None, want_stats=need)
-        if need:
-            ctx.save_for_backward(x, weight, mean, rstd)
-            ctx.with_bias = bias is not None
-            ctx.mg = _main_grads((weight, bias))
-        return y
+# ---- module ops: the function pairs under _autograd.module_op AND under the torch.library ops of torch_ops.py ------------------
+class _LnOp:
+    """LayerNorm.forward (Restormer.py:60-70).  params = (weight, bias); saved = [mean, rstd]."""
 
-    @staticmethod
-    def backward(ctx, dy):
-        x, weight, mean, rstd = ctx.saved_tensors
-        acc = ctx.mg is not None
-        dw, db = ctx.mg if acc else (torch.empty_like(weight), torch.empty_like(weight) if ctx.with_bias else None)
-        dx = ops.ln_bwd(dy.contiguous(), x, weight, mean, rstd, None, ctx.with_bias, dw, db, acc)
-        if acc:
-            return dx, None, None
-        return dx, dw, db
+    def forward(self, acts, params, need):
+        y, mean, rstd = ops.ln_fwd(acts[0], params[0], params[1], params[1] is not None, want_stats=need)
+        return y, [mean, rstd]
+
+    def backward(self, acts, saved, dout, params, grads, acc):
+        return (ops.ln_bwd(dout, acts[0], params[0], saved[0], saved[1], None, params[1] is not None, grads[0], grads[1], acc),)
 
 
-class _AttentionFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, heads, *params):
-        need = _grad_mode() and any(ctx.needs_input_grad)
-        out, saved = ops.mdta_fwd(x, None, params, heads, need)
-        if need:
-            ctx.heads = heads
-            ctx.mg = _main_grads(params)
-            ctx.n_params = len(params)
-            ctx.save_for_backward(x, saved, *[p for p in params if p is not None])
-            ctx.present = [p is not None for p in params]
-        return out
+class _MdtaOp:
+    """Attention.forward (Restormer.py:99-132).  params: ops.mdta_fwd; saved = [the kernels' blob]."""
 
-    @staticmethod
-    def backward(ctx, dout):
-        x, saved, *rest = ctx.saved_tensors
-        it = iter(rest)
-        params = tuple(next(it) if pr else None for pr in ctx.present)
-        acc = ctx.mg is not None
-        grads = ctx.mg if acc else _fresh_grads(params)
-        dx = ops.mdta_bwd(x, dout.contiguous(), params, ctx.heads, saved, grads, acc)
-        return (dx, None) + tuple(None if acc else g for g in grads)
+    def __init__(self, heads):
+        self.heads = heads
+
+    def forward(self, acts, params, need):
+        out, blob = ops.mdta_fwd(acts[0], None, params, self.heads, need)
+        return out, [blob]
+
+    def backward(self, acts, saved, dout, params, grads, acc):
+        return (ops.mdta_bwd(acts[0], dout, params, self.heads, saved[0], grads, acc),)
 
 
-class _FeedForwardFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, *params):
-        need = _grad_mode() and any(ctx.needs_input_grad)
-        out, saved = ops.gdfn_fwd(x, None, params, need)
-        if need:
-            ctx.mg = _main_grads(params)
-            ctx.save_for_backward(x, saved, *[p for p in params if p is not None])
-            ctx.present = [p is not None for p in params]
-        return out
+class _GdfnOp:
+    """FeedForward.forward (Restormer.py:76-93).  params: ops.gdfn_fwd; saved = [the kernels' blob]."""
 
-    @staticmethod
-    def backward(ctx, dout):
-        x, saved, *rest = ctx.saved_tensors
-        it = iter(rest)
-        params = tuple(next(it) if pr else None for pr in ctx.present)
-        acc = ctx.mg is not None
-        grads = ctx.mg if acc else _fresh_grads(params)
-        dx = ops.gdfn_bwd(x, dout.contiguous(), params, saved, grads, acc)
-        return (dx,) + tuple(None if acc else g for g in grads)
+    def forward(self, acts, params, need):
+        out, blob = ops.gdfn_fwd(acts[0], None, params, need)
+        return out, [blob]
+
+    def backward(self, acts, saved, dout, params, grads, acc):
+        return (ops.gdfn_bwd(acts[0], dout, params, saved[0], grads, acc),)
+
+
+class _XmdtaOp:
+    """Cross-MDTA: q from acts[0], k and v from acts[1].  params: ops.xmdta_fwd; saved = [the kernels' blob]."""
+
+    def __init__(self, heads):
+        self.heads = heads
+
+    def forward(self, acts, params, need):
+        out, blob = ops.xmdta_fwd(acts[0], acts[1], None, params, self.heads, need)
+        return out, [blob]
+
+    def backward(self, acts, saved, dout, params, grads, acc):
+        return ops.xmdta_bwd(acts[0], acts[1], dout, params, self.heads, saved[0], grads, acc)
+
+
+def split_block(params):
+    """The block's parameter (and gradient) layout: norm1 (2), attention (7), norm2 (2), feed-forward (6)."""
+    return params[0:2], params[2:9], params[9:11], params[11:17]
 
 
 def _block_plan(x: Tensor, heads: int, params, need: bool) -> dict:
@@ -161,9 +113,9 @@ def _block_plan(x: Tensor, heads: int, params, need: bool) -> dict:
     implementation reads).  Half-blocks whose backward can end in the one-launch tail (weight gradient + W^T dY + LayerNorm
     backward + residual add, csrc/bwd_tail.hip) rebuild LN(x) from x and the statistics, so its output is not kept - and where
     the first 1x1 conv can normalise its input as it loads it (mi_*_fwd_ln) it is never written at all."""
-    n1, att, ffn = params[0:2], params[2:9], params[11:17]
+    n1, att, _, ffn = split_block(params)
     wb = n1[1] is not None
-    ks_a, hidden, ks_f = att[3].shape[-1], ffn[4].shape[1], ffn[2].shape[-1]
+    ks_a, hidden, ks_f = att[3].shape[-1], hidden_of(ffn), ffn[2].shape[-1]
     tail_ok = need and wb and not ops.env("MI_NO_BWD_TAIL")                                # (A/B switches)
     tail_a = bool(tail_ok and ops.mdta_bwd_ln_ok(x, heads, ks_a, att[2] is not None))
     tail_f = bool(tail_ok and ops.gdfn_bwd_ln_ok(x, hidden, ks_f, ffn[1] is not None))
@@ -182,79 +134,54 @@ def hidden_of(ffn) -> int:
     return ffn[4].shape[1]
 
 
-def _block_forward(x: Tensor, heads: int, params, need: bool):
-    """x + attn(norm1(x)) ; + ffn(norm2(.))   (Restormer.py:146-150) with both residual adds fused into the producing 1x1 GEMM
-    epilogues.  -> (out, saved): ``saved`` = [xn, y, yn, mean1, rstd1, mean2, rstd2, sv_a, sv_f] (entries None where the
-    backward does not need them; all None when ``need`` is False).  Shared by the autograd.Function (_BlockFn) and the
-    torch.library custom op (torch_ops.transformer_block_fwd)."""
-    n1, att, n2, ffn = params[0:2], params[2:9], params[9:11], params[11:17]
-    plan = _block_plan(x, heads, params, need)
-    wb = plan["wb"]
-    xn = yn = None
-    if plan["head_a"]:
-        y, sv_a, mean1, rstd1 = ops.mdta_fwd(x, x, att, heads, need, ln=(n1[0], n1[1], need))
-    else:
-        xn, mean1, rstd1 = ops.ln_fwd(x, n1[0], n1[1], wb, want_stats=need)
-        y, sv_a = ops.mdta_fwd(xn, x, att, heads, need)
-    if plan["fused_f"]:
-        # (packed per call: the weights change every step; one small launch)
-        out, sv_f, mean2, rstd2 = ops.gdfn_fused_fwd_train(y, ops.gdfn_fused_pack(y, n2[0], n2[1], tuple(ffn)), hidden_of(ffn), wb)
-    elif plan["head_f"]:
-        out, sv_f, mean2, rstd2 = ops.gdfn_fwd(y, y, ffn, need, ln=(n2[0], n2[1], need))
-    else:
-        yn, mean2, rstd2 = ops.ln_fwd(y, n2[0], n2[1], wb, want_stats=need)
-        out, sv_f = ops.gdfn_fwd(yn, y, ffn, need)
-    if not need:
-        return out, [None] * 9
-    # (a half-block on the tail keeps no LayerNorm output: that IS the flag the backward reads)
-    return out, [None if plan["tail_a"] else xn, y, None if plan["tail_f"] else yn, mean1, rstd1, mean2, rstd2, sv_a, sv_f]
+class _BlockOp:
+    """The whole TransformerBlock as one module op: x + attn(norm1(x)) ; + ffn(norm2(.))   (Restormer.py:146-150) with both
+    residual adds fused into the producing 1x1 GEMM epilogues.  params: split_block."""
 
+    def __init__(self, heads):
+        self.heads = heads
 
-def _block_backward(x: Tensor, saved, dout: Tensor, heads: int, params, grads, acc: bool) -> Tensor:
-    """Backward of _block_forward: dx; parameter gradients are written (acc: accumulated) into ``grads``."""
-    xn, y, yn, mean1, rstd1, mean2, rstd2, sv_a, sv_f = saved
-    n1, att, n2, ffn = params[0:2], params[2:9], params[9:11], params[11:17]
-    g1, ga, g2, gf = grads[0:2], grads[2:9], grads[9:11], grads[11:17]
-    wb = n1[1] is not None
-    dout = dout.contiguous()
-    if yn is None:                     # one-launch tail: weight gradient + W^T dY + LayerNorm backward + residual
-        dy = ops.gdfn_bwd(y, dout, ffn, sv_f, gf, acc, ln=(n2[0], n2[1], mean2, rstd2, dout, g2[0], g2[1]))
-    else:
-        dyn = ops.gdfn_bwd(yn, dout, ffn, sv_f, gf, acc)
-        dy = ops.ln_bwd(dyn, y, n2[0], mean2, rstd2, dout, wb, g2[0], g2[1], acc)
-    if xn is None:
-        return ops.mdta_bwd(x, dy, att, heads, sv_a, ga, acc, ln=(n1[0], n1[1], mean1, rstd1, dy, g1[0], g1[1]))
-    dxn = ops.mdta_bwd(xn, dy, att, heads, sv_a, ga, acc)
-    return ops.ln_bwd(dxn, x, n1[0], mean1, rstd1, dy, wb, g1[0], g1[1], acc)
+    def forward(self, acts, params, need):
+        """-> (out, saved): ``saved`` = [xn, y, yn, mean1, rstd1, mean2, rstd2, sv_a, sv_f] (entries None where the backward
+        does not need them; all None when ``need`` is False)."""
+        x, heads = acts[0], self.heads
+        n1, att, n2, ffn = split_block(params)
+        plan = _block_plan(x, heads, params, need)
+        wb = plan["wb"]
+        xn = yn = None
+        if plan["head_a"]:
+            y, sv_a, mean1, rstd1 = ops.mdta_fwd(x, x, att, heads, need, ln=(n1[0], n1[1], need))
+        else:
+            xn, mean1, rstd1 = ops.ln_fwd(x, n1[0], n1[1], wb, want_stats=need)
+            y, sv_a = ops.mdta_fwd(xn, x, att, heads, need)
+        if plan["fused_f"]:
+            # (packed per call: the weights change every step; one small launch)
+            out, sv_f, mean2, rstd2 = ops.gdfn_fused_fwd_train(y, ops.gdfn_fused_pack(y, n2[0], n2[1], tuple(ffn)), hidden_of(ffn), wb)
+        elif plan["head_f"]:
+            out, sv_f, mean2, rstd2 = ops.gdfn_fwd(y, y, ffn, need, ln=(n2[0], n2[1], need))
+        else:
+            yn, mean2, rstd2 = ops.ln_fwd(y, n2[0], n2[1], wb, want_stats=need)
+            out, sv_f = ops.gdfn_fwd(yn, y, ffn, need)
+        if not need:
+            return out, [None] * 9
+        # (a half-block on the tail keeps no LayerNorm output: that IS the flag the backward reads)
+        return out, [None if plan["tail_a"] else xn, y, None if plan["tail_f"] else yn, mean1, rstd1, mean2, rstd2, sv_a, sv_f]
 
-
-class _BlockFn(torch.autograd.Function):
-    """The whole TransformerBlock as one autograd node (the implementation under torch_ops.transformer_block, and the direct
-    route with MI_TORCH_OPS=0)."""
-
-    N_LN, N_ATT, N_FFN = 2, 7, 6
-
-    @staticmethod
-    def forward(ctx, x, heads, *params):
-        need = _grad_mode() and any(ctx.needs_input_grad)
-        out, saved = _block_forward(x, heads, params, need)
-        if need:
-            ctx.heads = heads
-            ctx.mg = _main_grads(params)
-            ctx.present = [p is not None for p in params]
-            ctx.save_for_backward(x, *saved, *[p for p in params if p is not None])
-        return out
-
-    @staticmethod
-    def backward(ctx, dout):
-        x, *rest = ctx.saved_tensors
-        saved, rest = rest[:9], rest[9:]
-        it = iter(rest)
-        params = tuple(next(it) if pr else None for pr in ctx.present)
-        acc = ctx.mg is not None
-        grads = ctx.mg if acc else _fresh_grads(params)
-        dx = _block_backward(x, saved, dout, ctx.heads, params, grads, acc)
-        return (dx, None) + tuple(None if acc else g for g in grads)
+    def backward(self, acts, saved, dout, params, grads, acc):
+        x, heads = acts[0], self.heads
+        xn, y, yn, mean1, rstd1, mean2, rstd2, sv_a, sv_f = saved
+        n1, att, n2, ffn = split_block(params)
+        g1, ga, g2, gf = split_block(grads)
+        wb = n1[1] is not None
+        if yn is None:                     # one-launch tail: weight gradient + W^T dY + LayerNorm backward + residual
+            dy = ops.gdfn_bwd(y, dout, ffn, sv_f, gf, acc, ln=(n2[0], n2[1], mean2, rstd2, dout, g2[0], g2[1]))
+        else:
+            dyn = ops.gdfn_bwd(yn, dout, ffn, sv_f, gf, acc)
+            dy = ops.ln_bwd(dyn, y, n2[0], mean2, rstd2, dout, wb, g2[0], g2[1], acc)
+        if xn is None:
+            return (ops.mdta_bwd(x, dy, att, heads, sv_a, ga, acc, ln=(n1[0], n1[1], mean1, rstd1, dy, g1[0], g1[1])),)
+        dxn = ops.mdta_bwd(xn, dy, att, heads, sv_a, ga, acc)
+        return (ops.ln_bwd(dxn, x, n1[0], mean1, rstd1, dy, wb, g1[0], g1[1], acc),)
 
 
 def _fused_gdfn_pack(holder, like: Tensor, ln_params, ffn_params) -> Tensor:
@@ -356,7 +283,7 @@ def fp8_projections(model, mode: Optional[str]) -> None:
 
 def _block_calibrate(block, x: Tensor, params, cal: Tensor) -> Tensor:
     """The block's bf16 forward, unfused, recording the magnitudes the four projections read."""
-    n1, att, n2, ffn = params[0:2], params[2:9], params[9:11], params[11:17]
+    n1, att, n2, ffn = split_block(params)
     wb = n1[1] is not None
     Cc = x.shape[1]
     xn, _, _ = ops.ln_fwd(x, n1[0], n1[1], wb, want_stats=False)
@@ -379,7 +306,7 @@ def _block_infer(block, x: Tensor, params) -> Tensor:
     cal = getattr(block, "_f8_cal", None)
     if cal is not None:
         return _block_calibrate(block, x, params, cal)
-    n1, att, n2, ffn = params[0:2], params[2:9], params[9:11], params[11:17]
+    n1, att, n2, ffn = split_block(params)
     wb = n1[1] is not None
     heads = block.attn.num_heads
     mode = getattr(block, "_f8_mode", None) if x.dtype == torch.bfloat16 else None
@@ -434,29 +361,6 @@ def _gpu_block_input(x: Tensor) -> None:
         raise RuntimeError("image_restoration_amd ops need contiguous NCHW tensors")
 
 
-class _CrossAttentionFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, y, heads, *params):
-        need = _grad_mode() and any(ctx.needs_input_grad)
-        out, saved = ops.xmdta_fwd(x, y, None, params, heads, need)
-        if need:
-            ctx.heads = heads
-            ctx.mg = _main_grads(params)
-            ctx.present = [p is not None for p in params]
-            ctx.save_for_backward(x, y, saved, *[p for p in params if p is not None])
-        return out
-
-    @staticmethod
-    def backward(ctx, dout):
-        x, y, saved, *rest = ctx.saved_tensors
-        it = iter(rest)
-        params = tuple(next(it) if pr else None for pr in ctx.present)
-        acc = ctx.mg is not None
-        grads = ctx.mg if acc else _fresh_grads(params)
-        dx, dy = ops.xmdta_bwd(x, y, dout.contiguous(), params, ctx.heads, saved, grads, acc)
-        return (dx, dy, None) + tuple(None if acc else g for g in grads)
-
-
 class _DwConvFn(torch.autograd.Function):
     """Stand-alone depthwise k x k conv (stride 1, pad k/2): moce_ir.py:377-381 FFTAttention q_dwconv / kv_dwconv."""
 
@@ -498,11 +402,11 @@ class _Conv1x1Fn(torch.autograd.Function):
         k1 = x1.shape[1]
         w2 = weight.reshape(weight.shape[0], -1)
         # the two panels' weights are column blocks of one [M, K1+K2] matrix, used in place (row stride K1+K2)
-        dx1 = _dgrad_panel(dy, w2, 0, k1)
-        dx2 = _dgrad_panel(dy, w2, k1, w2.shape[1] - k1) if x2 is not None else None
+        dx1 = ops.conv1x1_dgrad_panel(dy, w2, 0, k1)
+        dx2 = ops.conv1x1_dgrad_panel(dy, w2, k1, w2.shape[1] - k1) if x2 is not None else None
         acc = ctx.mg is not None
         dw = ctx.mg[0] if acc else torch.empty_like(weight)
-        _wgrad_panels(dy, x1, x2, dw.reshape(w2.shape), acc)
+        ops.conv1x1_wgrad_panels(dy, x1, x2, dw.reshape(w2.shape), acc)
         db = None
         if ctx.has_bias:
             if acc:
@@ -517,45 +421,6 @@ def _conv1x1_module(x1: Tensor, x2: Optional[Tensor], conv: nn.Conv2d) -> Tensor
     y = _apply(_Conv1x1Fn, x1, x2, conv.weight, conv.bias)
     _fire_forward_hooks(conv, (x1, x2), y)
     return y
-
-
-def _dgrad_panel(dy: Tensor, w2: Tensor, k0: int, k: int) -> Tensor:
-    """dx[:, k0:k0+k] = W[:, k0:k0+k]^T dy  using the column block in place (row stride stays K1+K2)."""
-    import ctypes as C
-    from . import _lib as L
-    B, M, H, W = dy.shape
-    N = H * W
-    dx = torch.empty((B, k, H, W), dtype=dy.dtype, device=dy.device)
-    d = L.PwDesc()
-    d.x1, d.x1_bs, d.k1 = dy.data_ptr(), M * N, M
-    d.w = w2.data_ptr() + 4 * k0
-    d.w_sm, d.w_sk = 1, w2.shape[1]
-    d.y, d.y_bs = dx.data_ptr(), k * N
-    d.m, d.n, d.batch, d.groups, d.dtype = k, N, B, 1, ops._dt(dy)
-    ops.pw_gemm_desc(d, dy.device)
-    return dx
-
-
-def _wgrad_panels(dy: Tensor, x1: Tensor, x2: Optional[Tensor], dw2: Tensor, accumulate: bool) -> None:
-    import ctypes as C
-    from . import _lib as L
-    B, M, H, W = dy.shape
-    N = H * W
-    ld = dw2.shape[1]
-    k0 = 0
-    for xp in (x1, x2):
-        if xp is None:
-            continue
-        k = xp.shape[1]
-        d = L.GramDesc()
-        d.a, d.a_bs, d.ma = dy.data_ptr(), M * N, M
-        d.b, d.b_bs, d.mb = xp.data_ptr(), k * N, k
-        d.n, d.batch, d.groups, d.dtype = N, B, 1, ops._dt(dy)
-        d.sum_batch, d.accumulate = 1, int(accumulate)
-        d.out, d.out_ld, d.out_zs = dw2.data_ptr() + 4 * k0, ld, 0
-        ws = ops._blob(L.lib().mi_gram_workspace(C.byref(d)), dy.device)
-        L.check(L.lib().mi_gram(C.byref(d), ws.data_ptr(), ops._stream()), "gram(wgrad panel)")
-        k0 += k
 
 
 # ======================================================================================
@@ -601,7 +466,7 @@ class LayerNorm(nn.Module):
     def forward(self, x):
         if _use_torch_ops(x):
             return _torch_ops().layernorm(x, *self._params())
-        return _apply(_LayerNormFn, x, *self._params())
+        return module_op(_LnOp(), (x,), self._params())
 
 
 class FeedForward(nn.Module):
@@ -622,7 +487,7 @@ class FeedForward(nn.Module):
     def forward(self, x):
         if _use_torch_ops(x):
             return _torch_ops().gdfn(x, self._params())
-        return _apply(_FeedForwardFn, x, *self._params())
+        return module_op(_GdfnOp(), (x,), self._params())
 
 
 class Attention(nn.Module):
@@ -643,7 +508,7 @@ class Attention(nn.Module):
     def forward(self, x):
         if _use_torch_ops(x):
             return _torch_ops().mdta(x, self.num_heads, self._params())
-        return _apply(_AttentionFn, x, self.num_heads, *self._params())
+        return module_op(_MdtaOp(self.num_heads), (x,), self._params())
 
 
 class TransformerBlock(nn.Module):
@@ -862,8 +727,8 @@ def _up_cat(up: "Upsample", x: Tensor, skip: Tensor) -> Tensor:
     return _apply(_UpCatFn, z, skip)
 
 
-def _stage(dim, heads, n, ffn, bias, ln):
-    return nn.Sequential(*[TransformerBlock(dim=dim, num_heads=heads, ffn_expansion_factor=ffn, bias=bias,
+def _stage(dim, heads, n, ffn, bias, ln, block=TransformerBlock):
+    return nn.Sequential(*[block(dim=dim, num_heads=heads, ffn_expansion_factor=ffn, bias=bias,
                                             LayerNorm_type=ln) for _ in range(n)])
 
 

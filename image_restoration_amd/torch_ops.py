@@ -11,10 +11,10 @@ forward / backward pair with a fake (meta) implementation and ``register_autogra
 
 The forward ops return ``[out, saved...]``: what the backward needs (LayerNorm statistics, the kernels' saved-for-backward
 blobs) are op OUTPUTS, as the custom-op autograd contract wants; ``register_autograd`` stores them and calls the backward op.
-Under the ops sit the same helpers the ``torch.autograd.Function`` nodes of ``restormer.py`` use (``_block_forward`` /
-``_block_backward``, ``ops.mdta_fwd`` ...): one implementation, two front doors
+Under the ops sit the same function pairs the bare autograd node (``_autograd.module_op``) runs (``restormer._LnOp``,
+``_MdtaOp``, ``_GdfnOp``, ``_BlockOp``): one implementation, two front doors
 (modules route through these ops while torch.compile traces and with ``MI_TORCH_OPS=1``; eager calls take the bare
-autograd.Function nodes over the same implementation: restormer._use_torch_ops).
+autograd node over the same implementation: restormer._use_torch_ops).
 
 Arguments shared by all forward ops: ``need`` - build what backward needs (the caller's grad mode; an op body always runs
 with grad mode off and cannot see it); ``accumulate`` (backward ops) - parameter gradients are ADDED into each parameter's
@@ -28,8 +28,9 @@ from typing import List, Optional, Sequence
 import torch
 from torch.library import custom_op
 
-from . import _lib as L
 from . import ops
+from . import restormer as R
+from ._autograd import _present, _refill, _squeeze
 
 Tensor = torch.Tensor
 NS = "mi_restore"
@@ -96,11 +97,34 @@ def _blob(x: Tensor, nbytes: int) -> Tensor:
     return x.new_empty(max(int(nbytes), 256), dtype=torch.uint8)
 
 
-def _register(name: str, fwd_schema: str, bwd_schema: str, fwd_impl, fwd_fake, bwd_impl, bwd_fake, n_params: int,
-              n_lead: int, n_tail: int):
-    """One forward / backward op pair.  Forward inputs: ``n_lead`` leading arguments (tensors first), ``n_params`` parameters,
-    ``n_tail`` trailing scalars.  The backward op takes (dout, *forward inputs without the trailing scalars, saved[], accumulate)
-    and returns [d(lead tensors)..., d(params)...]."""
+def _register(name: str, pnames: Sequence[str], popt: Sequence[bool], pair, n_saved: int, fake_saved, heads: bool = False):
+    """One forward / backward op pair over the function pair ``pair(*scalars)`` (scalars: ``heads``, where the op has it).
+    Forward: (x, scalars, parameters ``pnames`` - optional where ``popt`` -, need) -> [out, saved...]; ``fake_saved(x, *scalars,
+    params)`` gives the ``n_saved`` saved tensors' stand-ins.  Backward: (dout, x, scalars, parameters, saved[], accumulate) ->
+    [dx, d(params)...]."""
+    n, k = len(pnames), int(heads)
+    lead = "Tensor x, int heads, " if heads else "Tensor x, "
+    fwd_schema = "(" + lead + _schema(pnames, popt, ", bool need")[1:]
+    bwd_schema = "(Tensor dout, " + lead + _schema(pnames, popt, ", Tensor[] saved, bool accumulate")[1:]
+    n_lead, n_tail = 1 + k, 1
+
+    def fwd_impl(x, *rest):
+        out, saved = pair(*rest[:k]).forward((x,), rest[k:k + n], rest[k + n])
+        return [out] + _pack(saved, x)
+
+    def fwd_fake(x, *rest):
+        saved = fake_saved(x, *rest[:k], rest[k:k + n]) if rest[k + n] else [_e(x) for _ in range(n_saved)]
+        return [torch.empty_like(x)] + saved
+
+    def bwd_impl(dout, x, *rest):
+        params, saved, accumulate = rest[k:k + n], rest[k + n], rest[k + n + 1]
+        grads = _grads_for(params, accumulate)
+        dx, = pair(*rest[:k]).backward((x,), _unpack(saved), dout, params, grads, accumulate)
+        return [dx] + _grad_outputs(params, grads, accumulate, x)
+
+    def bwd_fake(dout, x, *rest):
+        return [torch.empty_like(x)] + _fake_grads(rest[k:k + n], rest[k + n + 1], x)
+
     fwd = custom_op(f"{NS}::{name}_fwd", mutates_args=(), schema=fwd_schema)(fwd_impl)
     fwd.register_fake(fwd_fake)
     bwd = custom_op(f"{NS}::{name}_bwd", mutates_args=(), schema=bwd_schema)(bwd_impl)
@@ -108,10 +132,10 @@ def _register(name: str, fwd_schema: str, bwd_schema: str, fwd_impl, fwd_fake, b
     bwd_op = getattr(getattr(torch.ops, NS), f"{name}_bwd")
 
     def setup(ctx, inputs, output):
-        lead, params = inputs[:n_lead], inputs[n_lead:n_lead + n_params]
+        lead, params = inputs[:n_lead], inputs[n_lead:n_lead + n]
         ctx.scalars = [v for v in lead if not isinstance(v, Tensor)]
         ctx.lead_is_tensor = [isinstance(v, Tensor) for v in lead]
-        ctx.n_params_present = [p is not None for p in params]
+        ctx.n_params_present = _present(params)
         # The tensors autograd hands to setup_context are not the caller's Parameter objects, so the trainer's per-parameter
         # ``main_grad`` buffers (attributes of those objects) are picked up from the wrapper's hand-off (_MAIN_GRADS) instead.
         ctx.mg = _MAIN_GRADS.pop("next", None)
@@ -119,201 +143,63 @@ def _register(name: str, fwd_schema: str, bwd_schema: str, fwd_impl, fwd_fake, b
         # them to be, and unused-gradient zeros must not be materialised for them (GB-sized memsets per block otherwise)
         ctx.set_materialize_grads(False)
         ctx.mark_non_differentiable(*output[1:])
-        ctx.save_for_backward(*[v for v in lead if isinstance(v, Tensor)], *[p for p in params if p is not None], *output[1:])
+        ctx.save_for_backward(*[v for v in lead if isinstance(v, Tensor)], *_squeeze(params), *output[1:])
 
     def backward(ctx, grads):
         dout = grads[0]
         if dout is None:
-            return (None,) * (n_lead + n_params + n_tail)
+            return (None,) * (n_lead + n + n_tail)
         tens = list(ctx.saved_tensors)
         n_lt = sum(ctx.lead_is_tensor)
         n_pp = sum(ctx.n_params_present)
-        lead_t, ptens, saved = tens[:n_lt], tens[n_lt:n_lt + n_pp], tens[n_lt + n_pp:]
-        it = iter(ptens)
-        params = [next(it) if pr else None for pr in ctx.n_params_present]
+        lead_t, saved = tens[:n_lt], tens[n_lt + n_pp:]
+        params = _refill(ctx.n_params_present, tens[n_lt:n_lt + n_pp])
         accumulate = ctx.mg is not None
         _MAIN_GRADS["bwd"] = ctx.mg
         try:
             res = bwd_op(dout.contiguous(), *lead_t, *ctx.scalars, *params, saved, accumulate)
         finally:
             _MAIN_GRADS.pop("bwd", None)
-        d_lead_t = list(res[:n_lt])
-        d_par = res[n_lt:]
-        out = []
-        it = iter(d_lead_t)
-        for is_t in ctx.lead_is_tensor:
-            out.append(next(it) if is_t else None)
-        for p, g in zip(params, d_par):
-            out.append(None if (p is None or accumulate) else g)
-        return tuple(out) + (None,) * n_tail
+        d_par = [None if (p is None or accumulate) else g for p, g in zip(params, res[n_lt:])]
+        return tuple(_refill(ctx.lead_is_tensor, res[:n_lt])) + tuple(d_par) + (None,) * n_tail
 
     fwd.register_autograd(backward, setup_context=setup)
     return getattr(getattr(torch.ops, NS), f"{name}_fwd"), bwd_op
 
 
-# ------------------------------------------------------------------------------------------------ LayerNorm
 _LN_P = ("weight", "bias")
 _LN_O = (False, True)
-
-
-def _ln_fwd(x, weight, bias, need):
-    y, mean, rstd = ops.ln_fwd(x, weight, bias, bias is not None, want_stats=need)
-    return [y] + _pack([mean, rstd], x)
-
-
-def _ln_fwd_fake(x, weight, bias, need):
-    return [torch.empty_like(x)] + ([_stats(x), _stats(x)] if need else [_e(x), _e(x)])
-
-
-def _ln_bwd(dout, x, weight, bias, saved, accumulate):
-    mean, rstd = saved
-    params = (weight, bias)
-    dw, db = _grads_for(params, accumulate)
-    dx = ops.ln_bwd(dout, x, weight, mean, rstd, None, bias is not None, dw, db, accumulate)
-    return [dx] + _grad_outputs(params, (dw, db), accumulate, x)
-
-
-def _ln_bwd_fake(dout, x, weight, bias, saved, accumulate):
-    return [torch.empty_like(x)] + _fake_grads((weight, bias), accumulate, x)
-
-
-layernorm_fwd, layernorm_bwd = _register(
-    "layernorm",
-    _schema(("x",) + _LN_P, (False,) + _LN_O, ", bool need"),
-    _schema(("dout", "x") + _LN_P, (False, False) + _LN_O, ", Tensor[] saved, bool accumulate"),
-    _ln_fwd, _ln_fwd_fake, _ln_bwd, _ln_bwd_fake, n_params=2, n_lead=1, n_tail=1)
-
-# ------------------------------------------------------------------------------------------------ MDTA
 _AT_P = ("temperature", "qkv_w", "qkv_b", "dw_w", "dw_b", "proj_w", "proj_b")
 _AT_O = (False, False, True, False, True, False, True)
-
-
-def _mdta_saved_bytes(x: Tensor, heads: int, ks: int) -> int:
-    B, Cc, H, W = x.shape
-    import ctypes as C
-    s = L.MdtaShape(B, Cc, heads, H, W, L.MI_BF16 if x.dtype == torch.bfloat16 else L.MI_F32, ks)
-    return int(L.lib().mi_mdta_saved_bytes(C.byref(s)))
-
-
-def _gdfn_saved_bytes(x: Tensor, hidden: int, ks: int) -> int:
-    B, Cc, H, W = x.shape
-    import ctypes as C
-    s = L.GdfnShape(B, Cc, hidden, H, W, L.MI_BF16 if x.dtype == torch.bfloat16 else L.MI_F32, ks,
-                    1 if ops.env("MI_GDFN_STORE_Y") else 0)
-    return int(L.lib().mi_gdfn_saved_bytes(C.byref(s)))
-
-
-def _mdta_fwd(x, heads, *rest):
-    params, need = rest[:7], rest[7]
-    out, saved = ops.mdta_fwd(x, None, params, heads, need)
-    return [out] + _pack([saved], x)
-
-
-def _mdta_fwd_fake(x, heads, *rest):
-    params, need = rest[:7], rest[7]
-    return [torch.empty_like(x), _blob(x, _mdta_saved_bytes(x, heads, params[3].shape[-1])) if need else _e(x)]
-
-
-def _mdta_bwd(dout, x, heads, *rest):
-    params, saved, accumulate = rest[:7], rest[7], rest[8]
-    grads = _grads_for(params, accumulate)
-    dx = ops.mdta_bwd(x, dout, params, heads, saved[0], grads, accumulate)
-    return [dx] + _grad_outputs(params, grads, accumulate, x)
-
-
-def _mdta_bwd_fake(dout, x, heads, *rest):
-    params, accumulate = rest[:7], rest[8]
-    return [torch.empty_like(x)] + _fake_grads(params, accumulate, x)
-
-
-mdta_fwd, mdta_bwd = _register(
-    "mdta",
-    "(Tensor x, int heads, " + _schema(_AT_P, _AT_O, ", bool need")[1:],
-    "(Tensor dout, Tensor x, int heads, " + _schema(_AT_P, _AT_O, ", Tensor[] saved, bool accumulate")[1:],
-    _mdta_fwd, _mdta_fwd_fake, _mdta_bwd, _mdta_bwd_fake, n_params=7, n_lead=2, n_tail=1)
-
-# ------------------------------------------------------------------------------------------------ GDFN
 _FF_P = ("in_w", "in_b", "dw_w", "dw_b", "out_w", "out_b")
 _FF_O = (False, True, False, True, False, True)
-
-
-def _gdfn_fwd(x, *rest):
-    params, need = rest[:6], rest[6]
-    out, saved = ops.gdfn_fwd(x, None, params, need)
-    return [out] + _pack([saved], x)
-
-
-def _gdfn_fwd_fake(x, *rest):
-    params, need = rest[:6], rest[6]
-    return [torch.empty_like(x), _blob(x, _gdfn_saved_bytes(x, params[4].shape[1], params[2].shape[-1])) if need else _e(x)]
-
-
-def _gdfn_bwd(dout, x, *rest):
-    params, saved, accumulate = rest[:6], rest[6], rest[7]
-    grads = _grads_for(params, accumulate)
-    dx = ops.gdfn_bwd(x, dout, params, saved[0], grads, accumulate)
-    return [dx] + _grad_outputs(params, grads, accumulate, x)
-
-
-def _gdfn_bwd_fake(dout, x, *rest):
-    params, accumulate = rest[:6], rest[7]
-    return [torch.empty_like(x)] + _fake_grads(params, accumulate, x)
-
-
-gdfn_fwd, gdfn_bwd = _register(
-    "gdfn",
-    _schema(("x",) + _FF_P, (False,) + _FF_O, ", bool need"),
-    _schema(("dout", "x") + _FF_P, (False, False) + _FF_O, ", Tensor[] saved, bool accumulate"),
-    _gdfn_fwd, _gdfn_fwd_fake, _gdfn_bwd, _gdfn_bwd_fake, n_params=6, n_lead=1, n_tail=1)
-
-# ------------------------------------------------------------------------------------------------ TransformerBlock
 _BK_P = (("n1_w", "n1_b", "temperature", "qkv_w", "qkv_b", "qkv_dw_w", "qkv_dw_b", "proj_w", "proj_b", "n2_w", "n2_b")
          + ("in_w", "in_b", "ffn_dw_w", "ffn_dw_b", "out_w", "out_b"))
 _BK_O = ((False, True) + _AT_O + (False, True) + _FF_O)
 
 
-def _block_fwd(x, heads, *rest):
-    from . import restormer as R
-    params, need = rest[:17], rest[17]
-    out, saved = R._block_forward(x, heads, params, need)
-    return [out] + _pack(saved, x)
+def _mdta_blob(x, heads, att):
+    return _blob(x, ops.mdta_saved_bytes(x, heads, att[3].shape[-1]))
 
 
-def _block_fwd_fake(x, heads, *rest):
-    from . import restormer as R
-    params, need = rest[:17], rest[17]
-    out = torch.empty_like(x)
-    if not need:
-        return [out] + [_e(x) for _ in range(9)]
-    plan = R._block_plan(x, heads, params, need)
-    att, ffn = params[2:9], params[11:17]
-    return [out,
-            _e(x) if plan["tail_a"] else torch.empty_like(x),                  # xn
+def _gdfn_blob(x, ffn):
+    return _blob(x, ops.gdfn_saved_bytes(x, R.hidden_of(ffn), ffn[2].shape[-1]))
+
+
+def _block_fake_saved(x, heads, params):
+    plan = R._block_plan(x, heads, params, True)
+    _, att, _, ffn = R.split_block(params)
+    return [_e(x) if plan["tail_a"] else torch.empty_like(x),                  # xn
             torch.empty_like(x),                                               # y
             _e(x) if plan["tail_f"] else torch.empty_like(x),                  # yn
-            _stats(x), _stats(x), _stats(x), _stats(x),
-            _blob(x, _mdta_saved_bytes(x, heads, att[3].shape[-1])),
-            _blob(x, _gdfn_saved_bytes(x, ffn[4].shape[1], ffn[2].shape[-1]))]
+            _stats(x), _stats(x), _stats(x), _stats(x), _mdta_blob(x, heads, att), _gdfn_blob(x, ffn)]
 
 
-def _block_bwd(dout, x, heads, *rest):
-    from . import restormer as R
-    params, saved, accumulate = rest[:17], rest[17], rest[18]
-    grads = _grads_for(params, accumulate)
-    dx = R._block_backward(x, _unpack(saved), dout, heads, params, grads, accumulate)
-    return [dx] + _grad_outputs(params, grads, accumulate, x)
-
-
-def _block_bwd_fake(dout, x, heads, *rest):
-    params, accumulate = rest[:17], rest[18]
-    return [torch.empty_like(x)] + _fake_grads(params, accumulate, x)
-
-
-transformer_block_fwd, transformer_block_bwd = _register(
-    "transformer_block",
-    "(Tensor x, int heads, " + _schema(_BK_P, _BK_O, ", bool need")[1:],
-    "(Tensor dout, Tensor x, int heads, " + _schema(_BK_P, _BK_O, ", Tensor[] saved, bool accumulate")[1:],
-    _block_fwd, _block_fwd_fake, _block_bwd, _block_bwd_fake, n_params=17, n_lead=2, n_tail=1)
+layernorm_fwd, layernorm_bwd = _register("layernorm", _LN_P, _LN_O, R._LnOp, 2, lambda x, params: [_stats(x), _stats(x)])
+mdta_fwd, mdta_bwd = _register("mdta", _AT_P, _AT_O, R._MdtaOp, 1, lambda x, heads, att: [_mdta_blob(x, heads, att)], heads=True)
+gdfn_fwd, gdfn_bwd = _register("gdfn", _FF_P, _FF_O, R._GdfnOp, 1, lambda x, ffn: [_gdfn_blob(x, ffn)])
+transformer_block_fwd, transformer_block_bwd = _register("transformer_block", _BK_P, _BK_O, R._BlockOp, 9, _block_fake_saved,
+                                                         heads=True)
 
 OPS = {"layernorm": (layernorm_fwd, layernorm_bwd), "mdta": (mdta_fwd, mdta_bwd), "gdfn": (gdfn_fwd, gdfn_bwd),
        "transformer_block": (transformer_block_fwd, transformer_block_bwd)}
