@@ -977,16 +977,7 @@ static FmWs fm_ws_layout(const mi_mdta_shape* s, void* base) {
   w.nrm = cv.take<float>(Z * 2 * c * sizeof(float));
   w.M = cv.take<float>(B * C * C * sizeof(float));
   w.Mb = cv.take(B * C * C * 2);                          // bf16 M_b for the per-image-weight GEMM (mi_pw_desc.w_b16)
-  {
-    mi_pw_desc d;
-    memset(&d, 0, sizeof(d));
-    d.x1 = (void*)256; d.x1_bs = (int64_t)C * N; d.k1 = (int)C;
-    d.w = (const float*)256; d.w_sm = (int64_t)C; d.w_sk = 1; d.w_bs = (int64_t)C * C;
-    d.r = (void*)256; d.r_bs = (int64_t)C * N;
-    d.y = (void*)256; d.y_bs = (int64_t)C * N;
-    d.m = (int)C; d.n = (int64_t)N; d.batch = (int)B; d.groups = 1; d.dtype = s->dtype;
-    w.pw_ws = cv.take(mi_pw_gemm_workspace(&d));
-  }
+  w.pw_ws = cv.take(pw_ws_bytes(per_image(probe1x1(s->C, s->C, false, s->B, (int64_t)N, s->dtype))));
   w.v = cv.take(align_up(B * C * N * 2, 256));
   w.bytes = cv.off;
   return w;
@@ -1137,14 +1128,6 @@ extern "C" int mi_mdta_fused_fwd(const mi_mdta_shape* s, const mi_mdta_params* p
   }
   MI_TRY(launch_attn_fold(w.graw, w.ss, p->temperature, p->proj_w, w.P, w.A, w.nrm, w.M, s->B, s->C, s->heads, st, w.Mb, nullptr));
   const int64_t N = (int64_t)s->H * s->W;
-  mi_pw_desc d;
-  memset(&d, 0, sizeof(d));
-  d.x1 = w.v; d.x1_bs = (int64_t)s->C * N; d.k1 = s->C;
-  d.w = w.M; d.w_sm = s->C; d.w_sk = 1; d.w_bs = (int64_t)s->C * s->C;
-  d.w_b16 = w.Mb; d.w_b16_sm = s->C;
-  d.bias = p->proj_b;
-  d.r = residual; d.r_bs = (int64_t)s->C * N;
-  d.y = out; d.y_bs = (int64_t)s->C * N;
-  d.m = s->C; d.n = N; d.batch = s->B; d.groups = 1; d.dtype = s->dtype;
+  const mi_pw_desc d = per_image(conv1x1(w.v, s->C, w.M, false, s->C, p->proj_b, residual, out, s->C, s->B, N, s->dtype), w.Mb);
   return mi_pw_gemm(&d, w.pw_ws, stream);
 }

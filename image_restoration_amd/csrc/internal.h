@@ -1,5 +1,7 @@
 // Internal launchers shared between translation units (not part of the C-ABI).
 #pragma once
+#include <initializer_list>
+
 #include "common.h"
 
 namespace mi {
@@ -80,4 +82,64 @@ int pw_lds_launch(const mi_pw_desc* d, void* ws, hipStream_t st);
 // ---- fused GDFN forward, training form (fused_gdfn.hip): also writes h0 [B][2h][H][W] and g [B][h][H][W] ----
 int fused_gdfn_fwd_save(const mi_gdfn_fused_shape* s, const void* pack, const void* y, void* out, float* mean, float* rstd,
                         void* h0, void* g, hipStream_t st);
+
+// ---- host vocabulary of the module launch sequences (modules.hip, mefc.hip, fused_mdta.hip) ----
+static inline size_t fbytes(size_t n) { return align_up(n * sizeof(float), 256); }
+static inline size_t tbytes(size_t n, int dt) { return align_up(n * dtype_size(dt), 256); }
+static inline size_t max_of(std::initializer_list<size_t> v) {
+  size_t m = 0;
+  for (size_t x : v) m = x > m ? x : m;
+  return m;
+}
+// plain 1x1 conv: y[B,M,N] = W[M,K] x[B,K,N] (+bias) (+res);  transposed: W given as [K,M] used as its transpose.
+// x_bs / y_bs: batch strides in elements where x / y are channel slices of wider tensors (0: dense, K*N / M*N).
+static inline mi_pw_desc conv1x1(const void* x, int K, const float* w, bool transposed, int w_ld, const float* bias,
+                                 const void* res, void* y, int M, int B, int64_t N, int dtype, int64_t x_bs = 0, int64_t y_bs = 0) {
+  mi_pw_desc d;
+  memset(&d, 0, sizeof(d));
+  d.x1 = x; d.x1_bs = x_bs ? x_bs : (int64_t)K * N; d.k1 = K;
+  d.w = w;
+  if (transposed) { d.w_sm = 1; d.w_sk = w_ld; } else { d.w_sm = w_ld; d.w_sk = 1; }
+  d.bias = bias;
+  d.r = res; d.r_bs = (int64_t)M * N;
+  d.y = y; d.y_bs = y_bs ? y_bs : (int64_t)M * N;
+  d.m = M; d.n = N; d.batch = B; d.groups = 1; d.dtype = dtype;
+  return d;
+}
+// the same with one M x K matrix per image; w_b16: optional bf16 image of the matrices as the GEMM reads them ([B][M][K])
+static inline mi_pw_desc per_image(mi_pw_desc d, const void* w_b16 = nullptr) {
+  d.w_bs = (int64_t)d.m * d.k1;
+  if (w_b16) { d.w_b16 = w_b16; d.w_b16_sm = d.k1; }
+  return d;
+}
+// weight gradient of a 1x1 conv: out[m,k] (+)= sum_b dy[b] x[b]^T;  sum_batch = 0: one m x k product per image instead
+static inline mi_gram_desc wgrad_gram(const void* dy, int m, const void* x, int k, int B, int64_t N, int dtype, float* out,
+                                      int accumulate, int sum_batch = 1, int64_t dy_bs = 0, int64_t x_bs = 0) {
+  mi_gram_desc g;
+  memset(&g, 0, sizeof(g));
+  g.a = dy; g.a_bs = dy_bs ? dy_bs : (int64_t)m * N; g.ma = m;
+  g.b = x; g.b_bs = x_bs ? x_bs : (int64_t)k * N; g.mb = k;
+  g.n = N; g.batch = B; g.groups = 1; g.dtype = dtype;
+  g.sum_batch = sum_batch; g.accumulate = accumulate; g.out = out; g.out_ld = k; g.out_zs = sum_batch ? 0 : (int64_t)m * k;
+  return g;
+}
+// Workspaces are sized, and coverage is answered, before any tensor exists.  The planners (pw_plan, gram_plan) read shapes,
+// strides and whether the operands are 16-byte aligned, never the memory: one aligned placeholder stands in for every pointer.
+static void* const PROBE_PTR = (void*)256;
+static inline mi_pw_desc probe1x1(int K, int M, bool transposed, int B, int64_t N, int dtype, int64_t x_bs = 0, int64_t y_bs = 0) {
+  return conv1x1(PROBE_PTR, K, (const float*)PROBE_PTR, transposed, transposed ? M : K, nullptr, nullptr, PROBE_PTR, M, B, N, dtype,
+                 x_bs, y_bs);
+}
+static inline mi_gram_desc probe_wgrad(int m, int k, int B, int64_t N, int dtype, int sum_batch = 1, int64_t dy_bs = 0,
+                                       int64_t x_bs = 0) {
+  return wgrad_gram(PROBE_PTR, m, PROBE_PTR, k, B, N, dtype, (float*)PROBE_PTR, 0, sum_batch, dy_bs, x_bs);
+}
+static inline size_t pw_ws_bytes(const mi_pw_desc& d) { return mi_pw_gemm_workspace(&d); }
+static inline size_t gram_ws_bytes(const mi_gram_desc& d) { return mi_gram_workspace(&d); }
+// Backward of a 1x1 conv y = W x (+ b) whose input gradient leaves the module: dw (+)= sum_b dy x^T, db (+)= sum dy (optional),
+// dx = W^T dy.  dy [B,M,N], x and dx [B,K,N], w [M,K].  fork: run the Gram and the bias sum beside the GEMM where MI_CO_STREAM
+// asks for it (modules.hip); cross-MDTA and MEFC pass false: they never forked, and the switch must not change their streams.
+__attribute__((visibility("hidden")))   // (the library's dynamic symbol list stays as it was)
+int conv1x1_bwd_input(const void* dy, int M, const void* x, int K, const float* w, float* dw, float* db, void* dx, int B, int64_t N,
+                      int dtype, int accumulate, void* gram_ws, void* cs_ws, void* pw_ws, hipStream_t st, bool fork);
 }  // namespace mi

@@ -492,43 +492,12 @@ static int mf_wgrad(const void* x, int64_t x_bs, const void* g, int64_t g_bs, fl
 }
 
 // ------------------------------------------------------------------ host side: layouts
-static size_t mf_fb(size_t n) { return align_up(n * sizeof(float), 256); }
-static size_t mf_tb(size_t n, int dt) { return align_up(n * dtype_size(dt), 256); }
-template <typename A, typename B> static size_t mf_max(A a, B b) { return (size_t)a > (size_t)b ? (size_t)a : (size_t)b; }
-
-static mi_pw_desc mf_conv1x1(const void* x, int64_t x_bs, int K, const float* w, bool transposed, int w_ld, void* y, int64_t y_bs,
-                             int M, int B, int64_t N, int dtype) {
-  mi_pw_desc d;
-  memset(&d, 0, sizeof(d));
-  d.x1 = x; d.x1_bs = x_bs; d.k1 = K;
-  d.w = w;
-  if (transposed) { d.w_sm = 1; d.w_sk = w_ld; } else { d.w_sm = w_ld; d.w_sk = 1; }
-  d.y = y; d.y_bs = y_bs;
-  d.m = M; d.n = N; d.batch = B; d.groups = 1; d.dtype = dtype;
-  return d;
-}
 // the per-image products: pre[b] = M[b] Z[b] (K = 8C) and dZ[b] = M[b]^T dpre[b] (K = C, 8C outputs); bf16 images of M / M^T
 static mi_pw_desc mf_out_desc(const void* z, const float* M, const void* Mb, void* pre, int B, int C, int64_t N, int dt) {
-  mi_pw_desc d = mf_conv1x1(z, 8 * C * N, 8 * C, M, false, 8 * C, pre, C * N, C, B, N, dt);
-  d.w_bs = (int64_t)C * 8 * C;
-  if (Mb) { d.w_b16 = Mb; d.w_b16_sm = 8 * C; }
-  return d;
+  return per_image(conv1x1(z, 8 * C, M, false, 8 * C, nullptr, nullptr, pre, C, B, N, dt), Mb);
 }
 static mi_pw_desc mf_dz_desc(const void* dpre, const float* M, const void* Mtb, void* dz, int B, int C, int64_t N, int dt) {
-  mi_pw_desc d = mf_conv1x1(dpre, C * N, C, M, true, 8 * C, dz, 8 * C * N, 8 * C, B, N, dt);
-  d.w_bs = (int64_t)C * 8 * C;
-  if (Mtb) { d.w_b16 = Mtb; d.w_b16_sm = C; }
-  return d;
-}
-static mi_gram_desc mf_gram(const void* a, int64_t a_bs, int ma, const void* b, int64_t b_bs, int mb, int B, int64_t N, int dt,
-                            float* out, int sum_batch, int acc) {
-  mi_gram_desc g;
-  memset(&g, 0, sizeof(g));
-  g.a = a; g.a_bs = a_bs; g.ma = ma;
-  g.b = b; g.b_bs = b_bs; g.mb = mb;
-  g.n = N; g.batch = B; g.groups = 1; g.dtype = dt;
-  g.sum_batch = sum_batch; g.accumulate = acc; g.out = out; g.out_ld = mb; g.out_zs = sum_batch ? 0 : (int64_t)ma * mb;
-  return g;
+  return per_image(conv1x1(dpre, C, M, true, 8 * C, nullptr, nullptr, dz, 8 * C, B, N, dt), Mtb);
 }
 
 struct MfStep { void* s; void* d1; void* u; void* z; void* pre; float* M; void* Mb; void* Mtb; };
@@ -540,24 +509,24 @@ static MfSaved mf_saved_layout(const mi_mefc_shape* s, void* base, bool train) {
   Carver cv(base);
   MfSaved r;
   memset(&r, 0, sizeof(r));
-  r.pooled = cv.take<float>(mf_fb(B * C));
-  r.hpre = cv.take<float>(mf_fb(B * 16 * s->steps));
-  r.wts = cv.take<float>(mf_fb(B * 8 * s->steps));
+  r.pooled = cv.take<float>(fbytes(B * C));
+  r.hpre = cv.take<float>(fbytes(B * 16 * s->steps));
+  r.wts = cv.take<float>(fbytes(B * 8 * s->steps));
   const int nst = train ? s->steps : 1;
   for (int t = 0; t < nst; ++t) {
     MfStep& q = r.st[t];
-    q.s = cv.take(mf_tb(B * C * N, dt));
-    q.d1 = cv.take(mf_tb(B * 4 * C * N, dt));
-    q.u = cv.take(mf_tb(B * 4 * C * N, dt));
-    q.z = cv.take(mf_tb(B * 8 * C * N, dt));
-    q.pre = cv.take(mf_tb(B * C * N, dt));
-    q.M = cv.take<float>(mf_fb(B * C * 8 * C));
-    q.Mb = cv.take(mf_tb(B * C * 8 * C, MI_BF16));
-    q.Mtb = cv.take(mf_tb(B * C * 8 * C, MI_BF16));
+    q.s = cv.take(tbytes(B * C * N, dt));
+    q.d1 = cv.take(tbytes(B * 4 * C * N, dt));
+    q.u = cv.take(tbytes(B * 4 * C * N, dt));
+    q.z = cv.take(tbytes(B * 8 * C * N, dt));
+    q.pre = cv.take(tbytes(B * C * N, dt));
+    q.M = cv.take<float>(fbytes(B * C * 8 * C));
+    q.Mb = cv.take(tbytes(B * C * 8 * C, MI_BF16));
+    q.Mtb = cv.take(tbytes(B * C * 8 * C, MI_BF16));
   }
   if (!train) {
     for (int t = 1; t < s->steps; ++t) r.st[t] = r.st[0];
-    r.s_alt = cv.take(mf_tb(B * C * N, dt));
+    r.s_alt = cv.take(tbytes(B * C * N, dt));
   }
   r.bytes = cv.off;
   return r;
@@ -570,45 +539,36 @@ struct MfWs {
 static MfWs mf_ws_layout(const mi_mefc_shape* s, void* base) {
   const int B = s->B, C = s->C, dt = s->dtype;
   const int64_t N = (int64_t)s->H * s->W;
-  void* const p = (void*)256;
-  const float* const pf = (const float*)256;
   Carver cv(base);
   MfWs w;
-  {
-    mi_pw_desc a = mf_conv1x1(p, C * N, C, pf, false, C, p, C * N, C, B, N, dt);                // preprocess
-    mi_pw_desc a2 = mf_conv1x1(p, 4 * C * N, C, pf, false, C, p, 4 * C * N, C, B, N, dt);       // pw1 (and its transpose)
-    mi_pw_desc a3 = mf_conv1x1(p, 4 * C * N, C, pf, true, C, p, 4 * C * N, C, B, N, dt);
-    mi_pw_desc a4 = mf_conv1x1(p, C * N, C, pf, true, C, p, C * N, C, B, N, dt);
-    mi_pw_desc o = mf_out_desc(p, pf, nullptr, p, B, C, N, dt);
-    mi_pw_desc dz = mf_dz_desc(p, pf, nullptr, p, B, C, N, dt);
-    w.pw_ws = cv.take(mf_max(mf_max(mf_max(mi_pw_gemm_workspace(&a), mi_pw_gemm_workspace(&a2)),
-                                    mf_max(mi_pw_gemm_workspace(&a3), mi_pw_gemm_workspace(&a4))),
-                             mf_max(mi_pw_gemm_workspace(&o), mi_pw_gemm_workspace(&dz))));
-  }
-  {
-    mi_gram_desc g1 = mf_gram(p, C * N, C, p, 8 * C * N, 8 * C, B, N, dt, (float*)p, 0, 0);
-    mi_gram_desc g2 = mf_gram(p, 4 * C * N, C, p, 4 * C * N, C, B, N, dt, (float*)p, 1, 0);
-    mi_gram_desc g3 = mf_gram(p, C * N, C, p, C * N, C, B, N, dt, (float*)p, 1, 0);
-    w.gram_ws = cv.take(mf_max(mi_gram_workspace(&g1), mf_max(mi_gram_workspace(&g2), mi_gram_workspace(&g3))));
-  }
-  w.part = cv.take<float>(mf_fb((size_t)B * mf_splits(s->H, s->W) * C * 49));
-  w.G = cv.take<float>(mf_fb((size_t)B * C * 8 * C));
-  w.Hs = cv.take<float>(mf_fb((size_t)8 * C * C));
-  w.dwp = cv.take<float>(mf_fb((size_t)C * B * 8));
-  w.dws = cv.take<float>(mf_fb((size_t)s->steps * B * 8));
-  w.gp = cv.take<float>(mf_fb((size_t)B * C));
-  w.hscr = cv.take<float>(mf_fb((size_t)B * 24 * s->steps));
+  // preprocess and its transpose, pw1 and its transpose (slices of the 4C-plane tensors), the two per-image products
+  w.pw_ws = cv.take(max_of({pw_ws_bytes(probe1x1(C, C, false, B, N, dt)), pw_ws_bytes(probe1x1(C, C, true, B, N, dt)),
+                            pw_ws_bytes(probe1x1(C, C, false, B, N, dt, 4 * C * N, 4 * C * N)),
+                            pw_ws_bytes(probe1x1(C, C, true, B, N, dt, 4 * C * N, 4 * C * N)),
+                            pw_ws_bytes(per_image(probe1x1(8 * C, C, false, B, N, dt))),
+                            pw_ws_bytes(per_image(probe1x1(C, 8 * C, true, B, N, dt)))}));
+  // G[b] = dpre[b] Z[b]^T per image, the pw1 and the preprocess weight gradients
+  w.gram_ws = cv.take(max_of({gram_ws_bytes(probe_wgrad(C, 8 * C, B, N, dt, 0)),
+                              gram_ws_bytes(probe_wgrad(C, C, B, N, dt, 1, 4 * C * N, 4 * C * N)),
+                              gram_ws_bytes(probe_wgrad(C, C, B, N, dt))}));
+  w.part = cv.take<float>(fbytes((size_t)B * mf_splits(s->H, s->W) * C * 49));
+  w.G = cv.take<float>(fbytes((size_t)B * C * 8 * C));
+  w.Hs = cv.take<float>(fbytes((size_t)8 * C * C));
+  w.dwp = cv.take<float>(fbytes((size_t)C * B * 8));
+  w.dws = cv.take<float>(fbytes((size_t)s->steps * B * 8));
+  w.gp = cv.take<float>(fbytes((size_t)B * C));
+  w.hscr = cv.take<float>(fbytes((size_t)B * 24 * s->steps));
   const size_t mark = cv.off;
   w.inf = mf_saved_layout(s, base ? (char*)base + mark : nullptr, false);
   Carver big(base ? (char*)base + mark : nullptr);
-  const size_t plane = mf_tb((size_t)B * C * N, dt);
+  const size_t plane = tbytes((size_t)B * C * N, dt);
   w.dsa = big.take(plane);
   w.dsb = big.take(plane);
   w.dpre = big.take(plane);
-  w.dz = big.take(mf_tb((size_t)B * 8 * C * N, dt));
-  w.du = big.take(mf_tb((size_t)B * 4 * C * N, dt));
-  w.dd1 = big.take(mf_tb((size_t)B * 4 * C * N, dt));
-  w.bytes = mark + mf_max(w.inf.bytes, big.off);
+  w.dz = big.take(tbytes((size_t)B * 8 * C * N, dt));
+  w.du = big.take(tbytes((size_t)B * 4 * C * N, dt));
+  w.dd1 = big.take(tbytes((size_t)B * 4 * C * N, dt));
+  w.bytes = mark + max_of({w.inf.bytes, big.off});
   return w;
 }
 
@@ -704,7 +664,7 @@ extern "C" int mi_mefc_fwd(const mi_mefc_shape* s, const mi_mefc_params* p, cons
   }
   // s0 = relu(preprocess(x))  (:217 ReLUConv)
   void* cur = sv.st[0].s;
-  mi_pw_desc d0 = mf_conv1x1(x, CN, C, p->pre_w, false, C, cur, CN, C, B, N, dt);
+  mi_pw_desc d0 = conv1x1(x, C, p->pre_w, false, C, nullptr, nullptr, cur, C, B, N, dt);
   MI_TRY(mi_pw_gemm(&d0, w.pw_ws, stream));
   MI_TRY(mf_ew<MF_EW_RELU>(cur, nullptr, nullptr, cur, nullptr, B * CN, N, dt, st));
   for (int t = 0; t < steps; ++t) {
@@ -720,7 +680,7 @@ extern "C" int mi_mefc_fwd(const mi_mefc_shape* s, const mi_mefc_params* p, cons
     }
     for (int k = 0; k < 4; ++k) {     // U_k = pw1_k D1_k
       const size_t off = (size_t)k * CN * dtype_size(dt);
-      mi_pw_desc d = mf_conv1x1((const char*)q.d1 + off, 4 * CN, C, pp.sep_pw1[k], false, C, (char*)q.u + off, 4 * CN, C, B, N, dt);
+      mi_pw_desc d = conv1x1((const char*)q.d1 + off, C, pp.sep_pw1[k], false, C, nullptr, nullptr, (char*)q.u + off, C, B, N, dt, 4 * CN, 4 * CN);
       MI_TRY(mi_pw_gemm(&d, w.pw_ws, stream));
     }
     {
@@ -774,7 +734,7 @@ extern "C" int mi_mefc_bwd(const mi_mefc_shape* s, const mi_mefc_params* p, cons
     // dpre = dout (s' > 0)(pre > 0)
     MI_TRY(mf_ew<MF_EW_RES_BWD>(dcur, s_out, q.pre, w.dpre, nullptr, B * CN, N, dt, st));
     // fold backward: G[b] = dpre[b] Z[b]^T -> d w_i[b], d out_w, d pw_i
-    mi_gram_desc gd = mf_gram(w.dpre, CN, C, q.z, 8 * CN, 8 * C, B, N, dt, w.G, 0, 0);
+    mi_gram_desc gd = wgrad_gram(w.dpre, C, q.z, 8 * C, B, N, dt, w.G, 0, 0);
     MI_TRY(mi_gram(&gd, w.gram_ws, stream));
     const MfQ qq = mf_q(pp);
     {
@@ -807,9 +767,9 @@ extern "C" int mi_mefc_bwd(const mi_mefc_shape* s, const mi_mefc_params* p, cons
     // pw1: dD1_k = pw1_k^T dU_k, d pw1_k = sum_b dU_k D1_k^T
     for (int k = 0; k < 4; ++k) {
       const size_t off = (size_t)k * CN * es;
-      mi_pw_desc d = mf_conv1x1((const char*)w.du + off, 4 * CN, C, pp.sep_pw1[k], true, C, (char*)w.dd1 + off, 4 * CN, C, B, N, dt);
+      mi_pw_desc d = conv1x1((const char*)w.du + off, C, pp.sep_pw1[k], true, C, nullptr, nullptr, (char*)w.dd1 + off, C, B, N, dt, 4 * CN, 4 * CN);
       MI_TRY(mi_pw_gemm(&d, w.pw_ws, stream));
-      mi_gram_desc gw = mf_gram((const char*)w.du + off, 4 * CN, C, (const char*)q.d1 + off, 4 * CN, C, B, N, dt, gg.sep_pw1[k], 1, acc);
+      mi_gram_desc gw = wgrad_gram((const char*)w.du + off, C, (const char*)q.d1 + off, C, B, N, dt, gg.sep_pw1[k], acc, 1, 4 * CN, 4 * CN);
       MI_TRY(mi_gram(&gw, w.gram_ws, stream));
     }
     // stencil A backward: ds, plus the residual's gradient
@@ -834,10 +794,7 @@ extern "C" int mi_mefc_bwd(const mi_mefc_shape* s, const mi_mefc_params* p, cons
   // through the preprocess ReLU and 1x1
   void* dpre0 = w.dpre;
   MI_TRY(mf_ew<MF_EW_MASK>(dcur, sv.st[0].s, nullptr, dpre0, nullptr, B * CN, N, dt, st));
-  mi_gram_desc gw = mf_gram(dpre0, CN, C, x, CN, C, B, N, dt, g->pre_w, 1, acc);
-  MI_TRY(mi_gram(&gw, w.gram_ws, stream));
-  mi_pw_desc dxd = mf_conv1x1(dpre0, CN, C, p->pre_w, true, C, dx, CN, C, B, N, dt);
-  MI_TRY(mi_pw_gemm(&dxd, w.pw_ws, stream));
+  MI_TRY(conv1x1_bwd_input(dpre0, C, x, C, p->pre_w, g->pre_w, nullptr, dx, B, N, dt, acc, w.gram_ws, nullptr, w.pw_ws, st, false));
   // routing head: the d w of every step through the softmax and the MLP; the pooled gradient joins dx
   {
     ProfScope ps(st, K_MEFC_HEAD_BWD, 8.0 * (16.0 * steps * C + 128.0 * steps * steps) * B, 6.0 * (16.0 * steps * C + 128.0 * steps * steps) * B);

@@ -8,25 +8,6 @@
 
 namespace mi {
 
-static size_t fbytes(size_t n) { return align_up(n * sizeof(float), 256); }
-static size_t tbytes(size_t n, int dt) { return align_up(n * dtype_size(dt), 256); }
-template <typename A, typename B> static size_t max2(A a, B b) { return (size_t)a > (size_t)b ? (size_t)a : (size_t)b; }
-
-// plain 1x1 conv: y[B,M,N] = W[M,K] x[B,K,N] (+bias) (+res);  transposed: W given as [K,M] used as its transpose
-static mi_pw_desc conv1x1(const void* x, int K, const float* w, bool transposed, int w_ld, const float* bias,
-                          const void* res, void* y, int M, int B, int64_t N, int dtype) {
-  mi_pw_desc d;
-  memset(&d, 0, sizeof(d));
-  d.x1 = x; d.x1_bs = (int64_t)K * N; d.k1 = K;
-  d.w = w;
-  if (transposed) { d.w_sm = 1; d.w_sk = w_ld; } else { d.w_sm = w_ld; d.w_sk = 1; }
-  d.bias = bias;
-  d.r = res; d.r_bs = (int64_t)M * N;
-  d.y = y; d.y_bs = (int64_t)M * N;
-  d.m = M; d.n = N; d.batch = B; d.groups = 1; d.dtype = dtype;
-  return d;
-}
-
 // ------------------------------------------------------------------ weight gradient beside input gradient
 // The weight-gradient Gram (dW = dY X^T) and the input-gradient GEMM (dX = W^T dY) of one 1x1 conv both stream dY.  Run one
 // after the other over a 32-image batch, the second reads dY from HBM again (2 GB at C = 96: nothing survives in the 256 MiB
@@ -69,6 +50,26 @@ static int co_join(hipStream_t side, hipStream_t st) {
   MI_CHECK_HIP(hipStreamWaitEvent(st, c->join, 0));
   return MI_OK;
 }
+int conv1x1_bwd_input(const void* dy, int M, const void* x, int K, const float* w, float* dw, float* db, void* dx, int B, int64_t N,
+                      int dtype, int accumulate, void* gram_ws, void* cs_ws, void* pw_ws, hipStream_t st, bool fork) {
+  const mi_gram_desc g = wgrad_gram(dy, M, x, K, B, N, dtype, dw, accumulate);
+  const mi_pw_desc d = conv1x1(dy, M, w, true, K, nullptr, nullptr, dx, K, B, N, dtype);
+  const hipStream_t sd = fork ? co_fork(st) : st;
+  int rc = mi_gram(&g, gram_ws, sd);
+  if (rc == MI_OK && db) rc = launch_chan_sum(dy, db, B, M, N, dtype, accumulate, cs_ws, sd);
+  if (rc == MI_OK) rc = mi_pw_gemm(&d, pw_ws, st);
+  const int joined = co_join(sd, st);   // on every path: a forked side stream is never left behind
+  return rc != MI_OK ? rc : joined;
+}
+// Backward of a 1x1 conv inside a module (project_out of GDFN / MSFN): the bias sum first, dx into a scratch plane, one stream.
+static int conv1x1_bwd_output(const void* dy, int M, const void* x, int K, const float* w, float* dw, float* db, void* dx, int B,
+                              int64_t N, int dtype, int accumulate, void* gram_ws, void* cs_ws, void* pw_ws, hipStream_t st) {
+  if (db) MI_TRY(launch_chan_sum(dy, db, B, M, N, dtype, accumulate, cs_ws, st));
+  const mi_gram_desc g = wgrad_gram(dy, M, x, K, B, N, dtype, dw, accumulate);
+  MI_TRY(mi_gram(&g, gram_ws, st));
+  const mi_pw_desc d = conv1x1(dy, M, w, true, K, nullptr, nullptr, dx, K, B, N, dtype);
+  return mi_pw_gemm(&d, pw_ws, st);
+}
 
 // ------------------------------------------------------------------ attention core (shared by MDTA and cross-MDTA)
 // q, k, v are channel slices of NCHW tensors: base pointer + batch stride (elements); heads are contiguous channel
@@ -110,16 +111,6 @@ static mi_gram_desc attn_dm_gram(const AttnDims& d, const void* dout, const QkvV
   g.out = dM; g.out_ld = d.C; g.out_zs = (int64_t)d.C * d.C;
   return g;
 }
-static mi_gram_desc wgrad_gram(const void* dy, int m, const void* x, int k, int B, int64_t N, int dtype, float* out,
-                               int accumulate) {
-  mi_gram_desc g;
-  memset(&g, 0, sizeof(g));
-  g.a = dy; g.a_bs = (int64_t)m * N; g.ma = m;
-  g.b = x; g.b_bs = (int64_t)k * N; g.mb = k;
-  g.n = N; g.batch = B; g.groups = 1; g.dtype = dtype;
-  g.sum_batch = 1; g.accumulate = accumulate; g.out = out; g.out_ld = k; g.out_zs = 0;
-  return g;
-}
 // the grouped per-image GEMM(s) of the q/k gradients over the stacked operand [k; q] (two K-panels of c rows each); weights
 // [Z][2c][2c] (attn_bwd_finish_kernel): rows 0..c-1 give dq, rows c..2c-1 give dk.  rows = 2c with a second output: both in one pass.
 static mi_pw_desc attn_dqk_desc(const AttnDims& d, const QkvView& v, const float* w, int row0, int rows, void* y, int64_t y_bs,
@@ -153,29 +144,23 @@ static void attn_scratch_carve(Carver& cv, const AttnDims& d, AttnScratch* w) {
   w->wd = cv.take<float>(fbytes(Z * 2 * c * 2 * c));     // [Z][2c][2c]: rows of dq, then rows of dk, over the stacked [k; q]
   w->wdb = cv.take(Z * 2 * c * 2 * c * 2);               // the same in bf16
   w->attn_scr = cv.take<float>(fbytes(attn_bwd_scratch_floats((int)B, (int)C, d.heads)));
-  QkvView fake{(void*)256, 0, (void*)256, 0, (void*)256, 0};
-  mi_gram_desc g1 = attn_qk_gram(d, fake, (float*)256, (float*)256);
-  mi_gram_desc g2 = attn_dm_gram(d, (void*)256, fake, (float*)256);
   w->gram_ws = nullptr; w->pw_ws = nullptr; w->cs_ws = nullptr;  // sized by the caller together with its own GEMMs
-  (void)g1; (void)g2;
 }
+static const QkvView PROBE_QKV{PROBE_PTR, 0, PROBE_PTR, 0, PROBE_PTR, 0};
 static size_t attn_gram_ws_bytes(const AttnDims& d) {
-  QkvView fake{(void*)256, 0, (void*)256, 0, (void*)256, 0};
-  mi_gram_desc g1 = attn_qk_gram(d, fake, (float*)256, (float*)256);
-  mi_gram_desc g2 = attn_dm_gram(d, (void*)256, fake, (float*)256);
-  return max2(mi_gram_workspace(&g1), mi_gram_workspace(&g2));
+  float* const p = (float*)PROBE_PTR;
+  return max_of({gram_ws_bytes(attn_qk_gram(d, PROBE_QKV, p, p)), gram_ws_bytes(attn_dm_gram(d, PROBE_PTR, PROBE_QKV, p))});
 }
 static size_t attn_pw_ws_bytes(const AttnDims& d) {
-  mi_pw_desc b = conv1x1((void*)256, d.C, (const float*)256, false, d.C, nullptr, nullptr, (void*)256, d.C, d.B, d.N, d.dtype);
-  b.w_bs = (int64_t)d.C * d.C;  // per-image C x C (M_b and its transpose)
-  QkvView fake{(void*)256, 0, (void*)256, 0, (void*)256, 0};
-  mi_pw_desc q = attn_dqk_desc(d, fake, (const float*)256, 0, d.C / d.heads, (void*)256, 0);
-  mi_pw_desc q2 = attn_dqk_merged(d, fake, (const float*)256, (void*)256, 0, (void*)256, 0);
-  return max2(max2(mi_pw_gemm_workspace(&b), mi_pw_gemm_workspace(&q)), mi_pw_gemm_workspace(&q2));
+  const float* const p = (const float*)PROBE_PTR;
+  return max_of({pw_ws_bytes(per_image(probe1x1(d.C, d.C, false, d.B, d.N, d.dtype))),   // M_b and its transpose
+                 pw_ws_bytes(attn_dqk_desc(d, PROBE_QKV, p, 0, d.C / d.heads, PROBE_PTR, 0)),
+                 pw_ws_bytes(attn_dqk_merged(d, PROBE_QKV, p, PROBE_PTR, 0, PROBE_PTR, 0))});
 }
 
 // Top-k sparse attention (TKSA, DRSformer_arch.py:101-171): the c x c kernels of tksa.hip in place of attn_fold / attn_bwd_small.
 // S: the saved scores the masks are ranked from; scores: optional copy for the caller; dattn_part / g_attn: backward only.
+// The entry points fill tk, scores and g_attn; mdta_fwd_impl / mdta_bwd_impl point S and dattn_part into the blobs they carve.
 struct TopkHook { TopkArgs tk; float* S; float* scores; float* dattn_part; float* g_attn[4]; };
 
 // out = (residual?) + project_out(softmax(temperature * q^ k^T) v)        Restormer.py:121-131
@@ -190,10 +175,7 @@ static int attn_core_fwd(const AttnDims& d, const QkvView& v, const float* tempe
                             d.heads, st, sv.Mb, sv.Mtb));
   else
     MI_TRY(launch_attn_fold(w.graw, w.ss, temperature, proj_w, sv.P, sv.A, sv.nrm, sv.M, d.B, d.C, d.heads, st, sv.Mb, sv.Mtb));
-  mi_pw_desc d2 = conv1x1(v.v, d.C, sv.M, false, d.C, proj_b, residual, out, d.C, d.B, d.N, d.dtype);
-  d2.x1_bs = v.v_bs;
-  d2.w_bs = (int64_t)d.C * d.C;
-  d2.w_b16 = sv.Mb; d2.w_b16_sm = d.C;
+  mi_pw_desc d2 = per_image(conv1x1(v.v, d.C, sv.M, false, d.C, proj_b, residual, out, d.C, d.B, d.N, d.dtype, v.v_bs), sv.Mb);
   if (f8) { d2.f8 = 1; d2.f8_sx = f8->x2; d2.f8_sw = f8->w2; }
   return mi_pw_gemm(&d2, w.pw_ws, stream);
 }
@@ -238,11 +220,8 @@ static int attn_core_bwd(const AttnDims& d, const QkvView& v, const void* dout, 
     dd = attn_dqk_desc(d, v, w.wd, c, c, dk, dk_bs, w.wdb);
     MI_TRY(mi_pw_gemm(&dd, w.pw_ws, stream));
   }
-  // dv = M_b^T dY
-  mi_pw_desc dvd = conv1x1(dout, C, sv.M, true, C, nullptr, nullptr, dv, C, B, d.N, d.dtype);
-  dvd.w_bs = (int64_t)C * C;
-  dvd.y_bs = dv_bs;
-  dvd.w_b16 = sv.Mtb; dvd.w_b16_sm = C;                  // M_b^T, written row-major by attn_fold
+  // dv = M_b^T dY  (Mtb: M_b^T, written row-major by attn_fold)
+  mi_pw_desc dvd = per_image(conv1x1(dout, C, sv.M, true, C, nullptr, nullptr, dv, C, B, d.N, d.dtype, 0, dv_bs), sv.Mtb);
   return mi_pw_gemm(&dvd, w.pw_ws, stream);
 }
 
@@ -272,15 +251,10 @@ static MdtaWs mdta_ws_layout(const mi_mdta_shape* s, void* base) {
   Carver cv(base);
   MdtaWs w;
   attn_scratch_carve(cv, d, &w.at);
-  mi_gram_desc g3 = wgrad_gram((void*)256, 3 * (int)C, (void*)256, (int)C, (int)B, (int64_t)N, s->dtype, (float*)256, 0);
-  w.at.gram_ws = cv.take(max2(attn_gram_ws_bytes(d), mi_gram_workspace(&g3)));
-  {  // weight-pack scratch of the largest 1x1 GEMM of this module
-    mi_pw_desc a = conv1x1((void*)256, (int)C, (const float*)256, false, (int)C, nullptr, nullptr, (void*)256, 3 * (int)C,
-                           (int)B, (int64_t)N, s->dtype);
-    mi_pw_desc e = conv1x1((void*)256, 3 * (int)C, (const float*)256, true, (int)C, nullptr, nullptr, (void*)256, (int)C,
-                           (int)B, (int64_t)N, s->dtype);  // input gradient: W_qkv^T
-    w.at.pw_ws = cv.take(max2(max2(mi_pw_gemm_workspace(&a), mi_pw_gemm_workspace(&e)), attn_pw_ws_bytes(d)));
-  }
+  w.at.gram_ws = cv.take(max_of({attn_gram_ws_bytes(d), gram_ws_bytes(probe_wgrad(3 * d.C, d.C, d.B, d.N, d.dtype))}));
+  // weight-pack scratch of the largest 1x1 GEMM of this module: qkv, its input gradient (W_qkv^T), the attention core's
+  w.at.pw_ws = cv.take(max_of({pw_ws_bytes(probe1x1(d.C, 3 * d.C, false, d.B, d.N, d.dtype)),
+                               pw_ws_bytes(probe1x1(3 * d.C, d.C, true, d.B, d.N, d.dtype)), attn_pw_ws_bytes(d)}));
   w.dw_ws = cv.take(mi_dwconv_bwd_workspace((int)B, 3 * (int)C, s->H, s->W, s->ks));
   w.at.cs_ws = cv.take(chan_sum_workspace(3 * (int)C, (int64_t)N));
   // big activation-sized buffers last: forward(inference) and backward never run concurrently on one blob
@@ -289,7 +263,7 @@ static MdtaWs mdta_ws_layout(const mi_mdta_shape* s, void* base) {
   w.dqkv = base ? (char*)base + mark : nullptr;
   w.dqkv0 = base ? (char*)base + mark + tbytes(B * 3 * C * N, s->dtype) : nullptr;
   size_t bwd_big = 2 * tbytes(B * 3 * C * N, s->dtype);
-  w.bytes = mark + max2(w.inf.bytes, bwd_big);
+  w.bytes = mark + max_of({w.inf.bytes, bwd_big});
   return w;
 }
 
@@ -329,15 +303,9 @@ static XmdtaWs xmdta_ws_layout(const mi_xmdta_shape* s, void* base) {
   Carver cv(base);
   XmdtaWs w;
   attn_scratch_carve(cv, d, &w.at);
-  mi_gram_desc g3 = wgrad_gram((void*)256, 2 * (int)C, (void*)256, (int)C, (int)B, (int64_t)N, s->dtype, (float*)256, 0);
-  w.at.gram_ws = cv.take(max2(attn_gram_ws_bytes(d), mi_gram_workspace(&g3)));
-  {
-    mi_pw_desc a = conv1x1((void*)256, (int)C, (const float*)256, false, (int)C, nullptr, nullptr, (void*)256, 2 * (int)C,
-                           (int)B, (int64_t)N, s->dtype);
-    mi_pw_desc e = conv1x1((void*)256, 2 * (int)C, (const float*)256, true, (int)C, nullptr, nullptr, (void*)256, (int)C,
-                           (int)B, (int64_t)N, s->dtype);
-    w.at.pw_ws = cv.take(max2(max2(mi_pw_gemm_workspace(&a), mi_pw_gemm_workspace(&e)), attn_pw_ws_bytes(d)));
-  }
+  w.at.gram_ws = cv.take(max_of({attn_gram_ws_bytes(d), gram_ws_bytes(probe_wgrad(2 * d.C, d.C, d.B, d.N, d.dtype))}));
+  w.at.pw_ws = cv.take(max_of({pw_ws_bytes(probe1x1(d.C, 2 * d.C, false, d.B, d.N, d.dtype)),
+                               pw_ws_bytes(probe1x1(2 * d.C, d.C, true, d.B, d.N, d.dtype)), attn_pw_ws_bytes(d)}));
   const int ksm = s->ks_q > s->ks_kv ? s->ks_q : s->ks_kv;
   w.dw_ws = cv.take(mi_dwconv_bwd_workspace((int)B, 2 * (int)C, s->H, s->W, ksm));
   w.at.cs_ws = cv.take(chan_sum_workspace(2 * (int)C, (int64_t)N));
@@ -348,7 +316,7 @@ static XmdtaWs xmdta_ws_layout(const mi_xmdta_shape* s, void* base) {
   w.dq0 = big.take(tbytes(B * C * N, s->dtype));
   w.dkv = big.take(tbytes(B * 2 * C * N, s->dtype));
   w.dkv0 = big.take(tbytes(B * 2 * C * N, s->dtype));
-  w.bytes = mark + max2(w.inf.bytes, big.off);
+  w.bytes = mark + max_of({w.inf.bytes, big.off});
   return w;
 }
 static int xmdta_check(const mi_xmdta_shape* s) {
@@ -385,27 +353,20 @@ static GdfnSaved gdfn_saved_layout(const mi_gdfn_shape* s, void* base) {
 }
 struct GdfnWs { void* gram_ws; void* pw_ws; void* dw_ws; void* cs_ws; GdfnSaved inf; void* dg; void* dh0; size_t bytes; };
 static GdfnWs gdfn_ws_layout(const mi_gdfn_shape* s, void* base) {
-  const size_t N = (size_t)s->H * s->W, B = s->B, h = s->hidden, C = s->C;
+  const int B = s->B, C = s->C, h = s->hidden, dt = s->dtype;
+  const int64_t N = (int64_t)s->H * s->W;
   Carver cv(base);
   GdfnWs w;
-  mi_gram_desc g1 = wgrad_gram((void*)256, (int)C, (void*)256, (int)h, (int)B, (int64_t)N, s->dtype, (float*)256, 0);
-  mi_gram_desc g2 = wgrad_gram((void*)256, 2 * (int)h, (void*)256, (int)C, (int)B, (int64_t)N, s->dtype, (float*)256, 0);
-  w.gram_ws = cv.take(max2(mi_gram_workspace(&g1), mi_gram_workspace(&g2)));
-  {
-    mi_pw_desc a = conv1x1((void*)256, (int)C, (const float*)256, false, (int)C, nullptr, nullptr, (void*)256, 2 * (int)h,
-                           (int)B, (int64_t)N, s->dtype);
-    mi_pw_desc b = conv1x1((void*)256, 2 * (int)h, (const float*)256, true, (int)C, nullptr, nullptr, (void*)256, (int)C,
-                           (int)B, (int64_t)N, s->dtype);
-    w.pw_ws = cv.take(max2(mi_pw_gemm_workspace(&a), mi_pw_gemm_workspace(&b)));
-  }
-  w.dw_ws = cv.take(mi_dwconv_bwd_workspace((int)B, 2 * (int)h, s->H, s->W, s->ks));
-  w.cs_ws = cv.take(chan_sum_workspace(2 * (int)h > (int)C ? 2 * (int)h : (int)C, (int64_t)N));
+  w.gram_ws = cv.take(max_of({gram_ws_bytes(probe_wgrad(C, h, B, N, dt)), gram_ws_bytes(probe_wgrad(2 * h, C, B, N, dt))}));
+  w.pw_ws = cv.take(max_of({pw_ws_bytes(probe1x1(C, 2 * h, false, B, N, dt)), pw_ws_bytes(probe1x1(2 * h, C, true, B, N, dt))}));
+  w.dw_ws = cv.take(mi_dwconv_bwd_workspace(B, 2 * h, s->H, s->W, s->ks));
+  w.cs_ws = cv.take(chan_sum_workspace(2 * h > C ? 2 * h : C, N));
   size_t mark = cv.off;
   w.inf = gdfn_saved_layout(s, base ? (char*)base + mark : nullptr);
   w.dg = base ? (char*)base + mark : nullptr;
-  w.dh0 = base ? (char*)base + mark + tbytes(B * h * N, s->dtype) : nullptr;
-  size_t bwd_big = tbytes(B * h * N, s->dtype) + tbytes(B * 2 * h * N, s->dtype);
-  w.bytes = mark + max2(w.inf.bytes, bwd_big);
+  w.dh0 = base ? (char*)base + mark + tbytes((size_t)B * h * N, dt) : nullptr;
+  size_t bwd_big = tbytes((size_t)B * h * N, dt) + tbytes((size_t)B * 2 * h * N, dt);
+  w.bytes = mark + max_of({w.inf.bytes, bwd_big});
   return w;
 }
 static int gdfn_check(const mi_gdfn_shape* s) {
@@ -414,6 +375,32 @@ static int gdfn_check(const mi_gdfn_shape* s) {
   MI_CHECK_ARG(s->dtype == MI_F32 || s->dtype == MI_BF16, "gdfn: bad dtype %d", s->dtype);
   MI_CHECK_ARG(s->ks == 3 || s->ks == 5 || s->ks == 7, "gdfn: bad depthwise kernel size %d", s->ks);
   return MI_OK;
+}
+
+// ------------------------------------------------------------------ TKSA layouts (DRSformer_arch.py:101-171)
+// MDTA's layouts (qkv 1x1 -> depthwise 3x3 -> attention core) plus the saved scores S [B*heads][c][c] the top-k masks are ranked
+// from (forward and backward rank the same fp32 values), and the d attn_m partials [B*heads][4] in the workspace.
+static mi_mdta_shape tksa_mdta_shape(const mi_tksa_shape* s) { return mi_mdta_shape{s->B, s->C, s->heads, s->H, s->W, s->dtype, 3}; }
+static int tksa_shape_check(const mi_tksa_shape* s) {
+  MI_CHECK_ARG(s, "tksa: null shape");
+  const mi_mdta_shape m = tksa_mdta_shape(s);
+  MI_TRY(mdta_check(&m));
+  const int k[4] = {s->k1, s->k2, s->k3, s->k4};
+  return tksa_check(s->C, s->heads, k);
+}
+static size_t tksa_scores_bytes(const mi_mdta_shape* s) {
+  const size_t c = s->C / s->heads;
+  return fbytes((size_t)s->B * s->heads * c * c);
+}
+struct TksaWs { float* S_inf; float* dattn_part; size_t bytes; };
+// what TKSA adds behind MDTA's workspace of m_bytes
+static TksaWs tksa_ws_tail(const mi_mdta_shape* s, size_t m_bytes, void* base) {
+  Carver cv(base ? (char*)base + align_up(m_bytes, 256) : nullptr);
+  TksaWs w;
+  w.S_inf = cv.take<float>(tksa_scores_bytes(s));      // (no-grad forward: nothing saved)
+  w.dattn_part = cv.take<float>(fbytes((size_t)s->B * s->heads * 4));
+  w.bytes = align_up(m_bytes, 256) + cv.off;
+  return w;
 }
 
 }  // namespace mi
@@ -441,15 +428,23 @@ static int ln_head_check(const mi_ln_head* ln, const char* who) {
                "%s: LayerNorm head needs w (and b for WithBias); mean / rstd both or neither", who);
   return MI_OK;
 }
-static int mdta_fwd_impl(const mi_mdta_shape* s, const mi_mdta_params* p, const void* x, const void* residual, void* out,
-                         void* saved, void* ws, void* stream, const mi_ln_head* ln, const mi_f8_scales* f8 = nullptr) {
+// who: the entry point's name for error texts.  topk: TKSA's hook (its saved scores follow MDTA's saved blob, or MDTA's workspace).
+static int mdta_fwd_impl(const char* who, const mi_mdta_shape* s, const mi_mdta_params* p, const void* x, const void* residual,
+                         void* out, void* saved, void* ws, void* stream, const mi_ln_head* ln, const mi_f8_scales* f8 = nullptr,
+                         const TopkHook* topk = nullptr) {
   MI_TRY(mdta_check(s));
-  MI_CHECK_ARG(p && x && out && ws, "mdta_fwd: null pointer");
-  MI_CHECK_ARG(p->temperature && p->qkv_w && p->dw_w && p->proj_w, "mdta_fwd: null parameter");
+  MI_CHECK_ARG(p && x && out && ws, "%s: null pointer", who);
+  MI_CHECK_ARG(p->temperature && p->qkv_w && p->dw_w && p->proj_w, "%s: null parameter", who);
   const int B = s->B, C = s->C, dt = s->dtype;
   const int64_t N = (int64_t)s->H * s->W;
   MdtaWs w = mdta_ws_layout(s, ws);
   MdtaSaved sv = saved ? mdta_saved_layout(s, saved) : w.inf;
+  TopkHook hk;
+  if (topk) {
+    hk = *topk;
+    hk.S = saved ? (float*)((char*)saved + sv.bytes) : tksa_ws_tail(s, w.bytes, ws).S_inf;
+    topk = &hk;
+  }
   // qkv0 = qkv(x);  qkv = dw(qkv0)                               Restormer.py:114
   mi_pw_desc d1 = conv1x1(x, C, p->qkv_w, false, C, p->qkv_b, nullptr, sv.qkv0, 3 * C, B, N, dt);
   ln_head_apply(&d1, ln);
@@ -457,23 +452,22 @@ static int mdta_fwd_impl(const mi_mdta_shape* s, const mi_mdta_params* p, const 
   MI_TRY(mi_pw_gemm(&d1, w.at.pw_ws, stream));
   MI_TRY(mi_dwconv_fwd(sv.qkv0, p->dw_w, p->dw_b, sv.qkv, B, 3 * C, s->H, s->W, s->ks, dt, stream));
   return attn_core_fwd(mdta_dims(s), mdta_view(s, sv.qkv), p->temperature, p->proj_w, p->proj_b, residual, out, sv.at, w.at,
-                       stream, f8);
+                       stream, f8, topk);
 }
 extern "C" int mi_mdta_fwd(const mi_mdta_shape* s, const mi_mdta_params* p, const void* x, const void* residual, void* out,
                            void* saved, void* ws, void* stream) {
-  return mdta_fwd_impl(s, p, x, residual, out, saved, ws, stream, nullptr);
+  return mdta_fwd_impl("mdta_fwd", s, p, x, residual, out, saved, ws, stream, nullptr);
 }
 extern "C" int mi_mdta_fwd_ln_ok(const mi_mdta_shape* s) {
   if (mdta_check(s) != MI_OK) return 0;
-  mi_pw_desc d = conv1x1((void*)256, s->C, (const float*)256, false, s->C, nullptr, nullptr, (void*)256, 3 * s->C, s->B,
-                         (int64_t)s->H * s->W, s->dtype);
+  const mi_pw_desc d = probe1x1(s->C, 3 * s->C, false, s->B, (int64_t)s->H * s->W, s->dtype);
   return mi_pw_gemm_ln_ok(&d);
 }
 extern "C" int mi_mdta_fwd_ln(const mi_mdta_shape* s, const mi_mdta_params* p, const mi_ln_head* ln, const void* x,
                               const void* residual, void* out, void* saved, void* ws, void* stream) {
   MI_TRY(ln_head_check(ln, "mdta_fwd_ln"));
   MI_CHECK_ARG(mi_mdta_fwd_ln_ok(s), "mdta_fwd_ln: shape not covered (bf16, C <= 128, H*W %% 64 == 0)");
-  return mdta_fwd_impl(s, p, x, residual, out, saved, ws, stream, ln);
+  return mdta_fwd_impl("mdta_fwd", s, p, x, residual, out, saved, ws, stream, ln);
 }
 
 // fp8 MFMA operands in both projections (inference: nothing is saved).  ln may be NULL (x is then the LayerNorm output).
@@ -484,10 +478,8 @@ static int f8_check(const mi_f8_scales* f, const char* who) {
 extern "C" int mi_mdta_fwd_f8_ok(const mi_mdta_shape* s, int with_ln) {
   if (mdta_check(s) != MI_OK || s->dtype != MI_BF16) return 0;
   const int64_t N = (int64_t)s->H * s->W;
-  mi_pw_desc d1 = conv1x1((void*)256, s->C, (const float*)256, false, s->C, nullptr, nullptr, (void*)256, 3 * s->C, s->B, N, s->dtype);
-  mi_pw_desc d2 = conv1x1((void*)256, s->C, (const float*)256, false, s->C, nullptr, (void*)256, (void*)256, s->C, s->B, N, s->dtype);
-  d2.x1_bs = 3 * (int64_t)s->C * N;
-  d2.w_bs = (int64_t)s->C * s->C;
+  const mi_pw_desc d1 = probe1x1(s->C, 3 * s->C, false, s->B, N, s->dtype);
+  const mi_pw_desc d2 = per_image(probe1x1(s->C, s->C, false, s->B, N, s->dtype, 3 * (int64_t)s->C * N));   // v: a slice of qkv
   if (with_ln && !mi_pw_gemm_ln_ok(&d1)) return 0;
   return mi_pw_gemm_f8_ok(&d1) && mi_pw_gemm_f8_ok(&d2);
 }
@@ -496,26 +488,34 @@ extern "C" int mi_mdta_fwd_f8(const mi_mdta_shape* s, const mi_mdta_params* p, c
   MI_TRY(f8_check(f8, "mdta_fwd_f8"));
   if (ln) MI_TRY(ln_head_check(ln, "mdta_fwd_f8"));
   MI_CHECK_ARG(mi_mdta_fwd_f8_ok(s, ln != nullptr), "mdta_fwd_f8: shape not covered (bf16, both projections on a wave-owned form)");
-  return mdta_fwd_impl(s, p, x, residual, out, nullptr, ws, stream, ln, f8);
+  return mdta_fwd_impl("mdta_fwd", s, p, x, residual, out, nullptr, ws, stream, ln, f8);
 }
 
 // ln == nullptr: x is the conv input (LayerNorm OUTPUT) and dx its gradient.  ln != nullptr: x is the LayerNorm INPUT; the
 // qkv weight gradient, W_qkv^T dY, the LayerNorm backward and the residual add run as one launch (bwd_tail.hip) and dx is the
 // gradient of the half-block's input.
-static int mdta_bwd_impl(const mi_mdta_shape* s, const mi_mdta_params* p, const void* x, const void* dout, void* dx,
-                         const mi_mdta_grads* gr, const void* saved, void* ws, void* stream, const mi_ln_tail* ln) {
+static int mdta_bwd_impl(const char* who, const mi_mdta_shape* s, const mi_mdta_params* p, const void* x, const void* dout,
+                         void* dx, const mi_mdta_grads* gr, const void* saved, void* ws, void* stream, const mi_ln_tail* ln,
+                         const TopkHook* topk = nullptr) {
   MI_TRY(mdta_check(s));
-  MI_CHECK_ARG(p && x && dout && dx && gr && saved && ws, "mdta_bwd: null pointer");
-  MI_CHECK_ARG(gr->temperature && gr->qkv_w && gr->dw_w && gr->proj_w, "mdta_bwd: null gradient buffer");
+  MI_CHECK_ARG(p && x && dout && dx && gr && saved && ws, "%s: null pointer", who);
+  MI_CHECK_ARG(gr->temperature && gr->qkv_w && gr->dw_w && gr->proj_w, "%s: null gradient buffer", who);
   hipStream_t st = (hipStream_t)stream;
   const int B = s->B, C = s->C, dt = s->dtype, acc = gr->accumulate;
   const int64_t N = (int64_t)s->H * s->W, bs = 3 * (int64_t)C * N;
   const size_t plane = (size_t)C * N * dtype_size(dt);
   MdtaWs w = mdta_ws_layout(s, ws);
   MdtaSaved sv = mdta_saved_layout(s, const_cast<void*>(saved));
+  TopkHook hk;
+  if (topk) {
+    hk = *topk;
+    hk.S = (float*)((char*)const_cast<void*>(saved) + sv.bytes);
+    hk.dattn_part = tksa_ws_tail(s, w.bytes, ws).dattn_part;
+    topk = &hk;
+  }
   char* dq = (char*)w.dqkv;
   MI_TRY(attn_core_bwd(mdta_dims(s), mdta_view(s, sv.qkv), dout, dq, bs, dq + plane, bs, dq + 2 * plane, bs, sv.at,
-                       p->temperature, p->proj_w, gr->temperature, gr->proj_w, gr->proj_b, acc, w.at, stream));
+                       p->temperature, p->proj_w, gr->temperature, gr->proj_w, gr->proj_b, acc, w.at, stream, topk));
   // depthwise backward: d_qkv -> d_qkv0, weight/bias grads
   MI_TRY(mi_dwconv_bwd(w.dqkv, sv.qkv0, p->dw_w, w.dqkv0, gr->dw_w, gr->dw_b, B, 3 * C, s->H, s->W, s->ks, acc, dt, w.dw_ws,
                        stream));
@@ -523,17 +523,12 @@ static int mdta_bwd_impl(const mi_mdta_shape* s, const mi_mdta_params* p, const 
   if (ln)
     return launch_bwd_tail(w.dqkv0, 3 * C, x, C, ln->dres, ln->mean, ln->rstd, p->qkv_w, ln->w, ln->b, dx, gr->qkv_w, ln->dw,
                            ln->db, B, N, acc, (char*)ws + align_up(w.bytes, 256), st);
-  hipStream_t sd = co_fork(st);
-  mi_gram_desc g2 = wgrad_gram(w.dqkv0, 3 * C, x, C, B, N, dt, gr->qkv_w, acc);
-  MI_TRY(mi_gram(&g2, w.at.gram_ws, sd));
-  if (gr->qkv_b) MI_TRY(launch_chan_sum(w.dqkv0, gr->qkv_b, B, 3 * C, N, dt, acc, w.at.cs_ws, sd));
-  mi_pw_desc dxd = conv1x1(w.dqkv0, 3 * C, p->qkv_w, true, C, nullptr, nullptr, dx, C, B, N, dt);
-  MI_TRY(mi_pw_gemm(&dxd, w.at.pw_ws, stream));
-  return co_join(sd, st);
+  return conv1x1_bwd_input(w.dqkv0, 3 * C, x, C, p->qkv_w, gr->qkv_w, gr->qkv_b, dx, B, N, dt, acc, w.at.gram_ws, w.at.cs_ws,
+                           w.at.pw_ws, st, true);
 }
 extern "C" int mi_mdta_bwd(const mi_mdta_shape* s, const mi_mdta_params* p, const void* x, const void* dout, void* dx,
                            const mi_mdta_grads* gr, const void* saved, void* ws, void* stream) {
-  return mdta_bwd_impl(s, p, x, dout, dx, gr, saved, ws, stream, nullptr);
+  return mdta_bwd_impl("mdta_bwd", s, p, x, dout, dx, gr, saved, ws, stream, nullptr);
 }
 static int ln_tail_check(const mi_ln_tail* ln, const char* who) {
   MI_CHECK_ARG(ln && ln->w && ln->b && ln->mean && ln->rstd && ln->dw && ln->db, "%s: LayerNorm tail needs w, b, mean, rstd, dw, db", who);
@@ -551,7 +546,7 @@ extern "C" int mi_mdta_bwd_ln(const mi_mdta_shape* s, const mi_mdta_params* p, c
                               const void* dout, void* dx, const mi_mdta_grads* gr, const void* saved, void* ws, void* stream) {
   MI_TRY(ln_tail_check(ln, "mdta_bwd_ln"));
   MI_CHECK_ARG(gr && !gr->qkv_b && mi_mdta_bwd_ln_ok(s, 0), "mdta_bwd_ln: shape not covered (bf16, C 48/96, H*W %% 64 == 0, no qkv bias)");
-  return mdta_bwd_impl(s, p, x, dout, dx, gr, saved, ws, stream, ln);
+  return mdta_bwd_impl("mdta_bwd", s, p, x, dout, dx, gr, saved, ws, stream, ln);
 }
 
 extern "C" size_t mi_xmdta_saved_bytes(const mi_xmdta_shape* s) {
@@ -602,19 +597,13 @@ extern "C" int mi_xmdta_bwd(const mi_xmdta_shape* s, const mi_xmdta_params* p, c
   // q branch
   MI_TRY(mi_dwconv_bwd(w.dq, sv.q0, p->q_dw_w, w.dq0, gr->q_dw_w, gr->q_dw_b, B, C, s->H, s->W, s->ks_q, acc, dt, w.dw_ws,
                        stream));
-  mi_gram_desc g1 = wgrad_gram(w.dq0, C, x, C, B, N, dt, gr->q_w, acc);
-  MI_TRY(mi_gram(&g1, w.at.gram_ws, stream));
-  if (gr->q_b) MI_TRY(launch_chan_sum(w.dq0, gr->q_b, B, C, N, dt, acc, w.at.cs_ws, st));
-  mi_pw_desc dxd = conv1x1(w.dq0, C, p->q_w, true, C, nullptr, nullptr, dx, C, B, N, dt);
-  MI_TRY(mi_pw_gemm(&dxd, w.at.pw_ws, stream));
+  MI_TRY(conv1x1_bwd_input(w.dq0, C, x, C, p->q_w, gr->q_w, gr->q_b, dx, B, N, dt, acc, w.at.gram_ws, w.at.cs_ws, w.at.pw_ws, st,
+                           false));
   // kv branch
   MI_TRY(mi_dwconv_bwd(w.dkv, sv.kv0, p->kv_dw_w, w.dkv0, gr->kv_dw_w, gr->kv_dw_b, B, 2 * C, s->H, s->W, s->ks_kv, acc, dt,
                        w.dw_ws, stream));
-  mi_gram_desc g2 = wgrad_gram(w.dkv0, 2 * C, y, C, B, N, dt, gr->kv_w, acc);
-  MI_TRY(mi_gram(&g2, w.at.gram_ws, stream));
-  if (gr->kv_b) MI_TRY(launch_chan_sum(w.dkv0, gr->kv_b, B, 2 * C, N, dt, acc, w.at.cs_ws, st));
-  mi_pw_desc dyd = conv1x1(w.dkv0, 2 * C, p->kv_w, true, C, nullptr, nullptr, dy, C, B, N, dt);
-  return mi_pw_gemm(&dyd, w.at.pw_ws, stream);
+  return conv1x1_bwd_input(w.dkv0, 2 * C, y, C, p->kv_w, gr->kv_w, gr->kv_b, dy, B, N, dt, acc, w.at.gram_ws, w.at.cs_ws,
+                           w.at.pw_ws, st, false);
 }
 
 extern "C" size_t mi_gdfn_saved_bytes(const mi_gdfn_shape* s) {
@@ -652,8 +641,7 @@ extern "C" int mi_gdfn_fwd(const mi_gdfn_shape* s, const mi_gdfn_params* p, cons
 }
 extern "C" int mi_gdfn_fwd_ln_ok(const mi_gdfn_shape* s) {
   if (gdfn_check(s) != MI_OK) return 0;
-  mi_pw_desc d = conv1x1((void*)256, s->C, (const float*)256, false, s->C, nullptr, nullptr, (void*)256, 2 * s->hidden, s->B,
-                         (int64_t)s->H * s->W, s->dtype);
+  const mi_pw_desc d = probe1x1(s->C, 2 * s->hidden, false, s->B, (int64_t)s->H * s->W, s->dtype);
   return mi_pw_gemm_ln_ok(&d);
 }
 extern "C" int mi_gdfn_fwd_ln(const mi_gdfn_shape* s, const mi_gdfn_params* p, const mi_ln_head* ln, const void* x,
@@ -666,8 +654,8 @@ extern "C" int mi_gdfn_fwd_ln(const mi_gdfn_shape* s, const mi_gdfn_params* p, c
 extern "C" int mi_gdfn_fwd_f8_ok(const mi_gdfn_shape* s, int with_ln) {
   if (gdfn_check(s) != MI_OK || s->dtype != MI_BF16) return 0;
   const int64_t N = (int64_t)s->H * s->W;
-  mi_pw_desc d1 = conv1x1((void*)256, s->C, (const float*)256, false, s->C, nullptr, nullptr, (void*)256, 2 * s->hidden, s->B, N, s->dtype);
-  mi_pw_desc d2 = conv1x1((void*)256, s->hidden, (const float*)256, false, s->hidden, nullptr, (void*)256, (void*)256, s->C, s->B, N, s->dtype);
+  const mi_pw_desc d1 = probe1x1(s->C, 2 * s->hidden, false, s->B, N, s->dtype);
+  const mi_pw_desc d2 = probe1x1(s->hidden, s->C, false, s->B, N, s->dtype);
   if (with_ln && !mi_pw_gemm_ln_ok(&d1)) return 0;
   return mi_pw_gemm_f8_ok(&d1) && mi_pw_gemm_f8_ok(&d2);
 }
@@ -706,11 +694,7 @@ static int gdfn_bwd_impl(const mi_gdfn_shape* s, const mi_gdfn_params* p, const 
   const int64_t N = (int64_t)s->H * s->W;
   GdfnWs w = gdfn_ws_layout(s, ws);
   GdfnSaved sv = gdfn_saved_layout(s, const_cast<void*>(saved));
-  if (gr->out_b) MI_TRY(launch_chan_sum(dout, gr->out_b, B, C, N, dt, acc, w.cs_ws, st));
-  mi_gram_desc g1 = wgrad_gram(dout, C, sv.g, h, B, N, dt, gr->out_w, acc);
-  MI_TRY(mi_gram(&g1, w.gram_ws, stream));
-  mi_pw_desc d1 = conv1x1(dout, C, p->out_w, true, h, nullptr, nullptr, w.dg, h, B, N, dt);
-  MI_TRY(mi_pw_gemm(&d1, w.pw_ws, stream));
+  MI_TRY(conv1x1_bwd_output(dout, C, sv.g, h, p->out_w, gr->out_w, gr->out_b, w.dg, B, N, dt, acc, w.gram_ws, w.cs_ws, w.pw_ws, st));
   if (gdfn_recompute(s))
     MI_TRY(mi_dwconv_gate_bwd_recompute(w.dg, sv.h0, p->dw_w, p->dw_b, w.dh0, gr->dw_w, gr->dw_b, B, 2 * h, s->H, s->W, s->ks,
                                         acc, dt, w.dw_ws, stream));
@@ -720,13 +704,7 @@ static int gdfn_bwd_impl(const mi_gdfn_shape* s, const mi_gdfn_params* p, const 
   if (ln)
     return launch_bwd_tail(w.dh0, 2 * h, x, C, ln->dres, ln->mean, ln->rstd, p->in_w, ln->w, ln->b, dx, gr->in_w, ln->dw, ln->db,
                            B, N, acc, (char*)ws + align_up(w.bytes, 256), st);
-  hipStream_t sd = co_fork(st);
-  mi_gram_desc g2 = wgrad_gram(w.dh0, 2 * h, x, C, B, N, dt, gr->in_w, acc);
-  MI_TRY(mi_gram(&g2, w.gram_ws, sd));
-  if (gr->in_b) MI_TRY(launch_chan_sum(w.dh0, gr->in_b, B, 2 * h, N, dt, acc, w.cs_ws, sd));
-  mi_pw_desc d2 = conv1x1(w.dh0, 2 * h, p->in_w, true, C, nullptr, nullptr, dx, C, B, N, dt);
-  MI_TRY(mi_pw_gemm(&d2, w.pw_ws, stream));
-  return co_join(sd, st);
+  return conv1x1_bwd_input(w.dh0, 2 * h, x, C, p->in_w, gr->in_w, gr->in_b, dx, B, N, dt, acc, w.gram_ws, w.cs_ws, w.pw_ws, st, true);
 }
 extern "C" int mi_gdfn_bwd(const mi_gdfn_shape* s, const mi_gdfn_params* p, const void* x, const void* dout, void* dx,
                            const mi_gdfn_grads* gr, const void* saved, void* ws, void* stream) {
@@ -748,101 +726,48 @@ extern "C" int mi_gdfn_bwd_ln(const mi_gdfn_shape* s, const mi_gdfn_params* p, c
 }
 
 // ------------------------------------------------------------------ TKSA (DRSformer_arch.py:101-171)
-// MDTA's layouts (qkv 1x1 -> depthwise 3x3 -> attention core) plus the saved scores S [B*heads][c][c] the top-k masks are ranked
-// from (forward and backward rank the same fp32 values), and the d attn_m partials [B*heads][4] in the workspace.
-static mi_mdta_shape tksa_mdta_shape(const mi_tksa_shape* s) { return mi_mdta_shape{s->B, s->C, s->heads, s->H, s->W, s->dtype, 3}; }
-static int tksa_shape_check(const mi_tksa_shape* s) {
-  MI_CHECK_ARG(s, "tksa: null shape");
-  const mi_mdta_shape m = tksa_mdta_shape(s);
-  MI_TRY(mdta_check(&m));
-  const int k[4] = {s->k1, s->k2, s->k3, s->k4};
-  return tksa_check(s->C, s->heads, k);
-}
-static size_t tksa_scores_bytes(const mi_tksa_shape* s) {
-  const size_t c = s->C / s->heads;
-  return fbytes((size_t)s->B * s->heads * c * c);
-}
-struct TksaWs { MdtaWs m; float* S_inf; float* dattn_part; size_t bytes; };
-static TksaWs tksa_ws_layout(const mi_tksa_shape* s, void* base) {
-  const mi_mdta_shape ms = tksa_mdta_shape(s);
-  TksaWs w;
-  w.m = mdta_ws_layout(&ms, base);
-  Carver cv(base ? (char*)base + align_up(w.m.bytes, 256) : nullptr);
-  w.S_inf = cv.take<float>(tksa_scores_bytes(s));      // (no-grad forward: nothing saved)
-  w.dattn_part = cv.take<float>(fbytes((size_t)s->B * s->heads * 4));
-  w.bytes = align_up(w.m.bytes, 256) + cv.off;
-  return w;
-}
-static TopkHook tksa_hook(const mi_tksa_shape* s, const mi_tksa_params* tp, float* S, float* scores) {
+static TopkHook tksa_hook(const mi_tksa_shape* s, const mi_tksa_params* tp, float* scores, const mi_tksa_grads* tg) {
   TopkHook hk;
   memset(&hk, 0, sizeof(hk));
   hk.tk.w[0] = tp->attn1; hk.tk.w[1] = tp->attn2; hk.tk.w[2] = tp->attn3; hk.tk.w[3] = tp->attn4;
   hk.tk.k[0] = s->k1; hk.tk.k[1] = s->k2; hk.tk.k[2] = s->k3; hk.tk.k[3] = s->k4;
-  hk.S = S; hk.scores = scores;
+  hk.scores = scores;
+  if (tg) { hk.g_attn[0] = tg->attn1; hk.g_attn[1] = tg->attn2; hk.g_attn[2] = tg->attn3; hk.g_attn[3] = tg->attn4; }
   return hk;
 }
 
 extern "C" size_t mi_tksa_saved_bytes(const mi_tksa_shape* s) {
   if (tksa_shape_check(s) != MI_OK) return 0;
   const mi_mdta_shape ms = tksa_mdta_shape(s);
-  return mdta_saved_layout(&ms, nullptr).bytes + tksa_scores_bytes(s);
+  return mdta_saved_layout(&ms, nullptr).bytes + tksa_scores_bytes(&ms);
 }
 extern "C" size_t mi_tksa_workspace(const mi_tksa_shape* s) {
   if (tksa_shape_check(s) != MI_OK) return 0;
-  return tksa_ws_layout(s, nullptr).bytes;
+  const mi_mdta_shape ms = tksa_mdta_shape(s);
+  return tksa_ws_tail(&ms, mdta_ws_layout(&ms, nullptr).bytes, nullptr).bytes;
 }
 
+// qkv0 = qkv(x);  qkv = qkv_dwconv(qkv0);  the attention core with the top-k hook        DRSformer_arch.py:123
 extern "C" int mi_tksa_fwd(const mi_tksa_shape* s, const mi_mdta_params* p, const mi_tksa_params* tp, const void* x,
                            const void* residual, void* out, void* saved, void* ws, float* scores, void* stream) {
   MI_TRY(tksa_shape_check(s));
-  MI_CHECK_ARG(p && tp && x && out && ws, "tksa_fwd: null pointer");
-  MI_CHECK_ARG(p->temperature && p->qkv_w && p->dw_w && p->proj_w, "tksa_fwd: null parameter");
+  MI_CHECK_ARG(tp, "tksa_fwd: null pointer");
   MI_CHECK_ARG(tp->attn1 && tp->attn2 && tp->attn3 && tp->attn4, "tksa_fwd: null attn1..4");
   const mi_mdta_shape ms = tksa_mdta_shape(s);
-  const int B = s->B, C = s->C, dt = s->dtype;
-  const int64_t N = (int64_t)s->H * s->W;
-  TksaWs w = tksa_ws_layout(s, ws);
-  MdtaSaved sv = saved ? mdta_saved_layout(&ms, saved) : w.m.inf;
-  float* S = saved ? (float*)((char*)saved + sv.bytes) : w.S_inf;
-  // qkv0 = qkv(x);  qkv = qkv_dwconv(qkv0)                        DRSformer_arch.py:123
-  mi_pw_desc d1 = conv1x1(x, C, p->qkv_w, false, C, p->qkv_b, nullptr, sv.qkv0, 3 * C, B, N, dt);
-  MI_TRY(mi_pw_gemm(&d1, w.m.at.pw_ws, stream));
-  MI_TRY(mi_dwconv_fwd(sv.qkv0, p->dw_w, p->dw_b, sv.qkv, B, 3 * C, s->H, s->W, 3, dt, stream));
-  const TopkHook hk = tksa_hook(s, tp, S, scores);
-  return attn_core_fwd(mdta_dims(&ms), mdta_view(&ms, sv.qkv), p->temperature, p->proj_w, p->proj_b, residual, out, sv.at, w.m.at,
-                       stream, nullptr, &hk);
+  const TopkHook hk = tksa_hook(s, tp, scores, nullptr);
+  return mdta_fwd_impl("tksa_fwd", &ms, p, x, residual, out, saved, ws, stream, nullptr, nullptr, &hk);
 }
 
 extern "C" int mi_tksa_bwd(const mi_tksa_shape* s, const mi_mdta_params* p, const mi_tksa_params* tp, const void* x,
                            const void* dout, void* dx, const mi_mdta_grads* gr, const mi_tksa_grads* tg, const void* saved, void* ws,
                            void* stream) {
   MI_TRY(tksa_shape_check(s));
-  MI_CHECK_ARG(p && tp && x && dout && dx && gr && tg && saved && ws, "tksa_bwd: null pointer");
+  MI_CHECK_ARG(tp && tg, "tksa_bwd: null pointer");
   MI_CHECK_ARG(tp->attn1 && tp->attn2 && tp->attn3 && tp->attn4, "tksa_bwd: null attn1..4");
-  MI_CHECK_ARG(gr->temperature && gr->qkv_w && gr->dw_w && gr->proj_w, "tksa_bwd: null gradient buffer");
   MI_CHECK_ARG(tg->attn1 && tg->attn2 && tg->attn3 && tg->attn4, "tksa_bwd: null attn1..4 gradient buffer");
-  hipStream_t st = (hipStream_t)stream;
   const mi_mdta_shape ms = tksa_mdta_shape(s);
-  const int B = s->B, C = s->C, dt = s->dtype, acc = gr->accumulate;
-  const int64_t N = (int64_t)s->H * s->W, bs = 3 * (int64_t)C * N;
-  const size_t plane = (size_t)C * N * dtype_size(dt);
-  TksaWs w = tksa_ws_layout(s, ws);
-  MdtaSaved sv = mdta_saved_layout(&ms, const_cast<void*>(saved));
-  TopkHook hk = tksa_hook(s, tp, (float*)((char*)saved + sv.bytes), nullptr);
-  hk.dattn_part = w.dattn_part;
-  hk.g_attn[0] = tg->attn1; hk.g_attn[1] = tg->attn2; hk.g_attn[2] = tg->attn3; hk.g_attn[3] = tg->attn4;
-  char* dq = (char*)w.m.dqkv;
-  MI_TRY(attn_core_bwd(mdta_dims(&ms), mdta_view(&ms, sv.qkv), dout, dq, bs, dq + plane, bs, dq + 2 * plane, bs, sv.at,
-                       p->temperature, p->proj_w, gr->temperature, gr->proj_w, gr->proj_b, acc, w.m.at, stream, &hk));
-  MI_TRY(mi_dwconv_bwd(w.m.dqkv, sv.qkv0, p->dw_w, w.m.dqkv0, gr->dw_w, gr->dw_b, B, 3 * C, s->H, s->W, 3, acc, dt, w.m.dw_ws,
-                       stream));
-  hipStream_t sd = co_fork(st);
-  mi_gram_desc g2 = wgrad_gram(w.m.dqkv0, 3 * C, x, C, B, N, dt, gr->qkv_w, acc);
-  MI_TRY(mi_gram(&g2, w.m.at.gram_ws, sd));
-  if (gr->qkv_b) MI_TRY(launch_chan_sum(w.m.dqkv0, gr->qkv_b, B, 3 * C, N, dt, acc, w.m.at.cs_ws, sd));
-  mi_pw_desc dxd = conv1x1(w.m.dqkv0, 3 * C, p->qkv_w, true, C, nullptr, nullptr, dx, C, B, N, dt);
-  MI_TRY(mi_pw_gemm(&dxd, w.m.at.pw_ws, stream));
-  return co_join(sd, st);
+  const TopkHook hk = tksa_hook(s, tp, nullptr, tg);
+  return mdta_bwd_impl("tksa_bwd", &ms, p, x, dout, dx, gr, saved, ws, stream, nullptr, &hk);
 }
 
 // ------------------------------------------------------------------ MSFN (DRSformer_arch.py:62-98)
@@ -867,17 +792,9 @@ static MsfnWs msfn_ws_layout(const mi_msfn_shape* s, void* base) {
   const int64_t N = (int64_t)s->H * s->W;
   Carver cv(base);
   MsfnWs w;
-  mi_gram_desc g1 = wgrad_gram((void*)256, C, (void*)256, h2, B, N, dt, (float*)256, 0);
-  mi_gram_desc g2 = wgrad_gram((void*)256, h2, (void*)256, C, B, N, dt, (float*)256, 0);
-  w.gram_ws = cv.take(max2(mi_gram_workspace(&g1), mi_gram_workspace(&g2)));
-  {
-    mi_pw_desc a = conv1x1((void*)256, C, (const float*)256, false, C, nullptr, nullptr, (void*)256, h2, B, N, dt);
-    mi_pw_desc b = conv1x1((void*)256, h2, (const float*)256, false, h2, nullptr, nullptr, (void*)256, C, B, N, dt);
-    mi_pw_desc c = conv1x1((void*)256, C, (const float*)256, true, h2, nullptr, nullptr, (void*)256, h2, B, N, dt);
-    mi_pw_desc e = conv1x1((void*)256, h2, (const float*)256, true, C, nullptr, nullptr, (void*)256, C, B, N, dt);
-    w.pw_ws = cv.take(max2(max2(mi_pw_gemm_workspace(&a), mi_pw_gemm_workspace(&b)),
-                           max2(mi_pw_gemm_workspace(&c), mi_pw_gemm_workspace(&e))));
-  }
+  w.gram_ws = cv.take(max_of({gram_ws_bytes(probe_wgrad(C, h2, B, N, dt)), gram_ws_bytes(probe_wgrad(h2, C, B, N, dt))}));
+  w.pw_ws = cv.take(max_of({pw_ws_bytes(probe1x1(C, h2, false, B, N, dt)), pw_ws_bytes(probe1x1(h2, C, false, B, N, dt)),
+                            pw_ws_bytes(probe1x1(C, h2, true, B, N, dt)), pw_ws_bytes(probe1x1(h2, C, true, B, N, dt))}));
   w.cs_ws = cv.take(chan_sum_workspace(h2 > C ? h2 : C, N));
   w.part = cv.take<float>(fbytes(msfn_part_floats(B, s->hidden, s->H, s->W)));
   const size_t mark = cv.off;
@@ -887,7 +804,7 @@ static MsfnWs msfn_ws_layout(const mi_msfn_shape* s, void* base) {
   w.dY = big.take(plane);           // gradient of cat(y1, y2); then of h0
   w.dza = big.take(plane);
   w.dzb = big.take(plane);
-  w.bytes = mark + max2(w.inf.bytes, big.off);
+  w.bytes = mark + max_of({w.inf.bytes, big.off});
   return w;
 }
 static int msfn_check(const mi_msfn_shape* s) {
@@ -936,21 +853,12 @@ extern "C" int mi_msfn_bwd(const mi_msfn_shape* s, const mi_msfn_params* p, cons
   const int64_t N = (int64_t)s->H * s->W;
   MsfnWs w = msfn_ws_layout(s, ws);
   MsfnSaved sv = msfn_saved_layout(s, const_cast<void*>(saved));
-  if (gr->out_b) MI_TRY(launch_chan_sum(dout, gr->out_b, B, C, N, dt, acc, w.cs_ws, st));
-  mi_gram_desc g1 = wgrad_gram(dout, C, sv.y, 2 * hd, B, N, dt, gr->out_w, acc);
-  MI_TRY(mi_gram(&g1, w.gram_ws, stream));
-  mi_pw_desc d1 = conv1x1(dout, C, p->out_w, true, 2 * hd, nullptr, nullptr, w.dY, 2 * hd, B, N, dt);
-  MI_TRY(mi_pw_gemm(&d1, w.pw_ws, stream));
+  MI_TRY(conv1x1_bwd_output(dout, C, sv.y, 2 * hd, p->out_w, gr->out_w, gr->out_b, w.dY, B, N, dt, acc, w.gram_ws, w.cs_ws, w.pw_ws,
+                            st));
   MI_TRY(launch_msfn_s2_bwd(w.dY, sv.y, sv.a, sv.b, p->g3_w, p->g5_w, w.dza, w.dzb, gr->g3_w, gr->g3_b, gr->g5_w, gr->g5_b, acc,
                             w.part, B, hd, s->H, s->W, dt, st));
   void* dh0 = w.dY;                 // (dY is dead once stage 2 is through)
   MI_TRY(launch_msfn_s1_bwd(w.dza, w.dzb, sv.h0, p->dw3_w, p->dw5_w, dh0, gr->dw3_w, gr->dw3_b, gr->dw5_w, gr->dw5_b, acc, w.part,
                             B, hd, s->H, s->W, dt, st));
-  hipStream_t sd = co_fork(st);
-  mi_gram_desc g2 = wgrad_gram(dh0, 2 * hd, x, C, B, N, dt, gr->in_w, acc);
-  MI_TRY(mi_gram(&g2, w.gram_ws, sd));
-  if (gr->in_b) MI_TRY(launch_chan_sum(dh0, gr->in_b, B, 2 * hd, N, dt, acc, w.cs_ws, sd));
-  mi_pw_desc d2 = conv1x1(dh0, 2 * hd, p->in_w, true, C, nullptr, nullptr, dx, C, B, N, dt);
-  MI_TRY(mi_pw_gemm(&d2, w.pw_ws, stream));
-  return co_join(sd, st);
+  return conv1x1_bwd_input(dh0, 2 * hd, x, C, p->in_w, gr->in_w, gr->in_b, dx, B, N, dt, acc, w.gram_ws, w.cs_ws, w.pw_ws, st, true);
 }
