@@ -426,14 +426,6 @@ __global__ __launch_bounds__(256) void scale_add_wgrad_kernel(const T* __restric
 }
 
 constexpr int FS_MAXH = 4, FS_MAXW = 4;   // rectangles up to 8 x 8 frequencies: feature maps up to 639 pixels (h / 128 <= 4)
-
-#define AD_DISPATCH(dtype, CALL_F32, CALL_BF16)           \
-  do {                                                    \
-    if ((dtype) == MI_F32) { CALL_F32; }                  \
-    else if ((dtype) == MI_BF16) { CALL_BF16; }           \
-    else { set_error("adair: bad dtype %d", (int)(dtype)); return MI_ERR_ARG; } \
-  } while (0)
-
 }  // namespace
 }  // namespace mi
 
@@ -446,12 +438,11 @@ extern "C" int mi_box_down(const void* img, void* out, int B, int C, int Hi, int
   const int64_t total = (int64_t)B * C * (Hi / factor) * (Wi / factor);
   hipStream_t st = (hipStream_t)stream;
   ProfScope ps(st, K_ADAIR, 0.0, 0.0);
-  int blocks = cdiv(total, 256);
-  if (blocks > 8192) blocks = 8192;
-  AD_DISPATCH(dtype, hipLaunchKernelGGL((box_down_kernel<float>), dim3(blocks), dim3(256), 0, st, (const float*)img, (float*)out, Hi, Wi, factor, total),
-              hipLaunchKernelGGL((box_down_kernel<bf16>), dim3(blocks), dim3(256), 0, st, (const bf16*)img, (bf16*)out, Hi, Wi, factor, total));
-  MI_LAUNCH_CHECK();
-  return MI_OK;
+  const int blocks = cdiv_cap(total, 256, 8192);
+  return with_dtype(dtype, "box_down", [&](auto tag) {
+    using T = decltype(tag);
+    hipLaunchKernelGGL((box_down_kernel<T>), dim3(blocks), dim3(256), 0, st, (const T*)img, (T*)out, Hi, Wi, factor, total);
+  });
 }
 
 extern "C" int mi_fre_rect(const float* pooled, const float* w0, const float* w2, int* half, int B, int C, int R, int H, int W,
@@ -479,15 +470,16 @@ extern "C" int mi_fre_split_fwd(const void* feat, const int* half, void* high, v
   const int64_t N = (int64_t)H * W;
   dim3 grid(cdiv(N, 256), B * C);
   MI_CHECK_ARG(grid.y <= 65535, "fre_split_fwd: too many planes");
-  if (half) {
-    AD_DISPATCH(dtype, hipLaunchKernelGGL((lowfreq_coef_kernel<float, FS_MAXH, FS_MAXW>), dim3(B * C), dim3(256), 0, st, (const float*)feat, nullptr, nullptr, half, coef, C, H, W),
-                hipLaunchKernelGGL((lowfreq_coef_kernel<bf16, FS_MAXH, FS_MAXW>), dim3(B * C), dim3(256), 0, st, (const bf16*)feat, nullptr, nullptr, half, coef, C, H, W));
+  return with_dtype(dtype, "fre_split_fwd", [&](auto tag) -> int {
+    using T = decltype(tag);
+    if (half) {
+      hipLaunchKernelGGL((lowfreq_coef_kernel<T, FS_MAXH, FS_MAXW>), dim3(B * C), dim3(256), 0, st, (const T*)feat, nullptr, nullptr, half, coef, C, H, W);
+      MI_LAUNCH_CHECK();
+    }
+    hipLaunchKernelGGL((fre_split_fwd_kernel<T, FS_MAXH, FS_MAXW>), grid, dim3(256), 0, st, (const T*)feat, half, half ? coef : nullptr, (T*)high, (T*)low, C, H, W);
     MI_LAUNCH_CHECK();
-  }
-  AD_DISPATCH(dtype, hipLaunchKernelGGL((fre_split_fwd_kernel<float, FS_MAXH, FS_MAXW>), grid, dim3(256), 0, st, (const float*)feat, half, half ? coef : nullptr, (float*)high, (float*)low, C, H, W),
-              hipLaunchKernelGGL((fre_split_fwd_kernel<bf16, FS_MAXH, FS_MAXW>), grid, dim3(256), 0, st, (const bf16*)feat, half, half ? coef : nullptr, (bf16*)high, (bf16*)low, C, H, W));
-  MI_LAUNCH_CHECK();
-  return MI_OK;
+    return MI_OK;
+  });
 }
 
 extern "C" int mi_fre_split_bwd(const void* feat, const int* half, const float* coef, const void* dhigh, const void* dlow,
@@ -503,17 +495,18 @@ extern "C" int mi_fre_split_bwd(const void* feat, const int* half, const float* 
   float* fre = cv.take<float>((size_t)B * C * N * sizeof(float));
   float* fim = cv.take<float>((size_t)B * C * N * sizeof(float));
   float* coef_f = cv.take<float>(mi_fre_split_coef_bytes(B, C));
-  AD_DISPATCH(dtype, hipLaunchKernelGGL((fre_split_bwd1_kernel<float, FS_MAXH, FS_MAXW>), grid, dim3(256), 0, st, (const float*)feat, half, half ? coef : nullptr, (const float*)dhigh, (const float*)dlow, dre, half ? fre : nullptr, fim, C, H, W),
-              hipLaunchKernelGGL((fre_split_bwd1_kernel<bf16, FS_MAXH, FS_MAXW>), grid, dim3(256), 0, st, (const bf16*)feat, half, half ? coef : nullptr, (const bf16*)dhigh, (const bf16*)dlow, dre, half ? fre : nullptr, fim, C, H, W));
-  MI_LAUNCH_CHECK();
-  if (half) {
-    hipLaunchKernelGGL((lowfreq_coef_kernel<float, FS_MAXH, FS_MAXW>), dim3(B * C), dim3(256), 0, st, (const float*)nullptr, fre, fim, half, coef_f, C, H, W);
+  return with_dtype(dtype, "fre_split_bwd", [&](auto tag) -> int {
+    using T = decltype(tag);
+    hipLaunchKernelGGL((fre_split_bwd1_kernel<T, FS_MAXH, FS_MAXW>), grid, dim3(256), 0, st, (const T*)feat, half, half ? coef : nullptr, (const T*)dhigh, (const T*)dlow, dre, half ? fre : nullptr, fim, C, H, W);
     MI_LAUNCH_CHECK();
-  }
-  AD_DISPATCH(dtype, hipLaunchKernelGGL((fre_split_bwd2_kernel<float, FS_MAXH, FS_MAXW>), grid, dim3(256), 0, st, dre, half, half ? coef_f : nullptr, (float*)dfeat, C, H, W),
-              hipLaunchKernelGGL((fre_split_bwd2_kernel<bf16, FS_MAXH, FS_MAXW>), grid, dim3(256), 0, st, dre, half, half ? coef_f : nullptr, (bf16*)dfeat, C, H, W));
-  MI_LAUNCH_CHECK();
-  return MI_OK;
+    if (half) {   // the spectrum of the fp32 intermediate, whatever the activations' dtype
+      hipLaunchKernelGGL((lowfreq_coef_kernel<float, FS_MAXH, FS_MAXW>), dim3(B * C), dim3(256), 0, st, (const float*)nullptr, fre, fim, half, coef_f, C, H, W);
+      MI_LAUNCH_CHECK();
+    }
+    hipLaunchKernelGGL((fre_split_bwd2_kernel<T, FS_MAXH, FS_MAXW>), grid, dim3(256), 0, st, dre, half, half ? coef_f : nullptr, (T*)dfeat, C, H, W);
+    MI_LAUNCH_CHECK();
+    return MI_OK;
+  });
 }
 
 extern "C" int mi_chan_maxmean_fwd(const void* x, void* out, int* idx, int B, int C, int64_t N, int dtype, void* stream) {
@@ -521,40 +514,40 @@ extern "C" int mi_chan_maxmean_fwd(const void* x, void* out, int* idx, int B, in
   hipStream_t st = (hipStream_t)stream;
   ProfScope ps(st, K_ADAIR, 0.0, 0.0);
   dim3 grid(cdiv(N, 256), B);
-  AD_DISPATCH(dtype, hipLaunchKernelGGL((chan_maxmean_fwd_kernel<float>), grid, dim3(256), 0, st, (const float*)x, (float*)out, idx, C, N),
-              hipLaunchKernelGGL((chan_maxmean_fwd_kernel<bf16>), grid, dim3(256), 0, st, (const bf16*)x, (bf16*)out, idx, C, N));
-  MI_LAUNCH_CHECK();
-  return MI_OK;
+  return with_dtype(dtype, "chan_maxmean_fwd", [&](auto tag) {
+    using T = decltype(tag);
+    hipLaunchKernelGGL((chan_maxmean_fwd_kernel<T>), grid, dim3(256), 0, st, (const T*)x, (T*)out, idx, C, N);
+  });
 }
 extern "C" int mi_chan_maxmean_bwd(const void* dout, const int* idx, void* dx, int B, int C, int64_t N, int dtype, void* stream) {
   MI_CHECK_ARG(dout && idx && dx && B > 0 && C > 0 && N > 0, "chan_maxmean_bwd: bad arguments");
   hipStream_t st = (hipStream_t)stream;
   ProfScope ps(st, K_ADAIR, 0.0, 0.0);
   dim3 grid(cdiv(N, 256), B);
-  AD_DISPATCH(dtype, hipLaunchKernelGGL((chan_maxmean_bwd_kernel<float>), grid, dim3(256), 0, st, (const float*)dout, idx, (float*)dx, C, N),
-              hipLaunchKernelGGL((chan_maxmean_bwd_kernel<bf16>), grid, dim3(256), 0, st, (const bf16*)dout, idx, (bf16*)dx, C, N));
-  MI_LAUNCH_CHECK();
-  return MI_OK;
+  return with_dtype(dtype, "chan_maxmean_bwd", [&](auto tag) {
+    using T = decltype(tag);
+    hipLaunchKernelGGL((chan_maxmean_bwd_kernel<T>), grid, dim3(256), 0, st, (const T*)dout, idx, (T*)dx, C, N);
+  });
 }
 
 extern "C" int mi_plane_max_fwd(const void* x, float* out, int* idx, int planes, int64_t N, int dtype, void* stream) {
   MI_CHECK_ARG(x && out && idx && planes > 0 && N > 0, "plane_max_fwd: bad arguments");
   hipStream_t st = (hipStream_t)stream;
   ProfScope ps(st, K_ADAIR, 0.0, 0.0);
-  AD_DISPATCH(dtype, hipLaunchKernelGGL((plane_max_fwd_kernel<float>), dim3(planes), dim3(256), 0, st, (const float*)x, out, idx, N),
-              hipLaunchKernelGGL((plane_max_fwd_kernel<bf16>), dim3(planes), dim3(256), 0, st, (const bf16*)x, out, idx, N));
-  MI_LAUNCH_CHECK();
-  return MI_OK;
+  return with_dtype(dtype, "plane_max_fwd", [&](auto tag) {
+    using T = decltype(tag);
+    hipLaunchKernelGGL((plane_max_fwd_kernel<T>), dim3(planes), dim3(256), 0, st, (const T*)x, out, idx, N);
+  });
 }
 extern "C" int mi_pool_pair_bwd(const float* davg, const float* dmax, const int* idx, void* dx, int planes, int64_t N, int dtype,
                                 void* stream) {
   MI_CHECK_ARG(davg && dmax && idx && dx && planes > 0 && N > 0, "pool_pair_bwd: bad arguments");
   hipStream_t st = (hipStream_t)stream;
   ProfScope ps(st, K_ADAIR, 0.0, 0.0);
-  AD_DISPATCH(dtype, hipLaunchKernelGGL((pool_pair_bwd_kernel<float>), dim3(planes), dim3(256), 0, st, davg, dmax, idx, (float*)dx, N),
-              hipLaunchKernelGGL((pool_pair_bwd_kernel<bf16>), dim3(planes), dim3(256), 0, st, davg, dmax, idx, (bf16*)dx, N));
-  MI_LAUNCH_CHECK();
-  return MI_OK;
+  return with_dtype(dtype, "pool_pair_bwd", [&](auto tag) {
+    using T = decltype(tag);
+    hipLaunchKernelGGL((pool_pair_bwd_kernel<T>), dim3(planes), dim3(256), 0, st, davg, dmax, idx, (T*)dx, N);
+  });
 }
 
 extern "C" int mi_chan_gate_fwd(const float* avg, const float* mx, const float* w1, const float* w2, float* cw, float* hid, int B,
@@ -582,10 +575,10 @@ extern "C" int mi_refine_mix_fwd(const void* low, const void* high, const void* 
   hipStream_t st = (hipStream_t)stream;
   ProfScope ps(st, K_ADAIR, 0.0, 0.0);
   dim3 grid(cdiv(N, 256), B);
-  AD_DISPATCH(dtype, hipLaunchKernelGGL((refine_mix_fwd_kernel<float>), grid, dim3(256), 0, st, (const float*)low, (const float*)high, (const float*)s, cw, (float*)out, C, N),
-              hipLaunchKernelGGL((refine_mix_fwd_kernel<bf16>), grid, dim3(256), 0, st, (const bf16*)low, (const bf16*)high, (const bf16*)s, cw, (bf16*)out, C, N));
-  MI_LAUNCH_CHECK();
-  return MI_OK;
+  return with_dtype(dtype, "refine_mix_fwd", [&](auto tag) {
+    using T = decltype(tag);
+    hipLaunchKernelGGL((refine_mix_fwd_kernel<T>), grid, dim3(256), 0, st, (const T*)low, (const T*)high, (const T*)s, cw, (T*)out, C, N);
+  });
 }
 extern "C" int mi_refine_mix_bwd(const void* low, const void* high, const void* s, const float* cw, const void* dout, void* dlow,
                                  void* dhigh, void* ds, float* dcw, int B, int C, int64_t N, int dtype, void* stream) {
@@ -593,13 +586,14 @@ extern "C" int mi_refine_mix_bwd(const void* low, const void* high, const void* 
   hipStream_t st = (hipStream_t)stream;
   ProfScope ps(st, K_ADAIR, 0.0, 0.0);
   dim3 grid(cdiv(N, 256), B);
-  AD_DISPATCH(dtype, hipLaunchKernelGGL((refine_mix_bwd_kernel<float>), grid, dim3(256), 0, st, (const float*)low, (const float*)s, cw, (const float*)dout, (float*)dlow, (float*)dhigh, (float*)ds, C, N),
-              hipLaunchKernelGGL((refine_mix_bwd_kernel<bf16>), grid, dim3(256), 0, st, (const bf16*)low, (const bf16*)s, cw, (const bf16*)dout, (bf16*)dlow, (bf16*)dhigh, (bf16*)ds, C, N));
-  MI_LAUNCH_CHECK();
-  AD_DISPATCH(dtype, hipLaunchKernelGGL((plane_dot_kernel<float>), dim3(B * C), dim3(256), 0, st, (const float*)dout, (const float*)high, dcw, N),
-              hipLaunchKernelGGL((plane_dot_kernel<bf16>), dim3(B * C), dim3(256), 0, st, (const bf16*)dout, (const bf16*)high, dcw, N));
-  MI_LAUNCH_CHECK();
-  return MI_OK;
+  return with_dtype(dtype, "refine_mix_bwd", [&](auto tag) -> int {
+    using T = decltype(tag);
+    hipLaunchKernelGGL((refine_mix_bwd_kernel<T>), grid, dim3(256), 0, st, (const T*)low, (const T*)s, cw, (const T*)dout, (T*)dlow, (T*)dhigh, (T*)ds, C, N);
+    MI_LAUNCH_CHECK();
+    hipLaunchKernelGGL((plane_dot_kernel<T>), dim3(B * C), dim3(256), 0, st, (const T*)dout, (const T*)high, dcw, N);
+    MI_LAUNCH_CHECK();
+    return MI_OK;
+  });
 }
 
 extern "C" int mi_scale_add_fwd(const void* a, const void* y, const float* p1, const float* p2, void* out, int B, int C, int64_t N,
@@ -608,10 +602,10 @@ extern "C" int mi_scale_add_fwd(const void* a, const void* y, const float* p1, c
   hipStream_t st = (hipStream_t)stream;
   ProfScope ps(st, K_ADAIR, 0.0, 0.0);
   dim3 grid(cdiv(N, 256), B * C);
-  AD_DISPATCH(dtype, hipLaunchKernelGGL((scale_add_fwd_kernel<float>), grid, dim3(256), 0, st, (const float*)a, (const float*)y, p1, p2, (float*)out, C, N),
-              hipLaunchKernelGGL((scale_add_fwd_kernel<bf16>), grid, dim3(256), 0, st, (const bf16*)a, (const bf16*)y, p1, p2, (bf16*)out, C, N));
-  MI_LAUNCH_CHECK();
-  return MI_OK;
+  return with_dtype(dtype, "scale_add_fwd", [&](auto tag) {
+    using T = decltype(tag);
+    hipLaunchKernelGGL((scale_add_fwd_kernel<T>), grid, dim3(256), 0, st, (const T*)a, (const T*)y, p1, p2, (T*)out, C, N);
+  });
 }
 extern "C" int mi_scale_add_bwd(const void* a, const void* y, const float* p1, const float* p2, const void* dout, void* da, void* dy,
                                 float* dp1, float* dp2, int B, int C, int64_t N, int accumulate, int dtype, void* stream) {
@@ -620,11 +614,12 @@ extern "C" int mi_scale_add_bwd(const void* a, const void* y, const float* p1, c
   hipStream_t st = (hipStream_t)stream;
   ProfScope ps(st, K_ADAIR, 0.0, 0.0);
   dim3 grid(cdiv(N, 256), B * C);
-  AD_DISPATCH(dtype, hipLaunchKernelGGL((scale_add_bwd_kernel<float>), grid, dim3(256), 0, st, (const float*)dout, p1, p2, (float*)da, (float*)dy, C, N),
-              hipLaunchKernelGGL((scale_add_bwd_kernel<bf16>), grid, dim3(256), 0, st, (const bf16*)dout, p1, p2, (bf16*)da, (bf16*)dy, C, N));
-  MI_LAUNCH_CHECK();
-  AD_DISPATCH(dtype, hipLaunchKernelGGL((scale_add_wgrad_kernel<float>), dim3(C), dim3(256), 0, st, (const float*)a, (const float*)y, (const float*)dout, dp1, dp2, B, C, N, accumulate),
-              hipLaunchKernelGGL((scale_add_wgrad_kernel<bf16>), dim3(C), dim3(256), 0, st, (const bf16*)a, (const bf16*)y, (const bf16*)dout, dp1, dp2, B, C, N, accumulate));
-  MI_LAUNCH_CHECK();
-  return MI_OK;
+  return with_dtype(dtype, "scale_add_bwd", [&](auto tag) -> int {
+    using T = decltype(tag);
+    hipLaunchKernelGGL((scale_add_bwd_kernel<T>), grid, dim3(256), 0, st, (const T*)dout, p1, p2, (T*)da, (T*)dy, C, N);
+    MI_LAUNCH_CHECK();
+    hipLaunchKernelGGL((scale_add_wgrad_kernel<T>), dim3(C), dim3(256), 0, st, (const T*)a, (const T*)y, (const T*)dout, dp1, dp2, B, C, N, accumulate);
+    MI_LAUNCH_CHECK();
+    return MI_OK;
+  });
 }

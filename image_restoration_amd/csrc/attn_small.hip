@@ -16,7 +16,6 @@ constexpr float NORM_EPS = 1e-12f;  // F.normalize eps (Restormer.py:121-122)
 constexpr int ATTN_MAX_C = 128;     // 16x16 threads x (up to) 8x8 register tile
 constexpr int ATT_RC = 16;          // rows of W_o / dM handled by one workgroup
 
-static inline int attn_ld(int c) { return c + 1; }
 static inline int attn_ct(int c) { return (c + 15) / 16; }
 static inline int attn_rchunks(int C) { return (C + ATT_RC - 1) / ATT_RC; }
 
@@ -433,20 +432,21 @@ int chan_sum_splits(int C, int64_t N) {
 size_t chan_sum_workspace(int C, int64_t N) { return align_up((size_t)chan_sum_splits(C, N) * C * sizeof(float), 256); }
 
 int launch_chan_sum(const void* x, float* out, int B, int C, int64_t N, int dtype, int accumulate, void* ws, hipStream_t st) {
-  const int splits = chan_sum_splits(C, N);
-  int64_t per = (N + splits - 1) / splits;
-  per = (per + 7) / 8 * 8;                              // split bounds on 16-byte vectors (the last split takes the remainder)
-  float* part = (float*)ws;
-  if (accumulate) {          // a parameter gradient accumulated in place: the split sum may wait for mi_deferred_flush (common.h)
-    float* arena = deferred_take((size_t)splits * C, st);
-    if (arena) part = arena;
-  }
-  dim3 grid(C, splits), block(256);
-  ProfScope ps(st, K_CHAN_SUM, (double)B * C * N * dtype_size(dtype), (double)B * C * N);
-  if (dtype == MI_F32) hipLaunchKernelGGL((chan_sum_kernel<float>), grid, block, 0, st, (const float*)x, part, B, C, N, per);
-  else hipLaunchKernelGGL((chan_sum_kernel<bf16>), grid, block, 0, st, (const bf16*)x, part, B, C, N, per);
-  MI_LAUNCH_CHECK();
-  return launch_reduce_rows(part, out, splits, C, C, accumulate, 1.0f, st);
+  return with_dtype(dtype, "chan_sum", [&](auto tag) -> int {
+    using T = decltype(tag);
+    const int splits = chan_sum_splits(C, N);
+    int64_t per = (N + splits - 1) / splits;
+    per = (per + 7) / 8 * 8;                              // split bounds on 16-byte vectors (the last split takes the remainder)
+    float* part = (float*)ws;
+    if (accumulate) {          // a parameter gradient accumulated in place: the split sum may wait for mi_deferred_flush (common.h)
+      float* arena = deferred_take((size_t)splits * C, st);
+      if (arena) part = arena;
+    }
+    ProfScope ps(st, K_CHAN_SUM, (double)B * C * N * sizeof(T), (double)B * C * N);
+    hipLaunchKernelGGL((chan_sum_kernel<T>), dim3(C, splits), dim3(256), 0, st, (const T*)x, part, B, C, N, per);
+    MI_LAUNCH_CHECK();
+    return launch_reduce_rows(part, out, splits, C, C, accumulate, 1.0f, st);
+  });
 }
 
 #define ATTN_CT_SWITCH(ct, CALL)                                       \
@@ -515,6 +515,5 @@ int launch_attn_bwd_small(const float* dM, const float* A, const float* P, const
 extern "C" size_t mi_chan_sum_workspace(int C, int64_t N) { return (C > 0 && N > 0) ? mi::chan_sum_workspace(C, N) : 0; }
 extern "C" int mi_chan_sum(const void* x, float* out, int B, int C, int64_t N, int dtype, int accumulate, void* ws, void* stream) {
   MI_CHECK_ARG(x && out && ws && B >= 1 && C >= 1 && N >= 1, "chan_sum: null pointer / bad shape");
-  MI_CHECK_ARG(dtype == MI_F32 || dtype == MI_BF16, "chan_sum: bad dtype %d", dtype);
   return mi::launch_chan_sum(x, out, B, C, N, dtype, accumulate, ws, (hipStream_t)stream);
 }

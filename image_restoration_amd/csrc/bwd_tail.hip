@@ -87,19 +87,19 @@ struct BtCfg {
   static_assert(BYTES <= 160 * 1024, "LDS budget");
 };
 
-// element index of (channel c, pixel px) in an unpadded [C][64] bf16 tile whose 16-byte chunks are XOR-swizzled by the row:
+// (channel c, pixel px) of an unpadded [C][64] bf16 tile sits at element c * 64 + ((((px >> 3) ^ (c >> 1)) & 7) << 3) + (px & 7):
+// the 16-byte chunks are XOR-swizzled by the row.
 // 128-byte rows would put every row on the same banks; with chunk position (px/8) ^ ((c/2) & 7) the 8-byte operand reads of 16
 // consecutive rows, the 2-byte reads of the LayerNorm phase and the row-wise store all spread over the banks, and the tile can
 // be filled by LDS-DMA (which writes a wave's 1 KiB linearly) by permuting the SOURCE chunks instead.
-__device__ __forceinline__ int bt_swz(int c, int px) { return c * 64 + ((((px >> 3) ^ (c >> 1)) & 7) << 3) + (px & 7); }
 
 template <int C, int NW, int MPW>
 __global__ __launch_bounds__(64 * NW, (BtCfg<C, NW, MPW>::BYTES <= 80 * 1024 ? 2 : 1)) void bt_kernel(BtArgs a) {
   using K = BtCfg<C, NW, MPW>;
-  constexpr int CT = K::CT, KS = K::KS, PS = BT_PS, XS = K::XS, NT = K::NT, LPP = K::LPP, CPL = K::CPL, ITEMS = K::ITEMS;
+  constexpr int CT = K::CT, KS = K::KS, PS = BT_PS, XS = K::XS, NT = K::NT, LPP = K::LPP, ITEMS = K::ITEMS;
   constexpr int XP = K::XP, PPW = K::PPW;
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
-  const int t = threadIdx.x, lane = t & 63, li = lane & 15, g = lane >> 4, qq = li >> 2, pp = li & 3;
+  const int t = threadIdx.x, lane = t & 63, li = lane & 15, g = lane >> 4;
   const int wv = __builtin_amdgcn_readfirstlane(t >> 6);               // wave index in a scalar register: everything derived from
                                                                         // it (row range, patch, DMA pieces, channel tile) is scalar too
   bf16* const patch = reinterpret_cast<bf16*>(lds) + wv * K::PATCH_E;

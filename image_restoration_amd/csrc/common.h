@@ -4,6 +4,7 @@
 #include <stdint.h>
 #include <stdio.h>
 #include <string.h>
+#include <type_traits>
 
 #include "../../include/mi_restore.h"
 
@@ -94,7 +95,28 @@ void set_error(const char* fmt, ...);
 static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 static inline int cdiv(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
+static inline int cdiv_cap(int64_t a, int64_t b, int cap) { const int64_t n = (a + b - 1) / b; return n < cap ? (int)n : cap; }   // a capped grid
 static inline size_t dtype_size(int dt) { return dt == MI_BF16 ? 2 : 4; }
+
+// The one place where a dtype code picks a template instantiation.  f is a generic lambda, called as f(T{}) with T = float or
+// bf16; any other code fails with "<who>: bad dtype <code>" before anything is launched.  f either returns int (a sequence with
+// its own MI_LAUNCH_CHECK / MI_TRY: write `-> int`, those macros return enumerators) or returns nothing (it only launches: the
+// launch is checked here).
+template <typename T, typename F> static inline int call_typed(F& f) {
+  if constexpr (std::is_void<decltype(f(T{}))>::value) {
+    f(T{});
+    MI_LAUNCH_CHECK();
+    return MI_OK;
+  } else {
+    return f(T{});
+  }
+}
+template <typename F> static inline int with_dtype(int dtype, const char* who, F&& f) {
+  if (dtype == MI_F32) return call_typed<float>(f);
+  if (dtype == MI_BF16) return call_typed<bf16>(f);
+  set_error("%s: bad dtype %d", who, dtype);
+  return MI_ERR_ARG;
+}
 
 // Bump allocator over a caller-provided blob (saved-for-backward / workspace carving).
 struct Carver {

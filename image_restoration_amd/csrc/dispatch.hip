@@ -8,8 +8,6 @@
 namespace mi {
 namespace {
 
-constexpr int DV = 8;  // elements per thread step
-
 // out[i] = x[idx[i]]
 template <typename T>
 __global__ __launch_bounds__(256) void rows_gather_kernel(const T* __restrict__ x, const int64_t* __restrict__ idx,
@@ -92,45 +90,39 @@ using namespace mi;
 
 extern "C" int mi_rows_gather(const void* x, const int64_t* idx, void* out, int n_out, int64_t row, int dtype, void* stream) {
   MI_CHECK_ARG(x && idx && out && n_out >= 0 && row > 0, "rows_gather: bad arguments");
-  MI_CHECK_ARG(dtype == MI_F32 || dtype == MI_BF16, "rows_gather: bad dtype %d", dtype);
-  if (n_out == 0) return MI_OK;
-  hipStream_t st = (hipStream_t)stream;
-  const int64_t vec = 16 / (int64_t)dtype_size(dtype);
-  const int ok = (row % vec == 0) && aligned16(x) && aligned16(out);
-  dim3 grid(row_blocks(row), n_out);
-  if (dtype == MI_F32) hipLaunchKernelGGL((rows_gather_kernel<float>), grid, dim3(256), 0, st, (const float*)x, idx, (float*)out, row, ok);
-  else hipLaunchKernelGGL((rows_gather_kernel<bf16>), grid, dim3(256), 0, st, (const bf16*)x, idx, (bf16*)out, row, ok);
-  MI_LAUNCH_CHECK();
-  return MI_OK;
+  return with_dtype(dtype, "rows_gather", [&](auto tag) -> int {
+    using T = decltype(tag);
+    if (n_out == 0) return MI_OK;
+    const int64_t vec = 16 / (int64_t)sizeof(T);
+    const int ok = (row % vec == 0) && aligned16(x) && aligned16(out);
+    hipLaunchKernelGGL((rows_gather_kernel<T>), dim3(row_blocks(row), n_out), dim3(256), 0, (hipStream_t)stream, (const T*)x, idx, (T*)out, row, ok);
+    MI_LAUNCH_CHECK();
+    return MI_OK;
+  });
 }
 
 extern "C" int mi_rows_gather_scaled(const float* x, const int64_t* idx, const float* scale, void* out, int n_out, int64_t row,
                                      int out_dtype, void* stream) {
   MI_CHECK_ARG(x && idx && out && n_out >= 0 && row > 0, "rows_gather_scaled: bad arguments");
-  MI_CHECK_ARG(out_dtype == MI_F32 || out_dtype == MI_BF16, "rows_gather_scaled: bad dtype %d", out_dtype);
-  if (n_out == 0) return MI_OK;
-  hipStream_t st = (hipStream_t)stream;
-  dim3 grid(row_blocks(row), n_out);
-  if (out_dtype == MI_F32) hipLaunchKernelGGL((rows_gather_scaled_kernel<float>), grid, dim3(256), 0, st, x, idx, scale, (float*)out, row);
-  else hipLaunchKernelGGL((rows_gather_scaled_kernel<bf16>), grid, dim3(256), 0, st, x, idx, scale, (bf16*)out, row);
-  MI_LAUNCH_CHECK();
-  return MI_OK;
+  return with_dtype(out_dtype, "rows_gather_scaled", [&](auto tag) -> int {
+    using T = decltype(tag);
+    if (n_out == 0) return MI_OK;
+    hipLaunchKernelGGL((rows_gather_scaled_kernel<T>), dim3(row_blocks(row), n_out), dim3(256), 0, (hipStream_t)stream, x, idx, scale, (T*)out, row);
+    MI_LAUNCH_CHECK();
+    return MI_OK;
+  });
 }
 
 extern "C" int mi_rows_scatter_add(const void* src, const int64_t* idx, const float* scale, void* out, int n_src, int n_rows,
                                    int64_t row, int dtype, int out_f32, void* stream) {
   MI_CHECK_ARG(src && idx && out && n_src >= 0 && n_rows > 0 && row > 0, "rows_scatter_add: bad arguments");
-  MI_CHECK_ARG(dtype == MI_F32 || dtype == MI_BF16, "rows_scatter_add: bad dtype %d", dtype);
   hipStream_t st = (hipStream_t)stream;
   dim3 grid(row_blocks(row), n_rows);
-  if (dtype == MI_F32)
-    hipLaunchKernelGGL((rows_scatter_kernel<float, float>), grid, dim3(256), 0, st, (const float*)src, idx, scale, (float*)out, n_src, row);
-  else if (out_f32)
-    hipLaunchKernelGGL((rows_scatter_kernel<bf16, float>), grid, dim3(256), 0, st, (const bf16*)src, idx, scale, (float*)out, n_src, row);
-  else
-    hipLaunchKernelGGL((rows_scatter_kernel<bf16, bf16>), grid, dim3(256), 0, st, (const bf16*)src, idx, scale, (bf16*)out, n_src, row);
-  MI_LAUNCH_CHECK();
-  return MI_OK;
+  return with_dtype(dtype, "rows_scatter_add", [&](auto tag) {   // fp32 rows always land in an fp32 `out`
+    using T = decltype(tag);
+    if (out_f32) hipLaunchKernelGGL((rows_scatter_kernel<T, float>), grid, dim3(256), 0, st, (const T*)src, idx, scale, (float*)out, n_src, row);
+    else hipLaunchKernelGGL((rows_scatter_kernel<T, T>), grid, dim3(256), 0, st, (const T*)src, idx, scale, (T*)out, n_src, row);
+  });
 }
 
 extern "C" size_t mi_rows_dot_workspace(int n_src, int64_t row) {
@@ -140,14 +132,14 @@ extern "C" size_t mi_rows_dot_workspace(int n_src, int64_t row) {
 extern "C" int mi_rows_dot(const float* g, const void* src, const int64_t* idx, float* out, int n_src, int64_t row, int dtype,
                            void* ws, void* stream) {
   MI_CHECK_ARG(g && src && idx && out && ws && n_src >= 0 && row > 0, "rows_dot: bad arguments");
-  MI_CHECK_ARG(dtype == MI_F32 || dtype == MI_BF16, "rows_dot: bad dtype %d", dtype);
-  if (n_src == 0) return MI_OK;
-  hipStream_t st = (hipStream_t)stream;
-  const int nb = row_blocks(row);
-  dim3 grid(nb, n_src);
-  float* part = (float*)ws;
-  if (dtype == MI_F32) hipLaunchKernelGGL((rows_dot_kernel<float>), grid, dim3(256), 0, st, g, (const float*)src, idx, part, row);
-  else hipLaunchKernelGGL((rows_dot_kernel<bf16>), grid, dim3(256), 0, st, g, (const bf16*)src, idx, part, row);
-  MI_LAUNCH_CHECK();
-  return launch_reduce_rows(part, out, nb, n_src, n_src, 0, 1.0f, st);
+  return with_dtype(dtype, "rows_dot", [&](auto tag) -> int {
+    using T = decltype(tag);
+    if (n_src == 0) return MI_OK;
+    hipStream_t st = (hipStream_t)stream;
+    const int nb = row_blocks(row);
+    float* part = (float*)ws;
+    hipLaunchKernelGGL((rows_dot_kernel<T>), dim3(nb, n_src), dim3(256), 0, st, g, (const T*)src, idx, part, row);
+    MI_LAUNCH_CHECK();
+    return launch_reduce_rows(part, out, nb, n_src, n_src, 0, 1.0f, st);
+  });
 }

@@ -625,20 +625,15 @@ static int check_common(const char* who, int B, int C, int H, int W, int ks, int
   return MI_OK;
 }
 
-#define DW_DISPATCH(T_, KS_, CALL)                 \
-  do {                                             \
-    if (dtype == MI_F32) {                         \
-      using T_ = float;                            \
-      if (ks == 3) { constexpr int KS_ = 3; CALL; } \
-      else if (ks == 5) { constexpr int KS_ = 5; CALL; } \
-      else { constexpr int KS_ = 7; CALL; }        \
-    } else {                                       \
-      using T_ = bf16;                             \
-      if (ks == 3) { constexpr int KS_ = 3; CALL; } \
-      else if (ks == 5) { constexpr int KS_ = 5; CALL; } \
-      else { constexpr int KS_ = 7; CALL; }        \
-    }                                              \
-  } while (0)
+// dtype and ks (checked by check_common) -> the types T_ and KS_ that CALL names; the value is CALL's return code
+#define DW_DISPATCH(T_, KS_, CALL)                             \
+  with_dtype(dtype, "dwconv", [&](auto tag_) -> int {          \
+    using T_ = decltype(tag_);                                 \
+    if (ks == 3) { constexpr int KS_ = 3; return CALL; }       \
+    if (ks == 5) { constexpr int KS_ = 5; return CALL; }       \
+    constexpr int KS_ = 7;                                     \
+    return CALL;                                               \
+  })
 
 }  // namespace mi
 
@@ -649,9 +644,7 @@ extern "C" int mi_dwconv_fwd(const void* x, const float* w, const float* bias, v
   MI_CHECK_ARG(x && w && y, "dwconv_fwd: null pointer");
   MI_TRY(check_common("dwconv_fwd", B, C, H, W, ks, dtype));
   DwArgs a{x, nullptr, w, bias, y, nullptr, C, H, W, 0, 0};
-  int rc = MI_OK;
-  DW_DISPATCH(T, KS, (rc = dw_launch<T, KS, false>(a, B, (hipStream_t)stream)));
-  return rc;
+  return DW_DISPATCH(T, KS, (dw_launch<T, KS, false>(a, B, (hipStream_t)stream)));
 }
 
 extern "C" int mi_dwconv_gate_fwd(const void* x, const float* w, const float* bias, void* y, void* g, int B, int C2, int H,
@@ -660,9 +653,7 @@ extern "C" int mi_dwconv_gate_fwd(const void* x, const float* w, const float* bi
   MI_CHECK_ARG(C2 % 2 == 0, "dwconv_gate_fwd: channel count %d must be even", C2);
   MI_TRY(check_common("dwconv_gate_fwd", B, C2, H, W, ks, dtype));
   DwArgs a{x, nullptr, w, bias, y, g, C2, H, W, C2 / 2, 0};
-  int rc = MI_OK;
-  DW_DISPATCH(T, KS, (rc = dw_launch<T, KS, true>(a, B, (hipStream_t)stream)));
-  return rc;
+  return DW_DISPATCH(T, KS, (dw_launch<T, KS, true>(a, B, (hipStream_t)stream)));
 }
 
 extern "C" size_t mi_dwconv_bwd_workspace(int B, int C, int H, int W, int ks) {
@@ -683,15 +674,14 @@ static int dw_bwd_common(const void* dy_or_dg, const void* gy, const void* x, co
   DwArgs a{dy_or_dg, gy, w, nullptr, dx, nullptr, Cc, H, W, gate ? Cc / 2 : 0, 0};
   MI_CHECK_ARG(dx || dwg, "dwconv_bwd: nothing to compute");
   MI_CHECK_ARG(!dwg || (ws && x), "dwconv_bwd: weight gradient needs x and a workspace");
-  int rc = MI_OK, rows = 0;
+  int rows = 0;
   float* part = (float*)ws;
   if (dwg && accumulate) {   // parameter gradients accumulated in place: partials may wait for mi_deferred_flush (common.h)
     float* arena = deferred_take(mi_dwconv_bwd_workspace(B, Cc, H, W, ks) / sizeof(float), st);
     if (arena) part = arena;
   }
-  if (gate) DW_DISPATCH(T, KS, (rc = dw_gate_bwd_launch<T, KS>(a, x, part, B, dwg != nullptr, &rows, st)));
-  else DW_DISPATCH(T, KS, (rc = dw_bwd_launch<T, KS, IN_PLAIN>(a, x, part, B, dx != nullptr, dwg != nullptr, &rows, st)));
-  if (rc != MI_OK) return rc;
+  if (gate) MI_TRY(DW_DISPATCH(T, KS, (dw_gate_bwd_launch<T, KS>(a, x, part, B, dwg != nullptr, &rows, st))));
+  else MI_TRY(DW_DISPATCH(T, KS, (dw_bwd_launch<T, KS, IN_PLAIN>(a, x, part, B, dx != nullptr, dwg != nullptr, &rows, st))));
   if (dwg) {
     const int kk = ks * ks;
     const int64_t ld = (int64_t)Cc * (kk + 1);

@@ -641,15 +641,13 @@ int dws_fwd(const DwArgs& a, int B, bool gate, bool flip, int dtype, hipStream_t
   const int64_t planes = (int64_t)B * (gate ? a.hidden : a.Cc);
   const Plan p = make_plan(a.H, a.W, planes);
   dim3 grid(p.blocks), block(256);
-#define DWS_FWD(T_)                                                                                                      \
-  DWS_LPR_SWITCH(a.W, {                                                                                                  \
-    if (gate) hipLaunchKernelGGL((dws_gate_fwd2_kernel<T_, LPR, UNI>), grid, block, 0, st, a, (int)planes, p.nb, p.band);     \
-    else hipLaunchKernelGGL((dws_fwd_kernel<T_, false, LPR, UNI>), grid, block, 0, st, a, (int)planes, p.nb, p.band, flip ? 1 : 0); \
-  })
-  if (dtype == MI_F32) { DWS_FWD(float); } else { DWS_FWD(bf16); }
-#undef DWS_FWD
-  MI_LAUNCH_CHECK();
-  return MI_OK;
+  return with_dtype(dtype, "dws_fwd", [&](auto tag) {
+    using T = decltype(tag);
+    DWS_LPR_SWITCH(a.W, {
+      if (gate) hipLaunchKernelGGL((dws_gate_fwd2_kernel<T, LPR, UNI>), grid, block, 0, st, a, (int)planes, p.nb, p.band);
+      else hipLaunchKernelGGL((dws_fwd_kernel<T, false, LPR, UNI>), grid, block, 0, st, a, (int)planes, p.nb, p.band, flip ? 1 : 0);
+    })
+  });
 }
 
 int dws_bwd(const DwArgs& a, const void* xin, float* part, int B, bool want_dx, int* rows_out, int dtype, hipStream_t st) {
@@ -657,17 +655,15 @@ int dws_bwd(const DwArgs& a, const void* xin, float* part, int B, bool want_dx, 
   const Plan p = make_plan(a.H, a.W, planes);
   *rows_out = p.nb * B;
   dim3 grid(p.blocks), block(256);
-#define DWS_BWD(T_)                                                                                              \
-  DWS_LPR_SWITCH(a.W, {                                                                                          \
-    if (want_dx) hipLaunchKernelGGL((dws_bwd_kernel<T_, LPR, UNI, true>), grid, block, 0, st, a, (const T_*)xin, part, \
-                                    (int)planes, p.nb, p.band);                                                  \
-    else hipLaunchKernelGGL((dws_bwd_kernel<T_, LPR, UNI, false>), grid, block, 0, st, a, (const T_*)xin, part,        \
-                            (int)planes, p.nb, p.band);                                                          \
-  })
-  if (dtype == MI_F32) { DWS_BWD(float); } else { DWS_BWD(bf16); }
-#undef DWS_BWD
-  MI_LAUNCH_CHECK();
-  return MI_OK;
+  return with_dtype(dtype, "dws_bwd", [&](auto tag) {
+    using T = decltype(tag);
+    DWS_LPR_SWITCH(a.W, {
+      if (want_dx) hipLaunchKernelGGL((dws_bwd_kernel<T, LPR, UNI, true>), grid, block, 0, st, a, (const T*)xin, part,
+                                      (int)planes, p.nb, p.band);
+      else hipLaunchKernelGGL((dws_bwd_kernel<T, LPR, UNI, false>), grid, block, 0, st, a, (const T*)xin, part,
+                              (int)planes, p.nb, p.band);
+    })
+  });
 }
 
 int dws_gate_bwd(const DwArgs& a, const void* xin, float* part, int B, bool want_dw, int* rows_out, int dtype,
@@ -676,17 +672,15 @@ int dws_gate_bwd(const DwArgs& a, const void* xin, float* part, int B, bool want
   const Plan p = make_plan(a.H, a.W, planes);
   *rows_out = p.nb * B;
   dim3 grid(p.blocks), block(256);
-#define DWS_GB(T_)                                                                                                    \
-  DWS_LPR_SWITCH(a.W, {                                                                                               \
-    if (want_dw) hipLaunchKernelGGL((dws_gate_bwd_kernel<T_, LPR, UNI, true>), grid, block, 0, st, a, (const T_*)xin, part, \
-                                    (int)planes, p.nb, p.band);                                                       \
-    else hipLaunchKernelGGL((dws_gate_bwd_kernel<T_, LPR, UNI, false>), grid, block, 0, st, a, (const T_*)xin, part,        \
-                            (int)planes, p.nb, p.band);                                                               \
-  })
-  if (dtype == MI_F32) { DWS_GB(float); } else { DWS_GB(bf16); }
-#undef DWS_GB
-  MI_LAUNCH_CHECK();
-  return MI_OK;
+  return with_dtype(dtype, "dws_gate_bwd", [&](auto tag) {
+    using T = decltype(tag);
+    DWS_LPR_SWITCH(a.W, {
+      if (want_dw) hipLaunchKernelGGL((dws_gate_bwd_kernel<T, LPR, UNI, true>), grid, block, 0, st, a, (const T*)xin, part,
+                                      (int)planes, p.nb, p.band);
+      else hipLaunchKernelGGL((dws_gate_bwd_kernel<T, LPR, UNI, false>), grid, block, 0, st, a, (const T*)xin, part,
+                              (int)planes, p.nb, p.band);
+    })
+  });
 }
 
 
@@ -696,17 +690,15 @@ int dws_gate_bwd_recompute(const DwArgs& a, float* part, int B, bool want_dw, in
   const Plan p = make_plan(a.H, a.W, planes);
   *rows_out = p.nb * B;
   dim3 grid(p.blocks), block(256);
-#define DWS_GBR(T_)                                                                                                       \
-  DWS_LPR_SWITCH(a.W, {                                                                                                   \
-    if (want_dw) hipLaunchKernelGGL((dws_gate_bwd_rc_kernel<T_, LPR, UNI, true>), grid, block, 0, st, a, part, (int)planes, \
-                                    p.nb, p.band);                                                                        \
-    else hipLaunchKernelGGL((dws_gate_bwd_rc_kernel<T_, LPR, UNI, false>), grid, block, 0, st, a, part, (int)planes, p.nb,  \
-                            p.band);                                                                                      \
-  })
-  if (dtype == MI_F32) { DWS_GBR(float); } else { DWS_GBR(bf16); }
-#undef DWS_GBR
-  MI_LAUNCH_CHECK();
-  return MI_OK;
+  return with_dtype(dtype, "dws_gate_bwd_recompute", [&](auto tag) {
+    using T = decltype(tag);
+    DWS_LPR_SWITCH(a.W, {
+      if (want_dw) hipLaunchKernelGGL((dws_gate_bwd_rc_kernel<T, LPR, UNI, true>), grid, block, 0, st, a, part, (int)planes,
+                                      p.nb, p.band);
+      else hipLaunchKernelGGL((dws_gate_bwd_rc_kernel<T, LPR, UNI, false>), grid, block, 0, st, a, part, (int)planes, p.nb,
+                              p.band);
+    })
+  });
 }
 
 }  // namespace mi

@@ -140,17 +140,14 @@ extern "C" int mi_patch_batch(const unsigned char* pool, const int64_t* src_off,
   MI_CHECK_ARG(pool && src_off && src_h && src_w && sample && top && left && mode && B > 0 && P > 0, "patch_batch: bad arguments");
   MI_CHECK_ARG(clean || degraded, "patch_batch: nothing to write");
   MI_CHECK_ARG(!degraded || (sigma && noise), "patch_batch: the degraded output needs sigma and noise");
-  MI_CHECK_ARG(dtype == MI_F32 || dtype == MI_BF16, "patch_batch: bad dtype %d", dtype);
   PatchArgs a{pool, src_off, src_h, src_w, sample, top, left, mode, sigma, noise, clean, degraded, B, P, dtype};
   hipStream_t st = (hipStream_t)stream;
   const int64_t total = (int64_t)3 * P * P * B;
-  int blocks = cdiv(total, 256 * 4);
-  if (blocks > 16384) blocks = 16384;
-  ProfScope ps(st, K_CAST, (double)total * (1.0 + 4.0 + 2.0 * dtype_size(dtype)), 4.0 * total);
-  if (dtype == MI_F32) hipLaunchKernelGGL((patch_batch_kernel<float>), dim3(blocks), dim3(256), 0, st, a);
-  else hipLaunchKernelGGL((patch_batch_kernel<bf16>), dim3(blocks), dim3(256), 0, st, a);
-  MI_LAUNCH_CHECK();
-  return MI_OK;
+  const int blocks = cdiv_cap(total, 256 * 4, 16384);
+  return with_dtype(dtype, "patch_batch", [&](auto tag) {
+    ProfScope ps(st, K_CAST, (double)total * (1.0 + 4.0 + 2.0 * sizeof(tag)), 4.0 * total);
+    hipLaunchKernelGGL((patch_batch_kernel<decltype(tag)>), dim3(blocks), dim3(256), 0, st, a);
+  });
 }
 
 extern "C" size_t mi_psnr_ssim_workspace(int B, int C, int H, int W) {
@@ -162,17 +159,18 @@ extern "C" int mi_psnr_ssim(const void* restored, const void* clean, float* psnr
                             int dtype, void* ws, void* stream) {
   MI_CHECK_ARG(restored && clean && psnr && ssim && ws && B > 0 && C > 0, "psnr_ssim: bad arguments");
   MI_CHECK_ARG(H >= 7 && W >= 7, "psnr_ssim: images must be at least 7 x 7 (the SSIM window)");
-  MI_CHECK_ARG(dtype == MI_F32 || dtype == MI_BF16, "psnr_ssim: bad dtype %d", dtype);
-  hipStream_t st = (hipStream_t)stream;
-  dim3 grid(cdiv(W, SS_T), cdiv(H, SS_T), (unsigned)((int64_t)B * C));
-  MI_CHECK_ARG((int64_t)B * C < 65536 * 16 && grid.y < 65536, "psnr_ssim: grid too large");
-  const double px = (double)B * C * H * W;
-  ProfScope ps(st, K_L1, 2.0 * px * dtype_size(dtype), 260.0 * px);
-  if (dtype == MI_F32) hipLaunchKernelGGL((psnr_ssim_kernel<float>), grid, dim3(256), 0, st, (const float*)restored, (const float*)clean, (float*)ws, H, W);
-  else hipLaunchKernelGGL((psnr_ssim_kernel<bf16>), grid, dim3(256), 0, st, (const bf16*)restored, (const bf16*)clean, (float*)ws, H, W);
-  MI_LAUNCH_CHECK();
-  hipLaunchKernelGGL(psnr_ssim_finish_kernel, dim3(cdiv(B, 64)), dim3(64), 0, st, (const float*)ws, psnr, ssim, B, C,
-                     (int64_t)grid.x * grid.y, H, W);
-  MI_LAUNCH_CHECK();
-  return MI_OK;
+  return with_dtype(dtype, "psnr_ssim", [&](auto tag) -> int {
+    using T = decltype(tag);
+    hipStream_t st = (hipStream_t)stream;
+    dim3 grid(cdiv(W, SS_T), cdiv(H, SS_T), (unsigned)((int64_t)B * C));
+    MI_CHECK_ARG((int64_t)B * C < 65536 * 16 && grid.y < 65536, "psnr_ssim: grid too large");
+    const double px = (double)B * C * H * W;
+    ProfScope ps(st, K_L1, 2.0 * px * sizeof(T), 260.0 * px);
+    hipLaunchKernelGGL((psnr_ssim_kernel<T>), grid, dim3(256), 0, st, (const T*)restored, (const T*)clean, (float*)ws, H, W);
+    MI_LAUNCH_CHECK();
+    hipLaunchKernelGGL(psnr_ssim_finish_kernel, dim3(cdiv(B, 64)), dim3(64), 0, st, (const float*)ws, psnr, ssim, B, C,
+                       (int64_t)grid.x * grid.y, H, W);
+    MI_LAUNCH_CHECK();
+    return MI_OK;
+  });
 }

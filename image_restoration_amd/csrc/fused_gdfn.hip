@@ -750,7 +750,7 @@ struct Fg4Args {
 template <int C, int GP, bool SAVE, bool STAMP = false>
 __global__ __launch_bounds__(512, 2) void fg4_fwd_kernel(Fg4Args a) {
   using K = Fg4Cfg<C, GP>;
-  constexpr int NT = K::NT, TW = K::TW, TH = K::TH, NW = K::NW, CT = K::CT, NCG = K::NCG;
+  constexpr int TW = K::TW, TH = K::TH, NW = K::NW, CT = K::CT, NCG = K::NCG;
   typedef __attribute__((address_space(3))) void* lds_ptr;
   extern __shared__ __attribute__((aligned(16))) unsigned char fg4_lds[];
   unsigned char* const H0 = fg4_lds;                                       // [2][NCG chunk buffers]

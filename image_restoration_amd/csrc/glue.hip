@@ -266,116 +266,77 @@ extern "C" int mi_glue3x3_ok(int H, int W) { return g_ok(H, W) ? 1 : 0; }
 
 extern "C" int mi_im2col3x3(const void* x, void* out, int B, int C, int H, int W, int flip, int dtype, void* stream) {
   MI_CHECK_ARG(x && out && B > 0 && C > 0 && g_ok(H, W), "im2col3x3: bad arguments");
-  MI_CHECK_ARG(dtype == MI_F32 || dtype == MI_BF16, "im2col3x3: bad dtype %d", dtype);
   hipStream_t st = (hipStream_t)stream;
   const int64_t planes = (int64_t)B * C;
-  ProfScope ps(st, K_IM2COL, 10.0 * planes * H * W * dtype_size(dtype), 0.0);
-  if (!(g_fast(H, W) && aligned16(x) && aligned16(out))) {             // general form
-    const int64_t total = planes * 9 * H * W;
-    const unsigned blocks = (unsigned)(total / 256 + 1 > 65536 ? 65536 : total / 256 + 1);
-    if (dtype == MI_F32) {
-      if (flip) hipLaunchKernelGGL((im2col3x3_any_kernel<float, true>), dim3(blocks), dim3(256), 0, st, (const float*)x, (float*)out, planes, H, W);
-      else hipLaunchKernelGGL((im2col3x3_any_kernel<float, false>), dim3(blocks), dim3(256), 0, st, (const float*)x, (float*)out, planes, H, W);
-    } else {
-      if (flip) hipLaunchKernelGGL((im2col3x3_any_kernel<bf16, true>), dim3(blocks), dim3(256), 0, st, (const bf16*)x, (bf16*)out, planes, H, W);
-      else hipLaunchKernelGGL((im2col3x3_any_kernel<bf16, false>), dim3(blocks), dim3(256), 0, st, (const bf16*)x, (bf16*)out, planes, H, W);
+  return with_dtype(dtype, "im2col3x3", [&](auto tag) {
+    using T = decltype(tag);
+    ProfScope ps(st, K_IM2COL, 10.0 * planes * H * W * sizeof(T), 0.0);
+    if (!(g_fast(H, W) && aligned16(x) && aligned16(out))) {             // general form
+      const int64_t total = planes * 9 * H * W;
+      const unsigned blocks = (unsigned)(total / 256 + 1 > 65536 ? 65536 : total / 256 + 1);
+      if (flip) hipLaunchKernelGGL((im2col3x3_any_kernel<T, true>), dim3(blocks), dim3(256), 0, st, (const T*)x, (T*)out, planes, H, W);
+      else hipLaunchKernelGGL((im2col3x3_any_kernel<T, false>), dim3(blocks), dim3(256), 0, st, (const T*)x, (T*)out, planes, H, W);
+      return;
     }
-    MI_LAUNCH_CHECK();
-    return MI_OK;
-  }
-  const GPlan p = g_plan(H, W, planes);
-  if (dtype == MI_F32) {
-    if (flip) { G_LPR_SWITCH(W, hipLaunchKernelGGL((im2col3x3_kernel<float, LPR, true>), dim3(p.blocks), dim3(256), 0, st, (const float*)x,
-                                                   (float*)out, (int)planes, H, W, p.nb, p.band)); }
-    else { G_LPR_SWITCH(W, hipLaunchKernelGGL((im2col3x3_kernel<float, LPR, false>), dim3(p.blocks), dim3(256), 0, st, (const float*)x,
-                                              (float*)out, (int)planes, H, W, p.nb, p.band)); }
-  } else {
-    if (flip) { G_LPR_SWITCH(W, hipLaunchKernelGGL((im2col3x3_kernel<bf16, LPR, true>), dim3(p.blocks), dim3(256), 0, st, (const bf16*)x,
-                                                   (bf16*)out, (int)planes, H, W, p.nb, p.band)); }
-    else { G_LPR_SWITCH(W, hipLaunchKernelGGL((im2col3x3_kernel<bf16, LPR, false>), dim3(p.blocks), dim3(256), 0, st, (const bf16*)x,
-                                              (bf16*)out, (int)planes, H, W, p.nb, p.band)); }
-  }
-  MI_LAUNCH_CHECK();
-  return MI_OK;
+    const GPlan p = g_plan(H, W, planes);
+    if (flip) { G_LPR_SWITCH(W, hipLaunchKernelGGL((im2col3x3_kernel<T, LPR, true>), dim3(p.blocks), dim3(256), 0, st, (const T*)x, (T*)out, (int)planes, H, W, p.nb, p.band)); }
+    else { G_LPR_SWITCH(W, hipLaunchKernelGGL((im2col3x3_kernel<T, LPR, false>), dim3(p.blocks), dim3(256), 0, st, (const T*)x, (T*)out, (int)planes, H, W, p.nb, p.band)); }
+  });
 }
 
 extern "C" int mi_col2im3x3(const void* z, const float* bias, const void* residual, void* y, int B, int M, int H, int W,
                             int flip, int dtype, void* stream) {
   MI_CHECK_ARG(z && y && B > 0 && M > 0 && g_ok(H, W), "col2im3x3: bad arguments");
-  MI_CHECK_ARG(dtype == MI_F32 || dtype == MI_BF16, "col2im3x3: bad dtype %d", dtype);
   hipStream_t st = (hipStream_t)stream;
   const int64_t planes = (int64_t)B * M;
-  ProfScope ps(st, K_COL2IM, (10.0 + (residual ? 1.0 : 0.0)) * planes * H * W * dtype_size(dtype), 9.0 * planes * H * W);
-  if (!(g_fast(H, W) && aligned16(z) && aligned16(y) && aligned16(residual))) {   // general form
-    const int64_t total = planes * H * W;
-    const unsigned blocks = (unsigned)(total / 256 + 1 > 65536 ? 65536 : total / 256 + 1);
-    if (dtype == MI_F32)
-      hipLaunchKernelGGL((col2im3x3_any_kernel<float>), dim3(blocks), dim3(256), 0, st, (const float*)z, bias, (const float*)residual,
-                         (float*)y, planes, M, H, W, flip);
-    else
-      hipLaunchKernelGGL((col2im3x3_any_kernel<bf16>), dim3(blocks), dim3(256), 0, st, (const bf16*)z, bias, (const bf16*)residual,
-                         (bf16*)y, planes, M, H, W, flip);
-    MI_LAUNCH_CHECK();
-    return MI_OK;
-  }
-  const GPlan p = g_plan(H, W, planes);
-  if (dtype == MI_F32) {
-    G_LPR_SWITCH(W, hipLaunchKernelGGL((col2im3x3_kernel<float, LPR>), dim3(p.blocks), dim3(256), 0, st, (const float*)z, bias,
-                                       (const float*)residual, (float*)y, (int)planes, M, H, W, p.nb, p.band, flip));
-  } else {
-    G_LPR_SWITCH(W, hipLaunchKernelGGL((col2im3x3_kernel<bf16, LPR>), dim3(p.blocks), dim3(256), 0, st, (const bf16*)z, bias,
-                                       (const bf16*)residual, (bf16*)y, (int)planes, M, H, W, p.nb, p.band, flip));
-  }
-  MI_LAUNCH_CHECK();
-  return MI_OK;
+  return with_dtype(dtype, "col2im3x3", [&](auto tag) {
+    using T = decltype(tag);
+    ProfScope ps(st, K_COL2IM, (10.0 + (residual ? 1.0 : 0.0)) * planes * H * W * sizeof(T), 9.0 * planes * H * W);
+    if (!(g_fast(H, W) && aligned16(z) && aligned16(y) && aligned16(residual))) {   // general form
+      const int64_t total = planes * H * W;
+      const unsigned blocks = (unsigned)(total / 256 + 1 > 65536 ? 65536 : total / 256 + 1);
+      hipLaunchKernelGGL((col2im3x3_any_kernel<T>), dim3(blocks), dim3(256), 0, st, (const T*)z, bias, (const T*)residual, (T*)y, planes, M, H, W, flip);
+      return;
+    }
+    const GPlan p = g_plan(H, W, planes);
+    G_LPR_SWITCH(W, hipLaunchKernelGGL((col2im3x3_kernel<T, LPR>), dim3(p.blocks), dim3(256), 0, st, (const T*)z, bias, (const T*)residual, (T*)y, (int)planes, M, H, W, p.nb, p.band, flip));
+  });
 }
 
 extern "C" int mi_pixel_shuffle2(const void* in, int64_t in_bs, void* out, int64_t out_bs, int B, int c, int H, int W,
                                  int unshuffle, int dtype, void* stream) {
   MI_CHECK_ARG(in && out && B > 0 && c > 0 && H > 0 && W > 0, "pixel_shuffle2: bad arguments");
-  MI_CHECK_ARG(dtype == MI_F32 || dtype == MI_BF16, "pixel_shuffle2: bad dtype %d", dtype);
   const int64_t dense_lo = (int64_t)4 * c * H * W;  // both sides hold 4*c*H*W elements per image
   const int64_t ibs = in_bs ? in_bs : dense_lo, obs = out_bs ? out_bs : dense_lo;
-  int V = dtype == MI_BF16 ? 8 : 4;                 // 16-byte accesses on the planar side ...
-  if (W % V != 0 || !aligned16(in) || !aligned16(out) || ibs % V != 0 || obs % V != 0) V = 1;   // ... or the element-wise general form
-  hipStream_t st = (hipStream_t)stream;
-  const int64_t total = (int64_t)B * c * 2 * H * (W / V);
-  int blocks = cdiv(total, 256);
-  if (blocks > 16384) blocks = 16384;
-  ProfScope ps(st, K_COL2IM, 2.0 * B * dense_lo * dtype_size(dtype), 0.0);
-#define PS_LAUNCH(T, VV, UN) hipLaunchKernelGGL((pixel_shuffle_kernel<T, VV, UN>), dim3(blocks), dim3(256), 0, st, (const T*)in, (T*)out, c, H, W, ibs, obs, total)
-  if (dtype == MI_BF16) {
-    if (V == 8) { if (unshuffle) PS_LAUNCH(bf16, 8, true); else PS_LAUNCH(bf16, 8, false); }
-    else { if (unshuffle) PS_LAUNCH(bf16, 1, true); else PS_LAUNCH(bf16, 1, false); }
-  } else {
-    if (V == 4) { if (unshuffle) PS_LAUNCH(float, 4, true); else PS_LAUNCH(float, 4, false); }
-    else { if (unshuffle) PS_LAUNCH(float, 1, true); else PS_LAUNCH(float, 1, false); }
-  }
+  return with_dtype(dtype, "pixel_shuffle2", [&](auto tag) {
+    using T = decltype(tag);
+    constexpr int VW = 16 / sizeof(T);               // 16-byte accesses on the planar side ...
+    const int V = (W % VW != 0 || !aligned16(in) || !aligned16(out) || ibs % VW != 0 || obs % VW != 0) ? 1 : VW;   // ... or the element-wise general form
+    hipStream_t st = (hipStream_t)stream;
+    const int64_t total = (int64_t)B * c * 2 * H * (W / V);
+    const int blocks = cdiv_cap(total, 256, 16384);
+    ProfScope ps(st, K_COL2IM, 2.0 * B * dense_lo * sizeof(T), 0.0);
+#define PS_LAUNCH(VV, UN) hipLaunchKernelGGL((pixel_shuffle_kernel<T, VV, UN>), dim3(blocks), dim3(256), 0, st, (const T*)in, (T*)out, c, H, W, ibs, obs, total)
+    if (V == VW) { if (unshuffle) PS_LAUNCH(VW, true); else PS_LAUNCH(VW, false); }
+    else { if (unshuffle) PS_LAUNCH(1, true); else PS_LAUNCH(1, false); }
 #undef PS_LAUNCH
-  MI_LAUNCH_CHECK();
-  return MI_OK;
+  });
 }
 
 extern "C" int mi_copy_rows(const void* src, int64_t src_rs, void* dst, int64_t dst_rs, int64_t rows, int64_t L, int dtype,
                             void* stream) {
   MI_CHECK_ARG(src && dst && rows > 0 && L > 0, "copy_rows: bad arguments");
-  MI_CHECK_ARG(dtype == MI_F32 || dtype == MI_BF16, "copy_rows: bad dtype %d", dtype);
-  int V = dtype == MI_BF16 ? 8 : 4;
   if (!src_rs) src_rs = L;
   if (!dst_rs) dst_rs = L;
-  if (L % V != 0 || src_rs % V != 0 || dst_rs % V != 0 || !aligned16(src) || !aligned16(dst)) V = 1;   // element-wise general form
-  hipStream_t st = (hipStream_t)stream;
-  const int64_t total = rows * (L / V);
-  int blocks = cdiv(total, 256);
-  if (blocks > 16384) blocks = 16384;
-  ProfScope ps(st, K_CAST, 2.0 * rows * L * dtype_size(dtype), 0.0);
-  if (dtype == MI_BF16) {
-    if (V == 8) hipLaunchKernelGGL((copy_rows_kernel<bf16, 8>), dim3(blocks), dim3(256), 0, st, (const bf16*)src, src_rs, (bf16*)dst, dst_rs, L, total);
-    else hipLaunchKernelGGL((copy_rows_kernel<bf16, 1>), dim3(blocks), dim3(256), 0, st, (const bf16*)src, src_rs, (bf16*)dst, dst_rs, L, total);
-  } else {
-    if (V == 4) hipLaunchKernelGGL((copy_rows_kernel<float, 4>), dim3(blocks), dim3(256), 0, st, (const float*)src, src_rs, (float*)dst, dst_rs, L, total);
-    else hipLaunchKernelGGL((copy_rows_kernel<float, 1>), dim3(blocks), dim3(256), 0, st, (const float*)src, src_rs, (float*)dst, dst_rs, L, total);
-  }
-  MI_LAUNCH_CHECK();
-  return MI_OK;
+  return with_dtype(dtype, "copy_rows", [&](auto tag) {
+    using T = decltype(tag);
+    constexpr int VW = 16 / sizeof(T);
+    const int V = (L % VW != 0 || src_rs % VW != 0 || dst_rs % VW != 0 || !aligned16(src) || !aligned16(dst)) ? 1 : VW;   // element-wise general form
+    hipStream_t st = (hipStream_t)stream;
+    const int64_t total = rows * (L / V);
+    const int blocks = cdiv_cap(total, 256, 16384);
+    ProfScope ps(st, K_CAST, 2.0 * rows * L * sizeof(T), 0.0);
+    if (V == VW) hipLaunchKernelGGL((copy_rows_kernel<T, VW>), dim3(blocks), dim3(256), 0, st, (const T*)src, src_rs, (T*)dst, dst_rs, L, total);
+    else hipLaunchKernelGGL((copy_rows_kernel<T, 1>), dim3(blocks), dim3(256), 0, st, (const T*)src, src_rs, (T*)dst, dst_rs, L, total);
+  });
 }

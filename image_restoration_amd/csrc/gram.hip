@@ -639,7 +639,6 @@ static int gram_stream_launch(const mi_gram_desc* d, void* ws, hipStream_t st) {
   } else if (!direct) {
     ProfScope ps2(st, K_GRAM_REDUCE, 4.0 * (g.splits + 1) * g.Z * d->ma * d->mb, (double)g.splits * g.Z * d->ma * d->mb);
     const int zo = d->sum_batch ? d->groups : g.Z;
-    const int64_t per = (int64_t)d->ma * d->mb;
     launch_gram_reduce(k.part, d->out, g.splits, g.fold ? 1 : d->batch, d->groups, d->ma, d->mb, d->out_ld, d->out_zs, d->sum_batch,
                        d->accumulate, zo, st);
     MI_LAUNCH_CHECK();
@@ -711,7 +710,6 @@ extern "C" int mi_gram(const mi_gram_desc* d, void* ws, void* stream) {
   } else if (!direct) {
     ProfScope ps2(st, K_GRAM_REDUCE, 4.0 * (g.splits + 1) * g.Z * d->ma * d->mb, (double)g.splits * g.Z * d->ma * d->mb);
     const int zo = d->sum_batch ? d->groups : g.Z;
-    const int64_t per = (int64_t)d->ma * d->mb;
     launch_gram_reduce(k.part, d->out, g.splits, g.fold ? 1 : d->batch, d->groups, d->ma, d->mb, d->out_ld, d->out_zs, d->sum_batch,
                        d->accumulate, zo, st);
     MI_LAUNCH_CHECK();

@@ -147,7 +147,6 @@ extern "C" int mi_grouped_pw_gemm(const mi_grouped_problem* probs, int np, const
                                   int max_rows, int64_t N, int dtype, void* stream) {
   MI_CHECK_ARG(probs && np >= 1 && np <= GP_MAX, "grouped_pw_gemm: 1..%d problems per launch", GP_MAX);
   MI_CHECK_ARG(dev_counts && dev_offsets && max_rows >= 1 && max_rows <= 65535 && N >= 1, "grouped_pw_gemm: bad row table / shape");
-  MI_CHECK_ARG(dtype == MI_F32 || dtype == MI_BF16, "grouped_pw_gemm: bad dtype %d", dtype);
   GpArgs a;
   memset(&a, 0, sizeof(a));
   int tiles = 0;
@@ -174,8 +173,5 @@ extern "C" int mi_grouped_pw_gemm(const mi_grouped_problem* probs, int np, const
   // (algorithmic bytes / flops are booked for ONE row per problem: the row counts live on the device)
   ProfScope ps(st, K_PW_GEMM, bytes, flops);
   const dim3 grid((unsigned)cdiv(N, 64), (unsigned)tiles, (unsigned)max_rows);
-  if (dtype == MI_BF16) hipLaunchKernelGGL((grouped_pw_kernel<bf16>), grid, dim3(256), 0, st, a);
-  else hipLaunchKernelGGL((grouped_pw_kernel<float>), grid, dim3(256), 0, st, a);
-  MI_LAUNCH_CHECK();
-  return MI_OK;
+  return with_dtype(dtype, "grouped_pw_gemm", [&](auto tag) { hipLaunchKernelGGL((grouped_pw_kernel<decltype(tag)>), grid, dim3(256), 0, st, a); });
 }

@@ -568,13 +568,12 @@ extern "C" int mi_ln_fwd(const void* x, const float* w, const float* b, void* y,
   MI_CHECK_ARG((int64_t)C * N < (1ll << 31), "ln_fwd: C*H*W must be below 2^31");
   MI_CHECK_ARG(!with_bias || b, "ln_fwd: with_bias needs b");
   MI_CHECK_ARG((mean == nullptr) == (rstd == nullptr), "ln_fwd: mean/rstd must both be given or both NULL");
-  MI_CHECK_ARG(dtype == MI_F32 || dtype == MI_BF16, "ln_fwd: bad dtype %d", dtype);
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == MI_F32)
-    return with_bias ? ln_fwd_dispatch<float, true>((const float*)x, w, b, (float*)y, mean, rstd, B, C, N, st)
-                     : ln_fwd_dispatch<float, false>((const float*)x, w, b, (float*)y, mean, rstd, B, C, N, st);
-  return with_bias ? ln_fwd_dispatch<bf16, true>((const bf16*)x, w, b, (bf16*)y, mean, rstd, B, C, N, st)
-                   : ln_fwd_dispatch<bf16, false>((const bf16*)x, w, b, (bf16*)y, mean, rstd, B, C, N, st);
+  return with_dtype(dtype, "ln_fwd", [&](auto tag) -> int {
+    using T = decltype(tag);
+    return with_bias ? ln_fwd_dispatch<T, true>((const T*)x, w, b, (T*)y, mean, rstd, B, C, N, st)
+                     : ln_fwd_dispatch<T, false>((const T*)x, w, b, (T*)y, mean, rstd, B, C, N, st);
+  });
 }
 
 extern "C" size_t mi_ln_bwd_workspace(int B, int C, int64_t N) {
@@ -589,29 +588,21 @@ extern "C" int mi_ln_bwd(const void* dy, const void* x, const float* w, const fl
   MI_CHECK_ARG(B > 0 && C > 0 && N > 0, "ln_bwd: bad shape");
   MI_CHECK_ARG((int64_t)C * N < (1ll << 31), "ln_bwd: C*H*W must be below 2^31");
   MI_CHECK_ARG(!with_bias || db, "ln_bwd: with_bias needs db");
-  MI_CHECK_ARG(dtype == MI_F32 || dtype == MI_BF16, "ln_bwd: bad dtype %d", dtype);
-  hipStream_t st = (hipStream_t)stream;
-  float* part = (float*)ws;
-  if (accumulate) {          // parameter gradients accumulated in place: partials may wait for mi_deferred_flush (common.h)
-    float* arena = deferred_take(mi_ln_bwd_workspace(B, C, N) / sizeof(float), st);
-    if (arena) part = arena;
-  }
-  int rows = 0, rc;
-  if (dtype == MI_F32) {
-    rc = with_bias ? ln_bwd_dispatch<float, true>((const float*)dy, (const float*)x, w, mean, rstd, (const float*)dres,
-                                                  (float*)dx, part, B, C, N, &rows, st)
-                   : ln_bwd_dispatch<float, false>((const float*)dy, (const float*)x, w, mean, rstd, (const float*)dres,
-                                                   (float*)dx, part, B, C, N, &rows, st);
-  } else {
-    rc = with_bias ? ln_bwd_dispatch<bf16, true>((const bf16*)dy, (const bf16*)x, w, mean, rstd, (const bf16*)dres,
-                                                 (bf16*)dx, part, B, C, N, &rows, st)
-                   : ln_bwd_dispatch<bf16, false>((const bf16*)dy, (const bf16*)x, w, mean, rstd, (const bf16*)dres,
-                                                  (bf16*)dx, part, B, C, N, &rows, st);
-  }
-  if (rc != MI_OK) return rc;
-  float* tmp = part + (int64_t)rows * 2 * C;  // two-stage scratch: [REDUCE_GROUPS][2C]
-  // d gamma and d beta are adjacent column blocks of the partial rows: one reduction writes both tensors
-  if (with_bias) MI_TRY(launch_reduce_rows(part, dw, rows, 2 * C, 2 * C, accumulate, 1.0f, st, tmp, db, C));
-  else MI_TRY(launch_reduce_rows(part, dw, rows, C, 2 * C, accumulate, 1.0f, st, tmp));
-  return MI_OK;
+  return with_dtype(dtype, "ln_bwd", [&](auto tag) -> int {
+    using T = decltype(tag);
+    hipStream_t st = (hipStream_t)stream;
+    float* part = (float*)ws;
+    if (accumulate) {          // parameter gradients accumulated in place: partials may wait for mi_deferred_flush (common.h)
+      float* arena = deferred_take(mi_ln_bwd_workspace(B, C, N) / sizeof(float), st);
+      if (arena) part = arena;
+    }
+    int rows = 0;
+    if (with_bias) MI_TRY((ln_bwd_dispatch<T, true>((const T*)dy, (const T*)x, w, mean, rstd, (const T*)dres, (T*)dx, part, B, C, N, &rows, st)));
+    else MI_TRY((ln_bwd_dispatch<T, false>((const T*)dy, (const T*)x, w, mean, rstd, (const T*)dres, (T*)dx, part, B, C, N, &rows, st)));
+    float* tmp = part + (int64_t)rows * 2 * C;  // two-stage scratch: [REDUCE_GROUPS][2C]
+    // d gamma and d beta are adjacent column blocks of the partial rows: one reduction writes both tensors
+    if (with_bias) MI_TRY(launch_reduce_rows(part, dw, rows, 2 * C, 2 * C, accumulate, 1.0f, st, tmp, db, C));
+    else MI_TRY(launch_reduce_rows(part, dw, rows, C, 2 * C, accumulate, 1.0f, st, tmp));
+    return MI_OK;
+  });
 }

@@ -455,24 +455,17 @@ __global__ __launch_bounds__(256) void mefc_ew_kernel(const T* a, const T* __res
   }
 }
 
-template <int MODE>
-static int mf_ew(const void* a, const void* b, const void* c, void* o, const float* cst, int64_t n, int64_t N, int dt, hipStream_t st) {
-  int64_t g = (n + 255) / 256;
-  if (g > 8192) g = 8192;
-  ProfScope ps(st, K_MEFC_EW, 3.0 * n * dtype_size(dt), (double)n);
-  if (dt == MI_F32)
-    hipLaunchKernelGGL((mefc_ew_kernel<float, MODE>), dim3((unsigned)g), dim3(256), 0, st, (const float*)a, (const float*)b,
-                       (const float*)c, (float*)o, cst, n, N);
-  else
-    hipLaunchKernelGGL((mefc_ew_kernel<bf16, MODE>), dim3((unsigned)g), dim3(256), 0, st, (const bf16*)a, (const bf16*)b,
-                       (const bf16*)c, (bf16*)o, cst, n, N);
+template <typename T, int MODE>
+static int mf_ew(const void* a, const void* b, const void* c, void* o, const float* cst, int64_t n, int64_t N, hipStream_t st) {
+  ProfScope ps(st, K_MEFC_EW, 3.0 * n * sizeof(T), (double)n);
+  hipLaunchKernelGGL((mefc_ew_kernel<T, MODE>), dim3(cdiv_cap(n, 256, 8192)), dim3(256), 0, st, (const T*)a, (const T*)b, (const T*)c, (T*)o, cst, n, N);
   MI_LAUNCH_CHECK();
   return MI_OK;
 }
 
 template <typename T, int K, int D, int MODE>
-static int mf_wgrad_t(const void* x, int64_t x_bs, const void* g, int64_t g_bs, float* part, float* out, int acc, int B, int C, int H,
-                      int W, hipStream_t st) {
+static int mf_wgrad(const void* x, int64_t x_bs, const void* g, int64_t g_bs, float* part, float* out, int acc, int B, int C, int H,
+                    int W, hipStream_t st) {
   const int splits = mf_splits(H, W);
   {
     const double n = (double)B * C * H * W;
@@ -483,12 +476,6 @@ static int mf_wgrad_t(const void* x, int64_t x_bs, const void* g, int64_t g_bs, 
   }
   const int64_t cols = (int64_t)C * K * K;
   return launch_reduce_rows(part, out, (int64_t)B * splits, cols, cols, acc, 1.0f, st);
-}
-template <int K, int D, int MODE>
-static int mf_wgrad(const void* x, int64_t x_bs, const void* g, int64_t g_bs, float* part, float* out, int acc, int B, int C, int H,
-                    int W, int dt, hipStream_t st) {
-  if (dt == MI_F32) return mf_wgrad_t<float, K, D, MODE>(x, x_bs, g, g_bs, part, out, acc, B, C, H, W, st);
-  return mf_wgrad_t<bf16, K, D, MODE>(x, x_bs, g, g_bs, part, out, acc, B, C, H, W, st);
 }
 
 // ------------------------------------------------------------------ host side: layouts
@@ -648,61 +635,62 @@ extern "C" int mi_mefc_fwd(const mi_mefc_shape* s, const mi_mefc_params* p, cons
   MI_TRY(mf_check(s));
   MI_TRY(mf_check_params(s, p));
   MI_CHECK_ARG(x && out && ws, "mefc_fwd: null pointer");
-  hipStream_t st = (hipStream_t)stream;
-  const int B = s->B, C = s->C, H = s->H, W = s->W, dt = s->dtype, steps = s->steps;
-  const int64_t N = (int64_t)H * W, CN = (int64_t)C * N;
-  const bool train = saved != nullptr;
-  MfWs w = mf_ws_layout(s, ws);
-  MfSaved sv = train ? mf_saved_layout(s, saved, true) : w.inf;
-  // routing weights (OALayer + softmax, :346-349)
-  MI_TRY(mi_gap_fwd(x, sv.pooled, B, C, N, dt, stream));
-  {
-    ProfScope ps(st, K_MEFC_HEAD, 4.0 * (16.0 * steps * C + 128.0 * steps * steps) * B, 2.0 * (16.0 * steps * C + 128.0 * steps * steps) * B);
-    hipLaunchKernelGGL(mefc_head_fwd_kernel, dim3(B), dim3(256), 0, st, sv.pooled, p->fc1_w, p->fc1_b, p->fc2_w, p->fc2_b, sv.hpre,
-                       sv.wts, C, steps);
-    MI_LAUNCH_CHECK();
-  }
-  // s0 = relu(preprocess(x))  (:217 ReLUConv)
-  void* cur = sv.st[0].s;
-  mi_pw_desc d0 = conv1x1(x, C, p->pre_w, false, C, nullptr, nullptr, cur, C, B, N, dt);
-  MI_TRY(mi_pw_gemm(&d0, w.pw_ws, stream));
-  MI_TRY(mf_ew<MF_EW_RELU>(cur, nullptr, nullptr, cur, nullptr, B * CN, N, dt, st));
-  for (int t = 0; t < steps; ++t) {
-    const MfStep& q = sv.st[t];
-    const mi_mefc_step_params& pp = p->step[t];
-    void* nxt = t == steps - 1 ? out : (train ? sv.st[t + 1].s : (cur == sv.s_alt ? sv.st[0].s : sv.s_alt));
+  return with_dtype(s->dtype, "mefc_fwd", [&](auto tag) -> int {
+    using T = decltype(tag);
+    hipStream_t st = (hipStream_t)stream;
+    const int B = s->B, C = s->C, H = s->H, W = s->W, dt = s->dtype, steps = s->steps;
+    const int64_t N = (int64_t)H * W, CN = (int64_t)C * N;
+    const bool train = saved != nullptr;
+    MfWs w = mf_ws_layout(s, ws);
+    MfSaved sv = train ? mf_saved_layout(s, saved, true) : w.inf;
+    // routing weights (OALayer + softmax, :346-349)
+    MI_TRY(mi_gap_fwd(x, sv.pooled, B, C, N, dt, stream));
     {
-      const double n = (double)B * CN;
-      ProfScope ps(st, K_MEFC_STA, 8.0 * n * dtype_size(dt), 2.0 * (84 + 83 + 9) * n);
-      if (dt == MI_F32) mf_launch_sta<float>(cur, mf_w7(pp), q.d1, q.z, B, C, H, W, st);
-      else mf_launch_sta<bf16>(cur, mf_w7(pp), q.d1, q.z, B, C, H, W, st);
+      ProfScope ps(st, K_MEFC_HEAD, 4.0 * (16.0 * steps * C + 128.0 * steps * steps) * B, 2.0 * (16.0 * steps * C + 128.0 * steps * steps) * B);
+      hipLaunchKernelGGL(mefc_head_fwd_kernel, dim3(B), dim3(256), 0, st, sv.pooled, p->fc1_w, p->fc1_b, p->fc2_w, p->fc2_b, sv.hpre,
+                         sv.wts, C, steps);
       MI_LAUNCH_CHECK();
     }
-    for (int k = 0; k < 4; ++k) {     // U_k = pw1_k D1_k
-      const size_t off = (size_t)k * CN * dtype_size(dt);
-      mi_pw_desc d = conv1x1((const char*)q.d1 + off, C, pp.sep_pw1[k], false, C, nullptr, nullptr, (char*)q.u + off, C, B, N, dt, 4 * CN, 4 * CN);
+    // s0 = relu(preprocess(x))  (:217 ReLUConv)
+    void* cur = sv.st[0].s;
+    mi_pw_desc d0 = conv1x1(x, C, p->pre_w, false, C, nullptr, nullptr, cur, C, B, N, dt);
+    MI_TRY(mi_pw_gemm(&d0, w.pw_ws, stream));
+    MI_TRY((mf_ew<T, MF_EW_RELU>(cur, nullptr, nullptr, cur, nullptr, B * CN, N, st)));
+    for (int t = 0; t < steps; ++t) {
+      const MfStep& q = sv.st[t];
+      const mi_mefc_step_params& pp = p->step[t];
+      void* nxt = t == steps - 1 ? out : (train ? sv.st[t + 1].s : (cur == sv.s_alt ? sv.st[0].s : sv.s_alt));
+      {
+        const double n = (double)B * CN;
+        ProfScope ps(st, K_MEFC_STA, 8.0 * n * dtype_size(dt), 2.0 * (84 + 83 + 9) * n);
+        mf_launch_sta<T>(cur, mf_w7(pp), q.d1, q.z, B, C, H, W, st);
+        MI_LAUNCH_CHECK();
+      }
+      for (int k = 0; k < 4; ++k) {     // U_k = pw1_k D1_k
+        const size_t off = (size_t)k * CN * dtype_size(dt);
+        mi_pw_desc d = conv1x1((const char*)q.d1 + off, C, pp.sep_pw1[k], false, C, nullptr, nullptr, (char*)q.u + off, C, B, N, dt, 4 * CN, 4 * CN);
+        MI_TRY(mi_pw_gemm(&d, w.pw_ws, stream));
+      }
+      {
+        const double n = (double)B * 4 * CN;
+        ProfScope ps(st, K_MEFC_STB, 2.0 * n * dtype_size(dt), 2.0 * 21 * n);
+        mf_launch_stb<T>(q.u, 4 * CN, mf_w4(pp), q.z, 8 * CN, nullptr, B, C, H, W, st);
+        MI_LAUNCH_CHECK();
+      }
+      {
+        const bool b16 = dt == MI_BF16;
+        ProfScope ps(st, K_MEFC_FOLD, 4.0 * 8 * C * C * (1.0 + B * (b16 ? 2.0 : 1.0)), 2.0 * 7 * C * C * C);
+        hipLaunchKernelGGL(mefc_fold_kernel, dim3(8, C), dim3(256), 0, st, pp.out_w, mf_q(pp), sv.wts, steps, t, q.M,
+                           b16 ? (bf16*)q.Mb : nullptr, b16 ? (bf16*)q.Mtb : nullptr, B, C);
+        MI_LAUNCH_CHECK();
+      }
+      mi_pw_desc d = mf_out_desc(q.z, q.M, dt == MI_BF16 ? q.Mb : nullptr, q.pre, B, C, N, dt);
       MI_TRY(mi_pw_gemm(&d, w.pw_ws, stream));
+      MI_TRY((mf_ew<T, MF_EW_RES>(q.pre, cur, nullptr, nxt, nullptr, B * CN, N, st)));   // s = relu(relu(_out(.)) + s)  (:222-223)
+      cur = nxt;
     }
-    {
-      const double n = (double)B * 4 * CN;
-      ProfScope ps(st, K_MEFC_STB, 2.0 * n * dtype_size(dt), 2.0 * 21 * n);
-      if (dt == MI_F32) mf_launch_stb<float>(q.u, 4 * CN, mf_w4(pp), q.z, 8 * CN, nullptr, B, C, H, W, st);
-      else mf_launch_stb<bf16>(q.u, 4 * CN, mf_w4(pp), q.z, 8 * CN, nullptr, B, C, H, W, st);
-      MI_LAUNCH_CHECK();
-    }
-    {
-      const bool b16 = dt == MI_BF16;
-      ProfScope ps(st, K_MEFC_FOLD, 4.0 * 8 * C * C * (1.0 + B * (b16 ? 2.0 : 1.0)), 2.0 * 7 * C * C * C);
-      hipLaunchKernelGGL(mefc_fold_kernel, dim3(8, C), dim3(256), 0, st, pp.out_w, mf_q(pp), sv.wts, steps, t, q.M,
-                         b16 ? (bf16*)q.Mb : nullptr, b16 ? (bf16*)q.Mtb : nullptr, B, C);
-      MI_LAUNCH_CHECK();
-    }
-    mi_pw_desc d = mf_out_desc(q.z, q.M, dt == MI_BF16 ? q.Mb : nullptr, q.pre, B, C, N, dt);
-    MI_TRY(mi_pw_gemm(&d, w.pw_ws, stream));
-    MI_TRY(mf_ew<MF_EW_RES>(q.pre, cur, nullptr, nxt, nullptr, B * CN, N, dt, st));   // s = relu(relu(_out(.)) + s)  (:222-223)
-    cur = nxt;
-  }
-  return MI_OK;
+    return MI_OK;
+  });
 }
 
 extern "C" int mi_mefc_bwd(const mi_mefc_shape* s, const mi_mefc_params* p, const void* x, const void* out, const void* dout, void* dx,
@@ -718,89 +706,90 @@ extern "C" int mi_mefc_bwd(const mi_mefc_shape* s, const mi_mefc_params* p, cons
     for (int k = 0; k < 3; ++k) MI_CHECK_ARG(q.dil_dw[k] && q.dil_pw[k], "mefc_bwd: null DilConv gradient (step %d)", t);
     MI_CHECK_ARG(q.out_w, "mefc_bwd: null out gradient (step %d)", t);
   }
-  hipStream_t st = (hipStream_t)stream;
-  const int B = s->B, C = s->C, H = s->H, W = s->W, dt = s->dtype, steps = s->steps, acc = g->accumulate;
-  const int64_t N = (int64_t)H * W, CN = (int64_t)C * N;
-  const size_t es = dtype_size(dt);
-  MfWs w = mf_ws_layout(s, ws);
-  MfSaved sv = mf_saved_layout(s, const_cast<void*>(saved), true);
-  const void* dcur = dout;
-  for (int t = steps - 1; t >= 0; --t) {
-    const MfStep& q = sv.st[t];
-    const mi_mefc_step_params& pp = p->step[t];
-    const mi_mefc_step_grads& gg = g->step[t];
-    const void* s_out = t == steps - 1 ? out : sv.st[t + 1].s;
-    void* ds = dcur == w.dsa ? w.dsb : w.dsa;
-    // dpre = dout (s' > 0)(pre > 0)
-    MI_TRY(mf_ew<MF_EW_RES_BWD>(dcur, s_out, q.pre, w.dpre, nullptr, B * CN, N, dt, st));
-    // fold backward: G[b] = dpre[b] Z[b]^T -> d w_i[b], d out_w, d pw_i
-    mi_gram_desc gd = wgrad_gram(w.dpre, C, q.z, 8 * C, B, N, dt, w.G, 0, 0);
-    MI_TRY(mi_gram(&gd, w.gram_ws, stream));
-    const MfQ qq = mf_q(pp);
+  return with_dtype(s->dtype, "mefc_bwd", [&](auto tag) -> int {
+    using T = decltype(tag);
+    hipStream_t st = (hipStream_t)stream;
+    const int B = s->B, C = s->C, H = s->H, W = s->W, dt = s->dtype, steps = s->steps, acc = g->accumulate;
+    const int64_t N = (int64_t)H * W, CN = (int64_t)C * N;
+    const size_t es = dtype_size(dt);
+    MfWs w = mf_ws_layout(s, ws);
+    MfSaved sv = mf_saved_layout(s, const_cast<void*>(saved), true);
+    const void* dcur = dout;
+    for (int t = steps - 1; t >= 0; --t) {
+      const MfStep& q = sv.st[t];
+      const mi_mefc_step_params& pp = p->step[t];
+      const mi_mefc_step_grads& gg = g->step[t];
+      const void* s_out = t == steps - 1 ? out : sv.st[t + 1].s;
+      void* ds = dcur == w.dsa ? w.dsb : w.dsa;
+      // dpre = dout (s' > 0)(pre > 0)
+      MI_TRY((mf_ew<T, MF_EW_RES_BWD>(dcur, s_out, q.pre, w.dpre, nullptr, B * CN, N, st)));
+      // fold backward: G[b] = dpre[b] Z[b]^T -> d w_i[b], d out_w, d pw_i
+      mi_gram_desc gd = wgrad_gram(w.dpre, C, q.z, 8 * C, B, N, dt, w.G, 0, 0);
+      MI_TRY(mi_gram(&gd, w.gram_ws, stream));
+      const MfQ qq = mf_q(pp);
+      {
+        ProfScope ps(st, K_MEFC_FOLD_BWD, 4.0 * B * 8 * C * C + 4.0 * 16 * C * C, 2.0 * 8 * C * C * (C + 2.0 * B) + 2.0 * 14 * C * C * C);
+        hipLaunchKernelGGL(mefc_fold_bwd_kernel, dim3(8, C), dim3(256), 0, st, w.G, pp.out_w, qq, sv.wts, steps, t, w.Hs, w.dwp, B, C);
+        MI_LAUNCH_CHECK();
+        MfGQ gq;
+        for (int k = 0; k < 4; ++k) gq.q[k] = gg.sep_pw2[k];
+        for (int k = 0; k < 3; ++k) gq.q[4 + k] = gg.dil_pw[k];
+        hipLaunchKernelGGL(mefc_fold_wgrad_kernel, dim3(8, C), dim3(256), 0, st, w.Hs, pp.out_w, qq, gg.out_w, gq, acc, C);
+        MI_LAUNCH_CHECK();
+      }
+      MI_TRY(launch_reduce_rows(w.dwp, w.dws + (int64_t)t * B * 8, C, (int64_t)B * 8, (int64_t)B * 8, 0, 1.0f, st));
+      // dZ[b] = M[b]^T dpre[b]
+      mi_pw_desc dzd = mf_dz_desc(w.dpre, q.M, dt == MI_BF16 ? q.Mtb : nullptr, w.dz, B, C, N, dt);
+      MI_TRY(mi_pw_gemm(&dzd, w.pw_ws, stream));
+      // stencil B backward: dU_k = (U_k > 0) dw2_k^T dZ_k, and the dw2 weight gradients (input relu(U_k))
+      {
+        const double n = (double)B * 4 * CN;
+        ProfScope ps(st, K_MEFC_STB_BWD, 3.0 * n * es, 2.0 * 21 * n);
+        mf_launch_stb<T>(w.dz, 8 * CN, mf_w4(pp), w.du, 4 * CN, q.u, B, C, H, W, st);
+        MI_LAUNCH_CHECK();
+      }
+      // the dw2 weight gradients run before the data gradients: all of them through one partial-row region, in stream order
+      MI_TRY((mf_wgrad<T, 1, 1, MF_RELU>(q.u, 4 * CN, w.dz, 8 * CN, w.part, gg.sep_dw2[0], acc, B, C, H, W, st)));
+      MI_TRY((mf_wgrad<T, 3, 1, MF_RELU>((const char*)q.u + CN * es, 4 * CN, (const char*)w.dz + CN * es, 8 * CN, w.part, gg.sep_dw2[1], acc, B, C, H, W, st)));
+      MI_TRY((mf_wgrad<T, 5, 1, MF_RELU>((const char*)q.u + 2 * CN * es, 4 * CN, (const char*)w.dz + 2 * CN * es, 8 * CN, w.part, gg.sep_dw2[2], acc, B, C, H, W, st)));
+      MI_TRY((mf_wgrad<T, 7, 1, MF_RELU>((const char*)q.u + 3 * CN * es, 4 * CN, (const char*)w.dz + 3 * CN * es, 8 * CN, w.part, gg.sep_dw2[3], acc, B, C, H, W, st)));
+      // pw1: dD1_k = pw1_k^T dU_k, d pw1_k = sum_b dU_k D1_k^T
+      for (int k = 0; k < 4; ++k) {
+        const size_t off = (size_t)k * CN * es;
+        mi_pw_desc d = conv1x1((const char*)w.du + off, C, pp.sep_pw1[k], true, C, nullptr, nullptr, (char*)w.dd1 + off, C, B, N, dt, 4 * CN, 4 * CN);
+        MI_TRY(mi_pw_gemm(&d, w.pw_ws, stream));
+        mi_gram_desc gw = wgrad_gram((const char*)w.du + off, C, (const char*)q.d1 + off, C, B, N, dt, gg.sep_pw1[k], acc, 1, 4 * CN, 4 * CN);
+        MI_TRY(mi_gram(&gw, w.gram_ws, stream));
+      }
+      // stencil A backward: ds, plus the residual's gradient
+      {
+        const double n = (double)B * CN;
+        ProfScope ps(st, K_MEFC_STA_BWD, 11.0 * n * es, 2.0 * (84 + 83 + 9) * n);
+        mf_launch_sta_bwd<T>(w.dd1, w.dz, dcur, s_out, mf_w7(pp), ds, B, C, H, W, st);
+        MI_LAUNCH_CHECK();
+      }
+      const char* d1 = (const char*)w.dd1;
+      const char* dz = (const char*)w.dz;
+      MI_TRY((mf_wgrad<T, 1, 1, MF_PLAIN>(q.s, CN, d1, 4 * CN, w.part, gg.sep_dw1[0], acc, B, C, H, W, st)));
+      MI_TRY((mf_wgrad<T, 3, 1, MF_PLAIN>(q.s, CN, d1 + CN * es, 4 * CN, w.part, gg.sep_dw1[1], acc, B, C, H, W, st)));
+      MI_TRY((mf_wgrad<T, 5, 1, MF_PLAIN>(q.s, CN, d1 + 2 * CN * es, 4 * CN, w.part, gg.sep_dw1[2], acc, B, C, H, W, st)));
+      MI_TRY((mf_wgrad<T, 7, 1, MF_PLAIN>(q.s, CN, d1 + 3 * CN * es, 4 * CN, w.part, gg.sep_dw1[3], acc, B, C, H, W, st)));
+      MI_TRY((mf_wgrad<T, 3, 2, MF_PLAIN>(q.s, CN, dz + 4 * CN * es, 8 * CN, w.part, gg.dil_dw[0], acc, B, C, H, W, st)));
+      MI_TRY((mf_wgrad<T, 5, 2, MF_PLAIN>(q.s, CN, dz + 5 * CN * es, 8 * CN, w.part, gg.dil_dw[1], acc, B, C, H, W, st)));
+      MI_TRY((mf_wgrad<T, 7, 2, MF_PLAIN>(q.s, CN, dz + 6 * CN * es, 8 * CN, w.part, gg.dil_dw[2], acc, B, C, H, W, st)));
+      dcur = ds;
+    }
+    // through the preprocess ReLU and 1x1
+    void* dpre0 = w.dpre;
+    MI_TRY((mf_ew<T, MF_EW_MASK>(dcur, sv.st[0].s, nullptr, dpre0, nullptr, B * CN, N, st)));
+    MI_TRY(conv1x1_bwd_input(dpre0, C, x, C, p->pre_w, g->pre_w, nullptr, dx, B, N, dt, acc, w.gram_ws, nullptr, w.pw_ws, st, false));
+    // routing head: the d w of every step through the softmax and the MLP; the pooled gradient joins dx
     {
-      ProfScope ps(st, K_MEFC_FOLD_BWD, 4.0 * B * 8 * C * C + 4.0 * 16 * C * C, 2.0 * 8 * C * C * (C + 2.0 * B) + 2.0 * 14 * C * C * C);
-      hipLaunchKernelGGL(mefc_fold_bwd_kernel, dim3(8, C), dim3(256), 0, st, w.G, pp.out_w, qq, sv.wts, steps, t, w.Hs, w.dwp, B, C);
-      MI_LAUNCH_CHECK();
-      MfGQ gq;
-      for (int k = 0; k < 4; ++k) gq.q[k] = gg.sep_pw2[k];
-      for (int k = 0; k < 3; ++k) gq.q[4 + k] = gg.dil_pw[k];
-      hipLaunchKernelGGL(mefc_fold_wgrad_kernel, dim3(8, C), dim3(256), 0, st, w.Hs, pp.out_w, qq, gg.out_w, gq, acc, C);
+      ProfScope ps(st, K_MEFC_HEAD_BWD, 8.0 * (16.0 * steps * C + 128.0 * steps * steps) * B, 6.0 * (16.0 * steps * C + 128.0 * steps * steps) * B);
+      hipLaunchKernelGGL(mefc_head_bwd_kernel, dim3(1), dim3(256), 0, st, sv.pooled, sv.hpre, sv.wts, w.dws, p->fc1_w, p->fc2_w, g->fc1_w,
+                         g->fc1_b, g->fc2_w, g->fc2_b, w.gp, w.hscr, acc, B, C, steps, 1.0f / (float)N);
       MI_LAUNCH_CHECK();
     }
-    MI_TRY(launch_reduce_rows(w.dwp, w.dws + (int64_t)t * B * 8, C, (int64_t)B * 8, (int64_t)B * 8, 0, 1.0f, st));
-    // dZ[b] = M[b]^T dpre[b]
-    mi_pw_desc dzd = mf_dz_desc(w.dpre, q.M, dt == MI_BF16 ? q.Mtb : nullptr, w.dz, B, C, N, dt);
-    MI_TRY(mi_pw_gemm(&dzd, w.pw_ws, stream));
-    // stencil B backward: dU_k = (U_k > 0) dw2_k^T dZ_k, and the dw2 weight gradients (input relu(U_k))
-    {
-      const double n = (double)B * 4 * CN;
-      ProfScope ps(st, K_MEFC_STB_BWD, 3.0 * n * es, 2.0 * 21 * n);
-      if (dt == MI_F32) mf_launch_stb<float>(w.dz, 8 * CN, mf_w4(pp), w.du, 4 * CN, q.u, B, C, H, W, st);
-      else mf_launch_stb<bf16>(w.dz, 8 * CN, mf_w4(pp), w.du, 4 * CN, q.u, B, C, H, W, st);
-      MI_LAUNCH_CHECK();
-    }
-    // the dw2 weight gradients run before the data gradients: all of them through one partial-row region, in stream order
-    MI_TRY((mf_wgrad<1, 1, MF_RELU>(q.u, 4 * CN, w.dz, 8 * CN, w.part, gg.sep_dw2[0], acc, B, C, H, W, dt, st)));
-    MI_TRY((mf_wgrad<3, 1, MF_RELU>((const char*)q.u + CN * es, 4 * CN, (const char*)w.dz + CN * es, 8 * CN, w.part, gg.sep_dw2[1], acc, B, C, H, W, dt, st)));
-    MI_TRY((mf_wgrad<5, 1, MF_RELU>((const char*)q.u + 2 * CN * es, 4 * CN, (const char*)w.dz + 2 * CN * es, 8 * CN, w.part, gg.sep_dw2[2], acc, B, C, H, W, dt, st)));
-    MI_TRY((mf_wgrad<7, 1, MF_RELU>((const char*)q.u + 3 * CN * es, 4 * CN, (const char*)w.dz + 3 * CN * es, 8 * CN, w.part, gg.sep_dw2[3], acc, B, C, H, W, dt, st)));
-    // pw1: dD1_k = pw1_k^T dU_k, d pw1_k = sum_b dU_k D1_k^T
-    for (int k = 0; k < 4; ++k) {
-      const size_t off = (size_t)k * CN * es;
-      mi_pw_desc d = conv1x1((const char*)w.du + off, C, pp.sep_pw1[k], true, C, nullptr, nullptr, (char*)w.dd1 + off, C, B, N, dt, 4 * CN, 4 * CN);
-      MI_TRY(mi_pw_gemm(&d, w.pw_ws, stream));
-      mi_gram_desc gw = wgrad_gram((const char*)w.du + off, C, (const char*)q.d1 + off, C, B, N, dt, gg.sep_pw1[k], acc, 1, 4 * CN, 4 * CN);
-      MI_TRY(mi_gram(&gw, w.gram_ws, stream));
-    }
-    // stencil A backward: ds, plus the residual's gradient
-    {
-      const double n = (double)B * CN;
-      ProfScope ps(st, K_MEFC_STA_BWD, 11.0 * n * es, 2.0 * (84 + 83 + 9) * n);
-      if (dt == MI_F32) mf_launch_sta_bwd<float>(w.dd1, w.dz, dcur, s_out, mf_w7(pp), ds, B, C, H, W, st);
-      else mf_launch_sta_bwd<bf16>(w.dd1, w.dz, dcur, s_out, mf_w7(pp), ds, B, C, H, W, st);
-      MI_LAUNCH_CHECK();
-    }
-    const char* d1 = (const char*)w.dd1;
-    const char* dz = (const char*)w.dz;
-    MI_TRY((mf_wgrad<1, 1, MF_PLAIN>(q.s, CN, d1, 4 * CN, w.part, gg.sep_dw1[0], acc, B, C, H, W, dt, st)));
-    MI_TRY((mf_wgrad<3, 1, MF_PLAIN>(q.s, CN, d1 + CN * es, 4 * CN, w.part, gg.sep_dw1[1], acc, B, C, H, W, dt, st)));
-    MI_TRY((mf_wgrad<5, 1, MF_PLAIN>(q.s, CN, d1 + 2 * CN * es, 4 * CN, w.part, gg.sep_dw1[2], acc, B, C, H, W, dt, st)));
-    MI_TRY((mf_wgrad<7, 1, MF_PLAIN>(q.s, CN, d1 + 3 * CN * es, 4 * CN, w.part, gg.sep_dw1[3], acc, B, C, H, W, dt, st)));
-    MI_TRY((mf_wgrad<3, 2, MF_PLAIN>(q.s, CN, dz + 4 * CN * es, 8 * CN, w.part, gg.dil_dw[0], acc, B, C, H, W, dt, st)));
-    MI_TRY((mf_wgrad<5, 2, MF_PLAIN>(q.s, CN, dz + 5 * CN * es, 8 * CN, w.part, gg.dil_dw[1], acc, B, C, H, W, dt, st)));
-    MI_TRY((mf_wgrad<7, 2, MF_PLAIN>(q.s, CN, dz + 6 * CN * es, 8 * CN, w.part, gg.dil_dw[2], acc, B, C, H, W, dt, st)));
-    dcur = ds;
-  }
-  // through the preprocess ReLU and 1x1
-  void* dpre0 = w.dpre;
-  MI_TRY(mf_ew<MF_EW_MASK>(dcur, sv.st[0].s, nullptr, dpre0, nullptr, B * CN, N, dt, st));
-  MI_TRY(conv1x1_bwd_input(dpre0, C, x, C, p->pre_w, g->pre_w, nullptr, dx, B, N, dt, acc, w.gram_ws, nullptr, w.pw_ws, st, false));
-  // routing head: the d w of every step through the softmax and the MLP; the pooled gradient joins dx
-  {
-    ProfScope ps(st, K_MEFC_HEAD_BWD, 8.0 * (16.0 * steps * C + 128.0 * steps * steps) * B, 6.0 * (16.0 * steps * C + 128.0 * steps * steps) * B);
-    hipLaunchKernelGGL(mefc_head_bwd_kernel, dim3(1), dim3(256), 0, st, sv.pooled, sv.hpre, sv.wts, w.dws, p->fc1_w, p->fc2_w, g->fc1_w,
-                       g->fc1_b, g->fc2_w, g->fc2_b, w.gp, w.hscr, acc, B, C, steps, 1.0f / (float)N);
-    MI_LAUNCH_CHECK();
-  }
-  return mf_ew<MF_EW_ADDC>(dx, nullptr, nullptr, dx, w.gp, B * CN, N, dt, st);
+    return mf_ew<T, MF_EW_ADDC>(dx, nullptr, nullptr, dx, w.gp, B * CN, N, st);
+  });
 }

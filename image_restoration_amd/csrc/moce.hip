@@ -439,36 +439,34 @@ extern "C" int mi_moe_route_bwd(const float* pooled, const float* freq, const fl
 extern "C" int mi_patch_circconv(const void* x, int64_t x_bs, const void* y, int64_t y_bs, void* out, int64_t out_bs, int B, int C,
                                  int H, int W, int patch, int flip, int dtype, void* stream) {
   MI_CHECK_ARG(x && y && out && B > 0 && C > 0 && H > 0 && W > 0, "patch_circconv: bad arguments");
-  MI_CHECK_ARG(dtype == MI_F32 || dtype == MI_BF16, "patch_circconv: bad dtype %d", dtype);
-  hipStream_t st = (hipStream_t)stream;
-  const double px = (double)B * C * H * W;
-  ProfScope ps(st, K_CIRCCONV, 3.0 * px * dtype_size(dtype), 2.0 * px * patch * patch);
-  if (!x_bs) x_bs = (int64_t)C * H * W;
-  if (!y_bs) y_bs = (int64_t)C * H * W;
-  if (!out_bs) out_bs = (int64_t)C * H * W;
-  if (dtype == MI_F32) return circconv_launch<float>(x, y, out, B, C, H, W, patch, flip, x_bs, y_bs, out_bs, st);
-  return circconv_launch<bf16>(x, y, out, B, C, H, W, patch, flip, x_bs, y_bs, out_bs, st);
+  return with_dtype(dtype, "patch_circconv", [&](auto tag) -> int {
+    hipStream_t st = (hipStream_t)stream;
+    const double px = (double)B * C * H * W;
+    ProfScope ps(st, K_CIRCCONV, 3.0 * px * sizeof(tag), 2.0 * px * patch * patch);
+    if (!x_bs) x_bs = (int64_t)C * H * W;
+    if (!y_bs) y_bs = (int64_t)C * H * W;
+    if (!out_bs) out_bs = (int64_t)C * H * W;
+    return circconv_launch<decltype(tag)>(x, y, out, B, C, H, W, patch, flip, x_bs, y_bs, out_bs, st);
+  });
 }
 
 extern "C" int mi_gelu_gap_fwd(const void* x, float* out, int B, int C, int64_t N, int dtype, void* stream) {
   MI_CHECK_ARG(x && out && B > 0 && C > 0 && N > 0, "gelu_gap_fwd: bad arguments");
   hipStream_t st = (hipStream_t)stream;
   ProfScope ps(st, K_GAP, (double)B * C * N * dtype_size(dtype), 10.0 * B * C * N);
-  if (dtype == MI_F32) hipLaunchKernelGGL((gelu_gap_fwd_kernel<float>), dim3(B * C), dim3(256), 0, st, (const float*)x, out, N);
-  else if (dtype == MI_BF16) hipLaunchKernelGGL((gelu_gap_fwd_kernel<bf16>), dim3(B * C), dim3(256), 0, st, (const bf16*)x, out, N);
-  else { set_error("gelu_gap_fwd: bad dtype"); return MI_ERR_ARG; }
-  MI_LAUNCH_CHECK();
-  return MI_OK;
+  return with_dtype(dtype, "gelu_gap_fwd", [&](auto tag) {
+    using T = decltype(tag);
+    hipLaunchKernelGGL((gelu_gap_fwd_kernel<T>), dim3(B * C), dim3(256), 0, st, (const T*)x, out, N);
+  });
 }
 extern "C" int mi_gelu_gap_bwd(const void* x, const float* dout, void* dx, int B, int C, int64_t N, int dtype, void* stream) {
   MI_CHECK_ARG(x && dout && dx && B > 0 && C > 0 && N > 0, "gelu_gap_bwd: bad arguments");
   hipStream_t st = (hipStream_t)stream;
   ProfScope ps(st, K_GAP, 2.0 * B * C * N * dtype_size(dtype), 10.0 * B * C * N);
-  if (dtype == MI_F32) hipLaunchKernelGGL((gelu_gap_bwd_kernel<float>), dim3(B * C), dim3(256), 0, st, (const float*)x, dout, (float*)dx, N);
-  else if (dtype == MI_BF16) hipLaunchKernelGGL((gelu_gap_bwd_kernel<bf16>), dim3(B * C), dim3(256), 0, st, (const bf16*)x, dout, (bf16*)dx, N);
-  else { set_error("gelu_gap_bwd: bad dtype"); return MI_ERR_ARG; }
-  MI_LAUNCH_CHECK();
-  return MI_OK;
+  return with_dtype(dtype, "gelu_gap_bwd", [&](auto tag) {
+    using T = decltype(tag);
+    hipLaunchKernelGGL((gelu_gap_bwd_kernel<T>), dim3(B * C), dim3(256), 0, st, (const T*)x, dout, (T*)dx, N);
+  });
 }
 
 extern "C" int mi_ewise_fwd(const void* a, int64_t a_rs, const void* b, int64_t b_rs, void* out, int64_t rows, int64_t L, int op,
@@ -478,14 +476,12 @@ extern "C" int mi_ewise_fwd(const void* a, int64_t a_rs, const void* b, int64_t 
   if (!a_rs) a_rs = L;
   if (!b_rs) b_rs = L;
   hipStream_t st = (hipStream_t)stream;
-  int blocks = cdiv(n, 256 * 4);
-  if (blocks > 8192) blocks = 8192;
+  const int blocks = cdiv_cap(n, 256 * 4, 8192);
   ProfScope ps(st, K_EWISE, 3.0 * n * dtype_size(dtype), 4.0 * n);
-  if (dtype == MI_F32) hipLaunchKernelGGL((ewise_fwd_kernel<float>), dim3(blocks), dim3(256), 0, st, (const float*)a, (const float*)b, (float*)out, n, op, L, a_rs, b_rs);
-  else if (dtype == MI_BF16) hipLaunchKernelGGL((ewise_fwd_kernel<bf16>), dim3(blocks), dim3(256), 0, st, (const bf16*)a, (const bf16*)b, (bf16*)out, n, op, L, a_rs, b_rs);
-  else { set_error("ewise_fwd: bad dtype"); return MI_ERR_ARG; }
-  MI_LAUNCH_CHECK();
-  return MI_OK;
+  return with_dtype(dtype, "ewise_fwd", [&](auto tag) {
+    using T = decltype(tag);
+    hipLaunchKernelGGL((ewise_fwd_kernel<T>), dim3(blocks), dim3(256), 0, st, (const T*)a, (const T*)b, (T*)out, n, op, L, a_rs, b_rs);
+  });
 }
 extern "C" int mi_ewise_bwd(const void* a, int64_t a_rs, const void* b, int64_t b_rs, const void* dout, void* da, int64_t da_rs,
                             void* db, int64_t db_rs, int64_t rows, int64_t L, int op, int dtype, void* stream) {
@@ -496,12 +492,10 @@ extern "C" int mi_ewise_bwd(const void* a, int64_t a_rs, const void* b, int64_t 
   if (!da_rs) da_rs = L;
   if (!db_rs) db_rs = L;
   hipStream_t st = (hipStream_t)stream;
-  int blocks = cdiv(n, 256 * 4);
-  if (blocks > 8192) blocks = 8192;
+  const int blocks = cdiv_cap(n, 256 * 4, 8192);
   ProfScope ps(st, K_EWISE, 5.0 * n * dtype_size(dtype), 8.0 * n);
-  if (dtype == MI_F32) hipLaunchKernelGGL((ewise_bwd_kernel<float>), dim3(blocks), dim3(256), 0, st, (const float*)a, (const float*)b, (const float*)dout, (float*)da, (float*)db, n, op, L, a_rs, b_rs, da_rs, db_rs);
-  else if (dtype == MI_BF16) hipLaunchKernelGGL((ewise_bwd_kernel<bf16>), dim3(blocks), dim3(256), 0, st, (const bf16*)a, (const bf16*)b, (const bf16*)dout, (bf16*)da, (bf16*)db, n, op, L, a_rs, b_rs, da_rs, db_rs);
-  else { set_error("ewise_bwd: bad dtype"); return MI_ERR_ARG; }
-  MI_LAUNCH_CHECK();
-  return MI_OK;
+  return with_dtype(dtype, "ewise_bwd", [&](auto tag) {
+    using T = decltype(tag);
+    hipLaunchKernelGGL((ewise_bwd_kernel<T>), dim3(blocks), dim3(256), 0, st, (const T*)a, (const T*)b, (const T*)dout, (T*)da, (T*)db, n, op, L, a_rs, b_rs, da_rs, db_rs);
+  });
 }

@@ -270,14 +270,10 @@ int launch_msfn_s1_fwd(const void* h0, const float* w3, const float* b3, const f
   const double n = (double)B * C2 * H * W;
   ProfScope ps(st, K_MSFN_S1, 3.0 * n * dtype_size(dtype), 2.0 * 34 * n);
   dim3 grid(ms_tiles(H, W), C2, B);
-  if (dtype == MI_F32)
-    hipLaunchKernelGGL((msfn_s1_fwd_kernel<float>), grid, dim3(256), 0, st, (const float*)h0, w3, b3, w5, b5, (float*)a, (float*)b, C2,
-                       H, W, tx);
-  else
-    hipLaunchKernelGGL((msfn_s1_fwd_kernel<bf16>), grid, dim3(256), 0, st, (const bf16*)h0, w3, b3, w5, b5, (bf16*)a, (bf16*)b, C2, H,
-                       W, tx);
-  MI_LAUNCH_CHECK();
-  return MI_OK;
+  return with_dtype(dtype, "msfn_s1_fwd", [&](auto tag) {
+    using T = decltype(tag);
+    hipLaunchKernelGGL((msfn_s1_fwd_kernel<T>), grid, dim3(256), 0, st, (const T*)h0, w3, b3, w5, b5, (T*)a, (T*)b, C2, H, W, tx);
+  });
 }
 
 int launch_msfn_s2_fwd(const void* a, const void* b, const float* g3w, const float* g3b, const float* g5w, const float* g5b, void* y,
@@ -287,14 +283,10 @@ int launch_msfn_s2_fwd(const void* a, const void* b, const float* g3w, const flo
   const double n = (double)B * hd * H * W;
   ProfScope ps(st, K_MSFN_S2, 6.0 * n * dtype_size(dtype), 2.0 * 2 * (9 + 25) * n);
   dim3 grid(ms_tiles(H, W), 2 * hd, B);
-  if (dtype == MI_F32)
-    hipLaunchKernelGGL((msfn_s2_fwd_kernel<float>), grid, dim3(256), 0, st, (const float*)a, (const float*)b, g3w, g3b, g5w, g5b,
-                       (float*)y, hd, H, W, tx);
-  else
-    hipLaunchKernelGGL((msfn_s2_fwd_kernel<bf16>), grid, dim3(256), 0, st, (const bf16*)a, (const bf16*)b, g3w, g3b, g5w, g5b,
-                       (bf16*)y, hd, H, W, tx);
-  MI_LAUNCH_CHECK();
-  return MI_OK;
+  return with_dtype(dtype, "msfn_s2_fwd", [&](auto tag) {
+    using T = decltype(tag);
+    hipLaunchKernelGGL((msfn_s2_fwd_kernel<T>), grid, dim3(256), 0, st, (const T*)a, (const T*)b, g3w, g3b, g5w, g5b, (T*)y, hd, H, W, tx);
+  });
 }
 
 // dY: gradient of cat(y1, y2) [B][2h]; y: its forward value; a, b: stage-1 outputs.  -> dza, dzb (gradients at the stage-1
@@ -310,17 +302,13 @@ int launch_msfn_s2_bwd(const void* dY, const void* y, const void* a, const void*
   float* pb3 = p5 + rows * hd * 50;
   float* pb5 = pb3 + rows * hd;
   dim3 grid(splits, 2 * hd, B);
-  {
+  MI_TRY(with_dtype(dtype, "msfn_s2_bwd", [&](auto tag) {
+    using T = decltype(tag);
     const double n = (double)B * hd * H * W;
-    ProfScope ps(st, K_MSFN_S2_BWD, 10.0 * n * dtype_size(dtype), 4.0 * 2 * (9 + 25) * n);
-    if (dtype == MI_F32)
-      hipLaunchKernelGGL((msfn_s2_bwd_kernel<float>), grid, dim3(256), 0, st, (const float*)dY, (const float*)y, (const float*)a,
-                         (const float*)b, g3w, g5w, (float*)dza, (float*)dzb, p3, p5, pb3, pb5, hd, H, W, tx, nt);
-    else
-      hipLaunchKernelGGL((msfn_s2_bwd_kernel<bf16>), grid, dim3(256), 0, st, (const bf16*)dY, (const bf16*)y, (const bf16*)a,
-                         (const bf16*)b, g3w, g5w, (bf16*)dza, (bf16*)dzb, p3, p5, pb3, pb5, hd, H, W, tx, nt);
-    MI_LAUNCH_CHECK();
-  }
+    ProfScope ps(st, K_MSFN_S2_BWD, 10.0 * n * sizeof(T), 4.0 * 2 * (9 + 25) * n);
+    hipLaunchKernelGGL((msfn_s2_bwd_kernel<T>), grid, dim3(256), 0, st, (const T*)dY, (const T*)y, (const T*)a, (const T*)b, g3w, g5w,
+                       (T*)dza, (T*)dzb, p3, p5, pb3, pb5, hd, H, W, tx, nt);
+  }));
   MI_TRY(launch_reduce_rows(p3, g_g3w, rows, (int64_t)hd * 18, (int64_t)hd * 18, accumulate, 1.0f, st));
   MI_TRY(launch_reduce_rows(p5, g_g5w, rows, (int64_t)hd * 50, (int64_t)hd * 50, accumulate, 1.0f, st));
   if (g_g3b) MI_TRY(launch_reduce_rows(pb3, g_g3b, rows, hd, hd, accumulate, 1.0f, st));
@@ -339,17 +327,13 @@ int launch_msfn_s1_bwd(const void* dza, const void* dzb, const void* h0, const f
   float* pb3 = p5 + rows * C2 * 25;
   float* pb5 = pb3 + rows * C2;
   dim3 grid(splits, C2, B);
-  {
+  MI_TRY(with_dtype(dtype, "msfn_s1_bwd", [&](auto tag) {
+    using T = decltype(tag);
     const double n = (double)B * C2 * H * W;
-    ProfScope ps(st, K_MSFN_S1_BWD, 4.0 * n * dtype_size(dtype), 4.0 * 34 * n);
-    if (dtype == MI_F32)
-      hipLaunchKernelGGL((msfn_s1_bwd_kernel<float>), grid, dim3(256), 0, st, (const float*)dza, (const float*)dzb, (const float*)h0,
-                         w3, w5, (float*)dh0, p3, p5, pb3, pb5, C2, H, W, tx, nt);
-    else
-      hipLaunchKernelGGL((msfn_s1_bwd_kernel<bf16>), grid, dim3(256), 0, st, (const bf16*)dza, (const bf16*)dzb, (const bf16*)h0, w3,
-                         w5, (bf16*)dh0, p3, p5, pb3, pb5, C2, H, W, tx, nt);
-    MI_LAUNCH_CHECK();
-  }
+    ProfScope ps(st, K_MSFN_S1_BWD, 4.0 * n * sizeof(T), 4.0 * 34 * n);
+    hipLaunchKernelGGL((msfn_s1_bwd_kernel<T>), grid, dim3(256), 0, st, (const T*)dza, (const T*)dzb, (const T*)h0, w3, w5, (T*)dh0, p3, p5,
+                       pb3, pb5, C2, H, W, tx, nt);
+  }));
   MI_TRY(launch_reduce_rows(p3, g_w3, rows, (int64_t)C2 * 9, (int64_t)C2 * 9, accumulate, 1.0f, st));
   MI_TRY(launch_reduce_rows(p5, g_w5, rows, (int64_t)C2 * 25, (int64_t)C2 * 25, accumulate, 1.0f, st));
   if (g_b3) MI_TRY(launch_reduce_rows(pb3, g_b3, rows, C2, C2, accumulate, 1.0f, st));

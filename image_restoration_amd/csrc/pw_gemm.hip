@@ -385,8 +385,6 @@ __global__ __launch_bounds__(256) void pw_gemm_res_kernel(PwG q, int n_tiles, in
   constexpr int WC_ELEMS = TM * WS_ROW;                           // one weight chunk in LDS (packed back to back)
   constexpr int XC_ELEMS = PW_KC * PW_XS;                         // one X chunk
   constexpr int OS = PW_TN + 4;
-  constexpr int SLAB_ELEMS = 4 * 16 * OS * 2;                     // fp32 slabs of the four waves, in T units
-  constexpr int XBUF_ELEMS = PWR_MAXC * XC_ELEMS > SLAB_ELEMS ? PWR_MAXC * XC_ELEMS : SLAB_ELEMS;
   extern __shared__ __attribute__((aligned(16))) unsigned char lds_dyn[];
   const int nchunks = q.k_chunks;
   T* const Wl = reinterpret_cast<T*>(lds_dyn);                    // [nchunks][TM][WS_ROW]
@@ -836,7 +834,7 @@ __global__ __launch_bounds__(64 * PWW_MW) void pw_gemm_wave_xres_kernel(PwG q, i
   constexpr int WS_ROW = PwRow<bf16>::WS_ROW, TM = 64;
   extern __shared__ __attribute__((aligned(16))) unsigned char lds_dyn[];
   bf16* const Wl = reinterpret_cast<bf16*>(lds_dyn);                 // [m_tiles][KB][64][WS_ROW]
-  const int t = threadIdx.x, lane = t & 63, li = lane & 15, g = lane >> 4;
+  const int t = threadIdx.x, lane = t & 63;
   const int wv = __builtin_amdgcn_readfirstlane(t >> 6);   // scalar: the wave's patch, tile range and their addresses stay out of the VGPRs
   bf16* const patch = Wl + (int64_t)m_tiles * KB * TM * WS_ROW + wv * PWW_PATCH;
   const int z = blockIdx.z, zb = z / p.groups, zg = z - zb * p.groups;
@@ -1543,8 +1541,7 @@ extern "C" int mi_pw_gemm(const mi_pw_desc* d, void* ws, void* stream) {
   k.vec_ok = ok ? 1 : 0;
   const PwPlan pl = pw_plan(d);
   hipStream_t st = (hipStream_t)stream;
-  if (d->dtype == MI_F32) return pw_launch<float>(d, k, pl, ws, st);
-  return pw_launch<bf16>(d, k, pl, ws, st);
+  return with_dtype(d->dtype, "pw_gemm", [&](auto tag) -> int { return pw_launch<decltype(tag)>(d, k, pl, ws, st); });
 }
 
 extern "C" int mi_pw_gemm_ln_ok(const mi_pw_desc* d) {

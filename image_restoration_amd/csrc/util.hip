@@ -527,8 +527,7 @@ extern "C" int mi_adamw_step(float* p, const float* g, float* m, float* v, int64
   MI_CHECK_ARG(aligned16(p) && aligned16(g) && aligned16(m) && aligned16(v), "adamw: buffers must be 16-byte aligned");
   const float bc1 = 1.0f - powf(beta1, (float)step);
   const float bc2 = sqrtf(1.0f - powf(beta2, (float)step));
-  int blocks = cdiv(n, 256 * 4);
-  if (blocks > 2048) blocks = 2048;
+  const int blocks = cdiv_cap(n, 256 * 4, 2048);
   ProfScope ps((hipStream_t)stream, K_ADAMW, 28.0 * n, 12.0 * n);
   hipLaunchKernelGGL(adamw_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, lr, beta1, beta2, eps,
                      weight_decay, bc1, bc2, grad_scale, dev_scalars);
@@ -570,8 +569,7 @@ extern "C" int mi_adamw_step_ex(float* p, const float* g, float* m, float* v, fl
   const float bc1 = 1.0f - powf(beta1, (float)step);
   const float bc2 = sqrtf(1.0f - powf(beta2, (float)step));
   const float one_m_decay = (float)(1.0 - (double)ema_decay);
-  int blocks = cdiv(n, 256 * 4);
-  if (blocks > 2048) blocks = 2048;
+  const int blocks = cdiv_cap(n, 256 * 4, 2048);
   ProfScope ps((hipStream_t)stream, ema ? K_ADAMW_EMA : K_ADAMW_CLIP, (ema ? 36.0 : 28.0) * n, (ema ? 15.0 : 13.0) * n);
   hipLaunchKernelGGL(adamw_ex_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, p, g, m, v, ema, n, lr, beta1, beta2,
                      eps, weight_decay, bc1, bc2, grad_scale, dev_scalars, sumsq, max_norm, norm_out, ema_decay, one_m_decay);
@@ -583,39 +581,31 @@ extern "C" int mi_gap_fwd(const void* x, float* out, int B, int C, int64_t N, in
   MI_CHECK_ARG(x && out && B > 0 && C > 0 && N > 0, "gap_fwd: bad arguments");
   hipStream_t st = (hipStream_t)stream;
   ProfScope ps(st, K_GAP, (double)B * C * N * dtype_size(dtype), (double)B * C * N);
-  if (dtype == MI_F32) hipLaunchKernelGGL((gap_fwd_kernel<float>), dim3(B * C), dim3(256), 0, st, (const float*)x, out, N);
-  else if (dtype == MI_BF16) hipLaunchKernelGGL((gap_fwd_kernel<bf16>), dim3(B * C), dim3(256), 0, st, (const bf16*)x, out, N);
-  else { set_error("gap_fwd: bad dtype"); return MI_ERR_ARG; }
-  MI_LAUNCH_CHECK();
-  return MI_OK;
+  return with_dtype(dtype, "gap_fwd", [&](auto tag) {
+    using T = decltype(tag);
+    hipLaunchKernelGGL((gap_fwd_kernel<T>), dim3(B * C), dim3(256), 0, st, (const T*)x, out, N);
+  });
 }
 extern "C" int mi_gap_bwd(const float* dout, void* dx, int B, int C, int64_t N, int dtype, void* stream) {
   MI_CHECK_ARG(dout && dx && B > 0 && C > 0 && N > 0, "gap_bwd: bad arguments");
   hipStream_t st = (hipStream_t)stream;
   ProfScope ps(st, K_GAP, (double)B * C * N * dtype_size(dtype), 0.0);
-  if (dtype == MI_F32) hipLaunchKernelGGL((gap_bwd_kernel<float>), dim3(B * C), dim3(256), 0, st, dout, (float*)dx, N);
-  else if (dtype == MI_BF16) hipLaunchKernelGGL((gap_bwd_kernel<bf16>), dim3(B * C), dim3(256), 0, st, dout, (bf16*)dx, N);
-  else { set_error("gap_bwd: bad dtype"); return MI_ERR_ARG; }
-  MI_LAUNCH_CHECK();
-  return MI_OK;
+  return with_dtype(dtype, "gap_bwd", [&](auto tag) {
+    using T = decltype(tag);
+    hipLaunchKernelGGL((gap_bwd_kernel<T>), dim3(B * C), dim3(256), 0, st, dout, (T*)dx, N);
+  });
 }
 
 extern "C" int mi_cast(const void* src, int sdt, void* dst, int ddt, int64_t n, void* stream) {
   MI_CHECK_ARG(src && dst && n > 0, "cast: bad arguments");
-  int blocks = cdiv(n, 256);
-  if (blocks > 4096) blocks = 4096;
-  hipStream_t st = (hipStream_t)stream;
-  if (sdt == MI_F32 && ddt == MI_BF16)
-    hipLaunchKernelGGL((cast_kernel<float, bf16>), dim3(blocks), dim3(256), 0, st, (const float*)src, (bf16*)dst, n);
-  else if (sdt == MI_BF16 && ddt == MI_F32)
-    hipLaunchKernelGGL((cast_kernel<bf16, float>), dim3(blocks), dim3(256), 0, st, (const bf16*)src, (float*)dst, n);
-  else if (sdt == MI_F32 && ddt == MI_F32)
-    hipLaunchKernelGGL((cast_kernel<float, float>), dim3(blocks), dim3(256), 0, st, (const float*)src, (float*)dst, n);
-  else if (sdt == MI_BF16 && ddt == MI_BF16)
-    hipLaunchKernelGGL((cast_kernel<bf16, bf16>), dim3(blocks), dim3(256), 0, st, (const bf16*)src, (bf16*)dst, n);
-  else { set_error("cast: bad dtypes %d -> %d", sdt, ddt); return MI_ERR_ARG; }
-  MI_LAUNCH_CHECK();
-  return MI_OK;
+  const int blocks = cdiv_cap(n, 256, 4096);
+  return with_dtype(sdt, "cast (source)", [&](auto stag) -> int {
+    return with_dtype(ddt, "cast (destination)", [&](auto dtag) {
+      using S = decltype(stag);
+      using D = decltype(dtag);
+      hipLaunchKernelGGL((cast_kernel<S, D>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, (const S*)src, (D*)dst, n);
+    });
+  });
 }
 
 // loss[0] += mean|a-b| ; uses loss[1..] as scratch: caller passes a float buffer of >= 1+1024 entries
@@ -623,15 +613,11 @@ extern "C" int mi_l1_loss(const void* a, const void* b, void* da, float* loss, i
                           void* stream) {
   MI_CHECK_ARG(a && b && loss && n > 0, "l1_loss: bad arguments");
   hipStream_t st = (hipStream_t)stream;
-  int blocks = cdiv(n, 256 * 8);
-  if (blocks > 1024) blocks = 1024;
-  if (dtype == MI_F32)
-    hipLaunchKernelGGL((l1_kernel<float>), dim3(blocks), dim3(256), 0, st, (const float*)a, (const float*)b, (float*)da,
-                       loss + 1, n, scale);
-  else if (dtype == MI_BF16)
-    hipLaunchKernelGGL((l1_kernel<bf16>), dim3(blocks), dim3(256), 0, st, (const bf16*)a, (const bf16*)b, (bf16*)da,
-                       loss + 1, n, scale);
-  else { set_error("l1_loss: bad dtype"); return MI_ERR_ARG; }
-  MI_LAUNCH_CHECK();
-  return launch_reduce_rows(loss + 1, loss, blocks, 1, 1, 1, 1.0f / (float)n, st);
+  const int blocks = cdiv_cap(n, 256 * 8, 1024);
+  return with_dtype(dtype, "l1_loss", [&](auto tag) -> int {
+    using T = decltype(tag);
+    hipLaunchKernelGGL((l1_kernel<T>), dim3(blocks), dim3(256), 0, st, (const T*)a, (const T*)b, (T*)da, loss + 1, n, scale);
+    MI_LAUNCH_CHECK();
+    return launch_reduce_rows(loss + 1, loss, blocks, 1, 1, 1, 1.0f / (float)n, st);
+  });
 }

@@ -36,6 +36,13 @@ def test_library_exports_every_declared_symbol(lib):
     assert lib.lib().mi_version() == 100
 
 
+def test_unknown_dtype_code_is_refused_without_gpu(lib):
+    # the dtype dispatch returns before anything is launched: the buffers are never touched
+    src, dst = C.create_string_buffer(64), C.create_string_buffer(64)
+    assert lib.lib().mi_cast(src, lib.MI_F32, dst, 7, 16, None) == -1
+    assert b"bad dtype 7" in lib.lib().mi_last_error()
+
+
 def test_sizing_and_argument_errors_without_gpu(lib):
     L = lib
     s = L.MdtaShape(2, 48, 1, 16, 16, L.MI_F32, 3)
