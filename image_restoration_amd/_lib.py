@@ -173,6 +173,7 @@ SIGNATURES = {
     "mi_ln_bwd_workspace": (C.c_size_t, [C.c_int, C.c_int, c_i64]),
     "mi_ln_bwd": (C.c_int, [vp, vp, fp, fp, fp, vp, vp, fp, fp, C.c_int, C.c_int, c_i64, C.c_int, C.c_int, C.c_int,
                             vp, vp]),
+    "mi_ln_plan": (C.c_int, [C.c_int, C.c_int, c_i64, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int)]),
     "mi_dwconv_fwd": (C.c_int, [vp, fp, fp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
     "mi_dwconv_gate_fwd": (C.c_int, [vp, fp, fp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
     "mi_dwconv_bwd_workspace": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),

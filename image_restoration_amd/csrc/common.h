@@ -355,6 +355,8 @@ bool deferred_reduce_rows(const float* part, float* out, int64_t rows, int64_t c
 
 // generic small kernels implemented in util.hip, used by several modules
 constexpr int REDUCE_GROUPS = 32;
+// launch_reduce_rows, given scratch, sums this many rows in two stages (the rule is here so that a plan query can report it)
+static inline bool reduce_rows_two_stage(int64_t rows) { return rows > 4 * REDUCE_GROUPS; }
 int launch_reduce_rows(const float* part, float* out, int64_t rows, int64_t cols, int64_t part_ld,
                        int accumulate, float scale, hipStream_t st, float* tmp = nullptr, float* out2 = nullptr,
                        int64_t split = 0);  // out2: columns [split, cols) are written to out2[0 .. cols-split)

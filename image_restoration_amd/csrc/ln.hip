@@ -475,36 +475,89 @@ static LnCfg ln_cfg(int C, bool bwd, bool f32) {
   else c = {16, 48, 1};
   return c;
 }
-static bool ln_aligned(int vec, size_t es, int64_t N, const void* a, const void* b, const void* c, const void* d) {
+// the pointer part of "may a lane move `vec` elements as one access"; the shape part is N % vec == 0
+static bool ln_ptrs_aligned(int vec, size_t es, const void* a, const void* b, const void* c, const void* d) {
   const uintptr_t m = (uintptr_t)vec * es - 1;
   const uintptr_t bits = reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b) | reinterpret_cast<uintptr_t>(c) |
                          reinterpret_cast<uintptr_t>(d);
-  return N % vec == 0 && (bits & m) == 0;
+  return (bits & m) == 0;
+}
+
+// What one call launches.  The ONE place that decides it: the dispatchers launch what it says and mi_ln_plan reports it.
+// `aligned`: every activation pointer is a multiple of the widest per-lane access (4 bytes for both dtypes).
+struct LnPlan {
+  bool wave;        // wave-owned family, else the block family
+  int cb, ws, nw;   // wave: channels per slice, waves that share a tile, waves per workgroup
+  int waves, cpt;   // block: waves per workgroup, channels per thread
+  int vec;          // pixels per lane
+  int tiles;        // pixel tiles (64 * vec pixels) per workgroup
+  int gx;           // grid x (grid y = B)
+  int rows;         // backward: partial rows [2C] written, one per tile per image
+};
+static LnPlan ln_fwd_plan(int C, int64_t N, bool f32, bool aligned) {
+  LnCfg cf = ln_cfg(C, false, f32);
+  const int wvec = f32 ? 1 : 2;
+  if (!(N % cf.vec == 0 && aligned)) cf.vec = 1;
+  LnPlan p{};
+  p.vec = cf.vec;
+  if (ln_wave_form(C, false) && cf.vec == wvec) {
+    p.wave = true;
+    p.cb = C <= 16 ? 16 : (C <= 48 ? 48 : 96);
+    p.ws = C <= 96 ? 1 : (C <= 192 ? 2 : 4);
+    p.nw = 4;
+    p.tiles = p.nw / p.ws;
+  } else {
+    p.waves = cf.waves; p.cpt = cf.cpt;
+    p.tiles = 1;
+  }
+  p.gx = cdiv(N, 64 * p.vec * p.tiles);
+  return p;
+}
+static LnPlan ln_bwd_plan(int B, int C, int64_t N, bool f32, bool aligned) {
+  LnCfg cf = ln_cfg(C, true, f32);
+  const int wvec = f32 ? 1 : 2;
+  if (!(N % cf.vec == 0 && aligned)) cf.vec = 1;
+  LnPlan p{};
+  if (ln_wave_form(C, true) && N % wvec == 0 && aligned) {
+    // 24-channel slices: C / 24 waves share a 128-pixel tile (measured: 96-channel slices 1.35x slower than the block
+    // kernel at C = 96, 48-channel 1.28x faster, 24-channel 1.63x faster; profiles/r01_w_ln_forms_bs32.log)
+    p.wave = true;
+    p.vec = wvec;
+    p.cb = C <= 16 ? 16 : 24;
+    p.ws = C <= 24 ? 1 : (C <= 48 ? 2 : (C <= 96 ? 4 : (C <= 192 ? 8 : 16)));
+    p.nw = p.ws <= 4 ? 4 : p.ws;
+    p.tiles = p.nw / p.ws;
+  } else {
+    p.vec = cf.vec;
+    p.waves = cf.waves; p.cpt = cf.cpt;
+    p.tiles = 1;
+  }
+  const int tiles = cdiv(N, 64 * p.vec);   // same partial-row layout in both families: one row per 64*vec-pixel tile
+  p.gx = cdiv(tiles, p.tiles);
+  p.rows = tiles * B;
+  return p;
 }
 
 template <typename T, bool WB>
 static int ln_fwd_dispatch(const T* x, const float* w, const float* b, T* y, float* mean, float* rstd, int B, int C,
                            int64_t N, hipStream_t st) {
   constexpr bool F32 = sizeof(T) == 4;
-  LnCfg cf = ln_cfg(C, false, F32);
-  if (C > 768) { set_error("ln_fwd: C=%d > 768 unsupported", C); return MI_ERR_ARG; }
-  if (!ln_aligned(cf.vec, sizeof(T), N, x, y, nullptr, nullptr)) cf.vec = 1;
-  dim3 grid(cdiv(N, 64 * cf.vec), B);
-  ProfScope ps(st, K_LN_FWD, 2.0 * B * C * N * sizeof(T) + (mean ? 8.0 * B * N : 0.0), 8.0 * B * C * N);
   constexpr int WVEC = F32 ? 1 : 2;
-  if (ln_wave_form(C, false) && cf.vec == WVEC) {   // wave-owned form
-    const int ws = C <= 96 ? 1 : (C <= 192 ? 2 : 4);
-    dim3 wgrid(cdiv(N, 64 * WVEC * (4 / ws)), B);
-#define LN_FWDW_CASE(CB, WS_) \
-    hipLaunchKernelGGL((ln_fwd_wave_kernel<T, CB, WVEC, WB, WS_>), wgrid, dim3(256), 0, st, x, w, b, y, mean, rstd, C, N)
-    if (C <= 16) LN_FWDW_CASE(16, 1); else if (C <= 48) LN_FWDW_CASE(48, 1); else if (C <= 96) LN_FWDW_CASE(96, 1);
-    else if (C <= 192) LN_FWDW_CASE(96, 2); else LN_FWDW_CASE(96, 4);
+  if (C > 768) { set_error("ln_fwd: C=%d > 768 unsupported", C); return MI_ERR_ARG; }
+  const LnPlan p = ln_fwd_plan(C, N, F32, ln_ptrs_aligned(WVEC, sizeof(T), x, y, nullptr, nullptr));
+  dim3 grid(p.gx, B);
+  ProfScope ps(st, K_LN_FWD, 2.0 * B * C * N * sizeof(T) + (mean ? 8.0 * B * N : 0.0), 8.0 * B * C * N);
+  if (p.wave) {   // wave-owned form
+#define LN_FWDW_CASE(CB, WS_)                                                                                            \
+    if (p.cb == CB && p.ws == WS_)                                                                                       \
+      hipLaunchKernelGGL((ln_fwd_wave_kernel<T, CB, WVEC, WB, WS_>), grid, dim3(256), 0, st, x, w, b, y, mean, rstd, C, N)
+    LN_FWDW_CASE(16, 1); LN_FWDW_CASE(48, 1); LN_FWDW_CASE(96, 1); LN_FWDW_CASE(96, 2); LN_FWDW_CASE(96, 4);
 #undef LN_FWDW_CASE
     MI_LAUNCH_CHECK();
     return MI_OK;
   }
 #define LN_FWD_CASE(WV, CPT, VEC)                                                                                   \
-  if (cf.waves == WV && cf.cpt == CPT && cf.vec == VEC)                                                                 \
+  if (p.waves == WV && p.cpt == CPT && p.vec == VEC)                                                                    \
     hipLaunchKernelGGL((ln_fwd_kernel<T, WV, CPT, VEC, WB>), grid, dim3(64 * WV), 0, st, x, w, b, y, mean, rstd, C, N)
   if constexpr (!F32) {
     LN_FWD_CASE(8, 2, 2); LN_FWD_CASE(8, 6, 2); LN_FWD_CASE(8, 12, 2); LN_FWD_CASE(8, 24, 2); LN_FWD_CASE(16, 24, 2);
@@ -520,33 +573,28 @@ template <typename T, bool WB>
 static int ln_bwd_dispatch(const T* dy, const T* x, const float* w, const float* mean, const float* rstd, const T* dres,
                            T* dx, float* part, int B, int C, int64_t N, int* rows_out, hipStream_t st) {
   constexpr bool F32 = sizeof(T) == 4;
-  LnCfg cf = ln_cfg(C, true, F32);
-  if (C > 768) { set_error("ln_bwd: C=%d > 768 unsupported", C); return MI_ERR_ARG; }
-  if (!ln_aligned(cf.vec, sizeof(T), N, dy, x, dres, dx)) cf.vec = 1;
-  const int gx = cdiv(N, 64 * cf.vec);
-  *rows_out = gx * B;
-  dim3 grid(gx, B);
-  ProfScope ps(st, K_LN_BWD, (dres ? 4.0 : 3.0) * B * C * N * sizeof(T) + 8.0 * B * N, 16.0 * B * C * N);
   constexpr int WVEC = F32 ? 1 : 2;
-  if (ln_wave_form(C, true) && ln_aligned(WVEC, sizeof(T), N, dy, x, dres, dx)) {
-    // wave-owned form; same partial-row layout (one row per 64*VEC-pixel tile)
-    const int wtiles = cdiv(N, 64 * WVEC);
-    *rows_out = wtiles * B;
+  if (C > 768) { set_error("ln_bwd: C=%d > 768 unsupported", C); return MI_ERR_ARG; }
+  const LnPlan p = ln_bwd_plan(B, C, N, F32, ln_ptrs_aligned(WVEC, sizeof(T), dy, x, dres, dx));
+  *rows_out = p.rows;
+  dim3 grid(p.gx, B);
+  ProfScope ps(st, K_LN_BWD, (dres ? 4.0 : 3.0) * B * C * N * sizeof(T) + 8.0 * B * N, 16.0 * B * C * N);
+  if (p.wave) {   // wave-owned form
+    const int wtiles = p.rows / B;
 #define LN_BWDW_CASE(CB, WS_, NW_)                                                                                      \
-    hipLaunchKernelGGL((ln_bwd_wave_kernel<T, CB, WVEC, WB, WS_, true, true, NW_>), dim3(cdiv(wtiles, NW_ / WS_), B),       \
-                       dim3(64 * NW_), 0, st, dy, x, w, mean, rstd, dres, dx, part, C, N, wtiles)
-    // 24-channel slices: C / 24 waves share a 128-pixel tile (measured: 96-channel slices 1.35x slower than the block
-    // kernel at C = 96, 48-channel 1.28x faster, 24-channel 1.63x faster; profiles/r01_w_ln_forms_bs32.log)
-    if (C <= 16) LN_BWDW_CASE(16, 1, 4); else if (C <= 24) LN_BWDW_CASE(24, 1, 4); else if (C <= 48) LN_BWDW_CASE(24, 2, 4);
-    else if (C <= 96) LN_BWDW_CASE(24, 4, 4); else if (C <= 192) LN_BWDW_CASE(24, 8, 8); else LN_BWDW_CASE(24, 16, 16);
+    if (p.cb == CB && p.ws == WS_)                                                                                      \
+      hipLaunchKernelGGL((ln_bwd_wave_kernel<T, CB, WVEC, WB, WS_, true, true, NW_>), grid, dim3(64 * NW_), 0, st, dy, x, w, \
+                         mean, rstd, dres, dx, part, C, N, wtiles)
+    LN_BWDW_CASE(16, 1, 4); LN_BWDW_CASE(24, 1, 4); LN_BWDW_CASE(24, 2, 4); LN_BWDW_CASE(24, 4, 4); LN_BWDW_CASE(24, 8, 8);
+    LN_BWDW_CASE(24, 16, 16);
 #undef LN_BWDW_CASE
     MI_LAUNCH_CHECK();
     return MI_OK;
   }
 #define LN_BWD_CASE(WV, CPT, VEC)                                                                                     \
-  if (cf.waves == WV && cf.cpt == CPT && cf.vec == VEC)                                                                   \
+  if (p.waves == WV && p.cpt == CPT && p.vec == VEC)                                                                      \
     hipLaunchKernelGGL((ln_bwd_kernel<T, WV, CPT, VEC, WB, (CPT >= 24)>), grid, dim3(64 * WV), 0, st, dy, x, w, mean, rstd, \
-                       dres, dx, part, C, N, 1, gx)
+                       dres, dx, part, C, N, 1, p.gx)
   if constexpr (!F32) {
     LN_BWD_CASE(8, 2, 2); LN_BWD_CASE(8, 6, 2); LN_BWD_CASE(8, 12, 2); LN_BWD_CASE(8, 24, 2);
   }
@@ -579,6 +627,25 @@ extern "C" int mi_ln_fwd(const void* x, const float* w, const float* b, void* y,
 extern "C" size_t mi_ln_bwd_workspace(int B, int C, int64_t N) {
   // one partial row of 2C floats per 64-pixel tile in the worst case (one pixel per lane), plus the two-stage scratch
   return align_up(((size_t)cdiv(N, 64) * B + 2 * REDUCE_GROUPS) * 2 * C * sizeof(float), 256);
+}
+
+// What mi_ln_fwd (backward = 0) / mi_ln_bwd (1) launch for this call under the current MI_LN_FORM; aligned: every activation
+// pointer is a multiple of 4 bytes.  Host-side only: it calls the same ln_fwd_plan / ln_bwd_plan the dispatchers do.
+extern "C" int mi_ln_plan(int B, int C, int64_t N, int dtype, int backward, int aligned, int* out) {
+  MI_CHECK_ARG(out, "ln_plan: null pointer");
+  MI_CHECK_ARG(B > 0 && C > 0 && N > 0, "ln_plan: bad shape B=%d C=%d N=%lld", B, C, (long long)N);
+  MI_CHECK_ARG(C <= 768, "ln_plan: C=%d > 768 unsupported", C);
+  return with_dtype(dtype, "ln_plan", [&](auto tag) -> int {
+    constexpr bool F32 = sizeof(decltype(tag)) == 4;
+    const LnPlan p = backward ? ln_bwd_plan(B, C, N, F32, aligned != 0) : ln_fwd_plan(C, N, F32, aligned != 0);
+    out[0] = p.wave ? 1 : 0;
+    out[1] = p.wave ? p.cb : p.waves;
+    out[2] = p.wave ? p.ws : p.cpt;
+    out[3] = p.wave ? p.nw : 0;
+    out[4] = p.vec; out[5] = p.tiles; out[6] = p.gx; out[7] = p.rows;
+    out[8] = (backward && reduce_rows_two_stage(p.rows)) ? 1 : 0;
+    return MI_OK;
+  });
 }
 
 extern "C" int mi_ln_bwd(const void* dy, const void* x, const float* w, const float* mean, const float* rstd,

@@ -114,7 +114,7 @@ int launch_reduce_rows(const float* part, float* out, int64_t rows, int64_t cols
   if (cols <= 0) return MI_OK;
   // partials a producer placed in the deferred arena: record the sum, mi_deferred_flush runs it (common.h)
   if (deferred_reduce_rows(part, out, rows, cols, part_ld, accumulate, scale, out2, split)) return MI_OK;
-  if (tmp && rows > 4 * REDUCE_GROUPS) {
+  if (tmp && reduce_rows_two_stage(rows)) {
     const int64_t rpg = (rows + REDUCE_GROUPS - 1) / REDUCE_GROUPS;
     {
       ProfScope ps(st, K_REDUCE_ROWS, (double)(rows + REDUCE_GROUPS) * cols * 4, (double)rows * cols);

@@ -146,6 +146,17 @@ def ln_bwd(dy: Tensor, x: Tensor, w: Tensor, mean: Tensor, rstd: Tensor, dres: O
     return dx
 
 
+def ln_plan(B: int, C: int, N: int, dtype: torch.dtype, backward: bool, aligned: bool = True) -> dict:
+    """What ln_fwd / ln_bwd launch for this call under the current MI_LN_FORM (mi_ln_plan; no GPU work).  aligned: every
+    activation pointer is a multiple of 4 bytes.  rows / two_stage describe the backward's partial rows and their sum."""
+    out = (L.C.c_int * 9)()   # (C is the channel count here)
+    L.check(L.lib().mi_ln_plan(B, C, N, _dtype_code(dtype), int(backward), int(aligned), out), "ln_plan")
+    tail = {"vec": out[4], "tiles": out[5], "gx": out[6], "rows": out[7], "two_stage": bool(out[8])}
+    if out[0] == 1:
+        return {"family": "wave", "CB": out[1], "WS": out[2], "NW": out[3], **tail}
+    return {"family": "block", "waves": out[1], "CPT": out[2], **tail}
+
+
 # ----------------------------------------------------------------------------- depthwise conv
 def dwconv_fwd(x: Tensor, w: Tensor, bias: Optional[Tensor]) -> Tensor:
     _gpu(x, w, bias)

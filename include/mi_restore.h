@@ -80,6 +80,12 @@ int mi_ln_bwd(const void* dy, const void* x, const float* w, const float* mean, 
               const void* dres, void* dx, float* dw, float* db,
               int B, int C, int64_t N, int with_bias, int accumulate, int dtype,
               void* ws, void* stream);
+/* What mi_ln_fwd (backward = 0) / mi_ln_bwd (1) launch for this call (read-only; honours MI_LN_FORM).  aligned: every activation
+ * pointer of the call is a multiple of 4 bytes (bf16 then moves two pixels per lane when N is even).
+ * out[9] = {family (0 block, 1 wave-owned), waves per workgroup | channels per slice CB, channels per thread CPT | waves per
+ *           tile WS, 0 | waves per workgroup NW, pixels per lane, pixel tiles per workgroup, grid x, partial rows (backward),
+ *           1 when the row reduction takes two stages (backward, outside a deferred window)}. */
+int mi_ln_plan(int B, int C, int64_t N, int dtype, int backward, int aligned, int* out);
 
 /* ------------------------------------------------------------------------
  * Depthwise k x k convolution, stride 1, zero pad k/2, groups = channels

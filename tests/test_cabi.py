@@ -194,3 +194,53 @@ def test_glue_has_no_vendor_fallback(lib):
         rs._conv2d(torch.zeros(1, 4, 8, 8), nn.Conv2d(4, 4, 3, padding=1))
     with pytest.raises(RuntimeError, match="MI355X only"):
         rs._shuffle(torch.zeros(1, 4, 8, 8), False)
+
+
+def test_ln_plan_query_and_its_argument_errors(lib, monkeypatch):
+    """mi_ln_plan reports what mi_ln_fwd / mi_ln_bwd launch (the launchers call the same plan functions) without a GPU."""
+    from image_restoration_amd import ops
+    monkeypatch.delenv("MI_LN_FORM", raising=False)
+    f32, bf16 = torch.float32, torch.bfloat16
+    assert ops.ln_plan(2, 48, 130, bf16, False) == {"family": "wave", "CB": 48, "WS": 1, "NW": 4, "vec": 2, "tiles": 4, "gx": 1,
+                                                    "rows": 0, "two_stage": False}
+    assert ops.ln_plan(3, 49, 130, f32, True) == {"family": "wave", "CB": 24, "WS": 4, "NW": 4, "vec": 1, "tiles": 1, "gx": 3,
+                                                  "rows": 9, "two_stage": False}
+    # an odd pixel count or a misaligned pointer: one bf16 pixel per lane, and with it the block family
+    for kw in ({"N": 129}, {"N": 130, "aligned": False}):
+        assert ops.ln_plan(3, 96, dtype=bf16, backward=True, **kw) == {"family": "block", "waves": 8, "CPT": 12, "vec": 1, "tiles": 1,
+                                                                      "gx": 3, "rows": 9, "two_stage": False}
+    assert ops.ln_plan(1, 768, 64, f32, True)["family"] == "block" and ops.ln_plan(1, 768, 64, f32, True)["CPT"] == 48
+    assert ops.ln_plan(3, 16, 2753, f32, True)["rows"] == 132 and ops.ln_plan(3, 16, 2753, f32, True)["two_stage"]
+    assert ops.ln_plan(2, 16, 4033, f32, True)["rows"] == 128 and not ops.ln_plan(2, 16, 4033, f32, True)["two_stage"]
+    monkeypatch.setenv("MI_LN_FORM", "block")
+    assert ops.ln_plan(2, 48, 130, bf16, False) == {"family": "block", "waves": 8, "CPT": 6, "vec": 2, "tiles": 1, "gx": 2,
+                                                    "rows": 0, "two_stage": False}
+    monkeypatch.setenv("MI_LN_FORM", "wave")
+    assert ops.ln_plan(2, 384, 130, f32, False)["WS"] == 4 and ops.ln_plan(2, 385, 130, f32, False)["family"] == "block"
+    out = (C.c_int * 9)()
+    assert lib.lib().mi_ln_plan(1, 769, 64, lib.MI_F32, 0, 1, out) == -1 and b"769" in lib.lib().mi_last_error()
+    assert lib.lib().mi_ln_plan(1, 769, 64, lib.MI_BF16, 1, 1, out) == -1
+    assert lib.lib().mi_ln_plan(1, 48, 64, 7, 0, 1, out) == -1 and b"bad dtype 7" in lib.lib().mi_last_error()
+    assert lib.lib().mi_ln_plan(1, 48, 64, lib.MI_F32, 0, 1, None) == -1
+    assert lib.lib().mi_ln_plan(0, 48, 64, lib.MI_F32, 0, 1, out) == -1
+
+
+def test_ln_case_lists_reach_every_plan(lib, monkeypatch):
+    """Every kernel instance the LayerNorm dispatch can choose - over C = 1..768, both dtypes, both directions, aligned or not,
+    even or odd pixel counts and the three MI_LN_FORM settings - is run by a case of tests/test_gpu_ln.py.  A threshold that
+    moves in ln.hip shows up here as the plan that lost its case."""
+    import test_gpu_ln as T
+    possible = {}
+    for form in T.FORMS:
+        T.set_form(monkeypatch, form)
+        for c in range(1, 769):
+            for d in ("f32", "bf16"):
+                for n in (130, 65):
+                    for aligned in (True, False):
+                        pf, pb = T.plans(3, c, n, d, aligned)
+                        for key in (T.plan_key("fwd", d, pf), T.plan_key("bwd", d, pb)):
+                            possible.setdefault(key, (form, c, n, aligned))
+    reached = T.reached_plans(monkeypatch)
+    missing = {k: v for k, v in possible.items() if k not in reached}
+    assert not missing, "plans without a test case (plan: first (MI_LN_FORM, C, N, aligned) that takes it): %r" % missing
+    assert len(possible) >= 40 and reached <= set(possible)
