@@ -212,6 +212,7 @@ SIGNATURES = {
     "mi_gdfn_fwd_ln": (C.c_int, [C.POINTER(GdfnShape), C.POINTER(GdfnParams), C.POINTER(LnHead), vp, vp, vp, vp, vp, vp]),
     "mi_pw_gemm_f8_ok": (C.c_int, [C.POINTER(PwDesc)]),
     "mi_pw_gemm_split_ok": (C.c_int, [C.POINTER(PwDesc)]),
+    "mi_pw_plan": (C.c_int, [C.POINTER(PwDesc), C.POINTER(c_i64)]),
     "mi_mdta_fwd_f8_ok": (C.c_int, [C.POINTER(MdtaShape), C.c_int]),
     "mi_mdta_fwd_f8": (C.c_int, [C.POINTER(MdtaShape), C.POINTER(MdtaParams), C.POINTER(LnHead), C.POINTER(F8Scales), vp, vp, vp,
                                  vp, vp]),

@@ -16,6 +16,33 @@ struct PwK {
   int m; int64_t n; int groups; int vec_ok;
   void* y2; int64_t y2_bs, y2_gs; int y_split;   // rows >= y_split go to y2 (wave-owned forms, no residual); 0 = one output
 };
+// What one mi_pw_gemm call runs: filled by pw_plan (pw_gemm.hip), the ONE place that decides it; the launchers launch what it
+// says, the mi_pw_gemm_*_ok predicates and mi_pw_gemm_workspace read it, mi_pw_plan reports it.
+enum PwFamily { PW_CHUNKED = 0, PW_RESIDENT, PW_DMA, PW_XRES, PW_STREAM, PW_XWIDE, PW_LDS };
+enum PwWeights { PW_W_PACK = 0, PW_W_B16, PW_W_F32 };   // own packed image / the producer's bf16 copy / straight from fp32
+struct PwPlan {
+  int family;                                    // PwFamily
+  int tm, m_tiles, k_chunks;                     // the instance: rows per tile, tiles over M, K chunks (32 deep; PW_LDS: 64)
+  bool f8, ln;                                   // ... and its fp8 / LayerNorm-on-load template choices
+  bool vec_ok;                                   // 16-byte rows: every pointer and stride allows vector access
+  int slices, per_batch, per_group, chunk_elems; // the pw_pack image: [slice][m-tile][k-chunk][chunk_elems]
+  int64_t slice_elems;
+  size_t bytes;                                  // ... its size with the zero block (sized for every family: mi_pw_gemm_workspace)
+  size_t lds_image;                              // the LDS-tiled kernel's image, wherever dtype and depth could reach that kernel
+  dim3 grid, block; size_t lds;                  // the launch
+  int tpw, tpb, n_slabs, slabs_per, xcd_map;     // pixel tiles per wave (wave forms) / per workgroup (resident); X-wide M slabs
+  int weights;                                   // PwWeights
+  bool cacheable;                                // may use the packed-weight cache (static weights, own pack)
+  size_t ws_bytes() const { return family == PW_LDS ? align_up(lds_image, 256) : bytes; }   // what this call's workspace holds
+};
+// Launch with dynamic LDS: above 64 KiB the kernel's limit has to be raised first.
+template <typename... P, typename... A>
+static inline int launch_dyn_lds(void (*kernel)(P...), dim3 grid, dim3 block, size_t lds, hipStream_t st, A... args) {
+  if (lds > 64 * 1024) MI_CHECK_HIP(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  hipLaunchKernelGGL(kernel, grid, block, lds, st, args...);
+  MI_LAUNCH_CHECK();
+  return MI_OK;
+}
 int launch_attn_fold(const float* graw, const float* ss, const float* temperature, const float* wo, float* P, float* A,
                      float* nrm, float* M, int B, int C, int heads, hipStream_t st, void* Mb = nullptr, void* Mtb = nullptr);
 int launch_attn_bwd_small(const float* dM, const float* A, const float* P, const float* nrm, const float* temperature,
@@ -75,10 +102,11 @@ size_t bwd_tail_workspace(int M, int C);
 int launch_bwd_tail(const void* dy, int M, const void* x, int C, const void* dres, const float* mean, const float* rstd,
                     const float* w, const float* gamma, const float* beta, void* dx, float* dw, float* dgamma, float* dbeta,
                     int B, int64_t N, int accumulate, void* ws, hipStream_t st);
-// ---- LDS-tiled 1x1 GEMM for deep K (pw_lds.hip); mi_pw_gemm hands it the shapes pw_lds_ok accepts ----
-bool pw_lds_ok(const mi_pw_desc* d);
-size_t pw_lds_pack_bytes(const mi_pw_desc* d);
-int pw_lds_launch(const mi_pw_desc* d, void* ws, hipStream_t st);
+// ---- LDS-tiled 1x1 GEMM for deep K (pw_lds.hip): the PW_LDS family of pw_plan, which decides where it runs ----
+#define MI_HIDDEN __attribute__((visibility("hidden")))   // (internal: not in the library's dynamic symbol list)
+MI_HIDDEN int pw_lds_tm(int M);                 // its tile height (256 / 128 rows)
+MI_HIDDEN size_t pw_lds_lds_bytes(int tm);      // dynamic LDS of the instance with that tile height
+MI_HIDDEN int pw_lds_launch(const mi_pw_desc* d, const PwPlan& pl, void* ws, hipStream_t st);   // packs its image into ws, then launches
 // ---- fused GDFN forward, training form (fused_gdfn.hip): also writes h0 [B][2h][H][W] and g [B][h][H][W] ----
 int fused_gdfn_fwd_save(const mi_gdfn_fused_shape* s, const void* pack, const void* y, void* out, float* mean, float* rstd,
                         void* h0, void* g, hipStream_t st);

@@ -8,12 +8,14 @@
 // 16-byte copy (measured: per-tile scalar fp32 staging cost more issue slots than everything else in the kernel).
 // The epilogue stages accumulators through LDS and writes whole 128-byte row segments, 16 bytes per lane.
 // bf16 activations use v_mfma_f32_16x16x32_bf16, fp32 activations the exact v_mfma_f32_16x16x4_f32.
-// Kernel families, in the order pw_launch tries them:
-//   pw_gemm_wave_xres / pw_gemm_wave_stream  bf16, rows of whole 64-pixel tiles: weights resident in LDS, every wave streams its own
-//                                            pixel tiles through a private transpose patch - no workgroup barriers (the default)
-//   pw_gemm_res                              bf16, K <= 128: weight-resident persistent workgroups sharing each X chunk (MI_PW_WAVE=0)
-//   pw_gemm                                  any dtype / alignment / ragged pixel counts: chunked through LDS (MI_PW_CHUNKED=1)
-//   pw_gemm_dma                              opt-in LDS-DMA ring (MI_PW_DMA=1)
+// Kernel families (PwFamily, internal.h).  pw_plan alone decides which one runs and with what launch; mi_pw_plan reports it:
+//   PW_XRES / PW_STREAM / PW_XWIDE  pw_gemm_wave_*: bf16, rows of whole 64-pixel tiles: weights resident in LDS (X-wide: X resident, W
+//                                   streamed), every wave streams its own pixel tiles through a private transpose patch - no
+//                                   workgroup barriers (the default)
+//   PW_LDS                          pl_kernel (pw_lds.hip): bf16, deep K where it measured faster (MI_NO_PW_LDS=1 / MI_PW_LDS=all)
+//   PW_RESIDENT                     pw_gemm_res: bf16, K <= 128: weight-resident persistent workgroups sharing each X chunk (MI_PW_WAVE=0)
+//   PW_CHUNKED                      pw_gemm: any dtype / alignment / ragged pixel counts: chunked through LDS (MI_PW_CHUNKED=1)
+//   PW_DMA                          pw_gemm_dma: opt-in LDS-DMA ring (MI_PW_DMA=1)
 #include <stdlib.h>
 
 #include <algorithm>
@@ -648,7 +650,7 @@ __device__ __forceinline__ void pww_stage_weights(bf16* Wl, const bf16* wpk, int
 // Per-image weights (MDTA's project_out . softmax product and its transposes, the q / k gradient matrices) change with every call,
 // so a packed image of them is never reused: with MI_PW_DIRECT=1 the wave-owned kernels read such a matrix straight from fp32 and
 // round it to bf16 on the way into LDS - same values as the pack kernel, one launch less per GEMM, and measured slower (see
-// pw_launch): kept as an A/B switch.  Chunk images [img][tm][WS_ROW], img = mt * nk + kc.
+// pw_plan): kept as an A/B switch.  Chunk images [img][tm][WS_ROW], img = mt * nk + kc.
 __device__ __forceinline__ void pww_stage_weights_f32(bf16* Wl, const float* __restrict__ w, int64_t sm, int64_t sk, int M, int K,
                                                       int mt0, int n_mt, int nk, int tm, int t) {
   constexpr int WS_ROW = PwRow<bf16>::WS_ROW;
@@ -1207,7 +1209,6 @@ __global__ __launch_bounds__(64 * PWW_MW) void pw_gemm_wave_xwide_kernel(PwG q, 
   }
 }
 
-struct PwPlan { int tm, m_tiles, k_chunks, slices, per_batch, per_group, chunk_elems, wave; int64_t slice_elems; size_t bytes; };
 constexpr size_t PWW_LDS_MAX = 160 * 1024;
 
 static bool pw_vec_ok(const mi_pw_desc* d) {
@@ -1217,22 +1218,35 @@ static bool pw_vec_ok(const mi_pw_desc* d) {
   ok = ok && d->y_bs % vec == 0 && d->y_gs % vec == 0 && d->r_bs % vec == 0 && d->r_gs % vec == 0;
   return ok;
 }
+static bool env_off(const char* e) { return e && e[0] == '0'; }
 
-
-static PwPlan pw_plan(const mi_pw_desc* d, bool allow_wave = true) {
-  PwPlan pl;
+// The conditions of the optional features, shared by the checks of mi_pw_gemm and the mi_pw_gemm_*_ok predicates.
+static bool pw_wave_form(const PwPlan& pl) { return pl.family == PW_XRES || pl.family == PW_STREAM || pl.family == PW_XWIDE; }   // (bf16 only)
+// LayerNorm on load: the two X-resident forms; the W-streamed one up to K = 128 only: at K = 129 .. 192 the tile (96 load registers)
+// plus the statistics spill (60 / 252 bytes of scratch per lane) and the separate LayerNorm kernel is the better choice
+static bool pw_ln_form(const PwPlan& pl) { return pl.family == PW_XRES || (pl.family == PW_XWIDE && pl.k_chunks <= 4); }
+// What one call runs (PwPlan, internal.h).  The ONE place that decides it, and the only reader of the MI_PW_* / MI_NO_PW_LDS /
+// MI_PW_LDS switches (each read once): mi_pw_gemm launches what it says, the mi_pw_gemm_*_ok predicates and
+// mi_pw_gemm_workspace ask it, mi_pw_plan reports it.  Pointers are read for their alignment only.  assume_unaligned: the plan
+// of the same call with pointers that are not 16-byte aligned (workspaces are sized before the pointers exist).
+static PwPlan pw_plan(const mi_pw_desc* d, bool assume_unaligned = false) {
+  PwPlan pl{};
+  const bool bf = d->dtype == MI_BF16, dma = MI_ENV(MI_PW_DMA) != nullptr, chunked = MI_ENV(MI_PW_CHUNKED) != nullptr;
+  const int ktot = d->k1 + d->k2;
+  const size_t es = dtype_size(d->dtype), row = PwRow<bf16>::WS_ROW * sizeof(bf16), patches = (size_t)PWW_MW * PWW_PATCH * sizeof(bf16);
+  pl.vec_ok = !assume_unaligned && pw_vec_ok(d);
+  pl.f8 = d->f8 != 0;
+  pl.k_chunks = cdiv(ktot, PW_KC);
   // m-tile 128 when its padding stays within 25% of the 64-granular minimum, else 64.  (256-row tiles measured 5-8%
   // slower on the wide GDFN shapes: fewer resident workgroups; profiles/r01_n_pw_tile_staging_ab.log)
   // m-tile: every m-tile streams all of X again and writes its (padded) rows of Y, so the rows moved per pixel are
   // m_tiles * (K + tm); 96- and 48-row tiles keep 96- / 48- / 144- / 288-channel matrices from being padded by a third
   // (ties go to the larger tile; the LDS-DMA kernel only has 64 / 128).
   {
-    const bool dma = MI_ENV(MI_PW_DMA) != nullptr || MI_ENV(MI_PW_TM_EVEN) != nullptr;   // (the latter: A/B switch)
-    const int ktot = d->k1 + d->k2;
+    const bool even = dma || MI_ENV(MI_PW_TM_EVEN) != nullptr;   // (the latter: A/B switch)
     int64_t best_cost = 0;
-    pl.tm = 0;
     for (int tm : {128, 96, 64, 48}) {
-      if (dma && (tm == 96 || tm == 48)) continue;
+      if (even && (tm == 96 || tm == 48)) continue;
       // the uneven tiles only where they fit exactly (M = 48 / 96 / 288): a half-empty 96-row tile measured slower than
       // the 64-row tiling it would replace (M = 144: 291 vs 268 us; profiles/r01_zz_pw_tm96_bs32.log)
       if (tm == 96 && !(d->m <= 96 || d->m % 96 == 0)) continue;
@@ -1241,56 +1255,129 @@ static PwPlan pw_plan(const mi_pw_desc* d, bool allow_wave = true) {
       if (!pl.tm || cost < best_cost) { pl.tm = tm; best_cost = cost; }
     }
   }
-  pl.k_chunks = cdiv(d->k1 + d->k2, PW_KC);
-  // wave-owned forms (1: xres, 2: stream) where their LDS budget holds; they fix the packed tile height
-  pl.wave = 0;
-  {
-    const char* e = MI_ENV(MI_PW_WAVE);
-    const bool off = (e && e[0] == '0') || MI_ENV(MI_PW_DMA) || MI_ENV(MI_PW_CHUNKED);
-    if (allow_wave && !off && d->dtype == MI_BF16 && d->n % PW_TN == 0 && pw_vec_ok(d)) {
-      const size_t patches = (size_t)PWW_MW * PWW_PATCH * sizeof(bf16), row = PwRow<bf16>::WS_ROW * sizeof(bf16);
-      const char* xw = MI_ENV(MI_PW_XWIDE);                          // A/B switch
-      if (d->m > 96 && pl.k_chunks <= 3 && (size_t)pl.k_chunks * cdiv(d->m, 64) * 64 * row + patches + 768 <= PWW_LDS_MAX) {
-        pl.wave = 1; pl.tm = 64;
-      } else if (d->m >= 256 && pl.k_chunks >= 4 && pl.k_chunks <= 6 && !(xw && xw[0] == '0')) {   // (192 x 192 measured better on the streaming form)
-        pl.wave = 3; pl.tm = 64;                                       // X-resident, W streamed (K = 97 .. 192, wide outputs)
-      } else {
-        // stream: one 96- / 64- / 48-channel tile per workgroup; wide outputs tile M (every tile streams X again, like the
-        // chunked kernel), preferring the tile height that moves the fewest rows and fits beside the patches
-        int best = 0;
-        int64_t best_cost = 0;
-        for (int tm : {96, 64, 48}) {
-          if (d->m <= 48 && tm != 48) continue;
-          if (d->m <= 64 && tm == 96) continue;
-          if ((size_t)pl.k_chunks * tm * row + patches > PWW_LDS_MAX) continue;
-          const int64_t cost = (int64_t)cdiv(d->m, tm) * (d->k1 + d->k2 + tm);
-          if (!best || cost < best_cost) { best = tm; best_cost = cost; }
-        }
-        const char* w = MI_ENV(MI_PW_WAVE_WIDE);
-        if (best && (d->m <= 96 || !(w && w[0] == '0'))) { pl.wave = 2; pl.tm = best; }
+  // ---- the family.  Wave-owned forms where their LDS budget holds (they fix the packed tile height) ...
+  pl.family = PW_CHUNKED;
+  if (pl.vec_ok && bf && d->n % PW_TN == 0 && !env_off(MI_ENV(MI_PW_WAVE)) && !dma && !chunked) {
+    if (d->m > 96 && pl.k_chunks <= 3 && (size_t)pl.k_chunks * cdiv(d->m, 64) * 64 * row + patches + 768 <= PWW_LDS_MAX) {
+      pl.family = PW_XRES; pl.tm = 64;
+    } else if (d->m >= 256 && pl.k_chunks >= 4 && pl.k_chunks <= 6 && !env_off(MI_ENV(MI_PW_XWIDE))) {   // (192 x 192 measured better on the streaming form)
+      pl.family = PW_XWIDE; pl.tm = 64;                              // X-resident, W streamed (K = 97 .. 192, wide outputs)
+    } else {
+      // stream: one 96- / 64- / 48-channel tile per workgroup; wide outputs tile M (every tile streams X again, like the
+      // chunked kernel), preferring the tile height that moves the fewest rows and fits beside the patches
+      int best = 0;
+      int64_t best_cost = 0;
+      for (int tm : {96, 64, 48}) {
+        if (d->m <= 48 && tm != 48) continue;
+        if (d->m <= 64 && tm == 96) continue;
+        if ((size_t)pl.k_chunks * tm * row + patches > PWW_LDS_MAX) continue;
+        const int64_t cost = (int64_t)cdiv(d->m, tm) * (ktot + tm);
+        if (!best || cost < best_cost) { best = tm; best_cost = cost; }
       }
+      if (best && (d->m <= 96 || !env_off(MI_ENV(MI_PW_WAVE_WIDE)))) { pl.family = PW_STREAM; pl.tm = best; }
     }
   }
+  // ... else, for 16-byte rows, the LDS-DMA ring (opt-in: it measured 5-12% SLOWER than register staging on every Restormer shape - K
+  // is 2-16 chunks, so the per-tile prologue and epilogue dominate and its 3 x chunk LDS footprint halves the resident workgroups; it
+  // stays as the base of a persistent cross-tile pipeline) or the weight-resident persistent kernel (bf16, K <= 128; M <= 64 stays
+  // chunked: 48 x 48 is a tie and 48 x 127 loses 13%; profiles/r01_y_pw_resident_bs32.log).  Things that did NOT help the chunked
+  // kernel beyond the Infinity Cache (bs 32; profiles/r01_v_pw_*bs32*.log): a 128 x 128 tile, also persistent and cross-tile
+  // pipelined (-10..25%: 2-3 resident workgroups per CU instead of 5); two chunks of prefetch (-3..10%); an XCD-aware tile map
+  // running the m-tiles of a pixel tile together on one L2 (-15..35%: 4x more channel rows over 4x narrower pixel spans in flight).
+  if (pl.family == PW_CHUNKED && pl.vec_ok) {
+    if (dma) pl.family = PW_DMA;
+    else if (bf && pl.k_chunks <= PWR_MAXC && d->m > 64 && !chunked) pl.family = PW_RESIDENT;
+  }
+  // ---- the pw_pack image of that tile height
   pl.m_tiles = cdiv(d->m, pl.tm);
-  pl.per_batch = d->w_bs != 0;
-  pl.per_group = d->w_gs != 0;
+  pl.per_batch = d->w_bs != 0; pl.per_group = d->w_gs != 0;
   pl.slices = (pl.per_batch ? d->batch : 1) * (pl.per_group ? d->groups : 1);
-  const int ws_row = d->dtype == MI_F32 ? PwRow<float>::WS_ROW : PwRow<bf16>::WS_ROW;
-  const size_t es = dtype_size(d->dtype);
-  pl.chunk_elems = (int)(align_up((size_t)pl.tm * ws_row * es, 4096) / es);
+  pl.chunk_elems = (int)(align_up((size_t)pl.tm * (bf ? PwRow<bf16>::WS_ROW : PwRow<float>::WS_ROW) * es, 4096) / es);
   pl.slice_elems = (int64_t)pl.m_tiles * pl.k_chunks * pl.chunk_elems;
   pl.bytes = align_up(PW_ZERO_BYTES + (size_t)pl.slices * pl.slice_elems * es, 256);
+  // ---- the LDS-tiled kernel (pw_lds.hip) takes over: bf16, one X operand, static weights, no LayerNorm head / fp8 / split
+  // output, deep K, enough rows to fill the 128-row tiles, 16-byte aligned pixel rows.  Where it wins
+  // (profiles/r03_s_pw_lds_deep_gemm.txt, bs 32, incl. its pack launch): very wide outputs of a deep K (384 -> 2042 / 1021: 1.42x)
+  // and deep K into few rows (1020 / 576 -> 192: 1.3-1.6x).  Elsewhere the wave-owned kernels hold 430-530 TFLOP/s and stay
+  // (MI_PW_LDS=all takes every covered shape: tests, A/B).  Its image is sized wherever dtype and depth could reach it: switches
+  // and pointers may differ between the sizing of a workspace and the call.
+  if (bf && d->k1 > 128) {
+    const int ltm = pw_lds_tm(d->m);
+    pl.lds_image = (size_t)cdiv(d->m, ltm) * cdiv(d->k1, 64) * ltm * 64 * 2;
+    const char* all = MI_ENV(MI_PW_LDS);
+    bool ok = !MI_ENV(MI_NO_PW_LDS) && !assume_unaligned && d->k2 == 0 && d->groups == 1 && d->w_bs == 0 && d->ln_mode == 0 && !d->f8 && !d->y2;
+    ok = ok && d->m >= 128 && d->n % 8 == 0 && d->n >= 256;
+    ok = ok && ((all && all[0] == 'a') || (d->k1 >= 320 && d->m >= 1000) || (d->k1 >= 560 && d->m <= 256));
+    ok = ok && aligned16(d->x1) && aligned16(d->y) && d->x1_bs % 8 == 0 && d->y_bs % 8 == 0 && (!d->r || (aligned16(d->r) && d->r_bs % 8 == 0));
+    if (ok) { pl.family = PW_LDS; pl.tm = ltm; pl.m_tiles = cdiv(d->m, ltm); pl.k_chunks = cdiv(d->k1, 64); }
+  }
+  pl.ln = d->ln_mode != 0 && pw_ln_form(pl);
+  // ---- the launch
+  const unsigned Z = (unsigned)(d->batch * d->groups);
+  const int64_t n_tiles = cdiv(d->n, PW_TN);
+  pl.grid = dim3((unsigned)n_tiles, pl.m_tiles, Z);
+  pl.block = dim3(256);
+  switch (pl.family) {
+    case PW_LDS:
+      pl.grid = dim3(pl.m_tiles, (unsigned)cdiv(d->n, 256), (unsigned)d->batch);
+      pl.block = dim3(2 * pl.tm);
+      pl.lds = pw_lds_lds_bytes(pl.tm);
+      break;
+    case PW_DMA: pl.lds = 3 * (PW_KC * PW_TN + (size_t)pl.chunk_elems) * es; break;
+    case PW_RESIDENT: {
+      const int xbuf = std::max(PWR_MAXC * PW_KC * PW_XS, 4 * 16 * (PW_TN + 4) * 2);
+      pl.lds = ((size_t)pl.k_chunks * pl.tm * PwRow<bf16>::WS_ROW + xbuf) * sizeof(bf16);
+      // pixel tiles per workgroup: enough to amortise the weight load, while >= 2048 workgroups remain
+      int64_t tpb = n_tiles * pl.m_tiles * Z / 2048;
+      if (const char* e = MI_ENV(MI_PW_TPB)) tpb = atoi(e);
+      pl.tpb = (int)std::min<int64_t>(std::max<int64_t>(tpb, 1), 32);
+      pl.grid.x = (unsigned)cdiv(n_tiles, pl.tpb);
+      break;
+    }
+    case PW_XRES: case PW_STREAM: case PW_XWIDE: {
+      const size_t ln_bytes = d->ln_mode ? (size_t)2 * pl.k_chunks * PW_KC * sizeof(float) : 0;
+      const size_t wbytes = (size_t)(pl.family == PW_XRES ? pl.m_tiles : 1) * pl.k_chunks * pl.tm * row;
+      const int my = pl.family == PW_STREAM ? pl.m_tiles : 1;
+      // pixel tiles per wave: 2, or 4 to amortise a weight image near the LDS limit (510 x 96 at 256^2, bs 32: 535 vs 565 us;
+      // the smaller images lose 2-3% at 4), while at least ~4 workgroups per CU remain
+      int64_t tpw = std::min<int64_t>(wbytes > 96 * 1024 ? 4 : 2, n_tiles * Z * my / ((int64_t)PWW_MW * 256 * 4));
+      if (const char* e = MI_ENV(MI_PW_WAVE_TPW)) tpw = atoi(e);
+      pl.tpw = (int)std::min<int64_t>(std::max<int64_t>(tpw, 1), 8);
+      pl.block = dim3(64 * PWW_MW);
+      pl.grid = dim3((unsigned)cdiv(n_tiles, (int64_t)pl.tpw * PWW_MW), my, Z);
+      pl.lds = wbytes + patches + ln_bytes;
+      if (pl.family == PW_XWIDE) {                                    // one 64-pixel tile per wave; M split only to fill the chip
+        pl.grid.x = (unsigned)cdiv(n_tiles, PWW_MW);
+        pl.n_slabs = cdiv(d->m, PWX_SR);
+        const int64_t wgs = (int64_t)pl.grid.x * Z;
+        const int64_t split = wgs >= 200 ? 1 : std::min<int64_t>(pl.n_slabs, cdiv(256, wgs));
+        pl.slabs_per = cdiv(pl.n_slabs, split);
+        pl.grid.y = (unsigned)cdiv(pl.n_slabs, pl.slabs_per);
+        pl.lds = (size_t)2 * pl.k_chunks * PWX_SR * row + patches + ln_bytes;
+      }
+      const char* e = MI_ENV(MI_PW_XCD);                             // A/B switch
+      const int min_tiles = e ? atoi(e) : 0;   // off by default: measured no gain (profiles/r02_i_pw_xcd_map_ab.txt)
+      const uint64_t total = (uint64_t)pl.grid.x * pl.grid.y * pl.grid.z;
+      pl.xcd_map = pl.family == PW_STREAM && min_tiles > 0 && (int)pl.grid.y >= min_tiles && total % 8 == 0 && total < (1ull << 31);
+      break;
+    }
+    default: break;                                                   // chunked: static LDS
+  }
+  // ---- where the weights come from.  Static weights: a packed image, this call's own or the cache's.  Per-image weights on a
+  // wave-owned form may skip the pack launch: MI_PW_DIRECT=1 (A/B switch, off) stages them from fp32 inside the kernel - measured
+  // SLOWER (profiles/r02_m_per_image_weights_direct_ab.txt: 165.0 vs 157.2 ms per step): every one of the ~2000 workgroups of such
+  // a GEMM repeats the scalar fp32 -> bf16 walk that one 7 us pack launch does once.  Round 4: a producer that also wrote the
+  // matrices in bf16 (mi_pw_desc.w_b16) makes the direct staging free - 16-byte copies, as the packed path's own staging - and the
+  // pack launch (183 per training step) goes away.  MI_PW_B16=0 keeps the pack.
+  if (pw_wave_form(pl) && d->w_bs != 0) {
+    const char* b = MI_ENV(MI_PW_B16);
+    if (d->w_b16 && aligned16(d->w_b16) && d->w_b16_sm % 8 == 0 && d->w_bs % 8 == 0 && d->w_gs % 8 == 0 && ktot % 8 == 0 && !d->f8 &&
+        !(b && atoi(b) == 0))
+      pl.weights = PW_W_B16;
+    else if (MI_ENV(MI_PW_DIRECT)) pl.weights = PW_W_F32;
+  }
+  pl.cacheable = pl.weights == PW_W_PACK && pl.family != PW_LDS && !pl.per_batch;
   return pl;
-}
-
-template <typename T, int MF>
-static int pw_launch_dma(const PwG& q, dim3 grid, hipStream_t st) {
-  using IM = PwImg<T, 64 * MF>;
-  constexpr int lds = 3 * (PW_KC * PW_TN * (int)sizeof(T) + IM::W_PAD);
-  if (lds > 64 * 1024)
-    MI_CHECK_HIP(hipFuncSetAttribute((const void*)pw_gemm_dma_kernel<T, MF>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-  hipLaunchKernelGGL((pw_gemm_dma_kernel<T, MF>), grid, dim3(256), lds, st, q);
-  return MI_OK;
 }
 
 // ---- opt-in packed-weight cache (mi_pw_cache_*) -----------------------------------------------------------------------------
@@ -1337,171 +1424,6 @@ static const unsigned char* pw_cache_lookup(const PackJob& j, size_t image_bytes
   return nullptr;
 }
 
-template <typename T>
-static int pw_launch(const mi_pw_desc* d, const PwK& k, const PwPlan& pl, void* ws, hipStream_t st) {
-  PackJob job;
-  job.w = d->w; job.w_bs = d->w_bs; job.w_gs = d->w_gs; job.w_sm = d->w_sm; job.w_sk = d->w_sk;
-  job.ws = (unsigned char*)ws;
-  job.M = d->m; job.K = d->k1 + d->k2; job.tm = pl.tm; job.k_chunks = pl.k_chunks;
-  job.groups_w = pl.per_group ? d->groups : 1; job.chunk_elems = pl.chunk_elems; job.m_fast = d->w_sk != 1 ? 1 : 0;
-  job.dtype = d->dtype; job.slices = pl.slices; job.slice_elems = pl.slice_elems;
-  // MI_PW_DIRECT=1 (A/B switch, off): per-image weights on a wave-owned form without a packed image - the kernels stage them from
-  // fp32.  Measured SLOWER (profiles/r02_m_per_image_weights_direct_ab.txt: 165.0 vs 157.2 ms per step): every one of the ~2000
-  // workgroups of such a GEMM repeats the scalar fp32 -> bf16 walk that one 7 us pack launch does once.
-  // Round 4: a producer that also wrote the matrices in bf16 (mi_pw_desc.w_b16) makes the direct staging free - 16-byte copies, as
-  // the packed path's own staging - and the pack launch (183 per training step) goes away.  MI_PW_B16=0 keeps the pack.
-  const bool b16ok = pl.wave != 0 && d->w_bs != 0 && std::is_same<T, bf16>::value && d->w_b16 && aligned16(d->w_b16) &&
-                     d->w_b16_sm % 8 == 0 && d->w_bs % 8 == 0 && d->w_gs % 8 == 0 && (d->k1 + d->k2) % 8 == 0 && !d->f8 &&
-                     !(MI_ENV(MI_PW_B16) && atoi(MI_ENV(MI_PW_B16)) == 0);
-  const bool direct = b16ok || (pl.wave != 0 && d->w_bs != 0 && std::is_same<T, bf16>::value && MI_ENV(MI_PW_DIRECT));
-  const unsigned char* cached = direct ? nullptr : pw_cache_lookup(job, pl.bytes, st);
-  if (!cached && !direct) {  // re-pack the weights of every slice (and refresh the zero block)
-    const int64_t total = (int64_t)pl.m_tiles * pl.k_chunks * pl.tm * PW_KC;
-    int gx = cdiv(total, 256);
-    if (gx > 1024) gx = 1024;
-    ProfScope ps(st, K_PW_PACK, 4.0 * d->m * (d->k1 + d->k2) * pl.slices + (double)pl.bytes, 0.0);
-    hipLaunchKernelGGL((pw_pack_kernel<T>), dim3(gx, pl.slices), dim3(256), 0, st, job);
-    MI_LAUNCH_CHECK();
-  }
-  PwG q;
-  q.k = k; q.ws = cached ? cached : (const unsigned char*)ws; q.wp_slice = pl.slice_elems; q.wp_per_batch = pl.per_batch;
-  q.wp_per_group = pl.per_group; q.k_chunks = pl.k_chunks;
-  q.ln_w = d->ln_w; q.ln_b = d->ln_b; q.ln_mean = d->ln_mean; q.ln_rstd = d->ln_rstd; q.ln_mode = d->ln_mode;
-  q.f8_sx = d->f8_sx; q.f8_sw = d->f8_sw;
-  q.xcd_map = 0;
-  q.w_direct = direct ? 1 : 0;
-  q.wb16 = b16ok ? (const bf16*)d->w_b16 : nullptr; q.wb16_sm = d->w_b16_sm;
-  if (d->y_split) {
-    MI_CHECK_ARG(pl.wave != 0 && (std::is_same<T, bf16>::value), "pw_gemm: a split output needs a wave-owned bf16 form (mi_pw_gemm_split_ok)");
-    MI_CHECK_ARG(d->y2 && !d->r && d->y_split > 0 && d->y_split < d->m && aligned16(d->y2) && d->y2_bs % 8 == 0 && d->y2_gs % 8 == 0,
-                 "pw_gemm: split output: y2 (16-byte aligned), 0 < y_split < m, no residual");
-  }
-  if (d->f8) {
-    MI_CHECK_ARG(pl.wave != 0 && (std::is_same<T, bf16>::value), "pw_gemm: fp8 operands need a wave-owned bf16 form (mi_pw_gemm_f8_ok)");
-    MI_CHECK_ARG(d->f8_sx > 0.f && d->f8_sw > 0.f, "pw_gemm: fp8 operand scales must be positive (powers of two)");
-  }
-  if (d->ln_mode) {
-    MI_CHECK_ARG((pl.wave == 1 || (pl.wave == 3 && pl.k_chunks <= 4)) && d->k2 == 0 && d->groups == 1 && d->ln_w && (d->ln_mode == 2 || d->ln_b) &&
-                     (d->ln_mode == 1 || d->ln_mode == 2) && (d->ln_mean == nullptr) == (d->ln_rstd == nullptr),
-                 "pw_gemm: LayerNorm-on-load needs an X-resident form (bf16; 96 < M with K <= 96, or 256 <= M with K <= 128; one K panel, one group; "
-                 "mi_pw_gemm_ln_ok)");
-  }
-  dim3 grid(cdiv(k.n, PW_TN), pl.m_tiles, d->batch * k.groups), block(256);
-  if (grid.y > 65535 || grid.z > 65535) { set_error("pw_gemm: grid too large"); return MI_ERR_ARG; }
-  const double Z = (double)d->batch * k.groups, kt = k.k1 + k.k2;
-  // the forward attention product  out = M_b . v (+ x): per-image weights, one group, not transposed (modules.hip attn_core_fwd)
-  const bool is_av = d->w_bs != 0 && k.groups == 1 && d->w_sk == 1 && k.r != nullptr;
-  ProfScope ps(st, is_av ? K_PW_AV : K_PW_GEMM, (kt + k.m + (k.r ? k.m : 0)) * (double)k.n * Z * sizeof(T) + 4.0 * k.m * kt,
-               2.0 * k.m * kt * (double)k.n * Z);
-  // The LDS-DMA ring measured 5-12% SLOWER than register staging on every Restormer shape (K is 2-16 chunks, so the
-  // per-tile prologue and epilogue dominate and its 3 x chunk LDS footprint halves the resident workgroups).  It stays
-  // opt-in (MI_PW_DMA=1) as the base of a persistent cross-tile pipeline; tests run it through the same parity cases.
-  const bool dma = MI_ENV(MI_PW_DMA) != nullptr;
-  if (pl.wave) {
-    if constexpr (std::is_same<T, bf16>::value) {
-      const int64_t n_tiles = k.n / PW_TN;
-      const size_t row = PwRow<bf16>::WS_ROW * sizeof(bf16), patches = (size_t)PWW_MW * PWW_PATCH * sizeof(bf16);
-      const size_t wbytes = (size_t)(pl.wave == 1 ? pl.m_tiles : 1) * pl.k_chunks * pl.tm * row;
-      // pixel tiles per wave: 2, or 4 to amortise a weight image near the LDS limit (510 x 96 at 256^2, bs 32: 535 vs 565 us;
-      // the smaller images lose 2-3% at 4), while at least ~4 workgroups per CU remain
-      int64_t tpw = wbytes > 96 * 1024 ? 4 : 2;
-      const int64_t par = n_tiles * grid.z * (pl.wave == 2 ? pl.m_tiles : 1) / ((int64_t)PWW_MW * 256 * 4);
-      if (tpw > par) tpw = par;
-      if (const char* e = MI_ENV(MI_PW_WAVE_TPW)) tpw = atoi(e);
-      if (tpw < 1) tpw = 1;
-      if (tpw > 8) tpw = 8;
-      dim3 wgrid((unsigned)cdiv(n_tiles, tpw * PWW_MW), pl.wave == 2 ? pl.m_tiles : 1, grid.z), wblock(64 * PWW_MW);
-      size_t lds = wbytes + patches + (d->ln_mode ? (size_t)2 * pl.k_chunks * PW_KC * sizeof(float) : 0);
-      int n_slabs = 0, slabs_per = 0;
-      if (pl.wave == 3) {                                              // one 64-pixel tile per wave; M split only to fill the chip
-        const int sr = PWX_SR;
-        wgrid.x = (unsigned)cdiv(n_tiles, PWW_MW);
-        n_slabs = cdiv(d->m, sr);
-        const int64_t wgs = (int64_t)wgrid.x * grid.z;
-        const int64_t split = wgs >= 200 ? 1 : std::min<int64_t>(n_slabs, cdiv(256, wgs));
-        slabs_per = (int)cdiv(n_slabs, split);
-        wgrid.y = (unsigned)cdiv(n_slabs, slabs_per);
-        lds = (size_t)2 * pl.k_chunks * sr * row + patches + (d->ln_mode ? (size_t)2 * pl.k_chunks * PW_KC * sizeof(float) : 0);
-      }
-      {
-        const char* e = MI_ENV(MI_PW_XCD);                           // A/B switch
-        const int min_tiles = e ? atoi(e) : 0;   // off by default: measured no gain (profiles/r02_i_pw_xcd_map_ab.txt)
-        const uint64_t total = (uint64_t)wgrid.x * wgrid.y * wgrid.z;
-        q.xcd_map = (pl.wave == 2 && min_tiles > 0 && (int)wgrid.y >= min_tiles && total % 8 == 0 && total < (1ull << 31)) ? 1 : 0;
-      }
-#define PWW_LAUNCH(KERNEL, ...)                                                                                              \
-  do {                                                                                                                       \
-    if (lds > 64 * 1024) MI_CHECK_HIP(hipFuncSetAttribute((const void*)KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
-    hipLaunchKernelGGL(KERNEL, wgrid, wblock, lds, st, q, __VA_ARGS__);                                                      \
-  } while (0)
-      if (pl.wave == 3) {
-#define PWX_CASE(KB_, LNOK_)                                                                                                   \
-  if (pl.k_chunks == KB_) {                                                                                                    \
-    if (LNOK_ && d->f8 && d->ln_mode) PWW_LAUNCH((pw_gemm_wave_xwide_kernel<KB_, true, LNOK_>), n_slabs, slabs_per, pl.chunk_elems);  \
-    else if (d->f8) PWW_LAUNCH((pw_gemm_wave_xwide_kernel<KB_, true, false>), n_slabs, slabs_per, pl.chunk_elems);             \
-    else if (LNOK_ && d->ln_mode) PWW_LAUNCH((pw_gemm_wave_xwide_kernel<KB_, false, LNOK_>), n_slabs, slabs_per, pl.chunk_elems);     \
-    else PWW_LAUNCH((pw_gemm_wave_xwide_kernel<KB_, false, false>), n_slabs, slabs_per, pl.chunk_elems);                       \
-  }
-        PWX_CASE(4, true) else PWX_CASE(5, false) else PWX_CASE(6, false)
-#undef PWX_CASE
-      } else if (pl.wave == 1 && !d->f8) {
-        if (pl.k_chunks == 1) PWW_LAUNCH((pw_gemm_wave_xres_kernel<1, false>), pl.m_tiles, (int)tpw, pl.chunk_elems);
-        else if (pl.k_chunks == 2) PWW_LAUNCH((pw_gemm_wave_xres_kernel<2, false>), pl.m_tiles, (int)tpw, pl.chunk_elems);
-        else PWW_LAUNCH((pw_gemm_wave_xres_kernel<3, false>), pl.m_tiles, (int)tpw, pl.chunk_elems);
-      } else if (pl.wave == 1) {
-        if (pl.k_chunks == 1) PWW_LAUNCH((pw_gemm_wave_xres_kernel<1, true>), pl.m_tiles, (int)tpw, pl.chunk_elems);
-        else if (pl.k_chunks == 2) PWW_LAUNCH((pw_gemm_wave_xres_kernel<2, true>), pl.m_tiles, (int)tpw, pl.chunk_elems);
-        else PWW_LAUNCH((pw_gemm_wave_xres_kernel<3, true>), pl.m_tiles, (int)tpw, pl.chunk_elems);
-      } else if (!d->f8) {
-        if (pl.tm == 96) PWW_LAUNCH((pw_gemm_wave_stream_kernel<6, false>), (int)tpw, pl.chunk_elems);
-        else if (pl.tm == 64) PWW_LAUNCH((pw_gemm_wave_stream_kernel<4, false>), (int)tpw, pl.chunk_elems);
-        else PWW_LAUNCH((pw_gemm_wave_stream_kernel<3, false>), (int)tpw, pl.chunk_elems);
-      } else {
-        if (pl.tm == 96) PWW_LAUNCH((pw_gemm_wave_stream_kernel<6, true>), (int)tpw, pl.chunk_elems);
-        else if (pl.tm == 64) PWW_LAUNCH((pw_gemm_wave_stream_kernel<4, true>), (int)tpw, pl.chunk_elems);
-        else PWW_LAUNCH((pw_gemm_wave_stream_kernel<3, true>), (int)tpw, pl.chunk_elems);
-      }
-#undef PWW_LAUNCH
-    }
-  } else if (k.vec_ok && dma) {
-    if (pl.tm == 128) MI_TRY((pw_launch_dma<T, 2>(q, grid, st)));
-    else MI_TRY((pw_launch_dma<T, 1>(q, grid, st)));
-  } else if (std::is_same<T, bf16>::value && k.vec_ok && pl.k_chunks <= PWR_MAXC && k.m > 64 && !MI_ENV(MI_PW_CHUNKED)) {
-    // (M <= 64 stays chunked: 48 x 48 is a tie and 48 x 127 loses 13%; profiles/r01_y_pw_resident_bs32.log)
-    // weight-resident persistent kernel (K <= 128).  Things that did NOT help the chunked kernel beyond the Infinity Cache
-    // (bs 32; profiles/r01_v_pw_*bs32*.log): a 128 x 128 tile, also persistent and cross-tile pipelined (-10..25%: 2-3
-    // resident workgroups per CU instead of 5); two chunks of prefetch (-3..10%); an XCD-aware tile map running the
-    // m-tiles of a pixel tile together on one L2 (-15..35%: 4x more channel rows over 4x narrower pixel spans in flight).
-    const int n_tiles = (int)cdiv(k.n, PW_TN);
-    const int wc = pl.tm * PwRow<bf16>::WS_ROW;
-    const int xbuf = std::max(PWR_MAXC * PW_KC * PW_XS, 4 * 16 * (PW_TN + 4) * 2);
-    const size_t lds = ((size_t)pl.k_chunks * wc + xbuf) * sizeof(bf16);
-    // pixel tiles per workgroup: enough to amortise the weight load, while >= 2048 workgroups remain
-    int64_t tpb = (int64_t)n_tiles * pl.m_tiles * grid.z / 2048;
-    if (const char* e = MI_ENV(MI_PW_TPB)) tpb = atoi(e);
-    if (tpb < 1) tpb = 1;
-    if (tpb > 32) tpb = 32;
-    dim3 rgrid((unsigned)cdiv(n_tiles, tpb), pl.m_tiles, grid.z);
-    if (pl.tm == 128) {
-      if (lds > 64 * 1024) MI_CHECK_HIP(hipFuncSetAttribute((const void*)pw_gemm_res_kernel<2, 128>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-      hipLaunchKernelGGL((pw_gemm_res_kernel<2, 128>), rgrid, block, lds, st, q, n_tiles, pl.chunk_elems);
-    } else if (pl.tm == 96) {
-      hipLaunchKernelGGL((pw_gemm_res_kernel<2, 96>), rgrid, block, lds, st, q, n_tiles, pl.chunk_elems);
-    } else if (pl.tm == 64) {
-      hipLaunchKernelGGL((pw_gemm_res_kernel<1, 64>), rgrid, block, lds, st, q, n_tiles, pl.chunk_elems);
-    } else {
-      hipLaunchKernelGGL((pw_gemm_res_kernel<1, 48>), rgrid, block, lds, st, q, n_tiles, pl.chunk_elems);
-    }
-  } else {
-    if (pl.tm == 128) hipLaunchKernelGGL((pw_gemm_kernel<T, 2, 128>), grid, block, 0, st, q);
-    else if (pl.tm == 96) hipLaunchKernelGGL((pw_gemm_kernel<T, 2, 96>), grid, block, 0, st, q);
-    else if (pl.tm == 64) hipLaunchKernelGGL((pw_gemm_kernel<T, 1, 64>), grid, block, 0, st, q);
-    else hipLaunchKernelGGL((pw_gemm_kernel<T, 1, 48>), grid, block, 0, st, q);
-  }
-  MI_LAUNCH_CHECK();
-  return MI_OK;
-}
-
 static int pw_check(const mi_pw_desc* d) {
   MI_CHECK_ARG(d && d->x1 && d->w && d->y, "pw_gemm: null pointer");
   MI_CHECK_ARG(d->m > 0 && d->n > 0 && d->k1 > 0 && d->k2 >= 0 && d->batch > 0 && d->groups > 0, "pw_gemm: bad shape");
@@ -1510,56 +1432,182 @@ static int pw_check(const mi_pw_desc* d) {
   return MI_OK;
 }
 
-}  // namespace mi
-
-using namespace mi;
-
-extern "C" size_t mi_pw_gemm_workspace(const mi_pw_desc* d) {
-  if (!d || d->m <= 0 || d->k1 <= 0 || d->k2 < 0 || d->batch <= 0 || d->groups <= 0) return 0;
-  // the wave-owned forms tile the packed image differently; which form runs depends on pointer alignment at call time, and module
-  // entry points size their workspaces before they see the pointers: cover both
-  const size_t a = pw_plan(d).bytes, b = pw_plan(d, false).bytes;
-  const size_t c = (d->dtype == MI_BF16 && d->k1 > 128) ? align_up(pw_lds_pack_bytes(d), 256) : 0;   // the LDS-tiled kernel's image
-  const size_t ab = a > b ? a : b;
-  return ab > c ? ab : c;
+// The features the descriptor asks for against the plan, before anything is launched.  (The LDS-tiled family is only planned
+// for descriptors without them.)
+static int pw_validate(const mi_pw_desc* d, const PwPlan& pl) {
+  if (pl.family == PW_LDS) {
+    MI_CHECK_ARG(pl.grid.y <= 65535 && pl.grid.z <= 65535, "pw_gemm: grid too large");
+    return MI_OK;
+  }
+  if (d->y_split) {
+    MI_CHECK_ARG(pw_wave_form(pl), "pw_gemm: a split output needs a wave-owned bf16 form (mi_pw_gemm_split_ok)");
+    MI_CHECK_ARG(d->y2 && !d->r && d->y_split > 0 && d->y_split < d->m && aligned16(d->y2) && d->y2_bs % 8 == 0 && d->y2_gs % 8 == 0,
+                 "pw_gemm: split output: y2 (16-byte aligned), 0 < y_split < m, no residual");
+  }
+  if (d->f8) {
+    MI_CHECK_ARG(pw_wave_form(pl), "pw_gemm: fp8 operands need a wave-owned bf16 form (mi_pw_gemm_f8_ok)");
+    MI_CHECK_ARG(d->f8_sx > 0.f && d->f8_sw > 0.f, "pw_gemm: fp8 operand scales must be positive (powers of two)");
+  }
+  if (d->ln_mode) {
+    MI_CHECK_ARG(pw_ln_form(pl) && d->k2 == 0 && d->groups == 1 && d->ln_w && (d->ln_mode == 2 || d->ln_b) &&
+                     (d->ln_mode == 1 || d->ln_mode == 2) && (d->ln_mean == nullptr) == (d->ln_rstd == nullptr),
+                 "pw_gemm: LayerNorm-on-load needs an X-resident form (bf16; 96 < M with K <= 96, or 256 <= M with K <= 128; one K panel, one group; "
+                 "mi_pw_gemm_ln_ok)");
+  }
+  MI_CHECK_ARG(pl.m_tiles <= 65535 && pl.grid.z <= 65535, "pw_gemm: grid too large");
+  return MI_OK;
 }
 
-extern "C" int mi_pw_gemm(const mi_pw_desc* d, void* ws, void* stream) {
-  MI_TRY(pw_check(d));
-  MI_CHECK_ARG(ws && aligned16(ws), "pw_gemm: workspace missing or not 16-byte aligned");
-  if (pw_lds_ok(d)) return pw_lds_launch(d, ws, (hipStream_t)stream);     // deep K: the LDS-tiled kernel (pw_lds.hip)
-  PwK k;
+static PackJob pw_pack_job(const mi_pw_desc* d, const PwPlan& pl, void* ws) {
+  PackJob job;
+  job.w = d->w; job.w_bs = d->w_bs; job.w_gs = d->w_gs; job.w_sm = d->w_sm; job.w_sk = d->w_sk;
+  job.ws = (unsigned char*)ws;
+  job.M = d->m; job.K = d->k1 + d->k2; job.tm = pl.tm; job.k_chunks = pl.k_chunks;
+  job.groups_w = pl.per_group ? d->groups : 1; job.chunk_elems = pl.chunk_elems; job.m_fast = d->w_sk != 1 ? 1 : 0;
+  job.dtype = d->dtype; job.slices = pl.slices; job.slice_elems = pl.slice_elems;
+  return job;
+}
+
+static PwG pw_args(const mi_pw_desc* d, const PwPlan& pl, const unsigned char* image) {
+  PwG q;
+  PwK& k = q.k;
   k.x1 = d->x1; k.x1_bs = d->x1_bs; k.x1_gs = d->x1_gs; k.k1 = d->k1;
   k.x2 = d->x2; k.x2_bs = d->x2_bs; k.x2_gs = d->x2_gs; k.k2 = d->k2;
   k.w = d->w; k.w_bs = d->w_bs; k.w_gs = d->w_gs; k.w_sm = d->w_sm; k.w_sk = d->w_sk;
   k.bias = d->bias; k.bias_gs = d->bias_gs;
   k.r = d->r; k.r_bs = d->r_bs; k.r_gs = d->r_gs;
   k.y = d->y; k.y_bs = d->y_bs; k.y_gs = d->y_gs;
-  k.m = d->m; k.n = d->n; k.groups = d->groups;
+  k.m = d->m; k.n = d->n; k.groups = d->groups; k.vec_ok = pl.vec_ok ? 1 : 0;
   k.y2 = d->y2; k.y2_bs = d->y2_bs; k.y2_gs = d->y2_gs; k.y_split = d->y_split;
-  const bool ok = pw_vec_ok(d);
-  k.vec_ok = ok ? 1 : 0;
-  const PwPlan pl = pw_plan(d);
-  hipStream_t st = (hipStream_t)stream;
-  return with_dtype(d->dtype, "pw_gemm", [&](auto tag) -> int { return pw_launch<decltype(tag)>(d, k, pl, ws, st); });
+  q.ws = image; q.wp_slice = pl.slice_elems; q.wp_per_batch = pl.per_batch; q.wp_per_group = pl.per_group; q.k_chunks = pl.k_chunks;
+  q.ln_w = d->ln_w; q.ln_b = d->ln_b; q.ln_mean = d->ln_mean; q.ln_rstd = d->ln_rstd; q.ln_mode = d->ln_mode;
+  q.f8_sx = d->f8_sx; q.f8_sw = d->f8_sw;
+  q.xcd_map = pl.xcd_map;
+  q.w_direct = pl.weights != PW_W_PACK ? 1 : 0;
+  q.wb16 = pl.weights == PW_W_B16 ? (const bf16*)d->w_b16 : nullptr; q.wb16_sm = d->w_b16_sm;
+  return q;
 }
 
+// The instances of each family, keyed on plan fields.
+using PwFn = void (*)(PwG);
+using PwFn2 = void (*)(PwG, int, int);
+using PwFn3 = void (*)(PwG, int, int, int);
+static int pw_tm_index(int tm) { return tm == 128 ? 0 : (tm == 96 ? 1 : (tm == 64 ? 2 : 3)); }
+template <typename T> static PwFn pw_tile_kernel(const PwPlan& pl) {   // chunked; the LDS-DMA ring has the even tiles only
+  static const PwFn tab[2][4] = {{pw_gemm_kernel<T, 2, 128>, pw_gemm_kernel<T, 2, 96>, pw_gemm_kernel<T, 1, 64>, pw_gemm_kernel<T, 1, 48>},
+                                 {pw_gemm_dma_kernel<T, 2>, nullptr, pw_gemm_dma_kernel<T, 1>, nullptr}};
+  return tab[pl.family == PW_DMA][pw_tm_index(pl.tm)];
+}
+static PwFn2 pw_res_kernel(const PwPlan& pl) {
+  static const PwFn2 tab[4] = {pw_gemm_res_kernel<2, 128>, pw_gemm_res_kernel<2, 96>, pw_gemm_res_kernel<1, 64>, pw_gemm_res_kernel<1, 48>};
+  return tab[pw_tm_index(pl.tm)];
+}
+static PwFn3 pw_xres_kernel(const PwPlan& pl) {
+  static const PwFn3 tab[3][2] = {{pw_gemm_wave_xres_kernel<1, false>, pw_gemm_wave_xres_kernel<1, true>},
+                                  {pw_gemm_wave_xres_kernel<2, false>, pw_gemm_wave_xres_kernel<2, true>},
+                                  {pw_gemm_wave_xres_kernel<3, false>, pw_gemm_wave_xres_kernel<3, true>}};
+  return tab[pl.k_chunks - 1][pl.f8];
+}
+static PwFn2 pw_stream_kernel(const PwPlan& pl) {
+  static const PwFn2 tab[3][2] = {{pw_gemm_wave_stream_kernel<6, false>, pw_gemm_wave_stream_kernel<6, true>},
+                                  {pw_gemm_wave_stream_kernel<4, false>, pw_gemm_wave_stream_kernel<4, true>},
+                                  {pw_gemm_wave_stream_kernel<3, false>, pw_gemm_wave_stream_kernel<3, true>}};
+  return tab[pw_tm_index(pl.tm) - 1][pl.f8];
+}
+static PwFn3 pw_xwide_kernel(const PwPlan& pl) {   // [K chunks - 4][fp8][LayerNorm on load: K <= 128 only, pw_ln_form]
+  static const PwFn3 tab[3][2][2] = {{{pw_gemm_wave_xwide_kernel<4, false, false>, pw_gemm_wave_xwide_kernel<4, false, true>},
+                                      {pw_gemm_wave_xwide_kernel<4, true, false>, pw_gemm_wave_xwide_kernel<4, true, true>}},
+                                     {{pw_gemm_wave_xwide_kernel<5, false, false>, nullptr}, {pw_gemm_wave_xwide_kernel<5, true, false>, nullptr}},
+                                     {{pw_gemm_wave_xwide_kernel<6, false, false>, nullptr}, {pw_gemm_wave_xwide_kernel<6, true, false>, nullptr}}};
+  return tab[pl.k_chunks - 4][pl.f8][pl.ln];
+}
+
+// Steps 4 and 5 of mi_pw_gemm: pack the weights (or find them in the cache), then launch what the plan says.
+template <typename T>
+static int pw_launch(const mi_pw_desc* d, const PwPlan& pl, void* ws, hipStream_t st) {
+  const unsigned char* image = (const unsigned char*)ws;
+  if (pl.weights == PW_W_PACK) {
+    const PackJob job = pw_pack_job(d, pl, ws);
+    const unsigned char* cached = pl.cacheable ? pw_cache_lookup(job, pl.bytes, st) : nullptr;
+    if (cached) {
+      image = cached;
+    } else {   // re-pack the weights of every slice (and refresh the zero block)
+      const int64_t total = (int64_t)pl.m_tiles * pl.k_chunks * pl.tm * PW_KC;
+      ProfScope ps(st, K_PW_PACK, 4.0 * d->m * (d->k1 + d->k2) * pl.slices + (double)pl.bytes, 0.0);
+      hipLaunchKernelGGL((pw_pack_kernel<T>), dim3(cdiv_cap(total, 256, 1024), pl.slices), dim3(256), 0, st, job);
+      MI_LAUNCH_CHECK();
+    }
+  }
+  const PwG q = pw_args(d, pl, image);
+  const double Z = (double)d->batch * d->groups, kt = d->k1 + d->k2;
+  // the forward attention product  out = M_b . v (+ x): per-image weights, one group, not transposed (modules.hip attn_core_fwd)
+  const bool is_av = d->w_bs != 0 && d->groups == 1 && d->w_sk == 1 && d->r != nullptr;
+  ProfScope ps(st, is_av ? K_PW_AV : K_PW_GEMM, (kt + d->m + (d->r ? d->m : 0)) * (double)d->n * Z * sizeof(T) + 4.0 * d->m * kt,
+               2.0 * d->m * kt * (double)d->n * Z);
+  switch (pl.family) {
+    case PW_XRES: return launch_dyn_lds(pw_xres_kernel(pl), pl.grid, pl.block, pl.lds, st, q, pl.m_tiles, pl.tpw, pl.chunk_elems);
+    case PW_STREAM: return launch_dyn_lds(pw_stream_kernel(pl), pl.grid, pl.block, pl.lds, st, q, pl.tpw, pl.chunk_elems);
+    case PW_XWIDE: return launch_dyn_lds(pw_xwide_kernel(pl), pl.grid, pl.block, pl.lds, st, q, pl.n_slabs, pl.slabs_per, pl.chunk_elems);
+    case PW_RESIDENT: return launch_dyn_lds(pw_res_kernel(pl), pl.grid, pl.block, pl.lds, st, q, cdiv(d->n, PW_TN), pl.chunk_elems);
+    default: return launch_dyn_lds(pw_tile_kernel<T>(pl), pl.grid, pl.block, pl.lds, st, q);   // chunked, LDS-DMA
+  }
+}
+
+}  // namespace mi
+
+using namespace mi;
+
+extern "C" size_t mi_pw_gemm_workspace(const mi_pw_desc* d) {
+  if (!d || d->m <= 0 || d->k1 <= 0 || d->k2 < 0 || d->batch <= 0 || d->groups <= 0) return 0;
+  // which family runs depends on pointer alignment (and the switches) at call time, and module entry points size their workspaces
+  // before they see the pointers: cover the plan as given and the plan of unaligned pointers, with either kind of image
+  const PwPlan a = pw_plan(d), b = pw_plan(d, true);
+  return max_of({a.bytes, b.bytes, align_up(a.lds_image, 256)});
+}
+
+extern "C" int mi_pw_gemm(const mi_pw_desc* d, void* ws, void* stream) {
+  MI_TRY(pw_check(d));
+  MI_CHECK_ARG(ws && aligned16(ws), "pw_gemm: workspace missing or not 16-byte aligned");
+  const PwPlan pl = pw_plan(d);
+  MI_TRY(pw_validate(d, pl));
+  hipStream_t st = (hipStream_t)stream;
+  if (pl.family == PW_LDS) return pw_lds_launch(d, pl, ws, st);     // deep K: the LDS-tiled kernel (pw_lds.hip) packs its own image
+  return with_dtype(d->dtype, "pw_gemm", [&](auto tag) -> int { return pw_launch<decltype(tag)>(d, pl, ws, st); });
+}
+
+// The predicates: the plan of the descriptor with the feature switched on, read through the conditions pw_validate checks.
 extern "C" int mi_pw_gemm_ln_ok(const mi_pw_desc* d) {
   if (!d || pw_check(d) != MI_OK || d->k2 != 0 || d->groups != 1) return 0;
-  // the two X-resident forms; the W-streamed one up to K = 128 only: at K = 129 .. 192 the tile (96 load registers) plus the
-  // statistics spill (60 / 252 bytes of scratch per lane) and the separate LayerNorm kernel is the better choice
-  const PwPlan pl = pw_plan(d);
-  return (pl.wave == 1 || (pl.wave == 3 && pl.k_chunks <= 4)) ? 1 : 0;
+  mi_pw_desc e = *d;
+  if (!e.ln_mode) e.ln_mode = 1;
+  return pw_ln_form(pw_plan(&e));
 }
-
 extern "C" int mi_pw_gemm_split_ok(const mi_pw_desc* d) {
-  if (!d || pw_check(d) != MI_OK || d->dtype != MI_BF16 || d->r) return 0;
-  return pw_plan(d).wave != 0 ? 1 : 0;
+  if (!d || pw_check(d) != MI_OK || d->r) return 0;
+  mi_pw_desc e = *d;
+  if (!e.y2) e.y2 = e.y;
+  return pw_wave_form(pw_plan(&e));
+}
+extern "C" int mi_pw_gemm_f8_ok(const mi_pw_desc* d) {
+  if (!d || pw_check(d) != MI_OK) return 0;
+  mi_pw_desc e = *d;
+  e.f8 = 1;
+  return pw_wave_form(pw_plan(&e));
 }
 
-extern "C" int mi_pw_gemm_f8_ok(const mi_pw_desc* d) {
-  if (!d || pw_check(d) != MI_OK || d->dtype != MI_BF16) return 0;
-  return pw_plan(d).wave != 0 ? 1 : 0;
+// What mi_pw_gemm runs for this descriptor under the current switches.  Host-side only: the same pw_plan, and pointers are read
+// for their alignment only (any 16-byte-aligned placeholder will do).  out[18]: family (0 chunked, 1 weight-resident, 2 LDS-DMA,
+// 3 wave X-resident, 4 wave stream, 5 wave X-wide, 6 LDS-tiled), tile rows, K chunks, fp8, LayerNorm on load, grid x / y / z,
+// block, dynamic LDS bytes, pixel tiles per wave, per workgroup, X-wide slabs, slabs per workgroup, XCD map, weight source
+// (0 own pack, 1 bf16 copy, 2 direct fp32), may use the pack cache, workspace bytes.
+extern "C" int mi_pw_plan(const mi_pw_desc* d, int64_t* out) {
+  MI_TRY(pw_check(d));
+  MI_CHECK_ARG(out, "pw_plan: null pointer");
+  const PwPlan pl = pw_plan(d);
+  const int64_t v[18] = {pl.family, pl.tm, pl.k_chunks, pl.f8, pl.ln, pl.grid.x, pl.grid.y, pl.grid.z, pl.block.x, (int64_t)pl.lds,
+                         pl.tpw, pl.tpb, pl.n_slabs, pl.slabs_per, pl.xcd_map, pl.weights, pl.cacheable, (int64_t)pl.ws_bytes()};
+  memcpy(out, v, sizeof(v));
+  return MI_OK;
 }
 
 extern "C" int mi_pw_cache_enable(void* buf, size_t bytes, const void* params_lo, const void* params_hi) {

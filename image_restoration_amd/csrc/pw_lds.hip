@@ -162,60 +162,31 @@ __global__ __launch_bounds__(256 * NWM) void pl_kernel(PlArgs a) {
   }
 }
 
-// Shapes this kernel takes from the planner of pw_gemm.hip: bf16, one X operand, static weights, no LayerNorm head / fp8 /
-// split output, deep K, enough rows to fill the 128-row tiles, 16-byte aligned pixel rows.
-bool pw_lds_ok(const mi_pw_desc* d) {
-  if (MI_ENV(MI_NO_PW_LDS)) return false;
-  if (d->dtype != MI_BF16 || d->k2 != 0 || d->groups != 1 || d->w_bs != 0 || d->ln_mode != 0 || d->f8 || d->y2) return false;
-  if (d->k1 <= 128 || d->m < 128 || d->n % 8 != 0 || d->n < 256) return false;
-  // Where it wins (profiles/r03_s_pw_lds_deep_gemm.txt, bs 32, incl. its pack launch): very wide outputs of a deep K (384 ->
-  // 2042 / 1021: 1.42x) and deep K into few rows (1020 / 576 -> 192: 1.3-1.6x).  Elsewhere the wave-owned kernels hold
-  // 430-530 TFLOP/s and stay (MI_PW_LDS=all takes every covered shape: tests, A/B).
-  const char* e = MI_ENV(MI_PW_LDS);
-  if (!(e && e[0] == 'a') && !((d->k1 >= 320 && d->m >= 1000) || (d->k1 >= 560 && d->m <= 256))) return false;
-  if (!aligned16(d->x1) || !aligned16(d->y) || (d->r && !aligned16(d->r))) return false;
-  if (d->x1_bs % 8 != 0 || d->y_bs % 8 != 0 || (d->r && d->r_bs % 8 != 0)) return false;
-  return true;
-}
-
-static int pl_tm(int M) {                               // 256-row tiles unless 128-row tiles waste fewer padded rows
+// Where this kernel runs is pw_plan's decision (pw_gemm.hip, family PW_LDS); here are its tile height, its LDS footprint and its
+// launch.
+int pw_lds_tm(int M) {                                  // 256-row tiles unless 128-row tiles waste fewer padded rows
   return (int64_t)cdiv(M, 256) * 256 <= (int64_t)cdiv(M, 128) * 128 ? 256 : 128;
 }
-size_t pw_lds_pack_bytes(const mi_pw_desc* d) {
-  const int TM = pl_tm(d->m);
-  return (size_t)cdiv(d->m, TM) * cdiv(d->k1, 64) * TM * 64 * 2;
-}
+size_t pw_lds_lds_bytes(int tm) { return 64 * PL_XS * 2 + (size_t)tm * 64 * 2; }   // the X chunk + the weight chunk
 
-// ws: pw_lds_pack_bytes(d) bytes for the packed weight image (packed per call; TODO the trainer's pack cache)
-int pw_lds_launch(const mi_pw_desc* d, void* ws, hipStream_t st) {
-  const int TM = pl_tm(d->m);
+// ws: pl.lds_image bytes for the packed weight image (packed per call; TODO the trainer's pack cache)
+int pw_lds_launch(const mi_pw_desc* d, const PwPlan& pl, void* ws, hipStream_t st) {
   PlArgs a;
   a.x = (const bf16*)d->x1; a.wp = (const bf16*)ws; a.bias = d->bias; a.r = (const bf16*)d->r; a.y = (bf16*)d->y;
   a.x_bs = d->x1_bs; a.r_bs = d->r_bs; a.y_bs = d->y_bs; a.N = d->n;
-  a.M = d->m; a.K = d->k1; a.nchunk = cdiv(d->k1, 64); a.tiles_n = cdiv(d->n, 256);
-  MI_CHECK_ARG(a.tiles_n <= 65535 && d->batch <= 65535, "pw_gemm: grid too large");
+  a.M = d->m; a.K = d->k1; a.nchunk = pl.k_chunks; a.tiles_n = (int)pl.grid.y;
   {
     PlPackArgs pa;
-    pa.w = d->w; pa.wp = (bf16*)ws; pa.w_sm = d->w_sm; pa.w_sk = d->w_sk; pa.M = d->m; pa.K = d->k1; pa.TM = TM;
-    pa.nchunk = a.nchunk; pa.ntile = cdiv(d->m, TM);
-    const int64_t total = (int64_t)pa.ntile * pa.nchunk * TM * 64;
+    pa.w = d->w; pa.wp = (bf16*)ws; pa.w_sm = d->w_sm; pa.w_sk = d->w_sk; pa.M = d->m; pa.K = d->k1; pa.TM = pl.tm;
+    pa.nchunk = pl.k_chunks; pa.ntile = pl.m_tiles;
+    const int64_t total = (int64_t)pa.ntile * pa.nchunk * pl.tm * 64;
     ProfScope ps(st, K_PW_PACK, (double)total * 2 + 4.0 * d->m * d->k1, 0.0);
-    hipLaunchKernelGGL(pl_pack_kernel, dim3((unsigned)(cdiv(total, 1024) < 1024 ? cdiv(total, 1024) : 1024)), dim3(256), 0, st, pa);
+    hipLaunchKernelGGL(pl_pack_kernel, dim3((unsigned)cdiv_cap(total, 1024, 1024)), dim3(256), 0, st, pa);
     MI_LAUNCH_CHECK();
   }
-  const dim3 grid((unsigned)cdiv(d->m, TM), (unsigned)a.tiles_n, (unsigned)d->batch);
   const double N = (double)d->n * d->batch;
   ProfScope ps(st, K_PW_GEMM, (double)(d->k1 + d->m + (d->r ? d->m : 0)) * N * 2.0, 2.0 * d->m * d->k1 * N);
-  if (TM == 256) {
-    constexpr int LB = 64 * PL_XS * 2 + 256 * 64 * 2;
-    MI_CHECK_HIP(hipFuncSetAttribute((const void*)pl_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, LB));
-    hipLaunchKernelGGL((pl_kernel<2>), grid, dim3(512), LB, st, a);
-  } else {
-    constexpr int LB = 64 * PL_XS * 2 + 128 * 64 * 2;
-    hipLaunchKernelGGL((pl_kernel<1>), grid, dim3(256), LB, st, a);
-  }
-  MI_LAUNCH_CHECK();
-  return MI_OK;
+  return launch_dyn_lds(pl.tm == 256 ? pl_kernel<2> : pl_kernel<1>, pl.grid, pl.block, pl.lds, st, a);
 }
 
 }  // namespace mi

@@ -274,6 +274,41 @@ def pw_gemm_desc(d: "L.PwDesc", device) -> None:
     L.check(L.lib().mi_pw_gemm(C.byref(d), _p(ws), _stream()), "pw_gemm")
 
 
+PW_FAMILIES = ("chunked", "resident", "dma", "xres", "stream", "xwide", "lds")
+PW_WEIGHTS = ("pack", "b16", "f32")
+PW_PROBE = 256          # stands in for every pointer of a descriptor that is only planned: 16-byte aligned, never read
+
+
+def pw_probe(M: int, K: int, N: int, dtype: torch.dtype, B: int = 1, groups: int = 1, K2: int = 0, per_image: bool = False,
+             transposed: bool = False, residual: bool = False, misalign: int = 0) -> "L.PwDesc":
+    """A dense descriptor of placeholder pointers for pw_plan and the mi_pw_gemm_*_ok / _workspace queries: x [B, groups*K, N]
+    (+ a second panel of K2 channels), w [(B,) groups, M, K+K2] or its transpose, y (and residual) [B, groups*M, N].
+    misalign: bytes added to the x / y / residual pointers."""
+    d = L.PwDesc()
+    kt = K + K2
+    d.x1, d.x1_bs, d.x1_gs, d.k1 = PW_PROBE + misalign, groups * K * N, K * N, K
+    if K2:
+        d.x2, d.x2_bs, d.x2_gs, d.k2 = PW_PROBE, groups * K2 * N, K2 * N, K2
+    d.w, d.w_bs, d.w_gs = PW_PROBE, (groups * M * kt if per_image else 0), (M * kt if groups > 1 else 0)
+    d.w_sm, d.w_sk = (1, M) if transposed else (kt, 1)
+    if residual:
+        d.r = PW_PROBE + misalign
+    d.r_bs, d.r_gs = groups * M * N, M * N
+    d.y, d.y_bs, d.y_gs = PW_PROBE + misalign, groups * M * N, M * N
+    d.m, d.n, d.batch, d.groups, d.dtype = M, N, B, groups, _dtype_code(dtype)
+    return d
+
+
+def pw_plan(d: "L.PwDesc") -> dict:
+    """What mi_pw_gemm runs for ``d`` under the current MI_PW_* switches (mi_pw_plan; no GPU work)."""
+    out = (L.c_i64 * 18)()
+    L.check(L.lib().mi_pw_plan(C.byref(d), out), "pw_plan")
+    return {"family": PW_FAMILIES[out[0]], "tm": out[1], "kb": out[2], "f8": bool(out[3]), "ln": bool(out[4]),
+            "grid": (out[5], out[6], out[7]), "block": out[8], "lds": out[9], "tpw": out[10], "tpb": out[11], "n_slabs": out[12],
+            "slabs_per": out[13], "xcd_map": bool(out[14]), "weights": PW_WEIGHTS[out[15]], "cacheable": bool(out[16]),
+            "workspace": out[17]}
+
+
 def gram(a: Tensor, b: Tensor, groups: int = 1, sum_batch: bool = False, want_sumsq: bool = False,
          out: Optional[Tensor] = None, accumulate: bool = False):
     """G[z][i][j] = sum_n a[z][i][n] b[z][j][n] with a,b [B, groups*m, H, W] split head-major into groups.

@@ -167,6 +167,12 @@ int mi_pw_gemm(const mi_pw_desc* d, void* ws, void* stream);
 int mi_pw_gemm_ln_ok(const mi_pw_desc* d);
 int mi_pw_gemm_f8_ok(const mi_pw_desc* d);
 int mi_pw_gemm_split_ok(const mi_pw_desc* d);
+/* What mi_pw_gemm runs for d under the current A/B switches (host-only; the pointers are read for their 16-byte alignment only,
+ * so placeholders will do).  out[18]: family (0 chunked, 1 weight-resident, 2 LDS-DMA, 3 wave X-resident, 4 wave stream, 5 wave
+ * X-wide, 6 LDS-tiled deep K), tile rows, K chunks, fp8, LayerNorm on load, grid x, y, z, block, dynamic LDS bytes, pixel tiles
+ * per wave, pixel tiles per workgroup, X-wide slabs, slabs per workgroup, XCD map, weight source (0 own pack, 1 bf16 copy,
+ * 2 direct fp32), may use the pack cache, workspace bytes. */
+int mi_pw_plan(const mi_pw_desc* d, int64_t* out);
 
 /* Opt-in packed-weight cache.  By default every mi_pw_gemm (and every module entry point built on it) packs its weight
  * matrix into its own workspace, once per call, and the library keeps no state.  A caller that controls when the

@@ -244,3 +244,151 @@ def test_ln_case_lists_reach_every_plan(lib, monkeypatch):
     missing = {k: v for k, v in possible.items() if k not in reached}
     assert not missing, "plans without a test case (plan: first (MI_LN_FORM, C, N, aligned) that takes it): %r" % missing
     assert len(possible) >= 40 and reached <= set(possible)
+
+
+# --------------------------------------------------------------------------- the 1x1 GEMM plan (mi_pw_plan)
+PW_SWITCHES = ("MI_PW_WAVE", "MI_PW_CHUNKED", "MI_PW_DMA", "MI_PW_XWIDE", "MI_PW_WAVE_WIDE", "MI_PW_LDS", "MI_NO_PW_LDS", "MI_PW_DIRECT",
+               "MI_PW_B16", "MI_PW_TM_EVEN", "MI_PW_TPB", "MI_PW_WAVE_TPW", "MI_PW_XCD")
+PW_MS = (16, 48, 49, 64, 96, 97, 144, 192, 254, 256, 288, 510, 1021, 2042)
+PW_KS = (16, 33, 48, 96, 97, 128, 129, 192, 193, 384, 576, 1020)
+PW_NS = (35, 64, 256, 4096)
+PW_WAVE_FORMS = ("xres", "stream", "xwide")
+
+
+def _pw_switches(monkeypatch, **env):
+    for k in PW_SWITCHES:
+        monkeypatch.delenv(k, raising=False)
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+
+
+def _pw_sweep():
+    import itertools
+    from image_restoration_amd import ops
+    for M, K, N, dtype, groups, per_image, transposed in itertools.product(PW_MS, PW_KS, PW_NS, (torch.float32, torch.bfloat16),
+                                                                         (1, 2), (False, True), (False, True)):
+        yield dtype, ops.pw_probe(M, K, N, dtype, B=2, groups=groups, per_image=per_image, transposed=transposed)
+
+
+def test_pw_plan_pinned_for_every_family(lib, monkeypatch):
+    """ops.pw_plan, every field, for one descriptor per kernel family (batch 2, bias + residual).  Kernel instance, grid and
+    block are what a kernel trace of these calls showed BEFORE the plan became the one place of decision (the trace reports
+    static LDS only: the dynamic LDS bytes, the counts and the workspace follow the formulas of that launcher; planes this small
+    leave one pixel tile per wave / workgroup)."""
+    from image_restoration_amd import ops
+    f32, bf16 = torch.float32, torch.bfloat16
+
+    def plan(M, K, N, dtype, env={}, **kw):
+        _pw_switches(monkeypatch, **env)
+        return ops.pw_plan(ops.pw_probe(M, K, N, dtype, residual=True, **{"B": 2, **kw}))
+
+    def want(family, tm, kb, grid, block, lds, workspace, **kw):
+        base = {"family": family, "tm": tm, "kb": kb, "f8": False, "ln": False, "grid": grid, "block": block, "lds": lds, "tpw": 0,
+                "tpb": 0, "n_slabs": 0, "slabs_per": 0, "xcd_map": False, "weights": "pack", "cacheable": True, "workspace": workspace}
+        return {**base, **kw}
+
+    assert plan(48, 48, 35, f32) == want("chunked", 48, 2, (1, 1, 2), 256, 0, 16640)
+    assert plan(144, 48, 256, bf16, {"MI_PW_WAVE": "0"}) == want("resident", 64, 2, (4, 3, 2), 256, 30720, 49408, tpb=1)
+    assert plan(144, 48, 256, bf16, {"MI_PW_DMA": "1"}) == want("dma", 64, 2, (4, 3, 2), 256, 36864, 49408)
+    assert plan(254, 48, 256, bf16) == want("xres", 64, 2, (1, 1, 2), 512, 77824, 65792, tpw=1)
+    assert plan(96, 510, 256, bf16) == want("stream", 96, 16, (1, 1, 2), 512, 159744, 131328, tpw=1)
+    assert plan(64, 160, 256, bf16) == want("stream", 64, 5, (1, 1, 2), 512, 62464, 41216, tpw=1)
+    assert plan(48, 127, 256, bf16) == want("stream", 48, 4, (1, 1, 2), 512, 52224, 16640, tpw=1)
+    assert plan(510, 128, 256, bf16) == want("xwide", 64, 4, (1, 8, 2), 512, 77824, 262400, tpw=1, n_slabs=8, slabs_per=1)
+    assert plan(510, 192, 256, bf16) == want("xwide", 64, 6, (1, 8, 2), 512, 98304, 393472, tpw=1, n_slabs=8, slabs_per=1)
+    assert plan(1021, 384, 256, bf16) == want("lds", 256, 6, (4, 1, 2), 512, 67584, 786432, cacheable=False)
+    # a pointer off the 16-byte grid, or pixel rows that are no multiple of 8: the chunked kernel
+    assert plan(144, 48, 256, bf16, misalign=2) == want("chunked", 64, 2, (4, 3, 2), 256, 0, 49408)
+    assert plan(144, 48, 35, bf16) == want("chunked", 64, 2, (1, 3, 2), 256, 0, 49408)
+    # beyond the traced calls: a plane large enough for the per-wave / per-workgroup counts to leave 1, and the per-image weight sources
+    assert plan(510, 96, 65536, bf16, B=32)["tpw"] == 4 and plan(254, 48, 65536, bf16, B=32)["tpw"] == 2
+    assert plan(144, 48, 65536, bf16, {"MI_PW_WAVE": "0"})["tpb"] == 3
+    _pw_switches(monkeypatch)
+    d = ops.pw_probe(96, 96, 256, bf16, B=2, per_image=True)
+    assert (ops.pw_plan(d)["weights"], ops.pw_plan(d)["cacheable"]) == ("pack", False)
+    d.w_b16, d.w_b16_sm = ops.PW_PROBE, 96
+    assert ops.pw_plan(d)["weights"] == "b16"
+    d.w_b16 = None
+    _pw_switches(monkeypatch, MI_PW_DIRECT="1")
+    assert ops.pw_plan(d)["weights"] == "f32"
+
+
+def test_pw_predicates_and_workspace_follow_the_plan(lib, monkeypatch):
+    """mi_pw_gemm_ln_ok / _split_ok / _f8_ok say what the plan of the same descriptor says, and mi_pw_gemm_workspace covers the
+    plan for aligned and for unaligned pointers, over every shape class of the sweep."""
+    from image_restoration_amd import ops
+    _pw_switches(monkeypatch)
+    L, n = lib.lib(), 0
+
+    def family_with(d, **feature):                    # the family of the same call with one optional feature switched on
+        for k, v in feature.items():
+            setattr(d, k, v)
+        fam = ops.pw_plan(d)["family"]
+        for k in feature:
+            setattr(d, k, 0)
+        return fam
+
+    for dtype, d in _pw_sweep():
+        p = ops.pw_plan(d)
+        ln = d.groups == 1 and (family_with(d, ln_mode=1) == "xres" or (family_with(d, ln_mode=1) == "xwide" and d.k1 <= 128))
+        assert bool(L.mi_pw_gemm_ln_ok(C.byref(d))) == ln, (p, d.m, d.k1, d.n)
+        for ok, fam in ((L.mi_pw_gemm_split_ok, family_with(d, y2=ops.PW_PROBE)), (L.mi_pw_gemm_f8_ok, family_with(d, f8=1))):
+            assert bool(ok(C.byref(d))) == (dtype == torch.bfloat16 and fam in PW_WAVE_FORMS), (p, fam, d.m, d.k1, d.n)
+        ws = L.mi_pw_gemm_workspace(C.byref(d))
+        d.y += 2                                      # the same call with an unaligned output
+        q = ops.pw_plan(d)
+        assert q["family"] == "chunked" and ws >= p["workspace"] and ws >= q["workspace"], (p, q, ws)
+        n += 1
+    assert n == 14 * 12 * 4 * 2 * 2 * 2 * 2
+
+
+# every instance the launchers can select: (family, tile rows / K chunks, ...).  The weight-resident kernel has a 48-row instance
+# that no shape takes: 48-row tiles need M <= 48, and M <= 64 stays chunked.
+PW_INSTANCES = (
+    {("chunked", dt, tm) for dt in ("f32", "bf16") for tm in (128, 96, 64, 48)} | {("resident", tm) for tm in (128, 96, 64)} |
+    {("dma", dt, tm) for dt in ("f32", "bf16") for tm in (128, 64)} | {("xres", kb, f8) for kb in (1, 2, 3) for f8 in (False, True)} |
+    {("stream", tm, f8) for tm in (96, 64, 48) for f8 in (False, True)} |
+    {("xwide", kb, f8, ln) for kb in (4, 5, 6) for f8 in (False, True) for ln in ((False, True) if kb == 4 else (False,))} |
+    {("lds", 256), ("lds", 128)})
+
+
+def test_pw_every_family_and_instance_is_reachable(lib, monkeypatch):
+    """The sweep under the default switches and under each A/B switch reaches all seven families and every kernel instance (with
+    fp8 operands and LayerNorm on load wherever the predicates allow them).  A threshold that strands an instance shows up here."""
+    from image_restoration_amd import ops
+
+    def key(dtype, d, p):
+        dt = "bf16" if dtype == torch.bfloat16 else "f32"
+        return {"chunked": (p["family"], dt, p["tm"]), "dma": (p["family"], dt, p["tm"]), "resident": (p["family"], p["tm"]),
+                "lds": (p["family"], p["tm"]), "xres": (p["family"], p["kb"], p["f8"]), "stream": (p["family"], p["tm"], p["f8"]),
+                "xwide": (p["family"], p["kb"], p["f8"], p["ln"])}[p["family"]]
+
+    reached = set()
+    for env in ({}, {"MI_PW_WAVE": "0"}, {"MI_PW_CHUNKED": "1"}, {"MI_PW_DMA": "1"}, {"MI_PW_XWIDE": "0"}, {"MI_PW_WAVE_WIDE": "0"},
+                {"MI_PW_LDS": "all"}):
+        _pw_switches(monkeypatch, **env)
+        for dtype, d in _pw_sweep():
+            p = ops.pw_plan(d)
+            reached.add(key(dtype, d, p))
+            if p["family"] in PW_WAVE_FORMS:
+                ln_ok = bool(lib.lib().mi_pw_gemm_ln_ok(C.byref(d)))
+                for f8, ln in ((1, 0), (0, 1), (1, 1)):
+                    if ln and not ln_ok:
+                        continue
+                    d.f8, d.ln_mode = f8, ln
+                    q = ops.pw_plan(d)
+                    assert q["family"] == p["family"] and q["f8"] == bool(f8) and q["ln"] == bool(ln)
+                    reached.add(key(dtype, d, q))
+                d.f8, d.ln_mode = 0, 0
+    assert reached == PW_INSTANCES, (sorted(PW_INSTANCES - reached, key=str), sorted(reached - PW_INSTANCES, key=str))
+    assert {k[0] for k in reached} == set(ops.PW_FAMILIES)
+
+
+def test_pw_plan_argument_errors(lib):
+    from image_restoration_amd import ops
+    L, out = lib.lib(), (C.c_int64 * 18)()
+    d = ops.pw_probe(48, 48, 64, torch.float32)
+    assert L.mi_pw_plan(None, out) == -1 and b"null pointer" in L.mi_last_error()
+    assert L.mi_pw_plan(C.byref(d), None) == -1 and b"pw_plan: null pointer" in L.mi_last_error()
+    d.dtype = 7
+    assert L.mi_pw_plan(C.byref(d), out) == -1 and b"bad dtype 7" in L.mi_last_error()
