@@ -193,6 +193,7 @@ SIGNATURES = {
     "mi_pw_cache_pending": (C.c_int, []),
     "mi_gram_workspace": (C.c_size_t, [C.POINTER(GramDesc)]),
     "mi_gram": (C.c_int, [C.POINTER(GramDesc), vp, vp]),
+    "mi_gram_plan": (C.c_int, [C.POINTER(GramDesc), C.POINTER(c_i64)]),
     "mi_mdta_saved_bytes": (C.c_size_t, [C.POINTER(MdtaShape)]),
     "mi_mdta_workspace": (C.c_size_t, [C.POINTER(MdtaShape)]),
     "mi_mdta_fwd": (C.c_int, [C.POINTER(MdtaShape), C.POINTER(MdtaParams), vp, vp, vp, vp, vp, vp]),

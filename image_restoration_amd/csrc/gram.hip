@@ -9,7 +9,7 @@
 #include <algorithm>
 #include <type_traits>
 
-#include "common.h"
+#include "internal.h"
 
 namespace mi {
 
@@ -239,7 +239,7 @@ __global__ __launch_bounds__(256) void gram_stream_kernel(GramK p, int steps_per
     int ln = lane;
     asm volatile("" : "+v"(ln));
     const int li_ = ln & 15, g_ = ln >> 4;
-    // 32-bit element offsets from the (uniform) operand bases: one slice is at most rows * n < 2^31 elements (gram_stream_ok)
+    // 32-bit element offsets from the (uniform) operand bases: one slice is at most rows * n < 2^31 elements (gram_plan)
     const T* A = A0;
     const T* B = B0;
     int sl = s;                                          // step inside its image
@@ -451,88 +451,25 @@ __global__ __launch_bounds__(256) void gram_reduce_few_kernel(const float* __res
   float* o = out + (int64_t)zo * out_zs + (int64_t)i * out_ld + j;
   *o = (accumulate ? *o : 0.f) + s;
 }
-static void launch_gram_reduce(const float* part, float* out, int splits, int batch, int groups, int ma, int mb, int64_t out_ld,
-                               int64_t out_zs, int sum_batch, int accumulate, int zo, hipStream_t st) {
-  const int64_t per = (int64_t)ma * mb;
-  const int total = splits * (sum_batch ? batch : 1);
-  if (total <= 4)
-    hipLaunchKernelGGL(gram_reduce_few_kernel<4>, dim3(cdiv(per, 256), zo), dim3(256), 0, st, part, out, total, batch, groups, ma, mb,
-                       out_ld, out_zs, sum_batch, accumulate);
-  else if (total <= 16 || per * zo >= 16384)      // enough elements to fill the chip with one thread each: slices walked in the thread
-    hipLaunchKernelGGL(gram_reduce_few_kernel<16>, dim3(cdiv(per, 256), zo), dim3(256), 0, st, part, out, total, batch, groups, ma, mb,
-                       out_ld, out_zs, sum_batch, accumulate);
-  else
-    hipLaunchKernelGGL(gram_reduce_kernel, dim3(cdiv(per, 16), zo), dim3(256), 0, st, part, out, splits, batch, groups, ma, mb, out_ld,
-                       out_zs, sum_batch, accumulate);
-}
 
-// A weight-gradient Gram that accumulates into a dense [ma][mb] gradient may leave its split partials in the deferred arena
-// and have them summed by mi_deferred_flush (common.h): rows = splits x images of ma*mb floats, a plain fixed-order row sum.
-static bool gram_deferrable(const mi_gram_desc* d) {
-  return d->accumulate && d->sum_batch && d->groups == 1 && d->out_ld == d->mb && !d->sumsq;
-}
-
-struct GramPlan { int FA, FB, kc, nchunks, tiles_a, tiles_b, splits, cps, Z, fold; size_t part_bytes, ss_bytes; };
-
+// ---- the plan ---------------------------------------------------------------------------------------------------------------
 // Weight gradients sum over the batch: instead of one partial tile per image (and a reduction over batch x splits partials),
 // the images are chained along the contraction axis - a workgroup's pixel range may cross image boundaries - whenever an image
 // is a whole number of chunks / steps.  Returns the chunks per image, or 0.  Measured at bs 32 (profiles/r02_k_gram_fold_ab.txt):
 // it pays where an image is short (32 x 32 planes: 16 chunks per workgroup against a 64 KB partial tile each - 1152 x 384
 // 102 -> 76 us, 2042 x 384 144 -> 127 us) and where images x tiles leaves the chip half empty (576 x 192 at 64 x 64: 320
 // workgroups, 163 -> 125 us); on long planes the per-chunk image lookup costs 5-10 % and buys nothing, so those stay per image.
-static int gram_fold(const mi_gram_desc* d, int unit, int64_t tiles_per_image) {
-  const char* e = MI_ENV(MI_GRAM_FOLD);                            // A/B switch: 0 never, 2 wherever possible
-  if (e && e[0] == '0') return 0;
+// sw: MI_GRAM_FOLD (A/B switch: 0 never, 2 wherever possible).
+static int gram_fold(const mi_gram_desc* d, int unit, int64_t tiles_per_image, const char* sw) {
+  if (sw && sw[0] == '0') return 0;
   if (!d->sum_batch || d->batch <= 1 || d->sumsq || d->n % unit != 0 || d->n / unit > (1 << 20)) return 0;
   // (second case: the per-image plan would run ONE split - 512 / workgroups rounds to 1 - on a chip it does not fill)
   const int64_t wgs = tiles_per_image * d->batch;
   const bool pays = d->n / unit <= 16 || (wgs > 256 && wgs < 448);
-  if (!pays && !(e && e[0] == '2')) return 0;
+  if (!pays && !(sw && sw[0] == '2')) return 0;
   return (int)(d->n / unit);
 }
-static int gram_want(int dflt) {
-  const char* e = MI_ENV(MI_GRAM_WANT);                            // A/B switch: workgroups the pixel split aims for
-  return e ? atoi(e) : dflt;
-}
-
-static GramPlan gram_plan(const mi_gram_desc* d) {
-  GramPlan g;
-  g.FA = g.FB = (d->ma > 64 || d->mb > 64) ? 4 : 2;
-  // rectangular tiles (bf16): a tile that holds ALL of the shorter operand's rows reads the other operand once instead of once
-  // per 128-row tile of it - 96 x 255 (project_out's weight gradient) as ONE 96 x 256 tile, M x 192 (the C = 192 level) and the
-  // wide M x 384 as 128 x 192 tiles.  bs 32 (profiles/r02_o_gram_rect_tiles.txt): 96 x 255 at 256^2 343 -> 304 us, 1020 x 192
-  // 158 -> 116, 576 x 192 124 -> 85, 2042 x 384 128 -> 105 (384 x 384 loses: 35 -> 39, stays square); step 153.6 -> 152.1 ms.
-  // MI_GRAM_RECT=0: square tiles only (A/B switch).
-  {
-    const char* e = MI_ENV(MI_GRAM_RECT);
-    if (d->dtype == MI_BF16 && !(e && e[0] == '0') && d->ma > 64 && d->ma <= 96 && d->mb > 64 && d->mb <= 96) {
-      g.FA = g.FB = 3;                                               // 96 x 96 (q k^T and dM at c = 96): no padded fragments
-    } else if (d->dtype == MI_BF16 && !d->sumsq && !(e && e[0] == '0')) {
-      if (d->ma <= 96 && d->mb > 128 && d->mb <= 256) { g.FA = 3; g.FB = 8; }
-      else if (d->ma > 128 && d->mb > 128 && (d->mb <= 192 || (d->mb == 384 && d->ma > 384))) { g.FA = 4; g.FB = 6; }
-      else if ((d->ma > 128 && d->ma <= 192 && d->mb > 192) || (d->ma == 384 && d->mb > 384)) { g.FA = 6; g.FB = 4; }   // 192 x 510 (86 -> 65 us), 384 x 1021 (71 -> 62)
-    }
-  }
-  g.kc = d->dtype == MI_BF16 ? 64 : 32;
-  g.nchunks = cdiv(d->n, g.kc);
-  g.tiles_a = cdiv(d->ma, 32 * g.FA);
-  g.tiles_b = cdiv(d->mb, 32 * g.FB);
-  g.fold = gram_fold(d, g.kc, (int64_t)g.tiles_a * g.tiles_b * d->groups);
-  if (g.fold) g.nchunks = d->batch * g.fold;
-  g.Z = (g.fold ? 1 : d->batch) * d->groups;
-  const int64_t tiles = (int64_t)g.tiles_a * g.tiles_b * g.Z;
-  int64_t want = gram_want(512) / (tiles > 0 ? tiles : 1);
-  if (want < 1) want = 1;
-  if (want > g.nchunks) want = g.nchunks;
-  g.cps = cdiv(g.nchunks, want);
-  g.splits = cdiv(g.nchunks, g.cps);
-  g.part_bytes = align_up((size_t)g.splits * g.Z * d->ma * d->mb * sizeof(float), 256);
-  g.ss_bytes = d->sumsq ? align_up((size_t)g.splits * g.Z * (d->ma + d->mb) * sizeof(float), 256) : 0;
-  return g;
-}
-
-// streaming plan (bf16, 16-byte aligned rows): fragment counts per tile and the pixel split
-struct GramSPlan { int fa, fb, tiles_a, tiles_b, nsteps, spb, splits, Z, fold; size_t part_bytes, ss_bytes; };
+// streaming form: 16-row fragments per tile side, the count that pads the rows least (ties: the larger tile)
 static int gram_pick_frags(int m) {
   int best = 3, best_pad = 1 << 30;
   for (int f : {3, 4, 6}) {
@@ -541,51 +478,101 @@ static int gram_pick_frags(int m) {
   }
   return best;
 }
-static GramSPlan gram_splan(const mi_gram_desc* d) {
-  GramSPlan g;
-  g.fa = gram_pick_frags(d->ma);
-  g.fb = gram_pick_frags(d->mb);
-  if (g.fa * g.fb > 24) { if (g.fa >= g.fb) g.fa = 3; else g.fb = 3; }  // 6x6 -> 3x6: accumulators + two stages of loads <= 256 VGPRs
-  g.tiles_a = cdiv(d->ma, 16 * g.fa);
-  g.tiles_b = cdiv(d->mb, 16 * g.fb);
-  g.fold = gram_fold(d, 64, 0);                                     // (streaming form: short planes only)
+
+// What one call runs (GramPlan, internal.h).  The ONE place that decides it, and the only reader of the MI_GRAM_* switches (each
+// read once): mi_gram launches what it says, mi_gram_workspace sizes from it, mi_gram_plan reports it.  Pointers are read for
+// their alignment only.  force = GRAM_LDS / GRAM_STREAM: the plan of that family whatever dtype, alignment, switches and
+// thresholds say - for sizing only (workspaces are sized before the pointers exist), never launched.
+static GramPlan gram_plan(const mi_gram_desc* d, int force = -1) {
+  GramPlan g{};
+  const bool bf = d->dtype == MI_BF16;
+  const char* fold_sw = MI_ENV(MI_GRAM_FOLD);
+  const char* want_sw = MI_ENV(MI_GRAM_WANT);                       // A/B switch: workgroups the pixel split aims for
+  const char* rect_sw = MI_ENV(MI_GRAM_RECT);                       // MI_GRAM_RECT=0: square tiles only (A/B switch)
+  const bool rect = bf && !(rect_sw && rect_sw[0] == '0');
+  const int64_t vec = bf ? 8 : 4;
+  g.vec_ok = d->n % vec == 0 && aligned16(d->a) && aligned16(d->b) && d->a_bs % vec == 0 && d->a_gs % vec == 0 && d->b_bs % vec == 0 &&
+             d->b_gs % vec == 0;
+  g.ss = d->sumsq != nullptr;
+  // ---- the LDS-staged tile: 32-row fragments per side
+  int la, lb;
+  la = lb = (d->ma > 64 || d->mb > 64) ? 4 : 2;
+  // rectangular tiles (bf16): a tile that holds ALL of the shorter operand's rows reads the other operand once instead of once
+  // per 128-row tile of it - 96 x 255 (project_out's weight gradient) as ONE 96 x 256 tile, M x 192 (the C = 192 level) and the
+  // wide M x 384 as 128 x 192 tiles.  bs 32 (profiles/r02_o_gram_rect_tiles.txt): 96 x 255 at 256^2 343 -> 304 us, 1020 x 192
+  // 158 -> 116, 576 x 192 124 -> 85, 2042 x 384 128 -> 105 (384 x 384 loses: 35 -> 39, stays square); step 153.6 -> 152.1 ms.
+  if (rect && d->ma > 64 && d->ma <= 96 && d->mb > 64 && d->mb <= 96) {
+    la = lb = 3;                                                     // 96 x 96 (q k^T and dM at c = 96): no padded fragments
+  } else if (rect && !g.ss) {
+    if (d->ma <= 96 && d->mb > 128 && d->mb <= 256) { la = 3; lb = 8; }
+    else if (d->ma > 128 && d->mb > 128 && (d->mb <= 192 || (d->mb == 384 && d->ma > 384))) { la = 4; lb = 6; }
+    else if ((d->ma > 128 && d->ma <= 192 && d->mb > 192) || (d->ma == 384 && d->mb > 384)) { la = 6; lb = 4; }   // 192 x 510 (86 -> 65 us), 384 x 1021 (71 -> 62)
+  }
+  // ---- the streaming tile: 16-row fragments per side
+  int sa = gram_pick_frags(d->ma), sb = gram_pick_frags(d->mb);
+  if (sa * sb > 24) { if (sa >= sb) sa = 3; else sb = 3; }          // 6x6 -> 3x6: accumulators + two stages of loads <= 256 VGPRs
+  const int sfold = gram_fold(d, 64, 0, fold_sw);                    // (streaming form: short planes only)
+  // ---- the family.  Streaming: bf16 with 16-byte rows, and a slice its 32-bit element offsets can address
+  g.family = GRAM_LDS;
+  if (force >= 0) {
+    g.family = force;
+  } else if (bf && g.vec_ok && !MI_ENV(MI_GRAM_LDS) && (int64_t)std::max(d->ma, d->mb) * d->n < (1ll << 31)) {
+    // Measured (profiles/r01_s_gram_microbench.log): the streaming form wins while one or a few SMALL tiles cover the
+    // output (48x48 q k^T, the 144/254/127 x 48 weight gradients: 1.1-1.7x); with 96-wide or many tiles the operand
+    // re-reads and 1-wave occupancy lose to the LDS-staged 128x128 tiles (0.6-0.85x).
+    // ... and where the 128 x 128 LDS tiles would be mostly padding (288 x 96 fills 56% of 3 x 1 tiles: streaming 1.27x
+    // faster at bs 32; 96 x 255 and 510 x 96 fill 75% and stay on the LDS kernel; profiles/r01_y_gram_bs32.log)
+    const double lds_fill = (double)d->ma * d->mb / ((double)cdiv(d->ma, 32 * la) * 32 * la * cdiv(d->mb, 32 * lb) * 32 * lb);   // (the tile the LDS kernel would actually use)
+    bool stream;
+    if (MI_ENV(MI_GRAM_STREAM_ALL)) stream = true;                   // A/B switch
+    else if ((sfold ? (int64_t)d->batch * d->n : d->n) < 4096) stream = false;
+    else if (sa <= 4 && sb <= 4 && cdiv(d->ma, 16 * sa) * cdiv(d->mb, 16 * sb) <= 4) stream = true;
+    else stream = (d->ma > 64 || d->mb > 64) && lds_fill < 0.6;
+    if (stream) g.family = GRAM_STREAM;
+  }
+  // ---- the instance and the pixel split
+  const bool stream = g.family == GRAM_STREAM;
+  g.fa = stream ? sa : la;
+  g.fb = stream ? sb : lb;
+  g.unit = stream || bf ? 64 : 32;                                   // a streaming step / a staged chunk of 128 bytes per row
+  g.tiles_a = cdiv(d->ma, (stream ? 16 : 32) * g.fa);
+  g.tiles_b = cdiv(d->mb, (stream ? 16 : 32) * g.fb);
+  g.fold = stream ? sfold : gram_fold(d, g.unit, (int64_t)g.tiles_a * g.tiles_b * d->groups, fold_sw);
   g.Z = (g.fold ? 1 : d->batch) * d->groups;
-  g.nsteps = g.fold ? d->batch * g.fold : (int)cdiv(d->n, 64);
+  g.units = g.fold ? d->batch * g.fold : cdiv(d->n, g.unit);
   const int64_t tiles = (int64_t)g.tiles_a * g.tiles_b * g.Z;
-  int64_t want = gram_want(768) / (tiles > 0 ? tiles : 1);
-  const int64_t cap = g.nsteps / 32 > 0 ? g.nsteps / 32 : 1;   // >= 8 steps per wave: the prefetch pipeline needs a run
-  if (want > cap) want = cap;
-  if (want < 1) want = 1;
-  // several tiles re-read the same pixels: a split count that is a multiple of 8 puts them on one XCD (shared L2)
-  if (g.tiles_a * g.tiles_b > 1 && want >= 8) want = want / 8 * 8;
-  g.spb = (int)((cdiv(g.nsteps, want) + 3) / 4 * 4);
-  g.splits = (int)cdiv(g.nsteps, g.spb);
+  int64_t want = (want_sw ? atoi(want_sw) : (stream ? 768 : 512)) / (tiles > 0 ? tiles : 1);
+  if (stream) {
+    const int64_t cap = g.units / 32 > 0 ? g.units / 32 : 1;         // >= 8 steps per wave: the prefetch pipeline needs a run
+    want = std::max<int64_t>(std::min(want, cap), 1);
+    // several tiles re-read the same pixels: a split count that is a multiple of 8 puts them on one XCD (shared L2)
+    if (g.tiles_a * g.tiles_b > 1 && want >= 8) want = want / 8 * 8;
+    g.per_split = (int)((cdiv(g.units, want) + 3) / 4 * 4);
+  } else {
+    want = std::min<int64_t>(std::max<int64_t>(want, 1), g.units);
+    g.per_split = cdiv(g.units, want);
+  }
+  g.splits = cdiv(g.units, g.per_split);
+  g.grid = dim3(g.splits, g.tiles_a * g.tiles_b, g.Z);
+  g.block = dim3(256);
   g.part_bytes = align_up((size_t)g.splits * g.Z * d->ma * d->mb * sizeof(float), 256);
   g.ss_bytes = align_up((size_t)g.splits * g.Z * (d->ma + d->mb) * sizeof(float), 256);
+  // ---- how the launch finishes.  One split, one output slice per z, plain overwrite into a dense [Z][ma][mb] output: the
+  // kernel's "partial" IS the result, so it writes straight to the output and the reduce launch disappears (dM = dy v^T at
+  // C = 384: a 19 MB copy at 330 GB/s).  Else the partials are summed per output element, `total` of them in slice order:
+  // few slices, or enough output elements to fill the chip with one thread each, by the kernel that walks them in the thread.
+  const int64_t per = (int64_t)d->ma * d->mb;
+  g.images = g.fold ? 1 : d->batch;
+  g.total = g.splits * (d->sum_batch ? g.images : 1);
+  g.zo = d->sum_batch ? d->groups : g.Z;
+  if (g.splits == 1 && !d->sum_batch && !d->accumulate && d->out_ld == d->mb && d->out_zs == per) g.finish = GRAM_DIRECT;
+  else if (g.total <= 4) g.finish = GRAM_REDUCE_FEW4;
+  else if (g.total <= 16 || per * g.zo >= 16384) g.finish = GRAM_REDUCE_FEW16;
+  else g.finish = GRAM_REDUCE;
+  // A weight-gradient Gram that accumulates into a dense [ma][mb] gradient may leave its split partials in the deferred arena
+  // and have them summed by mi_deferred_flush (common.h): rows = splits x images of ma*mb floats, a plain fixed-order row sum.
+  g.deferrable = g.finish != GRAM_DIRECT && d->accumulate && d->sum_batch && d->groups == 1 && d->out_ld == d->mb && !g.ss;
   return g;
-}
-// One split, one output slice per z, plain overwrite into a dense [Z][ma][mb] output: the kernel's "partial" IS the result,
-// so it writes straight to the output and the reduce launch disappears (dM = dy v^T at C = 384: a 19 MB copy at 330 GB/s).
-static bool gram_direct(const mi_gram_desc* d, int splits) {
-  return splits == 1 && !d->sum_batch && !d->accumulate && d->out_ld == d->mb && d->out_zs == (int64_t)d->ma * d->mb;
-}
-static bool gram_stream_ok(const mi_gram_desc* d) {
-  if (d->dtype != MI_BF16 || MI_ENV(MI_GRAM_LDS)) return false;
-  bool ok = (d->n % 8 == 0) && aligned16(d->a) && aligned16(d->b);
-  ok = ok && d->a_bs % 8 == 0 && d->a_gs % 8 == 0 && d->b_bs % 8 == 0 && d->b_gs % 8 == 0;
-  if (!ok) return false;
-  // Measured (profiles/r01_s_gram_microbench.log): the streaming form wins while one or a few SMALL tiles cover the
-  // output (48x48 q k^T, the 144/254/127 x 48 weight gradients: 1.1-1.7x); with 96-wide or many tiles the operand
-  // re-reads and 1-wave occupancy lose to the LDS-staged 128x128 tiles (0.6-0.85x).
-  const GramSPlan g = gram_splan(d);
-  if (MI_ENV(MI_GRAM_STREAM_ALL)) return true;   // A/B switch
-  if ((g.fold ? (int64_t)d->batch * d->n : d->n) < 4096) return false;
-  if (g.fa <= 4 && g.fb <= 4 && g.tiles_a * g.tiles_b <= 4) return true;
-  // ... and where the 128 x 128 LDS tiles would be mostly padding (288 x 96 fills 56% of 3 x 1 tiles: streaming 1.27x
-  // faster at bs 32; 96 x 255 and 510 x 96 fill 75% and stay on the LDS kernel; profiles/r01_y_gram_bs32.log)
-  const GramPlan lp = gram_plan(d);                                  // (the tile the LDS kernel would actually use)
-  const double lds_fill = (double)d->ma * d->mb / ((double)lp.tiles_a * 32 * lp.FA * lp.tiles_b * 32 * lp.FB);
-  return (d->ma > 64 || d->mb > 64) && lds_fill < 0.6;
 }
 
 static int gram_check(const mi_gram_desc* d) {
@@ -597,126 +584,112 @@ static int gram_check(const mi_gram_desc* d) {
   return MI_OK;
 }
 
-}  // namespace mi
+// ---- the instances of each family, keyed on (dtype, fa, fb); fn[1]: with the row sums of squares.  The rectangular LDS tiles
+// have none: gram_plan gives them to calls without sumsq only.
+using GramFn = void (*)(GramK);
+using GramSFn = void (*)(GramK, int, int);
+template <typename Fn> struct GramInst { int dtype, fa, fb; Fn fn[2]; };
+static const GramInst<GramFn> GRAM_LDS_TABLE[] = {
+    {MI_F32, 2, 2, {gram_kernel<float, 2, 2, false>, gram_kernel<float, 2, 2, true>}},
+    {MI_F32, 4, 4, {gram_kernel<float, 4, 4, false>, gram_kernel<float, 4, 4, true>}},
+    {MI_BF16, 2, 2, {gram_kernel<bf16, 2, 2, false>, gram_kernel<bf16, 2, 2, true>}},
+    {MI_BF16, 3, 3, {gram_kernel<bf16, 3, 3, false>, gram_kernel<bf16, 3, 3, true>}},
+    {MI_BF16, 4, 4, {gram_kernel<bf16, 4, 4, false>, gram_kernel<bf16, 4, 4, true>}},
+    {MI_BF16, 3, 8, {gram_kernel<bf16, 3, 8, false>, nullptr}},
+    {MI_BF16, 4, 6, {gram_kernel<bf16, 4, 6, false>, nullptr}},
+    {MI_BF16, 6, 4, {gram_kernel<bf16, 6, 4, false>, nullptr}}};
+static const GramInst<GramSFn> GRAM_STREAM_TABLE[] = {
+    {MI_BF16, 3, 3, {gram_stream_kernel<3, 3, false>, gram_stream_kernel<3, 3, true>}},
+    {MI_BF16, 3, 4, {gram_stream_kernel<3, 4, false>, gram_stream_kernel<3, 4, true>}},
+    {MI_BF16, 3, 6, {gram_stream_kernel<3, 6, false>, gram_stream_kernel<3, 6, true>}},
+    {MI_BF16, 4, 3, {gram_stream_kernel<4, 3, false>, gram_stream_kernel<4, 3, true>}},
+    {MI_BF16, 4, 4, {gram_stream_kernel<4, 4, false>, gram_stream_kernel<4, 4, true>}},
+    {MI_BF16, 4, 6, {gram_stream_kernel<4, 6, false>, gram_stream_kernel<4, 6, true>}},
+    {MI_BF16, 6, 3, {gram_stream_kernel<6, 3, false>, gram_stream_kernel<6, 3, true>}},
+    {MI_BF16, 6, 4, {gram_stream_kernel<6, 4, false>, gram_stream_kernel<6, 4, true>}}};
+template <typename Fn, size_t N> static Fn gram_find(const GramInst<Fn> (&tab)[N], int dtype, const GramPlan& g) {
+  for (const GramInst<Fn>& e : tab)
+    if (e.dtype == dtype && e.fa == g.fa && e.fb == g.fb) return e.fn[g.ss];
+  return nullptr;
+}
 
-using namespace mi;
-
-static int gram_stream_launch(const mi_gram_desc* d, void* ws, hipStream_t st) {
-  const GramSPlan g = gram_splan(d);
+// Steps 4 and 5 of mi_gram: launch what the plan says, then finish as it says.
+static int gram_launch(const mi_gram_desc* d, const GramPlan& g, void* ws, hipStream_t st) {
+  const bool stream = g.family == GRAM_STREAM;
+  const GramFn fn = stream ? nullptr : gram_find(GRAM_LDS_TABLE, d->dtype, g);
+  const GramSFn sfn = stream ? gram_find(GRAM_STREAM_TABLE, d->dtype, g) : nullptr;
+  MI_CHECK_ARG(fn || sfn, "gram: no %s %s kernel with %d x %d fragments%s", stream ? "streaming" : "LDS-staged",
+               d->dtype == MI_BF16 ? "bf16" : "fp32", g.fa, g.fb, g.ss ? " and sumsq" : "");
   GramK k;
   k.a = d->a; k.a_bs = d->a_bs; k.a_gs = d->a_gs; k.ma = d->ma;
   k.b = d->b; k.b_bs = d->b_bs; k.b_gs = d->b_gs; k.mb = d->mb;
   k.n = d->n; k.groups = d->groups; k.Z = g.Z; k.fold = g.fold;
-  const bool direct = gram_direct(d, g.splits);
-  k.part = direct ? d->out : (float*)ws;
+  k.chunks_per_split = g.per_split; k.nchunks = g.units; k.tiles_b = g.tiles_b; k.vec_ok = g.vec_ok;
+  k.part = g.finish == GRAM_DIRECT ? d->out : (float*)ws;
+  k.ss_part = g.ss ? (float*)((char*)ws + g.part_bytes) : nullptr;
   bool deferred = false;
-  if (!direct && gram_deferrable(d)) {
+  if (g.deferrable) {
     float* arena = deferred_take(g.part_bytes / sizeof(float), st);
     if (arena) { k.part = arena; deferred = true; }
   }
-  k.ss_part = d->sumsq ? (float*)((char*)ws + g.part_bytes) : nullptr;
-  k.chunks_per_split = 0; k.nchunks = 0; k.tiles_b = g.tiles_b; k.vec_ok = 1;
-  dim3 grid(g.splits, g.tiles_a * g.tiles_b, g.Z), block(256);
-  MI_CHECK_ARG(grid.y <= 65535 && grid.z <= 65535, "gram: grid too large");
-  const bool ss = d->sumsq != nullptr;
+  const int64_t per = (int64_t)d->ma * d->mb;
   {
-    const double ZZ = (double)d->batch * d->groups;
-    ProfScope ps(st, d->sumsq ? K_GRAM_QK : K_GRAM, (double)(d->ma + d->mb) * d->n * ZZ * 2.0 + 4.0 * g.splits * g.Z * d->ma * d->mb,
-                 2.0 * d->ma * d->mb * (double)d->n * ZZ);
-#define GS_CASE(FA_, FB_)                                                                                           \
-  if (g.fa == FA_ && g.fb == FB_) {                                                                                 \
-    if (ss) hipLaunchKernelGGL((gram_stream_kernel<FA_, FB_, true>), grid, block, 0, st, k, g.spb, g.nsteps);       \
-    else hipLaunchKernelGGL((gram_stream_kernel<FA_, FB_, false>), grid, block, 0, st, k, g.spb, g.nsteps);         \
-  }
-    GS_CASE(3, 3) else GS_CASE(3, 4) else GS_CASE(3, 6) else GS_CASE(4, 3) else GS_CASE(4, 4) else GS_CASE(4, 6)
-    else GS_CASE(6, 3) else GS_CASE(6, 4) else { MI_CHECK_ARG(false, "gram: no streaming tile %dx%d", g.fa, g.fb); }
-#undef GS_CASE
+    const double ZZ = (double)d->batch * d->groups, es = (double)dtype_size(d->dtype);
+    ProfScope ps(st, g.ss ? K_GRAM_QK : K_GRAM, (double)(d->ma + d->mb) * d->n * ZZ * es + 4.0 * g.splits * g.Z * per,
+                 2.0 * per * (double)d->n * ZZ);
+    if (stream) hipLaunchKernelGGL(sfn, g.grid, g.block, 0, st, k, g.per_split, g.units);
+    else hipLaunchKernelGGL(fn, g.grid, g.block, 0, st, k);
   }
   MI_LAUNCH_CHECK();
   if (deferred) {
-    const int64_t per = (int64_t)d->ma * d->mb;
-    MI_TRY(launch_reduce_rows(k.part, d->out, (int64_t)g.splits * (g.fold ? 1 : d->batch), per, per, d->accumulate, 1.0f, st));
-  } else if (!direct) {
-    ProfScope ps2(st, K_GRAM_REDUCE, 4.0 * (g.splits + 1) * g.Z * d->ma * d->mb, (double)g.splits * g.Z * d->ma * d->mb);
-    const int zo = d->sum_batch ? d->groups : g.Z;
-    launch_gram_reduce(k.part, d->out, g.splits, g.fold ? 1 : d->batch, d->groups, d->ma, d->mb, d->out_ld, d->out_zs, d->sum_batch,
-                       d->accumulate, zo, st);
+    MI_TRY(launch_reduce_rows(k.part, d->out, (int64_t)g.splits * g.images, per, per, d->accumulate, 1.0f, st));
+  } else if (g.finish != GRAM_DIRECT) {
+    ProfScope ps2(st, K_GRAM_REDUCE, 4.0 * (g.splits + 1) * g.Z * per, (double)g.splits * g.Z * per);
+    const bool few = g.finish != GRAM_REDUCE;                        // one thread per output element / 16 slice-phases per element
+    const auto reduce = g.finish == GRAM_REDUCE_FEW4 ? gram_reduce_few_kernel<4> : (few ? gram_reduce_few_kernel<16> : gram_reduce_kernel);
+    hipLaunchKernelGGL(reduce, dim3(cdiv(per, few ? 256 : 16), g.zo), dim3(256), 0, st, (const float*)k.part, d->out,
+                       few ? g.total : g.splits, g.images, d->groups, d->ma, d->mb, d->out_ld, d->out_zs, d->sum_batch, d->accumulate);
     MI_LAUNCH_CHECK();
   }
-  if (ss) {
+  if (g.ss) {
     const int64_t cols = (int64_t)g.Z * (d->ma + d->mb);
     MI_TRY(launch_reduce_rows(k.ss_part, d->sumsq, g.splits, cols, cols, 0, 1.0f, st));
   }
   return MI_OK;
 }
 
+}  // namespace mi
+
+using namespace mi;
+
 extern "C" size_t mi_gram_workspace(const mi_gram_desc* d) {
   if (!d || d->ma <= 0 || d->mb <= 0 || d->n <= 0 || d->batch <= 0 || d->groups <= 0) return 0;
-  GramPlan g = gram_plan(d);
-  // sumsq presence may differ between the sizing call and the real call: always reserve it
-  const size_t ss = align_up((size_t)g.splits * g.Z * (d->ma + d->mb) * sizeof(float), 256);
-  const GramSPlan sp = gram_splan(d);  // either kernel may run (alignment decides at call time): cover both
-  return std::max(g.part_bytes + ss, sp.part_bytes + sp.ss_bytes);
+  // which family runs depends on pointer alignment (and the switches) at call time, and sumsq presence may differ between the
+  // sizing call and the real call: cover both families' plans, each with its sumsq rows (GramPlan::ws_bytes)
+  return max_of({gram_plan(d, GRAM_LDS).ws_bytes(), gram_plan(d, GRAM_STREAM).ws_bytes()});
 }
 
 extern "C" int mi_gram(const mi_gram_desc* d, void* ws, void* stream) {
   MI_TRY(gram_check(d));
   MI_CHECK_ARG(ws, "gram: null workspace");
-  if (gram_stream_ok(d)) return gram_stream_launch(d, ws, (hipStream_t)stream);
-  GramPlan g = gram_plan(d);
-  hipStream_t st = (hipStream_t)stream;
-  GramK k;
-  k.a = d->a; k.a_bs = d->a_bs; k.a_gs = d->a_gs; k.ma = d->ma;
-  k.b = d->b; k.b_bs = d->b_bs; k.b_gs = d->b_gs; k.mb = d->mb;
-  k.n = d->n; k.groups = d->groups; k.Z = g.Z; k.fold = g.fold;
-  const bool direct = gram_direct(d, g.splits);
-  k.part = direct ? d->out : (float*)ws;
-  bool deferred = false;
-  if (!direct && gram_deferrable(d)) {
-    float* arena = deferred_take(g.part_bytes / sizeof(float), st);
-    if (arena) { k.part = arena; deferred = true; }
-  }
-  k.ss_part = d->sumsq ? (float*)((char*)ws + g.part_bytes) : nullptr;
-  k.chunks_per_split = g.cps; k.nchunks = g.nchunks; k.tiles_b = g.tiles_b;
-  const int64_t vec = d->dtype == MI_BF16 ? 8 : 4;
-  bool ok = (d->n % vec == 0) && aligned16(d->a) && aligned16(d->b);
-  ok = ok && d->a_bs % vec == 0 && d->a_gs % vec == 0 && d->b_bs % vec == 0 && d->b_gs % vec == 0;
-  k.vec_ok = ok ? 1 : 0;
-  dim3 grid(g.splits, g.tiles_a * g.tiles_b, g.Z), block(256);
-  MI_CHECK_ARG(grid.y <= 65535 && grid.z <= 65535, "gram: grid too large");
-  const bool ss = d->sumsq != nullptr;
-  const double es = d->dtype == MI_BF16 ? 2.0 : 4.0;
-  {
-  const double ZZ = (double)d->batch * d->groups;
-  ProfScope ps(st, d->sumsq ? K_GRAM_QK : K_GRAM, (double)(d->ma + d->mb) * d->n * ZZ * es + 4.0 * g.splits * g.Z * d->ma * d->mb,
-               2.0 * d->ma * d->mb * (double)d->n * ZZ);
-#define GRAM_CASE(T, FA_, FB_)                                                                      \
-  do {                                                                                              \
-    if (ss) hipLaunchKernelGGL((gram_kernel<T, FA_, FB_, true>), grid, block, 0, st, k);            \
-    else hipLaunchKernelGGL((gram_kernel<T, FA_, FB_, false>), grid, block, 0, st, k);              \
-  } while (0)
-  if (d->dtype == MI_F32) { if (g.FA == 4) GRAM_CASE(float, 4, 4); else GRAM_CASE(float, 2, 2); }
-  else if (g.FA == 3 && g.FB == 3) GRAM_CASE(bf16, 3, 3);
-  else if (g.FA == 3 && g.FB == 8) GRAM_CASE(bf16, 3, 8);
-  else if (g.FA == 4 && g.FB == 6) GRAM_CASE(bf16, 4, 6);
-  else if (g.FA == 6 && g.FB == 4) GRAM_CASE(bf16, 6, 4);
-  else { if (g.FA == 4) GRAM_CASE(bf16, 4, 4); else GRAM_CASE(bf16, 2, 2); }
-#undef GRAM_CASE
-  }
-  MI_LAUNCH_CHECK();
-  if (deferred) {
-    const int64_t per = (int64_t)d->ma * d->mb;
-    MI_TRY(launch_reduce_rows(k.part, d->out, (int64_t)g.splits * (g.fold ? 1 : d->batch), per, per, d->accumulate, 1.0f, st));
-  } else if (!direct) {
-    ProfScope ps2(st, K_GRAM_REDUCE, 4.0 * (g.splits + 1) * g.Z * d->ma * d->mb, (double)g.splits * g.Z * d->ma * d->mb);
-    const int zo = d->sum_batch ? d->groups : g.Z;
-    launch_gram_reduce(k.part, d->out, g.splits, g.fold ? 1 : d->batch, d->groups, d->ma, d->mb, d->out_ld, d->out_zs, d->sum_batch,
-                       d->accumulate, zo, st);
-    MI_LAUNCH_CHECK();
-  }
-  if (ss) {
-    const int64_t cols = (int64_t)g.Z * (d->ma + d->mb);
-    MI_TRY(launch_reduce_rows(k.ss_part, d->sumsq, g.splits, cols, cols, 0, 1.0f, st));
-  }
+  const GramPlan g = gram_plan(d);
+  MI_CHECK_ARG(g.grid.y <= 65535 && g.grid.z <= 65535, "gram: grid too large");
+  return gram_launch(d, g, ws, (hipStream_t)stream);
+}
+
+// What mi_gram runs for this descriptor under the current switches.  Host-side only: the same gram_plan, and pointers are read
+// for their alignment only (any 16-byte-aligned placeholder will do).  out[22]: family (0 LDS-staged, 1 streaming), fragments
+// per tile side fa, fb (32 rows each; streaming: 16), sumsq, contraction unit in pixels, units in total, units per split, splits,
+// tiles over A, tiles over B, Z, fold (units per image, 0 = per image), 16-byte rows, grid x / y / z, block, partial bytes, sumsq
+// row bytes, finish (0 direct into the output, 1 reduce few<4>, 2 reduce few<16>, 3 general reduce), partials may go to the
+// deferred arena, workspace bytes.
+extern "C" int mi_gram_plan(const mi_gram_desc* d, int64_t* out) {
+  MI_TRY(gram_check(d));
+  MI_CHECK_ARG(out, "gram_plan: null pointer");
+  const GramPlan g = gram_plan(d);
+  const int64_t v[22] = {g.family, g.fa, g.fb, g.ss, g.unit, g.units, g.per_split, g.splits, g.tiles_a, g.tiles_b, g.Z, g.fold, g.vec_ok,
+                         g.grid.x, g.grid.y, g.grid.z, g.block.x, (int64_t)g.part_bytes, (int64_t)g.ss_bytes, g.finish, g.deferrable,
+                         (int64_t)g.ws_bytes()};
+  memcpy(out, v, sizeof(v));
   return MI_OK;
 }

@@ -35,6 +35,23 @@ struct PwPlan {
   bool cacheable;                                // may use the packed-weight cache (static weights, own pack)
   size_t ws_bytes() const { return family == PW_LDS ? align_up(lds_image, 256) : bytes; }   // what this call's workspace holds
 };
+// What one mi_gram call runs: filled by gram_plan (gram.hip), the ONE place that decides it; mi_gram launches and finishes as it
+// says, mi_gram_workspace sizes from it, mi_gram_plan reports it.
+enum GramFamily { GRAM_LDS = 0, GRAM_STREAM };   // LDS-staged tiles (either dtype) / register-streaming (bf16, 16-byte rows)
+enum GramFinish { GRAM_DIRECT = 0, GRAM_REDUCE_FEW4, GRAM_REDUCE_FEW16, GRAM_REDUCE };   // straight into the output / which kernel sums the partials
+struct GramPlan {
+  int family;                                    // GramFamily
+  int fa, fb; bool ss;                           // the instance: fragments per tile side (32 rows each; streaming: 16), sumsq rows (their row sum follows)
+  int unit, units, per_split;                    // contraction unit in pixels (32 / 64), units in total (folded: of all images), per workgroup
+  int splits, tiles_a, tiles_b, Z, fold;         // fold > 0: the batch is chained along the pixel axis, `fold` units per image
+  bool vec_ok;                                   // 16-byte rows: every pointer and stride allows vector access
+  dim3 grid, block;                              // the launch
+  size_t part_bytes, ss_bytes;                   // partial tiles [splits][Z][ma][mb]; sumsq rows [splits][Z][ma+mb] (sized whether asked for or not)
+  int finish;                                    // GramFinish
+  bool deferrable;                               // the partials may go to the deferred arena instead (summed at its flush)
+  int images, total, zo;                         // the reduce: images a partial keeps apart, partials per output element, output slices
+  size_t ws_bytes() const { return part_bytes + ss_bytes; }   // the workspace of this plan, sumsq rows reserved
+};
 // Launch with dynamic LDS: above 64 KiB the kernel's limit has to be raised first.
 template <typename... P, typename... A>
 static inline int launch_dyn_lds(void (*kernel)(P...), dim3 grid, dim3 block, size_t lds, hipStream_t st, A... args) {
@@ -151,8 +168,10 @@ static inline mi_gram_desc wgrad_gram(const void* dy, int m, const void* x, int 
   g.sum_batch = sum_batch; g.accumulate = accumulate; g.out = out; g.out_ld = k; g.out_zs = sum_batch ? 0 : (int64_t)m * k;
   return g;
 }
-// Workspaces are sized, and coverage is answered, before any tensor exists.  The planners (pw_plan, gram_plan) read shapes,
-// strides and whether the operands are 16-byte aligned, never the memory: one aligned placeholder stands in for every pointer.
+// Workspaces are sized, and coverage is answered, before any tensor exists.  The planners (pw_plan in pw_gemm.hip, gram_plan in
+// gram.hip: each the one place that decides its family's launches, and what mi_pw_gemm_workspace / mi_gram_workspace size from)
+// read shapes, strides and whether the operands are 16-byte aligned, never the memory: one aligned placeholder stands in for
+// every pointer.
 static void* const PROBE_PTR = (void*)256;
 static inline mi_pw_desc probe1x1(int K, int M, bool transposed, int B, int64_t N, int dtype, int64_t x_bs = 0, int64_t y_bs = 0) {
   return conv1x1(PROBE_PTR, K, (const float*)PROBE_PTR, transposed, transposed ? M : K, nullptr, nullptr, PROBE_PTR, M, B, N, dtype,

@@ -309,6 +309,48 @@ def pw_plan(d: "L.PwDesc") -> dict:
             "workspace": out[17]}
 
 
+GRAM_FAMILIES = ("lds", "stream")
+GRAM_FINISH = ("direct", "few4", "few16", "general")
+
+
+def gram_probe(ma: int, mb: int, N: int, dtype: torch.dtype, B: int = 1, groups: int = 1, sum_batch: bool = False, sumsq: bool = False,
+               accumulate: bool = False, out_ld: int = 0, misalign: int = 0) -> "L.GramDesc":
+    """A dense descriptor of placeholder pointers for gram_plan and mi_gram_workspace: a [B, groups*ma, N], b [B, groups*mb, N],
+    out [B*groups or groups, ma, mb] with row stride out_ld (0: mb).  misalign: bytes added to the a pointer."""
+    d = L.GramDesc()
+    d.a, d.a_bs, d.a_gs, d.ma = PW_PROBE + misalign, groups * ma * N, ma * N, ma
+    d.b, d.b_bs, d.b_gs, d.mb = PW_PROBE, groups * mb * N, mb * N, mb
+    d.n, d.batch, d.groups, d.dtype = N, B, groups, _dtype_code(dtype)
+    d.sum_batch, d.accumulate = int(sum_batch), int(accumulate)
+    d.out, d.out_ld, d.out_zs, d.sumsq = PW_PROBE, out_ld or mb, ma * mb, (PW_PROBE if sumsq else None)
+    return d
+
+
+def gram_desc(a: Tensor, b: Tensor, groups: int = 1, sum_batch: bool = False, want_sumsq: bool = False, out: Optional[Tensor] = None,
+              accumulate: bool = False, ss: Optional[Tensor] = None) -> "L.GramDesc":
+    """The descriptor ``gram`` runs for these operands.  out / ss not allocated yet keep the probe's placeholder: enough for
+    gram_plan, which reads pointers for their alignment only."""
+    B, Ca, H, W = a.shape
+    d = gram_probe(Ca // groups, b.shape[1] // groups, H * W, a.dtype, B=B, groups=groups, sum_batch=sum_batch, sumsq=want_sumsq,
+                   accumulate=accumulate)
+    d.a, d.b = _p(a), _p(b)
+    if out is not None:
+        d.out = _p(out)
+    if ss is not None:
+        d.sumsq = _p(ss)
+    return d
+
+
+def gram_plan(d: "L.GramDesc") -> dict:
+    """What mi_gram runs for ``d`` under the current MI_GRAM_* switches (mi_gram_plan; no GPU work)."""
+    out = (L.c_i64 * 22)()
+    L.check(L.lib().mi_gram_plan(C.byref(d), out), "gram_plan")
+    return {"family": GRAM_FAMILIES[out[0]], "fa": out[1], "fb": out[2], "sumsq": bool(out[3]), "unit": out[4], "units": out[5],
+            "per_split": out[6], "splits": out[7], "tiles_a": out[8], "tiles_b": out[9], "Z": out[10], "fold": out[11],
+            "vec_ok": bool(out[12]), "grid": (out[13], out[14], out[15]), "block": out[16], "part_bytes": out[17], "ss_bytes": out[18],
+            "finish": GRAM_FINISH[out[19]], "deferrable": bool(out[20]), "workspace": out[21]}
+
+
 def gram(a: Tensor, b: Tensor, groups: int = 1, sum_batch: bool = False, want_sumsq: bool = False,
          out: Optional[Tensor] = None, accumulate: bool = False):
     """G[z][i][j] = sum_n a[z][i][n] b[z][j][n] with a,b [B, groups*m, H, W] split head-major into groups.
@@ -316,9 +358,7 @@ def gram(a: Tensor, b: Tensor, groups: int = 1, sum_batch: bool = False, want_su
     trainer's flat buffer; under the trainer's deferral window the final sum then joins the one table-driven reduction launch."""
     _gpu(a, b, out)
     B, Ca, H, W = a.shape
-    Cb = b.shape[1]
-    N = H * W
-    ma, mb = Ca // groups, Cb // groups
+    ma, mb = Ca // groups, b.shape[1] // groups
     Z = groups if sum_batch else B * groups
     if out is None:
         if accumulate:
@@ -327,12 +367,7 @@ def gram(a: Tensor, b: Tensor, groups: int = 1, sum_batch: bool = False, want_su
     elif out.dtype != torch.float32 or out.numel() != Z * ma * mb:
         raise ValueError(f"gram: out must be float32 with {Z * ma * mb} elements")
     ss = torch.empty((B * groups, ma + mb), dtype=torch.float32, device=a.device) if want_sumsq else None
-    d = L.GramDesc()
-    d.a, d.a_bs, d.a_gs, d.ma = _p(a), Ca * N, ma * N, ma
-    d.b, d.b_bs, d.b_gs, d.mb = _p(b), Cb * N, mb * N, mb
-    d.n, d.batch, d.groups, d.dtype = N, B, groups, _dt(a)
-    d.sum_batch, d.accumulate = int(sum_batch), int(accumulate)
-    d.out, d.out_ld, d.out_zs, d.sumsq = _p(out), mb, ma * mb, _p(ss)
+    d = gram_desc(a, b, groups, sum_batch, want_sumsq, out, accumulate, ss)
     ws = _ws(L.lib().mi_gram_workspace(C.byref(d)), a.device)
     L.check(L.lib().mi_gram(C.byref(d), _p(ws), _stream()), "gram")
     return (out, ss) if want_sumsq else out
@@ -353,6 +388,13 @@ def conv1x1_dgrad_panel(dy: Tensor, w2: Tensor, k0: int, k: int) -> Tensor:
     return dx
 
 
+def wgrad_panel_desc(dy: Tensor, xp: Tensor, dw2: Tensor, k0: int, accumulate: bool) -> "L.GramDesc":
+    """The Gram of one K-panel: dy . xp^T summed over the batch into columns k0 .. of dw2 (row stride: dw2's full width)."""
+    d = gram_desc(dy, xp, 1, True, accumulate=accumulate)
+    d.out, d.out_ld = _p(dw2) + 4 * k0, dw2.shape[1]
+    return d
+
+
 def conv1x1_wgrad_panels(dy: Tensor, x1: Tensor, x2: Optional[Tensor], dw2: Tensor, accumulate: bool) -> None:
     """dw2[:, panel] (+)= dy . x^T for the K-panels x1, x2 of a 1x1 conv: each Gram lands in its column block of dw2 [M, K1+K2]."""
     B, M, H, W = dy.shape
@@ -362,12 +404,7 @@ def conv1x1_wgrad_panels(dy: Tensor, x1: Tensor, x2: Optional[Tensor], dw2: Tens
         if xp is None:
             continue
         k = xp.shape[1]
-        d = L.GramDesc()
-        d.a, d.a_bs, d.ma = _p(dy), M * N, M
-        d.b, d.b_bs, d.mb = _p(xp), k * N, k
-        d.n, d.batch, d.groups, d.dtype = N, B, 1, _dt(dy)
-        d.sum_batch, d.accumulate = 1, int(accumulate)
-        d.out, d.out_ld, d.out_zs = _p(dw2) + 4 * k0, dw2.shape[1], 0
+        d = wgrad_panel_desc(dy, xp, dw2, k0, accumulate)
         ws = _blob(L.lib().mi_gram_workspace(C.byref(d)), dy.device)
         L.check(L.lib().mi_gram(C.byref(d), _p(ws), _stream()), "gram(wgrad panel)")
         k0 += k

@@ -215,6 +215,13 @@ typedef struct {
 } mi_gram_desc;
 size_t mi_gram_workspace(const mi_gram_desc* d);
 int mi_gram(const mi_gram_desc* d, void* ws, void* stream);
+/* What mi_gram runs for d under the current A/B switches (host-only; the pointers are read for their 16-byte alignment only, so
+ * placeholders will do).  out[22]: family (0 LDS-staged, 1 streaming), fragments per tile side over A and over B (32 rows each;
+ * streaming: 16), sumsq, contraction unit in pixels, units in total, units per split, splits, tiles over A, tiles over B, Z
+ * (slices of partials), fold (units per image when the batch is chained along the pixel axis, else 0), 16-byte rows, grid x, y, z,
+ * block, partial bytes, sumsq row bytes, finish (0 direct into the output, 1 reduce few<4>, 2 reduce few<16>, 3 general reduce),
+ * partials may go to the deferred arena, workspace bytes of this plan (sumsq rows reserved). */
+int mi_gram_plan(const mi_gram_desc* d, int64_t* out);
 
 /* ------------------------------------------------------------------------
  * MDTA — Attention.forward / backward  (Restormer.py:99-132; moce_ir.py:283-321;

@@ -392,3 +392,143 @@ def test_pw_plan_argument_errors(lib):
     assert L.mi_pw_plan(C.byref(d), None) == -1 and b"pw_plan: null pointer" in L.mi_last_error()
     d.dtype = 7
     assert L.mi_pw_plan(C.byref(d), out) == -1 and b"bad dtype 7" in L.mi_last_error()
+
+
+# --------------------------------------------------------------------------- the Gram plan (mi_gram_plan)
+GRAM_SWITCHES = ("MI_GRAM_LDS", "MI_GRAM_STREAM_ALL", "MI_GRAM_RECT", "MI_GRAM_FOLD", "MI_GRAM_WANT")
+GRAM_MS = (16, 30, 48, 64, 65, 96, 97, 128, 129, 144, 192, 193, 254, 288, 384, 385, 510, 1021, 2042)
+GRAM_NS = (35, 64, 1024, 4096, 65536)
+GRAM_SWEEP_CASES = 19 * 19 * 5 * 2 * 3 * 2 * 3
+
+
+def _gram_switches(monkeypatch, **env):
+    for k in GRAM_SWITCHES:
+        monkeypatch.delenv(k, raising=False)
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+
+
+def _gram_sweep():
+    """(dtype, descriptor) over the shape classes; sumsq only where legal (not with sum_batch)."""
+    import itertools
+    from image_restoration_amd import ops
+    for ma, mb, N, dtype, B, groups, (sum_batch, sumsq) in itertools.product(
+            GRAM_MS, GRAM_MS, GRAM_NS, (torch.float32, torch.bfloat16), (1, 2, 32), (1, 2), ((False, False), (False, True), (True, False))):
+        yield dtype, ops.gram_probe(ma, mb, N, dtype, B=B, groups=groups, sum_batch=sum_batch, sumsq=sumsq)
+
+
+def test_gram_plan_pinned_for_every_family_and_finish(lib, monkeypatch):
+    """ops.gram_plan, every field, for one descriptor per family, tile and finish kind.  The values are what the launchers decided
+    BEFORE the plan became the one place of decision.  Family, tile (the kernel instance's fragment counts and its sumsq flag),
+    grid, block, fold, vec_ok and the reduce kernel that follows come from that commit's own planners and launch branches, asked
+    through a debug export of a build of it (which agreed with mi_gram_plan on every one of these fields over the whole sweep
+    below, aligned and not, accumulating and not).  What no launch shows follows the formulas of that launcher: unit = 32 pixels
+    (fp32) / 64, units = ceil(n / unit) (folded: batch * n / unit), the split rule (512 / tiles workgroups, LDS; 768 / tiles
+    capped at units / 32 and rounded up to 4 steps, streaming), part_bytes = splits * Z * ma * mb floats and ss_bytes = splits *
+    Z * (ma + mb) floats, each rounded up to 256; workspace = part_bytes + ss_bytes."""
+    from image_restoration_amd import ops
+    f32, bf16 = torch.float32, torch.bfloat16
+    _gram_switches(monkeypatch)
+
+    def plan(ma, mb, N, dtype, **kw):
+        return ops.gram_plan(ops.gram_probe(ma, mb, N, dtype, **kw))
+
+    def want(family, fa, fb, unit, units, per_split, splits, tiles, Z, part, ss, finish, **kw):
+        base = {"family": family, "fa": fa, "fb": fb, "sumsq": False, "unit": unit, "units": units, "per_split": per_split,
+                "splits": splits, "tiles_a": tiles[0], "tiles_b": tiles[1], "Z": Z, "fold": 0, "vec_ok": True,
+                "grid": (splits, tiles[0] * tiles[1], Z), "block": 256, "part_bytes": part, "ss_bytes": ss, "finish": finish,
+                "deferrable": False, "workspace": part + ss}
+        return {**base, **kw}
+
+    # the LDS-staged tiles: fp32 2 x 2 and 4 x 4, bf16 3 x 3 with sumsq, the three rectangular ones (folded weight gradients)
+    assert plan(48, 48, 1024, f32, B=2, sumsq=True) == want("lds", 2, 2, 32, 32, 1, 32, (1, 1), 2, 589824, 24576, "general", sumsq=True)
+    assert plan(144, 48, 1024, f32, B=2, sum_batch=True) == want("lds", 4, 4, 32, 32, 1, 32, (2, 1), 2, 1769472, 49152, "general")
+    assert plan(96, 96, 1024, bf16, B=2, sumsq=True) == want("lds", 3, 3, 64, 16, 1, 16, (1, 1), 2, 1179648, 24576, "few16", sumsq=True)
+    assert plan(96, 255, 1024, bf16, B=2, sum_batch=True) == want("lds", 3, 8, 64, 32, 1, 32, (1, 1), 1, 3133440, 45056, "few16", fold=16)
+    assert plan(576, 192, 1024, bf16, B=2, sum_batch=True) == want("lds", 4, 6, 64, 32, 1, 32, (5, 1), 1, 14155776, 98304, "few16", fold=16)
+    assert plan(192, 510, 1024, bf16, B=2, sum_batch=True) == want("lds", 6, 4, 64, 32, 1, 32, (1, 4), 1, 12533760, 89856, "few16", fold=16)
+    # streaming: one tile (per image, two heads, sumsq), several tiles (summed per image), folded
+    assert plan(48, 48, 4096, bf16, B=2, groups=2, sumsq=True) == want("stream", 3, 3, 64, 64, 32, 2, (1, 1), 4, 73728, 3072, "few4", sumsq=True)
+    assert plan(254, 48, 4096, bf16, B=2, sum_batch=True) == want("stream", 4, 3, 64, 64, 32, 2, (4, 1), 2, 195072, 4864, "few4")
+    assert plan(144, 48, 1024, bf16, B=4, sum_batch=True) == want("stream", 3, 3, 64, 64, 32, 2, (3, 1), 1, 55296, 1536, "few4", fold=16)
+    # the finish kinds: straight into the output; deferrable; reduce few<4> / few<16> / general
+    assert plan(48, 48, 64, bf16, B=2) == want("lds", 2, 2, 64, 1, 1, 1, (1, 1), 2, 18432, 768, "direct")
+    assert plan(48, 48, 1024, bf16, B=2, sum_batch=True, accumulate=True) == want("lds", 2, 2, 64, 32, 1, 32, (1, 1), 1, 294912, 12288,
+                                                                                 "general", fold=16, deferrable=True)
+    assert plan(48, 48, 256, bf16, B=2) == want("lds", 2, 2, 64, 4, 1, 4, (1, 1), 2, 73728, 3072, "few4")
+    assert plan(48, 48, 256, bf16, B=2, sum_batch=True) == want("lds", 2, 2, 64, 8, 1, 8, (1, 1), 1, 73728, 3072, "few16", fold=4)
+    assert plan(48, 48, 1024, f32, B=5, sum_batch=True) == want("lds", 2, 2, 32, 32, 1, 32, (1, 1), 5, 1474560, 61440, "general")
+    # a column block of a wider gradient (out_ld > mb) is summed at once, never deferred
+    assert plan(144, 48, 1024, bf16, B=2, sum_batch=True, accumulate=True, out_ld=96) == want("lds", 4, 4, 64, 32, 1, 32, (2, 1), 1, 884736,
+                                                                                            24576, "general", fold=16)
+    # a pointer off the 16-byte grid, or pixel rows that are no multiple of 8: the LDS-staged kernel with scalar loads
+    assert plan(48, 48, 4096, bf16, B=2, misalign=2) == want("lds", 2, 2, 64, 64, 1, 64, (1, 1), 2, 1179648, 49152, "general", vec_ok=False)
+    assert plan(48, 48, 35, bf16, B=2) == want("lds", 2, 2, 64, 1, 1, 1, (1, 1), 2, 18432, 768, "direct", vec_ok=False)
+
+
+def test_gram_workspace_follows_the_plan(lib, monkeypatch):
+    """mi_gram_workspace covers the plan of the descriptor as given and of the same call with `a` off the 16-byte grid, over
+    every shape class of the sweep."""
+    from image_restoration_amd import ops
+    _gram_switches(monkeypatch)
+    L, n = lib.lib(), 0
+    for dtype, d in _gram_sweep():
+        ws = L.mi_gram_workspace(C.byref(d))
+        p = ops.gram_plan(d)
+        d.a += 2
+        q = ops.gram_plan(d)
+        assert q["family"] == "lds" and not q["vec_ok"] and ws >= p["workspace"] and ws >= q["workspace"], (p, q, ws)
+        n += 1
+    assert n == GRAM_SWEEP_CASES
+
+
+# every instance the launcher's tables hold: (family, dtype, fa, fb, sumsq).  The rectangular LDS tiles go to calls without sumsq only.
+GRAM_INSTANCES = (
+    {("lds", dt, f, f, ss) for dt, fs in (("f32", (2, 4)), ("bf16", (2, 3, 4))) for f in fs for ss in (False, True)} |
+    {("lds", "bf16", fa, fb, False) for fa, fb in ((3, 8), (4, 6), (6, 4))} |
+    {("stream", "bf16", fa, fb, ss) for fa in (3, 4, 6) for fb in (3, 4, 6) if (fa, fb) != (6, 6) for ss in (False, True)})
+
+
+def test_gram_every_instance_is_reachable_and_none_unknown(lib, monkeypatch):
+    """The sweep under the default switches and under each A/B switch reaches every kernel instance of the launcher's two tables
+    and names none outside them.  A threshold that strands an instance, or a plan the launcher would refuse, shows up here."""
+    from image_restoration_amd import ops
+    reached = set()
+    for env in ({}, {"MI_GRAM_LDS": "1"}, {"MI_GRAM_STREAM_ALL": "1"}, {"MI_GRAM_RECT": "0"}, {"MI_GRAM_FOLD": "0"}, {"MI_GRAM_FOLD": "2"}):
+        _gram_switches(monkeypatch, **env)
+        n = 0
+        for dtype, d in _gram_sweep():
+            p = ops.gram_plan(d)
+            reached.add((p["family"], "bf16" if dtype == torch.bfloat16 else "f32", p["fa"], p["fb"], p["sumsq"]))
+            n += 1
+        assert n == GRAM_SWEEP_CASES
+    assert reached == GRAM_INSTANCES, "stranded: %r; unknown to the launcher: %r" % (
+        sorted(GRAM_INSTANCES - reached, key=str), sorted(reached - GRAM_INSTANCES, key=str))
+    assert len(GRAM_INSTANCES) == 29 and {k[0] for k in reached} == set(ops.GRAM_FAMILIES)
+
+
+def test_gram_plan_argument_errors_and_the_32_bit_guard(lib, monkeypatch):
+    from image_restoration_amd import ops
+    _gram_switches(monkeypatch)
+    L, out = lib.lib(), (C.c_int64 * 22)()
+    bf16 = torch.bfloat16
+    d = ops.gram_probe(48, 48, 64, torch.float32)
+    assert L.mi_gram_plan(None, out) == -1 and b"null pointer" in L.mi_last_error()
+    assert L.mi_gram_plan(C.byref(d), None) == -1 and b"gram_plan: null pointer" in L.mi_last_error()
+    for field, value, msg in (("dtype", 7, b"bad dtype 7"), ("ma", 0, b"bad shape"), ("out_ld", 47, b"out_ld < mb"), ("a", None, b"null pointer")):
+        e = ops.gram_probe(48, 48, 64, torch.float32)
+        setattr(e, field, value)
+        assert L.mi_gram_plan(C.byref(e), out) == -1 and msg in L.mi_last_error(), field
+    e = ops.gram_probe(48, 48, 64, torch.float32, sum_batch=True, sumsq=True)
+    assert L.mi_gram_plan(C.byref(e), out) == -1 and b"sumsq with sum_batch" in L.mi_last_error()
+    # the streaming kernel addresses a slice with 32-bit element offsets: max(ma, mb) * n < 2^31, beyond it the LDS-staged form
+    # (64-bit addressing) - also under the switch that streams everything
+    N = 4096 * 4096
+    assert ops.gram_plan(ops.gram_probe(127, 48, N, bf16))["family"] == "stream"                 # 127 * 2^24 < 2^31
+    assert ops.gram_plan(ops.gram_probe(128, 48, N, bf16))["family"] == "lds"                    # = 2^31
+    assert ops.gram_plan(ops.gram_probe(48, 128, N, bf16))["family"] == "lds"
+    big = ops.gram_plan(ops.gram_probe(254, 48, N, bf16))
+    assert (big["family"], big["fa"], big["fb"], big["vec_ok"]) == ("lds", 4, 4, True)
+    _gram_switches(monkeypatch, MI_GRAM_STREAM_ALL="1")
+    assert ops.gram_plan(ops.gram_probe(254, 48, N, bf16))["family"] == "lds"
+    assert ops.gram_plan(ops.gram_probe(127, 48, N, bf16))["family"] == "stream"

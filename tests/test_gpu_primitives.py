@@ -183,23 +183,47 @@ def test_conv1x1_ragged_and_two_panels(dtype, shape):
 
 
 # --------------------------------------------------------------------------- Gram
+# Every call first asks ops.gram_plan of the descriptor it is about to run (ops.gram_desc: the one ops.gram builds) and asserts
+# what the case is there for, so a retuned threshold cannot move a case to another kernel unnoticed.
+# (ma, mb, groups, hw) -> per dtype (fp32, bf16): (finish of the per-image call with sumsq, finish of the call summed over the batch)
+GRAM_EXACT = {(48, 48, 1, (16, 16)): (("few16", "few16"), ("few4", "few16")),
+              (48, 48, 2, (8, 40)): (("few16", None), ("few16", None)),
+              (96, 96, 1, (32, 32)): (("few16", "general"), ("few16", "general")),
+              (16, 16, 8, (4, 4)): (("direct", None), ("direct", None)),
+              (254, 48, 1, (16, 24)): (("few16", "general"), ("few16", "few16")),
+              (30, 70, 1, (5, 7)): (("few4", "few4"), ("direct", "few4")),
+              (48, 48, 2, (64, 64)): (("general", None), ("few4", None))}     # 4096 pixels: bf16 streams, one 48 x 48 tile per head
+
+
+def _planned(o, a, b, groups=1, sum_batch=False, want_sumsq=False, **want):
+    """The plan of the call ops.gram(a, b, groups, sum_batch, want_sumsq) is about to make, with `want` asserted on it."""
+    p = o.gram_plan(o.gram_desc(a, b, groups, sum_batch, want_sumsq))
+    assert {k: p[k] for k in want} == want, p
+    return p
+
+
 @pytest.mark.parametrize("dtype", DT)
-@pytest.mark.parametrize("ma,mb,groups,hw", [(48, 48, 1, (16, 16)), (48, 48, 2, (8, 40)), (96, 96, 1, (32, 32)),
-                                             (16, 16, 8, (4, 4)), (254, 48, 1, (16, 24)), (30, 70, 1, (5, 7))])
+@pytest.mark.parametrize("ma,mb,groups,hw", list(GRAM_EXACT))
 def test_gram_exact_on_integers_and_sumsq(dtype, ma, mb, groups, hw):
     o = ops()
     B = 2
+    bf = dtype == torch.bfloat16
+    fin_ss, fin_sum = GRAM_EXACT[(ma, mb, groups, hw)][bf]
+    family = "stream" if bf and hw == (64, 64) else "lds"              # (every other plane is shorter than 4096 pixels)
     a = ints((B, groups * ma, *hw), 51, -2, 3).to(dtype)
     b = ints((B, groups * mb, *hw), 52, -2, 3).to(dtype)
     af = a.float().reshape(B, groups, ma, -1)
-    bf = b.float().reshape(B, groups, mb, -1)
-    ref = torch.einsum("bgin,bgjn->bgij", af, bf).reshape(B * groups, ma, mb)
-    out, ss = o.gram(a.to(DEV), b.to(DEV), groups, False, True)
+    bf_ = b.float().reshape(B, groups, mb, -1)
+    ref = torch.einsum("bgin,bgjn->bgij", af, bf_).reshape(B * groups, ma, mb)
+    a, b = a.to(DEV), b.to(DEV)
+    _planned(o, a, b, groups, False, True, family=family, finish=fin_ss, sumsq=True, vec_ok=(hw[0] * hw[1]) % 8 == 0)
+    out, ss = o.gram(a, b, groups, False, True)
     assert torch.equal(out.cpu(), ref)
-    ssr = torch.cat([af.pow(2).sum(-1), bf.pow(2).sum(-1)], -1).reshape(B * groups, ma + mb)
+    ssr = torch.cat([af.pow(2).sum(-1), bf_.pow(2).sum(-1)], -1).reshape(B * groups, ma + mb)
     assert torch.equal(ss.cpu(), ssr)
     if groups == 1:
-        outb = o.gram(a.to(DEV), b.to(DEV), 1, True)
+        _planned(o, a, b, 1, True, family="lds", finish=fin_sum, sumsq=False)
+        outb = o.gram(a, b, 1, True)
         assert torch.equal(outb.cpu(), ref.sum(0, keepdim=True))
 
 
@@ -214,33 +238,144 @@ def test_gram_long_reduction_random(dtype):
     assert rel(out, ref) < (1e-5 if dtype == torch.float32 else 1e-2)
 
 
-@pytest.mark.parametrize("dtype", DT)
-@pytest.mark.parametrize("ma,mb,B,hw", [(48, 48, 4, (16, 64)), (144, 48, 5, (16, 64)), (576, 192, 3, (16, 64)), (300, 200, 2, (8, 64)),
-                                        (96, 255, 32, (4, 64)), (130, 70, 3, (24, 64)), (1020, 192, 2, (16, 64)), (90, 250, 2, (8, 72)),
-                                        (700, 384, 2, (8, 64)), (192, 510, 2, (8, 64)), (384, 1021, 2, (4, 64)), (150, 300, 3, (8, 72))])
-def test_gram_batch_fold_exact_on_integers(monkeypatch, dtype, ma, mb, B, hw):
-    """Weight-gradient Grams (sum over the batch) with the images chained along the contraction axis: workgroup pixel ranges that
-    cross image boundaries, both kernels (LDS-staged and streaming), against the per-image form and the host.  MI_GRAM_FOLD: 0 =
-    never, unset = where the planner finds it pays (short planes / half-empty chip), 2 = wherever an image is whole chunks."""
-    o = ops()
-    a = ints((B, ma, *hw), 151, -2, 3).to(dtype)
-    b = ints((B, mb, *hw), 152, -2, 3).to(dtype)
-    ref = torch.einsum("bin,bjn->ij", a.float().flatten(2), b.float().flatten(2))[None]
+# (ma, mb, B, hw) -> the rectangular LDS tile (fa, fb) the bf16 call is there for, or None: square tiles
+GRAM_FOLD = {(48, 48, 4, (16, 64)): None, (144, 48, 5, (16, 64)): None, (576, 192, 3, (16, 64)): (4, 6), (300, 200, 2, (8, 64)): None,
+             (96, 255, 32, (4, 64)): (3, 8), (130, 70, 3, (24, 64)): None, (1020, 192, 2, (16, 64)): (4, 6), (90, 250, 2, (8, 72)): (3, 8),
+             (700, 384, 2, (8, 64)): (4, 6), (192, 510, 2, (8, 64)): (6, 4), (384, 1021, 2, (4, 64)): (6, 4), (150, 300, 3, (8, 72)): (6, 4),
+             (48, 48, 9, (64, 64)): None}        # long planes stay per image: bf16 streams 9 x 2 partials into the general reduce
+
+
+def _fold_wanted(dtype, hw, mode):
+    """Whether a weight-gradient Gram of these planes chains the batch along the pixel axis: every plane here is whole units (64
+    pixels; the fp32 LDS chunk: 32) and no case leaves the chip half empty, so: never under MI_GRAM_FOLD=0, always under 2, and by
+    default where an image is short - at most 16 units.  Returns the units per image, or 0."""
+    units = hw[0] * hw[1] // (32 if dtype == torch.float32 else 64)
+    return units if mode == "2" or (mode is None and units <= 16) else 0
+
+
+def _fold_calls(monkeypatch):
+    """The nine switch settings of the fold test: (MI_GRAM_FOLD mode, "plain" / "square" / "stream"), set as they are yielded."""
     for mode in ("0", None, "2"):
         if mode is None:
             monkeypatch.delenv("MI_GRAM_FOLD", raising=False)
         else:
             monkeypatch.setenv("MI_GRAM_FOLD", mode)
-        out = o.gram(a.to(DEV), b.to(DEV), 1, True)
-        assert torch.equal(out.cpu(), ref), (mode, float((out.cpu() - ref).abs().max()))
+        yield mode, "plain"
         monkeypatch.setenv("MI_GRAM_RECT", "0")                 # square 128 x 128 tiles instead of 96 x 256 / 128 x 192
-        out = o.gram(a.to(DEV), b.to(DEV), 1, True)
+        yield mode, "square"
         monkeypatch.delenv("MI_GRAM_RECT")
-        assert torch.equal(out.cpu(), ref), ("square", mode)
         monkeypatch.setenv("MI_GRAM_STREAM_ALL", "1")
-        out = o.gram(a.to(DEV), b.to(DEV), 1, True)
+        yield mode, "stream"
         monkeypatch.delenv("MI_GRAM_STREAM_ALL")
-        assert torch.equal(out.cpu(), ref), ("stream", mode)
+
+
+def _fold_plan_check(p, dtype, ma, mb, B, hw, mode, kind):
+    bf = dtype == torch.bfloat16
+    rect = GRAM_FOLD[(ma, mb, B, hw)] if bf else None
+    square = 4 if max(ma, mb) > 64 else 2
+    assert p["fold"] == _fold_wanted(dtype, hw, mode), (mode, kind, p)
+    if kind == "stream" or not bf:
+        assert p["family"] == ("stream" if bf else "lds"), (mode, kind, p)
+    if p["family"] == "lds":
+        assert (p["fa"], p["fb"]) == (rect if rect and kind == "plain" else (square, square)), (mode, kind, p)
+    else:                            # bf16 streams by itself only where no rectangular tile is listed: small or badly filled tiles
+        assert kind == "stream" or rect is None, (mode, kind, p)
+
+
+@pytest.mark.parametrize("dtype", DT)
+@pytest.mark.parametrize("ma,mb,B,hw", list(GRAM_FOLD))
+def test_gram_batch_fold_exact_on_integers(monkeypatch, dtype, ma, mb, B, hw):
+    """Weight-gradient Grams (sum over the batch) with the images chained along the contraction axis: workgroup pixel ranges that
+    cross image boundaries, both kernels (LDS-staged and streaming), against the per-image form and the host.  MI_GRAM_FOLD: 0 =
+    never, unset = where the planner finds it pays (short planes / half-empty chip), 2 = wherever an image is whole chunks.
+    The plan of every call is asserted first: folded exactly where it should be, streaming under MI_GRAM_STREAM_ALL (bf16), square
+    tiles under MI_GRAM_RECT=0 and the rectangular tile the shape is listed for otherwise."""
+    o = ops()
+    a = ints((B, ma, *hw), 151, -2, 3).to(dtype)
+    b = ints((B, mb, *hw), 152, -2, 3).to(dtype)
+    ref = torch.einsum("bin,bjn->ij", a.float().flatten(2), b.float().flatten(2))[None]
+    a, b = a.to(DEV), b.to(DEV)
+    for mode, kind in _fold_calls(monkeypatch):
+        _fold_plan_check(_planned(o, a, b, 1, True), dtype, ma, mb, B, hw, mode, kind)
+        out = o.gram(a, b, 1, True)
+        assert torch.equal(out.cpu(), ref), (kind, mode, float((out.cpu() - ref).abs().max()))
+
+
+# finish kinds the cases above do not reach in bf16 or in the streaming family, by host arithmetic (checked through the plan):
+# (48, 48) at 16 x 16 pixels per image = 4 splits (few<4>), summed over the batch 8 (few<16>); B = 5 at 32 x 32 per image under
+# MI_GRAM_FOLD=0 = 5 x 16 partials of 2304 elements (general); a 64-pixel plane = one split, straight into the output.
+@pytest.mark.parametrize("dtype", DT)
+def test_gram_deferred_accumulate_and_panel_stride(monkeypatch, dtype):
+    """The two finishes that belong to weight gradients.  Deferred: inside ops.deferred_begin .. flush an accumulating Gram leaves
+    its partials in the arena and the flush adds their sum onto the prior - a random one; dy and x hold integers, so the sum is
+    exact, and it equals the immediate call bit for bit.  out_ld > mb (conv1x1_wgrad_panels): each panel's Gram lands in its
+    column block of a wider gradient, is never deferred, and leaves the other columns alone."""
+    o = ops()
+    B, M, K1, K2, hw = 2, 144, 48, 40, (16, 64)
+    dy = ints((B, M, *hw), 161, -2, 3).to(dtype).to(DEV)
+    x1 = ints((B, K1, *hw), 162, -2, 3).to(dtype).to(DEV)
+    x2 = ints((B, K2, *hw), 163, -2, 3).to(dtype).to(DEV)
+    prior = rnd((1, M, K1), 164).to(DEV)
+    ref = torch.einsum("bin,bjn->ij", dy.float().flatten(2), x1.float().flatten(2))[None] + prior      # (one rounding per element, as the kernel's)
+    p = o.gram_plan(o.gram_desc(dy, x1, 1, True, out=prior, accumulate=True))
+    assert p["deferrable"] and p["finish"] != "direct", p
+    now = o.gram(dy, x1, 1, True, out=prior.clone(), accumulate=True)
+    assert o.deferred_pending() == 0
+    assert torch.equal(now, ref)
+    tok = o.deferred_begin(4 * p["part_bytes"] + (8 << 20), torch.device(DEV))
+    assert tok is not None
+    try:
+        o.deferred_record(True)
+        got = o.gram(dy, x1, 1, True, out=prior.clone(), accumulate=True)
+        assert o.deferred_pending() > 0, "nothing was deferred"
+        o.deferred_flush()
+    finally:
+        o.deferred_end(tok)
+    torch.cuda.synchronize()
+    assert torch.equal(got, ref)
+    # the two K-panels of a 1x1 conv's weight gradient, inside a deferral window too: row stride K1 + K2, nothing deferred
+    dw2 = rnd((M, K1 + K2 + 3), 165).to(DEV)
+    before = dw2.clone()
+    for xp, k0 in ((x1, 0), (x2, K1)):
+        q = o.gram_plan(o.wgrad_panel_desc(dy, xp, dw2, k0, True))
+        assert not q["deferrable"] and q["finish"] != "direct", q
+    tok = o.deferred_begin(8 << 20, torch.device(DEV))
+    try:
+        o.deferred_record(True)
+        o.conv1x1_wgrad_panels(dy, x1, x2, dw2, True)
+        assert o.deferred_pending() == 0
+    finally:
+        o.deferred_end(tok)
+    want = before.clone()
+    want[:, :K1] += torch.einsum("bin,bjn->ij", dy.float().flatten(2), x1.float().flatten(2))
+    want[:, K1:K1 + K2] += torch.einsum("bin,bjn->ij", dy.float().flatten(2), x2.float().flatten(2))
+    assert torch.equal(dw2, want)
+
+
+def test_gram_cases_cover_every_family_and_finish(monkeypatch):
+    """The plans asserted by the Gram tests above, taken together (asked again here, host only): both families, each with sumsq and
+    folded; every finish - straight into the output, the three reduce kernels, deferrable partials - and a row stride out_ld > mb."""
+    o = ops()
+    seen = set()
+
+    def see(p):
+        seen.update({(p["family"], p["finish"]), (p["family"], "sumsq", p["sumsq"]), (p["family"], "fold", p["fold"] > 0)})
+        return p
+
+    for dtype in DT:
+        for (ma, mb, groups, hw), fin in GRAM_EXACT.items():
+            see(o.gram_plan(o.gram_probe(ma, mb, hw[0] * hw[1], dtype, B=2, groups=groups, sumsq=True)))
+            if groups == 1:
+                see(o.gram_plan(o.gram_probe(ma, mb, hw[0] * hw[1], dtype, B=2, sum_batch=True)))
+        for ma, mb, B, hw in GRAM_FOLD:
+            for mode, kind in _fold_calls(monkeypatch):
+                see(o.gram_plan(o.gram_probe(ma, mb, hw[0] * hw[1], dtype, B=B, sum_batch=True)))
+        p = see(o.gram_plan(o.gram_probe(144, 48, 1024, dtype, B=2, sum_batch=True, accumulate=True)))
+        q = see(o.gram_plan(o.gram_probe(144, 48, 1024, dtype, B=2, sum_batch=True, accumulate=True, out_ld=91)))
+        assert p["deferrable"] and not q["deferrable"]
+    want = {(f, k) for f in ("lds", "stream") for k in ("few4", "few16", "general")} | {("lds", "direct")}
+    want |= {(f, "sumsq", v) for f in ("lds", "stream") for v in (False, True)} | {(f, "fold", v) for f in ("lds", "stream") for v in (False, True)}
+    assert want <= seen, sorted(want - seen, key=str)
 
 
 # --------------------------------------------------------------------------- AdamW / L1
