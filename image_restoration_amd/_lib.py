@@ -239,6 +239,7 @@ SIGNATURES = {
     "mi_scale_add_bwd": (C.c_int, [vp, vp, fp, fp, vp, vp, vp, fp, fp, C.c_int, C.c_int, c_i64, C.c_int, C.c_int, vp]),
     "mi_bwd_tail_ok": (C.c_int, [C.c_int, C.c_int, c_i64, C.c_int]),
     "mi_bwd_tail_workspace": (C.c_size_t, [C.c_int, C.c_int]),
+    "mi_bwd_tail_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, c_i64, C.c_int, C.POINTER(c_i64)]),
     "mi_bwd_tail": (C.c_int, [vp, C.c_int, vp, C.c_int, vp, fp, fp, fp, fp, fp, vp, fp, fp, fp, C.c_int, c_i64, C.c_int,
                               C.c_int, vp, vp]),
     "mi_mdta_bwd_ln_ok": (C.c_int, [C.POINTER(MdtaShape), C.c_int]),

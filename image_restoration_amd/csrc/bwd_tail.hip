@@ -23,6 +23,7 @@
 //     through LDS and store 128-byte rows of dx.
 // The next tile's first dY half, x, dres and statistics are in flight while a tile is computed, and the LayerNorm phase and
 // store of tile i-1 run inside tile i behind the request for its second dY half (software pipeline across tiles).
+#include <limits.h>
 #include <stdlib.h>
 
 #include <type_traits>
@@ -478,14 +479,14 @@ __global__ __launch_bounds__(1024) void bt_finish2_kernel(const float* __restric
   }
 }
 
-struct BtPlan { int C, NW, MPW, grid, mpad; size_t lds; };
-static bool bt_plan(int M, int C, BtPlan* p) {
+// The form of the kernel for M rows over C channels (none: false), the ONE table of it.
+static bool bt_form(int M, int C, BtPlan* p) {
   int nw, mpw;
   const int mt = (M + 15) / 16;
   if (C == 96) { nw = 8; mpw = mt <= 24 ? 3 : 4; if (mt > 32) return false; }
   else if (C == 48) { nw = 4; mpw = mt <= 12 ? 3 : 4; if (mt > 16) return false; }
   else return false;
-  p->C = C; p->NW = nw; p->MPW = mpw; p->mpad = 16 * nw * mpw;
+  p->C = C; p->NW = nw; p->MPW = mpw; p->rows = 16 * mpw; p->mpad = 16 * nw * mpw;
   p->lds = C == 96 ? (mpw == 3 ? BtCfg<96, 8, 3>::BYTES : BtCfg<96, 8, 4>::BYTES)
                    : (mpw == 3 ? BtCfg<48, 4, 3>::BYTES : BtCfg<48, 4, 4>::BYTES);
   p->grid = C == 96 ? 256 : 512;
@@ -493,26 +494,32 @@ static bool bt_plan(int M, int C, BtPlan* p) {
 }
 }  // namespace
 
-bool bwd_tail_ok(int M, int C, int64_t N, int dtype) {
-  BtPlan p;
-  return dtype == MI_BF16 && N > 0 && N % 64 == 0 && M >= 16 && bt_plan(M, C, &p);
+// What one mi_bwd_tail call runs.  The ONE place that decides it: launch_bwd_tail launches what it says, bwd_tail_ok /
+// bwd_tail_pays / bwd_tail_workspace answer from it and mi_bwd_tail_plan reports it.
+BtPlan bwd_tail_plan(int M, int C, int B, int64_t N, int dtype) {
+  BtPlan p = {};
+  if (!(dtype == MI_BF16 && B > 0 && N > 0 && N % 64 == 0 && M >= 16 && bt_form(M, C, &p))) return BtPlan{};
+  p.covered = true;
+  const char* e = MI_ENV(MI_BT_WIDE);                                 // A/B switch, read per call: 0 keeps the 4-fragment form off
+  p.pays = !(C == 96 && p.MPW == 4) || !(e && atoi(e) == 0);
+  p.tiles_per_image = N / 64;
+  p.tiles = (int64_t)B * p.tiles_per_image;
+  p.launch = (int)(p.tiles < p.grid ? p.tiles : p.grid);              // workgroups: a persistent loop over the tiles beyond them
+  p.passes = (int)((p.tiles + p.launch - 1) / p.launch);
+  p.active = (M + p.rows - 1) / p.rows;                               // waves that hold dY rows
+  const size_t mc = (size_t)M * (C + 1);
+  // partial [G | S] per workgroup (sized for the full grid: the workspace is asked for before B and N are known), its sum, and
+  // the two-stage row reduction's scratch
+  p.ws_bytes = align_up((size_t)p.grid * mc * 4, 256) + align_up(mc * 4, 256) + align_up((size_t)REDUCE_GROUPS * mc * 4, 256);
+  return p;
 }
+
+bool bwd_tail_ok(int M, int C, int64_t N, int dtype) { return bwd_tail_plan(M, C, 1, N, dtype).covered; }
 // Where the tail beats the three kernels it replaces (tools/bench_tail.py, profiles/r02_d_bwd_tail_bs32.txt): every covered
 // shape, 1.06-1.30x.  (The 4-fragments-per-wave form, C = 96 and M > 384, runs at the register limit: with its reduction steps
 // unrolled it spilled 13 registers and lost, 0.92x; rolled it wins 1.10x.  MI_BT_WIDE=0 switches it off.)
-bool bwd_tail_pays(int M, int C) {
-  BtPlan p;
-  if (!bt_plan(M, C, &p)) return false;
-  const char* e = MI_ENV(MI_BT_WIDE);                                 // A/B switch, read per call: 0 keeps the 4-fragment form off
-  return !(C == 96 && p.MPW == 4) || !(e && atoi(e) == 0);
-}
-// partial [G | S] per workgroup, its sum, and the two-stage row reduction's scratch
-size_t bwd_tail_workspace(int M, int C) {
-  BtPlan p;
-  if (!bt_plan(M, C, &p)) return 0;
-  const size_t mc = (size_t)M * (C + 1);
-  return align_up((size_t)p.grid * mc * 4, 256) + align_up(mc * 4, 256) + align_up((size_t)REDUCE_GROUPS * mc * 4, 256);
-}
+bool bwd_tail_pays(int M, int C) { return bwd_tail_plan(M, C, 1, 64, MI_BF16).pays; }
+size_t bwd_tail_workspace(int M, int C) { return bwd_tail_plan(M, C, 1, 64, MI_BF16).ws_bytes; }
 
 template <int C, int NW, int MPW>
 static int bt_launch(const BtArgs& a, int grid, hipStream_t st) {
@@ -536,8 +543,8 @@ static int bt_launch(const BtArgs& a, int grid, hipStream_t st) {
 int launch_bwd_tail(const void* dy, int M, const void* x, int C, const void* dres, const float* mean, const float* rstd,
                     const float* w, const float* gamma, const float* beta, void* dx, float* dw, float* dgamma, float* dbeta,
                     int B, int64_t N, int accumulate, void* ws, hipStream_t st) {
-  BtPlan p;
-  MI_CHECK_ARG(bt_plan(M, C, &p) && N % 64 == 0, "bwd_tail: unsupported shape M=%d C=%d N=%lld", M, C, (long long)N);
+  const BtPlan p = bwd_tail_plan(M, C, B, N, MI_BF16);
+  MI_CHECK_ARG(p.covered && p.tiles <= INT_MAX, "bwd_tail: unsupported shape M=%d C=%d B=%d N=%lld", M, C, B, (long long)N);
   MI_CHECK_ARG(dy && x && mean && rstd && w && gamma && dx && dw && dgamma && ws, "bwd_tail: null pointer");
   MI_CHECK_ARG(aligned16(dy) && aligned16(x) && aligned16(dx) && (!dres || aligned16(dres)) && aligned16(mean) && aligned16(rstd),
                "bwd_tail: operands must be 16-byte aligned");
@@ -549,9 +556,9 @@ int launch_bwd_tail(const void* dy, int M, const void* x, int C, const void* dre
   BtArgs a;
   a.dy = (const bf16*)dy; a.x = (const bf16*)x; a.dres = (const bf16*)dres; a.mean = mean; a.rstd = rstd; a.w = w;
   a.gamma = gamma; a.dx = (bf16*)dx; a.gpart = gpart; a.M = M; a.mpad = p.mpad; a.N = N;
-  a.tiles_per_image = (int)(N / 64); a.ntiles = B * a.tiles_per_image;
+  a.tiles_per_image = (int)p.tiles_per_image; a.ntiles = (int)p.tiles;
   { const char* e = MI_ENV(MI_BT_DEBUG); a.dbg = e ? atoi(e) : 0; }
-  const int grid = a.ntiles < p.grid ? a.ntiles : p.grid;
+  const int grid = p.launch;
   {
     const double px = (double)B * N;
     ProfScope ps(st, K_BWD_TAIL, ((double)M + 3.0 * C) * px * 2 + 8.0 * px, 4.0 * M * C * px);
@@ -580,6 +587,21 @@ int launch_bwd_tail(const void* dy, int M, const void* x, int C, const void* dre
 // C-ABI: the tail by itself (tests, and callers that build their own half-blocks)
 extern "C" int mi_bwd_tail_ok(int M, int C, int64_t N, int dtype) { return mi::bwd_tail_ok(M, C, N, dtype) ? 1 : 0; }
 extern "C" size_t mi_bwd_tail_workspace(int M, int C) { return mi::bwd_tail_workspace(M, C); }
+// What mi_bwd_tail runs for this call under the current MI_BT_WIDE.  Host-side only: the same bwd_tail_plan.  out[12]: covered,
+// pays (covered and faster than the unfused chain), waves per workgroup, 16-row fragments per wave, rows per wave, rows the
+// workgroup has room for, workgroups launched, 64-pixel tiles, passes of the persistent loop (ceil(tiles / workgroups)), waves
+// that hold rows (ceil(M / rows per wave)), dynamic LDS bytes, workspace bytes.  A shape the kernel does not cover is no error:
+// covered = 0 and every other field 0.
+extern "C" int mi_bwd_tail_plan(int M, int C, int B, int64_t N, int dtype, int64_t* out) {
+  MI_CHECK_ARG(out, "bwd_tail_plan: null pointer");
+  MI_CHECK_ARG(dtype == MI_F32 || dtype == MI_BF16, "bwd_tail_plan: bad dtype %d", dtype);
+  MI_CHECK_ARG(M > 0 && B > 0 && N > 0, "bwd_tail_plan: bad shape M=%d B=%d N=%lld", M, B, (long long)N);
+  const mi::BtPlan p = mi::bwd_tail_plan(M, C, B, N, dtype);
+  const int64_t v[12] = {p.covered, p.pays, p.NW, p.MPW, p.rows, p.mpad, p.launch, p.tiles, p.passes, p.active, (int64_t)p.lds,
+                         (int64_t)p.ws_bytes};
+  memcpy(out, v, sizeof(v));
+  return MI_OK;
+}
 extern "C" int mi_bwd_tail(const void* dy, int M, const void* x, int C, const void* dres, const float* mean, const float* rstd,
                            const float* w, const float* gamma, const float* beta, void* dx, float* dw, float* dgamma,
                            float* dbeta, int B, int64_t N, int accumulate, int dtype, void* ws, void* stream) {

@@ -113,6 +113,17 @@ int dws_gate_bwd(const DwArgs& a, const void* xin, float* part, int B, bool want
 // same, with the conv outputs recomputed from the conv input: a.in = dg, a.gy = conv input x, a.bias = conv bias
 int dws_gate_bwd_recompute(const DwArgs& a, float* part, int B, bool want_dw, int* rows_out, int dtype, hipStream_t st);
 // ---- backward tail of a half-block (bwd_tail.hip): dW, W^T dY, LayerNorm backward and the residual add in one launch ----
+// What one mi_bwd_tail call runs: filled by bwd_tail_plan (bwd_tail.hip), the ONE place that decides it; launch_bwd_tail launches
+// what it says, the three predicates below answer from it, mi_bwd_tail_plan reports it.  Not covered: every field 0.
+struct BtPlan {
+  bool covered, pays;                            // the kernel takes the call / and beats the unfused chain (MI_BT_WIDE)
+  int C, NW, MPW, rows, mpad;                    // the instance: waves, 16-row fragments per wave, rows per wave, rows in all
+  int grid, launch;                              // workgroups the partials are sized for / launched (min(tiles, grid))
+  int64_t tiles_per_image, tiles;                // 64-pixel tiles
+  int passes, active;                            // trips of the persistent loop (ceil(tiles / launch)); waves that hold rows
+  size_t lds, ws_bytes;                          // dynamic LDS; the workspace (partials [grid][M][C + 1] and the row sum's scratch)
+};
+BtPlan bwd_tail_plan(int M, int C, int B, int64_t N, int dtype);
 bool bwd_tail_ok(int M, int C, int64_t N, int dtype);
 bool bwd_tail_pays(int M, int C);   // covered AND faster than the unfused chain (the module entry points use the tail only then)
 size_t bwd_tail_workspace(int M, int C);

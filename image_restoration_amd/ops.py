@@ -882,6 +882,20 @@ def bwd_tail_ok(M: int, Cc: int, N: int, dtype: torch.dtype) -> bool:
     return bool(L.lib().mi_bwd_tail_ok(M, Cc, N, _dtype_code(dtype)))
 
 
+BWD_TAIL_PLAN_FIELDS = ("covered", "pays", "waves", "fragments", "rows_per_wave", "mpad", "workgroups", "tiles", "passes",
+                        "active_waves", "lds", "workspace")
+
+
+def bwd_tail_plan(M: int, Cc: int, B: int, N: int, dtype: torch.dtype) -> dict:
+    """What bwd_tail launches for dy [B, M, N] over x [B, Cc, N] under the current MI_BT_WIDE (mi_bwd_tail_plan; no GPU work).
+    A shape the kernel does not cover gives covered = False and zeros."""
+    out = (L.c_i64 * 12)()
+    L.check(L.lib().mi_bwd_tail_plan(M, Cc, B, N, _dtype_code(dtype), out), "bwd_tail_plan")
+    p = dict(zip(BWD_TAIL_PLAN_FIELDS, out))
+    p["covered"], p["pays"] = bool(p["covered"]), bool(p["pays"])
+    return p
+
+
 def bwd_tail(dy: Tensor, x: Tensor, dres: Optional[Tensor], mean: Tensor, rstd: Tensor, w: Tensor, gamma: Tensor,
              beta: Tensor, dw: Tensor, dgamma: Tensor, dbeta: Tensor, accumulate: bool) -> Tensor:
     """The backward tail by itself (mi_bwd_tail): dy [B,M,H,W], x the LayerNorm input [B,C,H,W]; returns dx."""

@@ -470,6 +470,12 @@ int mi_mdta_fused_fwd(const mi_mdta_shape* s, const mi_mdta_params* p, const voi
                       const void* residual, void* out, float* mean, float* rstd, void* ws, void* stream);
 int mi_bwd_tail_ok(int M, int C, int64_t N, int dtype);
 size_t mi_bwd_tail_workspace(int M, int C);
+/* What mi_bwd_tail launches for this call under the current MI_BT_WIDE (host-only).  out[12]: covered, pays (covered and
+ * faster than the unfused chain), waves per workgroup, 16-row fragments per wave, rows per wave, rows the workgroup holds,
+ * workgroups launched, 64-pixel tiles, passes of the persistent loop, waves that hold rows, dynamic LDS bytes, workspace
+ * bytes.  A shape the kernel does not cover returns 0 with covered = 0 and every other field 0; -1 on a null out, a bad dtype
+ * code or M, B, N <= 0. */
+int mi_bwd_tail_plan(int M, int C, int B, int64_t N, int dtype, int64_t* out);
 int mi_bwd_tail(const void* dy, int M, const void* x, int C, const void* dres, const float* mean, const float* rstd,
                 const float* w, const float* gamma, const float* beta, void* dx, float* dw, float* dgamma, float* dbeta,
                 int B, int64_t N, int accumulate, int dtype, void* ws, void* stream);

@@ -532,3 +532,157 @@ def test_gram_plan_argument_errors_and_the_32_bit_guard(lib, monkeypatch):
     _gram_switches(monkeypatch, MI_GRAM_STREAM_ALL="1")
     assert ops.gram_plan(ops.gram_probe(254, 48, N, bf16))["family"] == "lds"
     assert ops.gram_plan(ops.gram_probe(127, 48, N, bf16))["family"] == "stream"
+
+
+# --------------------------------------------------------------------------- the backward tail's plan (mi_bwd_tail_plan)
+BT_FORMS = ((48, 1, 192, 4, 3, 512), (48, 193, 256, 4, 4, 512), (96, 1, 384, 8, 3, 256), (96, 385, 512, 8, 4, 256))   # C, M from..to, waves, fragments, grid
+
+
+def _bt_switches(monkeypatch, **env):
+    for k in ("MI_BT_WIDE", "MI_BT_DEBUG"):
+        monkeypatch.delenv(k, raising=False)
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+
+
+def test_bwd_tail_plan_sweep(lib, monkeypatch):
+    """ops.bwd_tail_plan over M = 1..520 for covered and uncovered C: the table of forms read from csrc/bwd_tail.hip, agreement
+    with mi_bwd_tail_ok and mi_bwd_tail_workspace everywhere, MI_BT_WIDE, and workgroups / passes around the grid."""
+    from image_restoration_amd import ops
+    L, bf16, f32 = lib.lib(), torch.bfloat16, torch.float32
+    _bt_switches(monkeypatch)
+    zeros = dict.fromkeys(ops.BWD_TAIL_PLAN_FIELDS, 0)
+    zeros.update(covered=False, pays=False)
+    plans = {}
+    for C_ in (48, 96, 64, 192):
+        form = [f for f in BT_FORMS if f[0] == C_]
+        for M in range(1, 521):
+            p = plans[(C_, M)] = ops.bwd_tail_plan(M, C_, 2, 576, bf16)
+            assert p["covered"] == bool(L.mi_bwd_tail_ok(M, C_, 576, lib.MI_BF16)), (C_, M)
+            row = [f for f in form if f[1] <= M <= f[2] and M >= 16]
+            if not row:                              # M < 16, M above the cap, another C
+                assert p == zeros and L.mi_bwd_tail_workspace(M, C_) == 0, (C_, M, p)
+                continue
+            _, _, _, waves, frags, grid = row[0]
+            assert p == {"covered": True, "pays": True, "waves": waves, "fragments": frags, "rows_per_wave": 16 * frags,
+                         "mpad": 16 * frags * waves, "workgroups": 18, "tiles": 18, "passes": 1, "active_waves": -(-M // (16 * frags)),
+                         "lds": {48: 76736, 96: 153472}[C_], "workspace": L.mi_bwd_tail_workspace(M, C_)}, (C_, M, p)
+            assert M <= p["mpad"] and 1 <= p["active_waves"] <= waves      # (LDS: 3 and 4 fragments both take two 32-row patch steps)
+            assert p["workspace"] >= 4 * grid * M * (C_ + 1)                       # a partial [M][C + 1] per workgroup of the full grid
+            for N, dt in ((577, bf16), (96, bf16), (576, f32)):                    # no multiple of the tile; fp32
+                assert ops.bwd_tail_plan(M, C_, 2, N, dt) == zeros
+                assert not L.mi_bwd_tail_ok(M, C_, N, lib.MI_BF16 if dt == bf16 else lib.MI_F32)
+            # workgroups and passes around the grid
+            if M in (16, 17, 192, 193, 256, 384, 385, 512):
+                for tiles, wgs, passes in ((1, 1, 1), (grid - 1, grid - 1, 1), (grid, grid, 1), (grid + 1, grid, 2), (2 * grid + 1, grid, 3)):
+                    for B, tpi in ((1, tiles), (tiles, 1)):
+                        q = ops.bwd_tail_plan(M, C_, B, 64 * tpi, bf16)
+                        assert (q["tiles"], q["workgroups"], q["passes"]) == (tiles, wgs, passes), (C_, M, B, tpi, q)
+                        assert {k: v for k, v in q.items() if k not in ("tiles", "workgroups", "passes")} == \
+                               {k: v for k, v in p.items() if k not in ("tiles", "workgroups", "passes")}
+    # MI_BT_WIDE=0 switches the C = 96 four-fragment form off for the module entry points, and nothing else
+    _bt_switches(monkeypatch, MI_BT_WIDE="0")
+    for (C_, M), p in plans.items():
+        q = ops.bwd_tail_plan(M, C_, 2, 576, bf16)
+        assert q == {**p, "pays": p["pays"] and not (C_ == 96 and p["fragments"] == 4)}, (C_, M)
+    _bt_switches(monkeypatch, MI_BT_WIDE="1")
+    assert all(ops.bwd_tail_plan(M, C_, 2, 576, bf16) == p for (C_, M), p in plans.items())
+
+
+def test_bwd_tail_plan_argument_errors(lib):
+    L, out = lib.lib(), (C.c_int64 * 12)()
+    assert L.mi_bwd_tail_plan(144, 48, 2, 576, lib.MI_BF16, None) == -1 and b"bwd_tail_plan: null pointer" in L.mi_last_error()
+    assert L.mi_bwd_tail_plan(144, 48, 2, 576, 7, out) == -1 and b"bad dtype 7" in L.mi_last_error()
+    for M, B, N in ((0, 2, 576), (144, 0, 576), (144, 2, 0), (-1, 2, 576), (144, -3, 576), (144, 2, -64)):
+        assert L.mi_bwd_tail_plan(M, 48, B, N, lib.MI_BF16, out) == -1 and b"bwd_tail_plan: bad shape" in L.mi_last_error(), (M, B, N)
+    assert L.mi_bwd_tail_plan(144, 64, 2, 576, lib.MI_BF16, out) == 0 and list(out) == [0] * 12      # uncovered: no error
+    assert L.mi_bwd_tail_plan(144, 48, 2, 576, lib.MI_BF16, out) == 0 and out[0] == 1
+
+
+def test_tail_case_lists_reach_every_plan(lib, monkeypatch):
+    """The case lists of tests/test_gpu_bwd_tail.py reach every form of the kernel with one, two and at least three passes of
+    the persistent loop, with and without a row tail, with idle waves, with dres given and absent, accumulating and not."""
+    from image_restoration_amd import ops
+    import test_gpu_bwd_tail as T
+    _bt_switches(monkeypatch)
+    seen = {}
+    for case in T.EXACT_CASES:
+        C_, f, M, B, tpi, passes, dres, accumulate, narrow = case
+        p = T.assert_plan(C_, f, M, B, tpi, passes)
+        for tag in ("passes %d" % min(p["passes"], 3), "tail" if M % 16 else "no tail", "dres" if dres else "no dres",
+                    "accumulate" if accumulate else "overwrite") + (("idle waves",) if p["active_waves"] < p["waves"] else ()):
+            seen.setdefault((C_, p["fragments"]), set()).add(tag)
+    assert set(seen) == set(T.FORMS)
+    every = {"passes 1", "passes 2", "passes 3", "tail", "no tail", "dres", "no dres", "accumulate", "overwrite"}
+    for form, tags in seen.items():
+        assert tags >= every | ({"idle waves"} if form[1] == 3 else set()), (form, every - tags)   # a 4-fragment form has rows for every wave
+    for form, ms in T.ROW_MS.items():                        # the row counts at the borders of each form
+        lo, hi = next((f[1], f[2]) for f in BT_FORMS if (f[0], f[4]) == form)
+        assert max(lo, 16) in ms and hi in ms and all(ops.bwd_tail_plan(M, form[0], 2, 576, torch.bfloat16)["fragments"] == form[1] for M in ms)
+    for case in T.MODEL_CASES:
+        assert T.assert_plan(*case)["passes"] == 1 and case[2] % 16
+    assert {c[:2] for c in T.MODEL_CASES} == set(T.FORMS)
+
+
+def _tail_host_cases(T):
+    """One Family-A and one Family-B case per C, small enough for the host: (inputs, fp64 reference)."""
+    out = []
+    for C_, f, M, B, tpi in ((48, 4, 254, 2, 9), (96, 4, 510, 1, 7)):
+        s = T.exact_inputs(C_, M, B, tpi)
+        r = T.reference(s, *T.exact_operands(s))
+        T.assert_exact_preconditions(s, r, 5.0)
+        m = T.float_inputs(C_, M, B, tpi, stats="cpu")
+        out.append((C_, f, s, r, m, T.reference(m, *T.model_operands(m))))
+    return out
+
+
+def test_tail_bounds_admit_a_correct_fp32_evaluation(lib, monkeypatch):
+    """The tail evaluated in torch fp32 on the CPU, in a permuted summation order, passes the assertions of both families of
+    tests/test_gpu_bwd_tail.py: the bounds ask nothing that correct fp32 arithmetic cannot give."""
+    import test_gpu_bwd_tail as T
+    _bt_switches(monkeypatch)
+    for C_, f, s, r, m, rm in _tail_host_cases(T):
+        plan = T.assert_plan(C_, f, s.M, s.B, s.tpi)
+        for wgs, accumulate, seed in ((plan["workgroups"], False, 0), (4, True, 1)):       # one pass; three passes of four workgroups
+            ratio, equal = T.assert_exact(T.evaluate_fp32(s, wgs, accumulate, seed=seed), s, r, plan, accumulate, "fp32 on the host")
+            assert ratio <= 1.0 and equal > 0.98
+        T.assert_model_near_statement(m, rm)
+        assert max(T.assert_model(T.evaluate_fp32(m, 4, seed=2), m, rm, plan, "fp32 on the host")) <= 1.0
+
+
+def test_tail_assertions_catch_four_deliberate_faults(lib, monkeypatch):
+    """Four faults of the kind the tail's masking, pipelining and partial sums can have, applied to the fp32 evaluation on the
+    CPU: each fails Family A's assertions, and the modelled bounds of Family B see the dropped row on float data too.
+
+    Contrast with the max-norm bars that guarded the kernel before (tests/test_gpu_fused.py: 2e-2 of max|dx|, 1e-2 for the
+    parameter gradients), on random float data with real statistics.  Measured here, error / max|ref| of (dx, dW, dgamma):
+        the last valid dY row left out of W^T dY    0.051 .. 0.136, unchanged, unchanged   (C, M, pixels) = (96, 510, 448) .. (48, 144, 2048)
+        two pixels' rstd swapped                    0.0145, 0.0020, 0.0027                 (96, 510, 3072)
+    A wholly dropped row is NOT under the old dx bar: its worst element is a product of two tail values against a maximum that
+    grows with sqrt(M) only, 5 % of it and more (1 / sqrt(510) = 4 % relates typical values).  The old tests miss it where they
+    never go - the row counts at a form's borders, a third pass, dres absent, a small call after a large one.  Where the bar
+    itself is blind is a statistic read for the wrong pixel: real rstd varies little between pixels, and the swap stays under
+    all three bars while Family A (rstd drawn from {0.5, 1, 2} per pixel) and the modelled bounds both fail it."""
+    import test_gpu_bwd_tail as T
+    _bt_switches(monkeypatch)
+    for C_, f, s, r, m, rm in _tail_host_cases(T):
+        plan = T.assert_plan(C_, f, s.M, s.B, s.tpi)
+        for fault, what in zip(T.FAULTS, ("dx off", "dw differs", "dx off", "dw differs")):      # (a statistic enters xh, so G too)
+            with pytest.raises(AssertionError, match=what):
+                T.assert_exact(T.evaluate_fp32(s, 4, fault=fault), s, r, plan, False, fault)
+        T.assert_exact(T.evaluate_fp32(s, 4), s, r, plan, False, "no fault")
+        pure = T.assert_model_near_statement(m, rm)
+        got = T.evaluate_fp32(m, 4, fault="drop_last_row")
+        assert T.max_norm(got[0], pure.dx) > T.MAX_NORM_DX                                 # the old bar sees a whole row ...
+        with pytest.raises(AssertionError, match="dx off"):                                # ... and so do the modelled bounds
+            T.assert_model(got, m, rm, plan, "dropped row")
+    C_, f, M, B, tpi = 96, 4, 510, 2, 24
+    m, plan = T.float_inputs(C_, M, B, tpi, stats="cpu"), T.assert_plan(C_, f, M, B, tpi)
+    rm = T.reference(m, *T.model_operands(m))
+    pure = T.assert_model_near_statement(m, rm)
+    got = T.evaluate_fp32(m, 4, fault="swap_rstd")
+    assert T.max_norm(got[0], pure.dx) < T.MAX_NORM_DX                                     # unseen by the old bars
+    assert max(T.max_norm(g_, getattr(pure, n)) for n, g_ in zip(("dw", "dgamma", "dbeta"), got[1:])) < T.MAX_NORM_PARAM
+    with pytest.raises(AssertionError, match="off at"):
+        T.assert_model(got, m, rm, plan, "swapped rstd")
+    assert max(T.assert_model(T.evaluate_fp32(m, 4), m, rm, plan, "no fault")) <= 1.0
