@@ -1112,34 +1112,19 @@ __global__ __launch_bounds__(512, 2) void fg4_fwd_kernel(Fg4Args a) {
 // Tile configurations.  Default: 4-wave workgroups on 32-pixel-wide tiles, two workgroups per CU - the two run out of
 // phase, so one's HBM prologue / epilogue and MFMA phases overlap the other's VALU-bound conv phase (a single 8-wave
 // workgroup per CU on 64-wide tiles serialises them: 1.5 ms instead of ... at C = 96, 256^2, bs 32).
-// A/B switch (read per call): MI_FG_CFG=w64 selects the 8-wave 64-wide tiles; th8 / pc16 / pc32 override rows / pairs per chunk.
-struct FgSel { int th, tw, pc, nw; };
-static FgSel fg_select(int C, int H) {
-  const char* e = MI_ENV(MI_FG_CFG);
-  FgSel f;
-  if (e && strstr(e, "w64")) {
-    f.tw = 64; f.nw = 8;
-    f.th = (C == 48 && !strstr(e, "th8") && H % 16 == 0) ? 16 : 8;
-    f.pc = (C == 48 && f.th == 16) ? 16 : 32;
-    if (strstr(e, "pc16")) f.pc = 16;
-    return f;
-  }
-  f.tw = 32; f.nw = 4;
-  f.th = (C == 48 && !(e && strstr(e, "th8")) && H % 16 == 0) ? 16 : 8;
-  f.pc = 16;
-  if (e && strstr(e, "pc32") && f.th == 8) f.pc = 32;
-  return f;
-}
-enum FgKind { FG_NONE = 0, FG_C48, FG_C96 };
-static FgKind fg_kind(const mi_gdfn_fused_shape* s) {
-  if (!s || s->B <= 0 || s->hidden <= 0) return FG_NONE;
-  if (s->W % 64 != 0 || s->H % 8 != 0) return FG_NONE;
-  if (s->C == 48) return FG_C48;
-  if (s->C == 96) return FG_C96;
-  return FG_NONE;
-}
+// A/B switch (read per call, by fg_plan alone): MI_FG_CFG=w64 selects the 8-wave 64-wide tiles; th8 / pc16 / pc32 override rows /
+// pairs per chunk; v2 keeps the tile forms everywhere, v4 takes the fourth form everywhere it exists.
+//
+// The instances each entry point is built with, (C, TH, TW, PC, NW): the plan answers from these lists and the launchers
+// instantiate from them, so a row is selectable exactly when it is compiled.
+#define FG_INFER_ROWS(X) \
+  X(48, 16, 32, 16, 4) X(48, 8, 32, 16, 4) X(48, 8, 32, 32, 4) X(96, 8, 32, 16, 4) X(96, 8, 32, 32, 4) \
+  X(48, 16, 64, 16, 8) X(48, 8, 64, 32, 8) X(48, 8, 64, 16, 8) X(96, 8, 64, 32, 8) X(96, 8, 64, 16, 8)
+#define FG_TRAIN_ROWS(X) \
+  X(48, 16, 32, 16, 4) X(48, 8, 32, 16, 4) X(96, 8, 32, 16, 4) X(48, 16, 64, 16, 8) X(96, 8, 64, 32, 8)
+#define FG_F8_ROWS(X) \
+  X(48, 16, 32, 16, 4) X(48, 8, 32, 16, 4) X(96, 8, 32, 16, 4)
 
-static bool fg_use_v2() { const char* e = MI_ENV(MI_FG_CFG); return e && strstr(e, "v2"); }
 static size_t fg_v2_pack_bytes(int C, int hidden) {
   const size_t a = fg_pack_layout(C, hidden, 16).bytes, b = fg_pack_layout(C, hidden, 32).bytes;
   return a > b ? a : b;
@@ -1150,19 +1135,84 @@ static int fg4_splits(int B, int tiles) {
   if (S > tiles / 2) S = tiles / 2 > 0 ? tiles / 2 : 1;
   return S;
 }
+template <int C> static Fg4PackLayout fg4_layout(int hidden) { return fg4_pack_layout<Fg4Cfg<C, 2>>(hidden, fg_v2_pack_bytes(C, hidden)); }
+
+// dynamic LDS of the row (C, th, tw, pc, nw) of an entry's list; 0: the entry has no such instance
+static size_t fg_row_lds(int entry, int C, int th, int tw, int pc, int nw) {
+#define FG_ROW_LDS(CC, TH, TW, PC, NW) \
+  if (C == CC && th == TH && tw == TW && pc == PC && nw == NW) return (size_t)FgCfg<CC, TH, TW, PC, NW>::LDS_BYTES;
+  if (entry == FG_INFER) { FG_INFER_ROWS(FG_ROW_LDS) }
+  if (entry == FG_TRAIN) { FG_TRAIN_ROWS(FG_ROW_LDS) }
+  if (entry == FG_F8) { FG_F8_ROWS(FG_ROW_LDS) }
+#undef FG_ROW_LDS
+  return 0;
+}
+
+FgPlan fg_plan(const mi_gdfn_fused_shape* s, int entry) {
+  FgPlan p = {};
+  if (!s || s->B <= 0 || s->hidden <= 0 || s->H <= 0 || s->W <= 0) return p;
+  if (s->W % 64 != 0 || s->H % 8 != 0 || (s->C != 48 && s->C != 96)) return p;
+  if (entry != FG_INFER && entry != FG_TRAIN && entry != FG_F8) return p;
+  const char* e = MI_ENV(MI_FG_CFG);
+  const bool w64 = e && strstr(e, "w64"), th8 = e && strstr(e, "th8"), pc16 = e && strstr(e, "pc16"), pc32 = e && strstr(e, "pc32"),
+             v2 = e && strstr(e, "v2"), v4 = e && strstr(e, "v4");
+  const int C = s->C;
+  // the tile form these switches select (also the chunk width mi_gdfn_fused_pack builds the tile sections for)
+  const int th = (C == 48 && !th8 && s->H % 16 == 0) ? 16 : 8;
+  int tw = 32, nw = 4, pc = 16;
+  if (w64) {
+    tw = 64; nw = 8;
+    pc = (C == 48 && th == 16) ? 16 : 32;
+    if (pc16) pc = 16;
+  } else if (pc32 && th == 8) {
+    pc = 32;
+  }
+  // fourth form (depthwise conv on the matrix cores): default at C = 48 inference (607 vs 666 us at 256^2, bs 32); at C = 96 its
+  // 8-wave form spills (xa + output accumulators + operand pipeline > 256 registers) and loses to the tile form: v4 forces it, v2
+  // keeps the tile forms everywhere.  Its SAVE kernel is opt-in (v4): its stores ADD their time (918 vs 607 us at C = 48, 256^2) -
+  // every later wait on a load (weight DMA, residual, prefetch) sits behind them in the wave's in-order vmcnt - so it does not
+  // beat the chain.  The fp8 operand form exists for the default tile forms only.
+  const bool fourth = entry == FG_INFER ? (!v2 && (C == 48 || v4)) : entry == FG_TRAIN ? v4 : false;
+  if (entry == FG_TRAIN && !mi_dwconv_gate_recompute_ok(s->H, s->W, 3)) return p;   // the blob it writes is the recomputing backward's
+  const Fg4PackLayout l4 = C == 48 ? fg4_layout<48>(s->hidden) : fg4_layout<96>(s->hidden);
+  if (fourth) {
+    p.family = FG_FOURTH;
+    p.th = 8; p.tw = 32; p.pc = 16; p.nw = 8;
+    p.ngr = l4.ngr;
+    p.tiles_x = s->W / 32; p.tiles_y = s->H / 8;
+    p.S = fg4_splits(s->B, p.tiles_x * p.tiles_y);
+    p.lds = C == 48 ? (size_t)Fg4Cfg<48, 2>::LDS_BYTES : (size_t)Fg4Cfg<96, 2>::LDS_BYTES;
+  } else {
+    const size_t lds = fg_row_lds(entry, C, th, tw, pc, nw);
+    if (!lds) return p;
+    p.family = FG_TILE;
+    p.th = th; p.tw = tw; p.pc = pc; p.nw = nw;
+    p.nch = cdiv(s->hidden, pc);
+    p.tiles_x = s->W / tw; p.tiles_y = s->H / th;
+    p.S = p.tiles_x * p.tiles_y;
+    p.lds = lds;
+  }
+  p.covered = true;
+  p.C = C; p.save = entry == FG_TRAIN; p.f8 = entry == FG_F8;
+  p.grid = (int64_t)s->B * p.S; p.block = 64 * p.nw;
+  p.xcd_pairs = p.family == FG_TILE && p.tw == 32 && p.grid % 16 == 0 && !MI_ENV(MI_FG_NOXCD);
+  p.pack_bytes = l4.bytes; p.pack_pc = pc;
+  return p;
+}
+
 template <int C, bool SAVE>
-static int fg4_launch(const mi_gdfn_fused_shape* s, const void* pack, const void* y, void* out, float* mean, float* rstd, void* h0s,
-                      void* gs, hipStream_t st) {
+static int fg4_launch(const mi_gdfn_fused_shape* s, const FgPlan& p, const void* pack, const void* y, void* out, float* mean, float* rstd,
+                      void* h0s, void* gs, hipStream_t st) {
   using K = Fg4Cfg<C, 2>;
-  const Fg4PackLayout l = fg4_pack_layout<K>(s->hidden, fg_v2_pack_bytes(s->C, s->hidden));
+  const Fg4PackLayout l = fg4_layout<C>(s->hidden);
   Fg4Args a;
   const unsigned char* pk = (const unsigned char*)pack;
   a.y = (const bf16*)y; a.out = (bf16*)out; a.mean = mean; a.rstd = rstd;
   a.grp = pk + l.grp; a.b2 = (const float*)(pk + l.b2);
   a.h0s = (bf16*)h0s; a.gs = (bf16*)gs;
   a.B = s->B; a.H = s->H; a.W = s->W; a.hidden = s->hidden; a.with_bias = s->ln_with_bias;
-  a.tiles_x = s->W / 32; a.tiles_y = s->H / 8; a.ngr = l.ngr;
-  a.S = fg4_splits(s->B, a.tiles_x * a.tiles_y);
+  a.tiles_x = p.tiles_x; a.tiles_y = p.tiles_y; a.ngr = p.ngr;
+  a.S = p.S;
   { const char* e = MI_ENV(MI_FG_DEBUG); a.dbg = e ? atoi(e) : 0; }
   static std::atomic<unsigned> attr_set{0};
   int dev = 0;
@@ -1176,16 +1226,16 @@ static int fg4_launch(const mi_gdfn_fused_shape* s, const void* pack, const void
   const double N = (double)s->H * s->W * s->B, h = s->hidden;
   ProfScope ps(st, K_GDFN_FUSED_FWD, (2.0 * C + (SAVE ? 3.0 * h : 0.0)) * N * 2.0, 2.0 * N * (3.0 * C * h) + 2.0 * N * 9.0 * 2.0 * h);
   if (a.dbg & 0x1000)
-    hipLaunchKernelGGL((fg4_fwd_kernel<C, 2, SAVE, true>), dim3((unsigned)(s->B * a.S)), dim3(64 * K::NW), K::LDS_BYTES, st, a);
+    hipLaunchKernelGGL((fg4_fwd_kernel<C, 2, SAVE, true>), dim3((unsigned)p.grid), dim3(p.block), p.lds, st, a);
   else
-    hipLaunchKernelGGL((fg4_fwd_kernel<C, 2, SAVE>), dim3((unsigned)(s->B * a.S)), dim3(64 * K::NW), K::LDS_BYTES, st, a);
+    hipLaunchKernelGGL((fg4_fwd_kernel<C, 2, SAVE>), dim3((unsigned)p.grid), dim3(p.block), p.lds, st, a);
   MI_LAUNCH_CHECK();
   return MI_OK;
 }
 template <int C>
 static int fg4_pack(const mi_gdfn_fused_shape* s, const float* ln_w, const float* ln_b, const mi_gdfn_params* p, void* pack, hipStream_t st) {
   using K = Fg4Cfg<C, 2>;
-  const Fg4PackLayout l = fg4_pack_layout<K>(s->hidden, fg_v2_pack_bytes(s->C, s->hidden));
+  const Fg4PackLayout l = fg4_layout<C>(s->hidden);
   unsigned char* pk = (unsigned char*)pack;
   Fg4PackArgs a;
   a.ln_w = ln_w; a.ln_b = ln_b; a.in_w = p->in_w; a.in_b = p->in_b; a.dw_w = p->dw_w; a.dw_b = p->dw_b; a.out_w = p->out_w; a.out_b = p->out_b;
@@ -1197,53 +1247,64 @@ static int fg4_pack(const mi_gdfn_fused_shape* s, const float* ln_w, const float
 }
 
 template <int C, int TH, int TW, int PC, int NW, bool F8 = false, bool SAVE = false>
-static int fg_launch(const mi_gdfn_fused_shape* s, const FgPackLayout& l, const void* pack, const void* y, void* out,
+static int fg_launch(const mi_gdfn_fused_shape* s, const FgPlan& p, const void* pack, const void* y, void* out,
                      float* mean, float* rstd, hipStream_t st, const mi_f8_scales* f8 = nullptr, void* h0s = nullptr,
                      void* gs = nullptr) {
-  using K = FgCfg<C, TH, TW, PC, NW>;
+  const FgPackLayout l = fg_pack_layout(C, s->hidden, PC);
   FgArgs a;
   const unsigned char* pk = (const unsigned char*)pack;
   a.y = (const bf16*)y; a.out = (bf16*)out; a.mean = mean; a.rstd = rstd;
   a.w1p = (const bf16*)(pk + l.w1p); a.w2p = (const bf16*)(pk + l.w2p);
   a.wdp = (const float*)(pk + l.wdp); a.b2 = (const float*)(pk + l.b2);
-  a.B = s->B; a.H = s->H; a.W = s->W; a.nch = l.nch; a.with_bias = s->ln_with_bias;
-  a.tiles_x = s->W / TW; a.tiles_y = s->H / TH;
+  a.B = s->B; a.H = s->H; a.W = s->W; a.nch = p.nch; a.with_bias = s->ln_with_bias;
+  a.tiles_x = p.tiles_x; a.tiles_y = p.tiles_y;
   a.f8_x1 = f8 ? f8->x1 : 1.f; a.f8_w1 = f8 ? f8->w1 : 1.f; a.f8_x2 = f8 ? f8->x2 : 1.f; a.f8_w2 = f8 ? f8->w2 : 1.f;
   a.h0s = (bf16*)h0s; a.gs = (bf16*)gs; a.hidden = s->hidden;
   { const char* e = MI_ENV(MI_FG_DEBUG); a.dbg = e ? atoi(e) : 0; }
-  const int64_t tiles = (int64_t)s->B * a.tiles_x * a.tiles_y;
-  MI_CHECK_ARG(tiles < (1ll << 31), "gdfn_fused: grid too large");
-  a.xcd_pairs = (TW == 32 && tiles % 16 == 0 && !MI_ENV(MI_FG_NOXCD)) ? 1 : 0;
+  MI_CHECK_ARG(p.grid < (1ll << 31), "gdfn_fused: grid too large");
+  a.xcd_pairs = p.xcd_pairs ? 1 : 0;
   MI_CHECK_HIP(hipFuncSetAttribute((const void*)fg_fwd_kernel<C, TH, TW, PC, NW, F8, SAVE>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   (int)K::LDS_BYTES));
+                                   (int)p.lds));
   const double N = (double)s->H * s->W * s->B, h = s->hidden;
   ProfScope ps(st, K_GDFN_FUSED_FWD, (2.0 * C + (SAVE ? 3.0 * h : 0.0)) * N * 2.0, 2.0 * N * (3.0 * C * h) + 2.0 * N * 9.0 * 2.0 * h);
-  hipLaunchKernelGGL((fg_fwd_kernel<C, TH, TW, PC, NW, F8, SAVE>), dim3((unsigned)tiles), dim3(64 * NW), K::LDS_BYTES, st, a);
+  hipLaunchKernelGGL((fg_fwd_kernel<C, TH, TW, PC, NW, F8, SAVE>), dim3((unsigned)p.grid), dim3(p.block), p.lds, st, a);
   MI_LAUNCH_CHECK();
   return MI_OK;
 }
+#define FG_ROW_IS(CC, TH, TW, PC, NW) (p.C == CC && p.th == TH && p.tw == TW && p.pc == PC && p.nw == NW)
 
 }  // namespace mi
 
 using namespace mi;
 
-extern "C" int mi_gdfn_fused_ok(const mi_gdfn_fused_shape* s) { return fg_kind(s) != FG_NONE ? 1 : 0; }
+extern "C" int mi_gdfn_fused_ok(const mi_gdfn_fused_shape* s) { return fg_plan(s, FG_INFER).covered ? 1 : 0; }
 
-extern "C" size_t mi_gdfn_fused_pack_bytes(const mi_gdfn_fused_shape* s) {
-  const FgKind k = fg_kind(s);
-  if (k == FG_NONE) return 0;
-  const size_t v2 = fg_v2_pack_bytes(s->C, s->hidden);
-  return s->C == 48 ? fg4_pack_layout<Fg4Cfg<48, 2>>(s->hidden, v2).bytes : fg4_pack_layout<Fg4Cfg<96, 2>>(s->hidden, v2).bytes;
+extern "C" size_t mi_gdfn_fused_pack_bytes(const mi_gdfn_fused_shape* s) { return fg_plan(s, FG_INFER).pack_bytes; }
+
+// What the three forwards run for this shape under the current MI_FG_CFG / MI_FG_NOXCD.  Host-side only: the same fg_plan.
+// entry: 0 mi_gdfn_fused_fwd, 1 mi_gdfn_fused_fwd_train, 2 mi_gdfn_fused_fwd_f8.  out[20]: covered, family (0 tile / 1 fourth), C,
+// TH, TW, pairs per chunk, waves, SAVE, F8, chunks (tile family), groups (fourth form), tiles_x, tiles_y, workgroups per image S,
+// grid (= B * S), block, dynamic LDS bytes, xcd_pairs, pack bytes, the chunk width mi_gdfn_fused_pack builds the tile sections for.
+// An entry with no instance for this shape and these switches is no error: covered = 0 and every other field 0.
+extern "C" int mi_gdfn_fused_plan(const mi_gdfn_fused_shape* s, int entry, int64_t* out) {
+  MI_CHECK_ARG(s && out, "gdfn_fused_plan: null pointer");
+  MI_CHECK_ARG(entry == FG_INFER || entry == FG_TRAIN || entry == FG_F8, "gdfn_fused_plan: bad entry %d", entry);
+  MI_CHECK_ARG(s->B > 0 && s->C > 0 && s->hidden > 0 && s->H > 0 && s->W > 0, "gdfn_fused_plan: bad shape");
+  const FgPlan p = fg_plan(s, entry);
+  const int64_t v[20] = {p.covered, p.family, p.C, p.th, p.tw, p.pc, p.nw, p.save, p.f8, p.nch, p.ngr, p.tiles_x, p.tiles_y, p.S,
+                         p.grid, p.block, (int64_t)p.lds, p.xcd_pairs, (int64_t)p.pack_bytes, p.pack_pc};
+  memcpy(out, v, sizeof(v));
+  return MI_OK;
 }
 
 extern "C" int mi_gdfn_fused_pack(const mi_gdfn_fused_shape* s, const float* ln_w, const float* ln_b,
                                   const mi_gdfn_params* p, void* pack, void* stream) {
-  const FgKind k = fg_kind(s);
-  MI_CHECK_ARG(k != FG_NONE, "gdfn_fused_pack: shape not covered by the fused kernels (mi_gdfn_fused_ok)");
+  const FgPlan pl = fg_plan(s, FG_INFER);
+  MI_CHECK_ARG(pl.covered, "gdfn_fused_pack: shape not covered by the fused kernels (mi_gdfn_fused_ok)");
   MI_CHECK_ARG(ln_w && p && p->in_w && p->dw_w && p->out_w && pack, "gdfn_fused_pack: null pointer");
   MI_CHECK_ARG((s->ln_with_bias != 0) == (ln_b != nullptr), "gdfn_fused_pack: ln_with_bias does not match ln_b");
   MI_CHECK_ARG(aligned16(pack), "gdfn_fused_pack: pack buffer must be 16-byte aligned");
-  const int PC = fg_select(s->C, s->H).pc;
+  const int PC = pl.pack_pc;
   const FgPackLayout l = fg_pack_layout(s->C, s->hidden, PC);
   unsigned char* pk = (unsigned char*)pack;
   FgPackArgs a;
@@ -1261,92 +1322,61 @@ extern "C" int mi_gdfn_fused_pack(const mi_gdfn_fused_shape* s, const float* ln_
 
 extern "C" int mi_gdfn_fused_fwd(const mi_gdfn_fused_shape* s, const void* pack, const void* y, void* out, float* mean,
                                  float* rstd, void* stream) {
-  const FgKind k = fg_kind(s);
-  MI_CHECK_ARG(k != FG_NONE, "gdfn_fused_fwd: shape not covered by the fused kernels (mi_gdfn_fused_ok)");
+  const FgPlan p = fg_plan(s, FG_INFER);
+  MI_CHECK_ARG(p.covered, "gdfn_fused_fwd: shape not covered by the fused kernels (mi_gdfn_fused_ok)");
   MI_CHECK_ARG(pack && y && out, "gdfn_fused_fwd: null pointer");
   MI_CHECK_ARG((mean == nullptr) == (rstd == nullptr), "gdfn_fused_fwd: mean and rstd go together");
   MI_CHECK_ARG(aligned16(pack) && aligned16(y) && aligned16(out), "gdfn_fused_fwd: pointers must be 16-byte aligned");
-  const FgSel f = fg_select(s->C, s->H);
-  const FgPackLayout l = fg_pack_layout(s->C, s->hidden, f.pc);
   hipStream_t st = (hipStream_t)stream;
-  // fourth form (depthwise conv on the matrix cores): default at C = 48 (607 vs 666 us at 256^2, bs 32); at C = 96 its 8-wave
-  // form spills (xa + output accumulators + operand pipeline > 256 registers) and loses to the form above: MI_FG_CFG=v4 forces it,
-  // MI_FG_CFG=v2... keeps the forms above everywhere
-  { const char* e = MI_ENV(MI_FG_CFG);
-    const bool v4 = e && strstr(e, "v4");
-    if (!fg_use_v2() && (s->C == 48 || v4))
-      return s->C == 48 ? fg4_launch<48, false>(s, pack, y, out, mean, rstd, nullptr, nullptr, st)
-                        : fg4_launch<96, false>(s, pack, y, out, mean, rstd, nullptr, nullptr, st); }
+  if (p.family == FG_FOURTH)
+    return p.C == 48 ? fg4_launch<48, false>(s, p, pack, y, out, mean, rstd, nullptr, nullptr, st)
+                     : fg4_launch<96, false>(s, p, pack, y, out, mean, rstd, nullptr, nullptr, st);
 #define FG_CASE(CC, TH, TW, PC, NW) \
-  if (s->C == CC && f.th == TH && f.tw == TW && f.pc == PC && f.nw == NW) \
-    return fg_launch<CC, TH, TW, PC, NW>(s, l, pack, y, out, mean, rstd, st)
-  FG_CASE(48, 16, 32, 16, 4);
-  FG_CASE(48, 8, 32, 16, 4);
-  FG_CASE(48, 8, 32, 32, 4);
-  FG_CASE(96, 8, 32, 16, 4);
-  FG_CASE(96, 8, 32, 32, 4);
-  FG_CASE(48, 16, 64, 16, 8);
-  FG_CASE(48, 8, 64, 32, 8);
-  FG_CASE(48, 8, 64, 16, 8);
-  FG_CASE(96, 8, 64, 32, 8);
-  FG_CASE(96, 8, 64, 16, 8);
+  if (FG_ROW_IS(CC, TH, TW, PC, NW)) return fg_launch<CC, TH, TW, PC, NW>(s, p, pack, y, out, mean, rstd, st);
+  FG_INFER_ROWS(FG_CASE)
 #undef FG_CASE
-  set_error("gdfn_fused_fwd: no kernel for C=%d th=%d tw=%d pc=%d", s->C, f.th, f.tw, f.pc);
+  set_error("gdfn_fused_fwd: the plan names no compiled kernel (C=%d th=%d tw=%d pc=%d)", p.C, p.th, p.tw, p.pc);
   return MI_ERR_ARG;
 }
 
 // Training form: the same launch also writes what the backward reads - the project_in output h0 [B][2h][H][W] (the depthwise
 // conv is recomputed from it) and the gate output g [B][h][H][W] (operand of project_out's weight gradient) - so the forward of
 // the half-block is one launch instead of GEMM -> depthwise gate -> GEMM: it reads y once and writes out, h0, g once
-// (10 C planes per pixel with h = 2.66 C against the chain's 19).  Default tile forms only.
+// (10 C planes per pixel with h = 2.66 C against the chain's 19).  Default tile forms only (FG_TRAIN_ROWS), and the fourth form under v4.
 namespace mi {
 int fused_gdfn_fwd_save(const mi_gdfn_fused_shape* s, const void* pack, const void* y, void* out, float* mean, float* rstd,
                         void* h0, void* g, hipStream_t st) {
-  const FgKind k = fg_kind(s);
-  MI_CHECK_ARG(k != FG_NONE, "gdfn_fused_fwd_train: shape not covered by the fused kernels (mi_gdfn_fused_ok)");
+  const FgPlan p = fg_plan(s, FG_TRAIN);
+  MI_CHECK_ARG(p.covered, "gdfn_fused_fwd_train: no saving kernel for this shape under the current MI_FG_CFG (mi_gdfn_fused_fwd_train_ok)");
   MI_CHECK_ARG(pack && y && out && mean && rstd && h0 && g, "gdfn_fused_fwd_train: null pointer");
   MI_CHECK_ARG(aligned16(pack) && aligned16(y) && aligned16(out) && aligned16(h0) && aligned16(g),
                "gdfn_fused_fwd_train: pointers must be 16-byte aligned");
-  // the fourth form's SAVE kernel is opt-in (MI_FG_CFG=v4): its stores ADD their time (918 vs 607 us at C = 48, 256^2) - every later
-  // wait on a load (weight DMA, residual, prefetch) sits behind them in the wave's in-order vmcnt - so it does not beat the chain
-  { const char* e = MI_ENV(MI_FG_CFG);
-    if (e && strstr(e, "v4"))
-      return s->C == 48 ? fg4_launch<48, true>(s, pack, y, out, mean, rstd, h0, g, st) : fg4_launch<96, true>(s, pack, y, out, mean, rstd, h0, g, st); }
-  const FgSel f = fg_select(s->C, s->H);
-  const FgPackLayout l = fg_pack_layout(s->C, s->hidden, f.pc);
+  if (p.family == FG_FOURTH)
+    return p.C == 48 ? fg4_launch<48, true>(s, p, pack, y, out, mean, rstd, h0, g, st) : fg4_launch<96, true>(s, p, pack, y, out, mean, rstd, h0, g, st);
 #define FGS_CASE(CC, TH, TW, PC, NW) \
-  if (s->C == CC && f.th == TH && f.tw == TW && f.pc == PC && f.nw == NW) \
-    return fg_launch<CC, TH, TW, PC, NW, false, true>(s, l, pack, y, out, mean, rstd, st, nullptr, h0, g)
-  FGS_CASE(48, 16, 32, 16, 4);
-  FGS_CASE(48, 8, 32, 16, 4);
-  FGS_CASE(96, 8, 32, 16, 4);
-  FGS_CASE(48, 16, 64, 16, 8);
-  FGS_CASE(96, 8, 64, 32, 8);
+  if (FG_ROW_IS(CC, TH, TW, PC, NW)) return fg_launch<CC, TH, TW, PC, NW, false, true>(s, p, pack, y, out, mean, rstd, st, nullptr, h0, g);
+  FG_TRAIN_ROWS(FGS_CASE)
 #undef FGS_CASE
-  set_error("gdfn_fused_fwd_train: no saving kernel for C=%d th=%d tw=%d pc=%d", s->C, f.th, f.tw, f.pc);
+  set_error("gdfn_fused_fwd_train: the plan names no compiled kernel (C=%d th=%d tw=%d pc=%d)", p.C, p.th, p.tw, p.pc);
   return MI_ERR_ARG;
 }
 }  // namespace mi
 
-// The same launch with fp8 (e4m3) MFMA operands in both projections (inference; default tile forms only).  f8->x1 scales the
-// NORMALISED input ((y - mu) rstd, |.| <= sqrt(C)) and f8->w1 the packed W_in . diag(gamma); x2 / w2 as in mi_gdfn_fwd_f8.
+// The same launch with fp8 (e4m3) MFMA operands in both projections (inference; default tile forms only: FG_F8_ROWS).  f8->x1 scales
+// the NORMALISED input ((y - mu) rstd, |.| <= sqrt(C)) and f8->w1 the packed W_in . diag(gamma); x2 / w2 as in mi_gdfn_fwd_f8.
 extern "C" int mi_gdfn_fused_fwd_f8(const mi_gdfn_fused_shape* s, const void* pack, const mi_f8_scales* f8, const void* y, void* out,
                                     void* stream) {
-  const FgKind k = fg_kind(s);
-  MI_CHECK_ARG(k != FG_NONE, "gdfn_fused_fwd_f8: shape not covered by the fused kernels (mi_gdfn_fused_ok)");
+  const FgPlan p = fg_plan(s, FG_F8);
+  MI_CHECK_ARG(p.covered, "gdfn_fused_fwd_f8: no fp8 kernel for this shape under the current MI_FG_CFG (default tile forms only; mi_gdfn_fused_plan)");
   MI_CHECK_ARG(pack && y && out && f8, "gdfn_fused_fwd_f8: null pointer");
   MI_CHECK_ARG(f8->x1 > 0.f && f8->w1 > 0.f && f8->x2 > 0.f && f8->w2 > 0.f, "gdfn_fused_fwd_f8: fp8 scales must be positive");
   MI_CHECK_ARG(aligned16(pack) && aligned16(y) && aligned16(out), "gdfn_fused_fwd_f8: pointers must be 16-byte aligned");
-  const FgSel f = fg_select(s->C, s->H);
-  const FgPackLayout l = fg_pack_layout(s->C, s->hidden, f.pc);
   hipStream_t st = (hipStream_t)stream;
 #define FG8_CASE(CC, TH, TW, PC, NW) \
-  if (s->C == CC && f.th == TH && f.tw == TW && f.pc == PC && f.nw == NW) \
-    return fg_launch<CC, TH, TW, PC, NW, true>(s, l, pack, y, out, nullptr, nullptr, st, f8)
-  FG8_CASE(48, 16, 32, 16, 4);
-  FG8_CASE(48, 8, 32, 16, 4);
-  FG8_CASE(96, 8, 32, 16, 4);
+  if (FG_ROW_IS(CC, TH, TW, PC, NW)) return fg_launch<CC, TH, TW, PC, NW, true>(s, p, pack, y, out, nullptr, nullptr, st, f8);
+  FG_F8_ROWS(FG8_CASE)
 #undef FG8_CASE
-  set_error("gdfn_fused_fwd_f8: fp8 operands are built for the default tile forms only (C=%d th=%d tw=%d pc=%d)", s->C, f.th, f.tw, f.pc);
+  set_error("gdfn_fused_fwd_f8: the plan names no compiled kernel (C=%d th=%d tw=%d pc=%d)", p.C, p.th, p.tw, p.pc);
   return MI_ERR_ARG;
 }
+#undef FG_ROW_IS

@@ -954,8 +954,7 @@ static FmKind fm_kind(const mi_mdta_shape* s) {
   if (s->C == 96 && s->heads == 1) return FM_96_1;
   return FM_NONE;
 }
-static int fm_splits(const mi_mdta_shape* s, int TH) {
-  const int tiles = (s->H / TH) * (s->W / 32);
+static int fm_splits(const mi_mdta_shape* s, int tiles) {
   int S = 256 / s->B;                                   // one 8-wave workgroup per CU
   if (S < 1) S = 1;
   if (S > 256) S = 256;
@@ -963,13 +962,13 @@ static int fm_splits(const mi_mdta_shape* s, int TH) {
   return S;
 }
 
-struct FmWs { void* v; float* part; float* graw; float* ss; float* P; float* A; float* nrm; float* M; void* Mb; void* pw_ws; size_t bytes; };
-static FmWs fm_ws_layout(const mi_mdta_shape* s, void* base) {
+struct FmWs { void* v; float* part; float* graw; float* ss; float* P; float* A; float* nrm; float* M; void* Mb; void* pw_ws; size_t part_bytes, bytes; };
+static FmWs fm_ws_layout(const mi_mdta_shape* s, int S, void* base) {
   const size_t N = (size_t)s->H * s->W, C = s->C, B = s->B, c = C / s->heads, Z = B * s->heads;
   Carver cv(base);
   FmWs w;
-  const int S = fm_splits(s, 8);
   w.part = cv.take<float>(B * S * 8 * (s->heads * c * c + 2 * C) * sizeof(float));   // (one partial per WAVE in the fourth form)
+  w.part_bytes = cv.off;
   w.graw = cv.take<float>(Z * c * c * sizeof(float));
   w.ss = cv.take<float>(Z * 2 * c * sizeof(float));
   w.P = cv.take<float>(Z * c * c * sizeof(float));
@@ -985,14 +984,14 @@ static FmWs fm_ws_layout(const mi_mdta_shape* s, void* base) {
 
 template <int C, int HEADS, int TH, int NW>
 static int fm_launch(const mi_mdta_shape* s, const FmPackLayout& l, const void* pack, const void* x, void* v, float* part, float* mean,
-                     float* rstd, int with_bias, int S, hipStream_t st) {
+                     float* rstd, int with_bias, const FmPlan& p, hipStream_t st) {
   using K = FmCfg<C, HEADS, TH, NW>;
   FmArgs a;
   const unsigned char* pk = (const unsigned char*)pack;
   a.x = (const bf16*)x; a.v = (bf16*)v; a.part = part; a.mean = mean; a.rstd = rstd;
   a.w1p = (const bf16*)(pk + l.w1p); a.wdp = (const float*)(pk + l.wdp);
   a.B = s->B; a.H = s->H; a.W = s->W; a.with_bias = with_bias;
-  a.tiles_x = s->W / 32; a.tiles_y = s->H / TH; a.S = S;
+  a.tiles_x = p.tiles_x; a.tiles_y = p.tiles_y; a.S = p.S;
   { const char* e = MI_ENV(MI_FM_DEBUG); a.dbg = e ? atoi(e) : 0; }
   static std::atomic<unsigned> attr_set{0};
   int dev = 0;
@@ -1005,14 +1004,14 @@ static int fm_launch(const mi_mdta_shape* s, const FmPackLayout& l, const void* 
   }
   const double N = (double)s->H * s->W * s->B;
   ProfScope ps(st, K_MDTA_FUSED_A, 2.0 * C * N * 2.0, 2.0 * N * (3.0 * C * C + (double)C * K::c) + 2.0 * N * 9.0 * 3.0 * C);
-  hipLaunchKernelGGL((fm_fwd_kernel<C, HEADS, TH, NW>), dim3((unsigned)(s->B * S)), dim3(64 * NW), K::LDS_BYTES, st, a);
+  hipLaunchKernelGGL((fm_fwd_kernel<C, HEADS, TH, NW>), dim3((unsigned)p.grid), dim3(p.block), p.lds, st, a);
   MI_LAUNCH_CHECK();
   return MI_OK;
 }
 
 template <int C, int HEADS, int G, bool SAVE>
 static int fm4_launch(const mi_mdta_shape* s, const void* pack, const void* x, void* v, float* part, float* mean, float* rstd,
-                      int with_bias, int S, void* qkv0, void* qk, hipStream_t st) {
+                      int with_bias, const FmPlan& p, void* qkv0, void* qk, hipStream_t st) {
   using K = Fm4Cfg<C, HEADS, G>;
   const Fm3PackLayout l3 = fm3_pack_layout(C, fm_pack_layout(C).bytes);
   Fm3Args a;
@@ -1020,7 +1019,7 @@ static int fm4_launch(const mi_mdta_shape* s, const void* pack, const void* x, v
   a.wt = (const unsigned char*)pack + l3.w1f;
   a.qkv0 = (bf16*)qkv0; a.qk = (bf16*)qk;
   a.B = s->B; a.H = s->H; a.W = s->W; a.with_bias = with_bias;
-  a.tiles_x = s->W / 32; a.tiles_y = s->H / 8; a.S = S;
+  a.tiles_x = p.tiles_x; a.tiles_y = p.tiles_y; a.S = p.S;
   { const char* e = MI_ENV(MI_FM_DEBUG); a.dbg = e ? atoi(e) : 0; }
   static std::atomic<unsigned> attr_set{0};
   int dev = 0;
@@ -1037,35 +1036,72 @@ static int fm4_launch(const mi_mdta_shape* s, const void* pack, const void* x, v
   ProfScope ps(st, K_MDTA_FUSED_A, (2.0 + (SAVE ? 5.0 : 0.0)) * C * N * 2.0,
                2.0 * N * (3.0 * C * C + (double)C * K::c) + 2.0 * N * 9.0 * 3.0 * C);
   if (a.dbg & 0x1000)
-    hipLaunchKernelGGL((fm4_fwd_kernel<C, HEADS, G, SAVE, true>), dim3((unsigned)(s->B * S)), dim3(64 * K::NW), K::LDS4_BYTES, st, a);
+    hipLaunchKernelGGL((fm4_fwd_kernel<C, HEADS, G, SAVE, true>), dim3((unsigned)p.grid), dim3(p.block), p.lds, st, a);
   else
-    hipLaunchKernelGGL((fm4_fwd_kernel<C, HEADS, G, SAVE>), dim3((unsigned)(s->B * S)), dim3(64 * K::NW), K::LDS4_BYTES, st, a);
+    hipLaunchKernelGGL((fm4_fwd_kernel<C, HEADS, G, SAVE>), dim3((unsigned)p.grid), dim3(p.block), p.lds, st, a);
   MI_LAUNCH_CHECK();
   return MI_OK;
 }
-static bool fm_use_v2() { const char* e = MI_ENV(MI_FM_CFG); return e && strstr(e, "v2"); }
+
+// The one place that decides what pass A runs.  Round-3 form (depthwise conv on the VALU): every kind; MI_FM_CFG=v2 keeps it at
+// C = 48 too.  Fourth form (the conv on the matrix cores, grouped phases, wave-local Gram): the default at C = 48 - one group of
+// all 9 chunks: 308 us at 256^2, bs 32; three double-buffered groups of 3 (GEMM1 of group g + 1 inside the wave-local interval of
+// group g) were measured at 418 us - two more barriers per tile cost more than the overlap buys.
+// pays: covered AND expected to beat the unfused chain: pass A runs one persistent 8-wave workgroup per CU, so it needs (close
+// to) a workgroup for every CU - B * splits >= 192 of the 256.  Measured (profiles/r03_c_*): bs 8 at 96 x 128^2 gives 128
+// workgroups and 0.75x of the chain; bs 8 at 256^2 and bs 25 / 32 everywhere fill the chip (1.06 - 1.18x).
+FmPlan fm_plan(const mi_mdta_shape* s) {
+  FmPlan p = {};
+  const FmKind k = fm_kind(s);
+  if (k == FM_NONE || s->H <= 0 || s->W <= 0) return p;
+  const char* e = MI_ENV(MI_FM_CFG);
+  const bool v2 = e && strstr(e, "v2");
+  p.covered = true;
+  p.kind = k; p.form = (k == FM_48_1 && !v2) ? FM_FOURTH : FM_ROUND3;
+  p.C = s->C; p.heads = s->heads; p.th = 8; p.nw = 8;
+  p.tiles_x = s->W / 32; p.tiles_y = s->H / p.th;
+  p.S = fm_splits(s, p.tiles_x * p.tiles_y);
+  p.grid = (int64_t)s->B * p.S; p.block = 64 * p.nw;
+  p.lds = p.form == FM_FOURTH ? (size_t)Fm4Cfg<48, 1, 9>::LDS4_BYTES
+        : k == FM_48_1 ? (size_t)FmCfg<48, 1, 8, 8>::LDS_BYTES
+        : k == FM_96_2 ? (size_t)FmCfg<96, 2, 8, 8>::LDS_BYTES : (size_t)FmCfg<96, 1, 8, 8>::LDS_BYTES;
+  p.part_mult = p.form == FM_FOURTH ? 8 : 1;
+  p.pays = p.grid >= 192;
+  const FmWs w = fm_ws_layout(s, p.S, nullptr);
+  p.part_bytes = w.part_bytes;
+  p.ws_bytes = w.bytes;
+  p.pack_bytes = fm3_pack_layout(s->C, fm_pack_layout(s->C).bytes).bytes;
+  return p;
+}
 
 }  // namespace mi
 
 using namespace mi;
 
-extern "C" int mi_mdta_fused_ok(const mi_mdta_shape* s) { return (fm_kind(s) != FM_NONE && !MI_ENV(MI_NO_FUSED_MDTA)) ? 1 : 0; }
-// Covered AND expected to beat the unfused chain: pass A runs one persistent 8-wave workgroup per CU, so it needs (close to) a
-// workgroup for every CU - B * splits >= 192 of the 256.  Measured (profiles/r03_c_*): bs 8 at 96 x 128^2 gives 128 workgroups and
-// 0.75x of the chain; bs 8 at 256^2 and bs 25 / 32 everywhere fill the chip (1.06 - 1.18x).
-extern "C" int mi_mdta_fused_pays(const mi_mdta_shape* s) {
-  if (!mi_mdta_fused_ok(s)) return 0;
-  return (int64_t)s->B * fm_splits(s, 8) >= 192 ? 1 : 0;
-}
+// (MI_NO_FUSED_MDTA=1 is the module paths' off switch: it answers "do not take it" here, the plan and the launcher do not read it)
+extern "C" int mi_mdta_fused_ok(const mi_mdta_shape* s) { return (fm_plan(s).covered && !MI_ENV(MI_NO_FUSED_MDTA)) ? 1 : 0; }
+extern "C" int mi_mdta_fused_pays(const mi_mdta_shape* s) { return (mi_mdta_fused_ok(s) && fm_plan(s).pays) ? 1 : 0; }
 
-extern "C" size_t mi_mdta_fused_pack_bytes(const mi_mdta_shape* s) {
-  if (fm_kind(s) == FM_NONE) return 0;
-  return fm3_pack_layout(s->C, fm_pack_layout(s->C).bytes).bytes;
+extern "C" size_t mi_mdta_fused_pack_bytes(const mi_mdta_shape* s) { return fm_plan(s).pack_bytes; }
+
+// What mi_mdta_fused_fwd's pass A runs for this shape under the current MI_FM_CFG.  Host-side only: the same fm_plan.  out[16]:
+// covered, pays, kind (1: C 48 one head, 2: C 96 two heads, 3: C 96 one head), form (0 round-3 / 1 fourth), tile rows TH, tiles_x,
+// tiles_y, persistent workgroups per image S, grid (= B * S), block, dynamic LDS bytes, part_mult (Gram partials a workgroup
+// writes), bytes of the partials' arena, workspace bytes, pack bytes, waves.  A shape the kernel does not cover is no error:
+// covered = 0 and every other field 0.
+extern "C" int mi_mdta_fused_plan(const mi_mdta_shape* s, int64_t* out) {
+  MI_CHECK_ARG(s && out, "mdta_fused_plan: null pointer");
+  MI_CHECK_ARG(s->B > 0 && s->C > 0 && s->heads > 0 && s->H > 0 && s->W > 0, "mdta_fused_plan: bad shape");
+  const FmPlan p = fm_plan(s);
+  const int64_t v[16] = {p.covered, p.pays, p.kind, p.form, p.th, p.tiles_x, p.tiles_y, p.S, p.grid, p.block, (int64_t)p.lds, p.part_mult,
+                         (int64_t)p.part_bytes, (int64_t)p.ws_bytes, (int64_t)p.pack_bytes, p.nw};
+  memcpy(out, v, sizeof(v));
+  return MI_OK;
 }
 
 extern "C" int mi_mdta_fused_pack(const mi_mdta_shape* s, const float* ln_w, const float* ln_b, const mi_mdta_params* p, void* pack,
                                   void* stream) {
-  MI_CHECK_ARG(fm_kind(s) != FM_NONE, "mdta_fused_pack: shape not covered by the fused kernel (mi_mdta_fused_ok)");
+  MI_CHECK_ARG(fm_plan(s).covered, "mdta_fused_pack: shape not covered by the fused kernel (mi_mdta_fused_ok)");
   MI_CHECK_ARG(ln_w && p && p->qkv_w && p->dw_w && pack && aligned16(pack), "mdta_fused_pack: null / unaligned pointer");
   const FmPackLayout l = fm_pack_layout(s->C);
   unsigned char* pk = (unsigned char*)pack;
@@ -1089,35 +1125,28 @@ extern "C" int mi_mdta_fused_pack(const mi_mdta_shape* s, const float* ln_w, con
   return MI_OK;
 }
 
-extern "C" size_t mi_mdta_fused_workspace(const mi_mdta_shape* s) {
-  if (fm_kind(s) == FM_NONE) return 0;
-  return fm_ws_layout(s, nullptr).bytes;
-}
+extern "C" size_t mi_mdta_fused_workspace(const mi_mdta_shape* s) { return fm_plan(s).ws_bytes; }
 
 // out = residual + project_out(softmax(temperature * q^ k^T) v) with q, k, v = dw3x3(qkv(LN(x))): pass A (this file), the
 // partial sum, the c x c fold (attn_small.hip) and the per-image-weight GEMM (pw_gemm.hip).  ln_with_bias: WithBias / BiasFree
 // LayerNorm (its affine lives in `pack`).  mean / rstd: optional [B][H*W] statistics outputs.
 extern "C" int mi_mdta_fused_fwd(const mi_mdta_shape* s, const mi_mdta_params* p, const void* pack, int ln_with_bias, const void* x,
                                  const void* residual, void* out, float* mean, float* rstd, void* ws, void* stream) {
-  const FmKind k = fm_kind(s);
-  MI_CHECK_ARG(k != FM_NONE, "mdta_fused_fwd: shape not covered by the fused kernel (mi_mdta_fused_ok)");
+  const FmPlan pl = fm_plan(s);
+  MI_CHECK_ARG(pl.covered, "mdta_fused_fwd: shape not covered by the fused kernel (mi_mdta_fused_ok)");
   MI_CHECK_ARG(p && p->temperature && p->proj_w && pack && x && out && ws, "mdta_fused_fwd: null pointer");
   MI_CHECK_ARG((mean == nullptr) == (rstd == nullptr), "mdta_fused_fwd: mean and rstd go together");
   MI_CHECK_ARG(aligned16(pack) && aligned16(x) && aligned16(out) && aligned16(ws), "mdta_fused_fwd: pointers must be 16-byte aligned");
   hipStream_t st = (hipStream_t)stream;
   const FmPackLayout l = fm_pack_layout(s->C);
-  FmWs w = fm_ws_layout(s, ws);
-  const int S = fm_splits(s, 8);
-  int part_mult = 1;
-  if (fm_use_v2() || k != FM_48_1) {                      // round-3 form (depthwise conv on the VALU): MI_FM_CFG=v2, and the shapes the fourth form does not cover yet
-    if (k == FM_48_1) MI_TRY((fm_launch<48, 1, 8, 8>(s, l, pack, x, w.v, w.part, mean, rstd, ln_with_bias, S, st)));
-    else if (k == FM_96_2) MI_TRY((fm_launch<96, 2, 8, 8>(s, l, pack, x, w.v, w.part, mean, rstd, ln_with_bias, S, st)));
-    else MI_TRY((fm_launch<96, 1, 8, 8>(s, l, pack, x, w.v, w.part, mean, rstd, ln_with_bias, S, st)));
-  } else {                                                // fourth form: the conv on the matrix cores, grouped phases, wave-local Gram
-    // one group of all 9 chunks: 308 us at 256^2, bs 32; three double-buffered groups of 3 (GEMM1 of group g + 1 inside the
-    // wave-local interval of group g) were measured at 418 us - two more barriers per tile cost more than the overlap buys
-    MI_TRY((fm4_launch<48, 1, 9, false>(s, pack, x, w.v, w.part, mean, rstd, ln_with_bias, S, nullptr, nullptr, st)));
-    part_mult = 8;
+  FmWs w = fm_ws_layout(s, pl.S, ws);
+  const int S = pl.S, part_mult = pl.part_mult;
+  if (pl.form == FM_ROUND3) {
+    if (pl.kind == FM_48_1) MI_TRY((fm_launch<48, 1, 8, 8>(s, l, pack, x, w.v, w.part, mean, rstd, ln_with_bias, pl, st)));
+    else if (pl.kind == FM_96_2) MI_TRY((fm_launch<96, 2, 8, 8>(s, l, pack, x, w.v, w.part, mean, rstd, ln_with_bias, pl, st)));
+    else MI_TRY((fm_launch<96, 1, 8, 8>(s, l, pack, x, w.v, w.part, mean, rstd, ln_with_bias, pl, st)));
+  } else {
+    MI_TRY((fm4_launch<48, 1, 9, false>(s, pack, x, w.v, w.part, mean, rstd, ln_with_bias, pl, nullptr, nullptr, st)));
   }
   {
     ProfScope ps(st, K_GRAM_REDUCE, 4.0 * s->B * (S + 1) * ((double)s->C * (s->C / s->heads) + 2.0 * s->C), 0.0);

@@ -138,6 +138,35 @@ MI_HIDDEN int pw_lds_launch(const mi_pw_desc* d, const PwPlan& pl, void* ws, hip
 // ---- fused GDFN forward, training form (fused_gdfn.hip): also writes h0 [B][2h][H][W] and g [B][h][H][W] ----
 int fused_gdfn_fwd_save(const mi_gdfn_fused_shape* s, const void* pack, const void* y, void* out, float* mean, float* rstd,
                         void* h0, void* g, hipStream_t st);
+// What one fused GDFN forward runs: filled by fg_plan (fused_gdfn.hip), the ONE place that decides it and that reads MI_FG_CFG /
+// MI_FG_NOXCD; the three launchers launch what it says, mi_gdfn_fused_ok / _pack_bytes / _pack / _fwd_train_ok answer from it,
+// mi_gdfn_fused_plan reports it.  An entry with no instance under the current switches: covered = false and every field 0.
+enum FgEntry { FG_INFER = 0, FG_TRAIN, FG_F8 };   // mi_gdfn_fused_fwd / mi_gdfn_fused_fwd_train / mi_gdfn_fused_fwd_f8
+enum FgFamily { FG_TILE = 0, FG_FOURTH };         // fg_fwd_kernel (conv on the VALU) / fg4_fwd_kernel (conv on the matrix cores, persistent)
+struct FgPlan {
+  bool covered;
+  int family;                                    // FgFamily
+  int C, th, tw, pc, nw; bool save, f8;          // the instance: tile rows / columns, gate pairs per chunk, waves, SAVE / F8 template choices
+  int nch, ngr;                                  // chunks of pc pairs (tile family) / groups of two 16-pair chunks, even (fourth form)
+  int tiles_x, tiles_y, S;                       // tiles of an image; workgroups per image (tile family: one per tile; fourth form: persistent ranges)
+  int64_t grid; int block; size_t lds;           // B * S workgroups, threads, dynamic LDS
+  bool xcd_pairs;                                // tile relabelling that puts vertical neighbours on one XCD (TW = 32, B * tiles % 16 == 0)
+  size_t pack_bytes; int pack_pc;                // the blob (tile sections sized for either chunk width, then the fourth form's), and the
+};                                               // chunk width its tile sections are built for / read with under the current switches
+MI_HIDDEN FgPlan fg_plan(const mi_gdfn_fused_shape* s, int entry);
+// What one fused MDTA forward (pass A) runs: filled by fm_plan (fused_mdta.hip), the ONE place that decides it and that reads
+// MI_FM_CFG; mi_mdta_fused_ok / _pays / _pack_bytes / _workspace / _fwd answer from it, mi_mdta_fused_plan reports it.
+enum FmForm { FM_ROUND3 = 0, FM_FOURTH };         // fm_fwd_kernel (conv on the VALU) / fm4_fwd_kernel (conv on the matrix cores)
+struct FmPlan {
+  bool covered, pays;                            // the kernel takes the shape / and fills the chip (B * S >= 192 of the 256 CUs)
+  int kind, form;                                // 1: C 48 one head, 2: C 96 two heads, 3: C 96 one head; FmForm
+  int C, heads, th, nw;
+  int tiles_x, tiles_y, S;                       // 8 x 32 tiles of an image; persistent workgroups per image (each a contiguous tile range)
+  int64_t grid; int block; size_t lds;
+  int part_mult;                                 // Gram partials a workgroup writes (fourth form: one per wave)
+  size_t part_bytes, ws_bytes, pack_bytes;       // the partials' arena (sized for 8 per workgroup in either form), the workspace, the blob
+};
+MI_HIDDEN FmPlan fm_plan(const mi_mdta_shape* s);
 
 // ---- host vocabulary of the module launch sequences (modules.hip, mefc.hip, fused_mdta.hip) ----
 static inline size_t fbytes(size_t n) { return align_up(n * sizeof(float), 256); }

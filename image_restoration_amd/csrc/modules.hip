@@ -671,9 +671,7 @@ extern "C" int mi_gdfn_fwd_f8(const mi_gdfn_shape* s, const mi_gdfn_params* p, c
 // mi_gdfn_saved_bytes sizes for this shape (flags 0: h0 and g; the conv output is recomputed in backward), so mi_gdfn_bwd /
 // mi_gdfn_bwd_ln read it exactly as after mi_gdfn_fwd_ln.
 extern "C" int mi_gdfn_fused_fwd_train_ok(const mi_gdfn_fused_shape* f) {
-  if (!f || !mi_gdfn_fused_ok(f)) return 0;
-  mi_gdfn_shape s = {f->B, f->C, f->hidden, f->H, f->W, MI_BF16, 3, 0};
-  return gdfn_check(&s) == MI_OK && gdfn_recompute(&s) ? 1 : 0;
+  return fg_plan(f, FG_TRAIN).covered ? 1 : 0;   // (an instance under the current MI_FG_CFG, and the recomputing backward's blob)
 }
 extern "C" int mi_gdfn_fused_fwd_train(const mi_gdfn_fused_shape* f, const void* pack, const void* y, void* out, float* mean,
                                        float* rstd, void* saved, void* stream) {

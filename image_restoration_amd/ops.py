@@ -958,6 +958,46 @@ def gdfn_fused_fwd(y: Tensor, pack: Tensor, hidden: int, with_bias: bool, want_s
     return out, mean, rstd
 
 
+GDFN_FUSED_ENTRIES = ("inference", "train", "f8")
+GDFN_FUSED_PLAN_FIELDS = ("covered", "family", "C", "th", "tw", "pc", "waves", "save", "f8", "nch", "ngr", "tiles_x", "tiles_y", "S",
+                          "grid", "block", "lds", "xcd_pairs", "pack_bytes", "pack_pc")
+
+
+def gdfn_fused_plan(shape, hidden: int, entry: str = "inference", with_bias: bool = True) -> dict:
+    """What gdfn_fused_fwd ("inference"), gdfn_fused_fwd_train ("train") or the fp8 form ("f8") launches for a [B, C, H, W]
+    activation under the current MI_FG_CFG / MI_FG_NOXCD (mi_gdfn_fused_plan; no GPU work).  family is "tile" or "fourth";
+    pack_pc is the chunk width gdfn_fused_pack builds the pack for: pack and run under the same switches.  An entry with no
+    kernel instance gives covered = False and zeros."""
+    B, Cc, H, W = shape
+    out = (L.c_i64 * 20)()
+    s = L.GdfnFusedShape(B, Cc, hidden, H, W, int(with_bias))
+    L.check(L.lib().mi_gdfn_fused_plan(C.byref(s), GDFN_FUSED_ENTRIES.index(entry), out), "gdfn_fused_plan")
+    p = dict(zip(GDFN_FUSED_PLAN_FIELDS, out))
+    for k in ("covered", "save", "f8", "xcd_pairs"):
+        p[k] = bool(p[k])
+    p["family"] = ("tile", "fourth")[p["family"]] if p["covered"] else None
+    return p
+
+
+MDTA_FUSED_PLAN_FIELDS = ("covered", "pays", "kind", "form", "th", "tiles_x", "tiles_y", "S", "grid", "block", "lds", "part_mult",
+                          "part_bytes", "workspace", "pack_bytes", "waves")
+
+
+def mdta_fused_plan(shape, heads: int, ks: int = 3, dtype: torch.dtype = torch.bfloat16) -> dict:
+    """What pass A of mdta_fused_fwd launches for a [B, C, H, W] activation under the current MI_FM_CFG (mi_mdta_fused_plan; no
+    GPU work).  kind is "48_1", "96_2" or "96_1" (C, heads), form "round3" or "fourth".  A shape the kernel does not cover gives
+    covered = False and zeros."""
+    B, Cc, H, W = shape
+    out = (L.c_i64 * 16)()
+    s = L.MdtaShape(B, Cc, heads, H, W, _dtype_code(dtype), ks)
+    L.check(L.lib().mi_mdta_fused_plan(C.byref(s), out), "mdta_fused_plan")
+    p = dict(zip(MDTA_FUSED_PLAN_FIELDS, out))
+    p["covered"], p["pays"] = bool(p["covered"]), bool(p["pays"])
+    p["kind"] = (None, "48_1", "96_2", "96_1")[p["kind"]]
+    p["form"] = ("round3", "fourth")[p["form"]] if p["covered"] else None
+    return p
+
+
 def gdfn_fused_train_ok(x: Tensor, hidden: int, ks: int = 3) -> bool:
     """True when the one-launch LN + GDFN forward can also write what the backward reads (mi_gdfn_fused_fwd_train)."""
     if x.dtype != torch.bfloat16 or ks != 3 or not x.is_cuda:

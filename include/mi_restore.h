@@ -403,6 +403,16 @@ int mi_gdfn_fused_fwd(const mi_gdfn_fused_shape* s, const void* pack, const void
 int mi_gdfn_fused_fwd_train_ok(const mi_gdfn_fused_shape* s);
 int mi_gdfn_fused_fwd_train(const mi_gdfn_fused_shape* s, const void* pack, const void* y, void* out, float* mean,
                             float* rstd, void* saved, void* stream);
+/* What the fused GDFN forwards launch for this shape under the current MI_FG_CFG / MI_FG_NOXCD (host-only).  entry: 0
+ * mi_gdfn_fused_fwd, 1 mi_gdfn_fused_fwd_train, 2 mi_gdfn_fused_fwd_f8.  out[20]: covered, family (0 tile form / 1 fourth form),
+ * C, tile rows TH, tile columns TW, gate pairs per chunk PC, waves, SAVE, F8, chunks of PC pairs (tile form), groups of two
+ * 16-pair chunks (fourth form), tiles_x, tiles_y, workgroups per image S (tile form: one per tile; fourth form: persistent tile
+ * ranges), grid (= B * S), block, dynamic LDS bytes, xcd_pairs (tile relabelling on), pack bytes, and the chunk width
+ * mi_gdfn_fused_pack builds the tile sections of the pack for.  A pack built under one chunk width and run under another gives
+ * wrong numbers without an error: pack and run under the same MI_FG_CFG.  An entry with no kernel instance for this shape and
+ * these switches returns 0 with covered = 0 and every other field 0 (the launcher returns -1, mi_gdfn_fused_ok /
+ * mi_gdfn_fused_fwd_train_ok say 0); -1 on a null pointer, a bad entry or a non-positive extent. */
+int mi_gdfn_fused_plan(const mi_gdfn_fused_shape* s, int entry, int64_t* out);
 
 /* ------------------------------------------------------------------------
  * Backward tail of a half-block  out = x + F(LN(x)),  F starting in the 1x1 conv h = W LN(x)
@@ -466,6 +476,12 @@ size_t mi_mdta_fused_pack_bytes(const mi_mdta_shape* s);
 int mi_mdta_fused_pack(const mi_mdta_shape* s, const float* ln_w, const float* ln_b, const mi_mdta_params* p, void* pack,
                        void* stream);
 size_t mi_mdta_fused_workspace(const mi_mdta_shape* s);
+/* What pass A of mi_mdta_fused_fwd launches for this shape under the current MI_FM_CFG (host-only).  out[16]: covered, pays,
+ * kind (1: C 48 one head, 2: C 96 two heads, 3: C 96 one head), form (0 round-3 / 1 fourth), tile rows TH, tiles_x, tiles_y,
+ * persistent workgroups per image S, grid (= B * S), block, dynamic LDS bytes, part_mult (Gram partials a workgroup writes),
+ * bytes of the partials' arena, workspace bytes, pack bytes, waves.  A shape the kernel does not cover returns 0 with
+ * covered = 0 and every other field 0; -1 on a null pointer or a non-positive extent. */
+int mi_mdta_fused_plan(const mi_mdta_shape* s, int64_t* out);
 int mi_mdta_fused_fwd(const mi_mdta_shape* s, const mi_mdta_params* p, const void* pack, int ln_with_bias, const void* x,
                       const void* residual, void* out, float* mean, float* rstd, void* ws, void* stream);
 int mi_bwd_tail_ok(int M, int C, int64_t N, int dtype);

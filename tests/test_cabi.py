@@ -686,3 +686,213 @@ def test_tail_assertions_catch_four_deliberate_faults(lib, monkeypatch):
     with pytest.raises(AssertionError, match="off at"):
         T.assert_model(got, m, rm, plan, "swapped rstd")
     assert max(T.assert_model(T.evaluate_fp32(m, 4), m, rm, plan, "no fault")) <= 1.0
+
+
+# --------------------------------------------------------------------------- the fused forwards' plans (mi_gdfn_fused_plan, mi_mdta_fused_plan)
+FUSED_CS, FUSED_HS, FUSED_WS = (48, 96, 192), tuple(range(8, 73, 8)) + (20,), (32, 64, 128, 192)
+FUSED_BS = (1, 2, 8, 32, 52, 86, 300)
+FUSED_HIDDEN = {48: (127, 96), 96: (255, 192), 192: (510,)}
+
+
+def _fg_layout_bytes(C_, hidden, pc):
+    """Bytes of the tile sections of the pack for one chunk width (fg_pack_layout in csrc/fused_gdfn.hip)."""
+    up = lambda v: -(-v // 256) * 256
+    nch = -(-hidden // pc)
+    return up(nch * 2 * pc * (C_ + 8) * 2) + up(nch * C_ * (pc + 8) * 2) + up(nch * pc * 20 * 4) + up(C_ * 4)
+
+
+def test_gdfn_fused_plan_sweep(lib, monkeypatch):
+    """ops.gdfn_fused_plan over shapes, batches, entries and every switch string the GPU cases use: covered agrees with the _ok
+    predicates, grid = B * S with 1 <= S <= tiles, the tiles cover the image, LDS within 160 KiB, the pack holds the tile
+    sections of either chunk width, xcd_pairs only on 32-wide tiles with a multiple of 16 of them, uncovered = all zeros."""
+    from image_restoration_amd import ops
+    import fused_forms as FF
+    L = lib.lib()
+    zeros = dict.fromkeys(ops.GDFN_FUSED_PLAN_FIELDS, 0)
+    zeros.update(covered=False, save=False, f8=False, xcd_pairs=False, family=None)
+    rows = FF.ladder_rows()
+    n = 0
+    for cfg in FF.GDFN_SWITCHES:
+        for noxcd in (False, True):
+            FF.set_switches(monkeypatch, cfg, noxcd=noxcd)
+            for C_ in FUSED_CS:
+                for H in FUSED_HS:
+                    for W in FUSED_WS:
+                        for B in FUSED_BS:
+                            hidden = FUSED_HIDDEN[C_][(H // 8 + B) % len(FUSED_HIDDEN[C_])]
+                            s = lib.GdfnFusedShape(B, C_, hidden, H, W, 1)
+                            shape_ok = C_ in (48, 96) and H % 8 == 0 and W % 64 == 0
+                            plans = {e: ops.gdfn_fused_plan((B, C_, H, W), hidden, e) for e in ops.GDFN_FUSED_ENTRIES}
+                            assert plans["inference"]["covered"] == bool(L.mi_gdfn_fused_ok(C.byref(s))) == shape_ok
+                            assert plans["train"]["covered"] == bool(L.mi_gdfn_fused_fwd_train_ok(C.byref(s)))
+                            assert L.mi_gdfn_fused_pack_bytes(C.byref(s)) == plans["inference"]["pack_bytes"]
+                            for e, p in plans.items():
+                                n += 1
+                                if not p["covered"]:
+                                    assert p == zeros, (cfg, e, p)
+                                    continue
+                                tiles = p["tiles_x"] * p["tiles_y"]
+                                assert p["tiles_x"] * p["tw"] == W and p["tiles_y"] * p["th"] == H and p["C"] == C_
+                                assert 1 <= p["S"] <= tiles and p["grid"] == B * p["S"] and p["block"] == 64 * p["waves"]
+                                assert 0 < p["lds"] <= 160 * 1024
+                                assert p["save"] == (e == "train") and p["f8"] == (e == "f8")
+                                assert p["pack_bytes"] >= max(_fg_layout_bytes(C_, hidden, 16), _fg_layout_bytes(C_, hidden, 32))
+                                assert p["pack_pc"] in (16, 32) and p["pack_pc"] == plans["inference"]["pack_pc"]
+                                if p["family"] == "tile":
+                                    assert p["S"] == tiles and p["nch"] == -(-hidden // p["pc"]) and p["pc"] == p["pack_pc"] and p["ngr"] == 0
+                                    assert (C_, p["th"], p["tw"], p["pc"], p["waves"]) in rows[e], (cfg, e, p)
+                                    assert p["xcd_pairs"] == (p["tw"] == 32 and (B * tiles) % 16 == 0 and not noxcd)
+                                else:
+                                    assert e != "f8" and (p["th"], p["tw"], p["waves"]) == (8, 32, 8) and not p["xcd_pairs"]
+                                    assert p["S"] == max(1, min(256 // B, tiles // 2)) and p["ngr"] % 2 == 0 and 32 * p["ngr"] >= hidden
+                                if p["xcd_pairs"]:
+                                    assert p["tw"] == 32 and (B * tiles) % 16 == 0
+    assert n == len(FF.GDFN_SWITCHES) * 2 * 3 * len(FUSED_HS) * 4 * 7 * 3
+    # the example of the plan's contract: training under w64,pc16 at C = 96 has no kernel, inference has
+    FF.set_switches(monkeypatch, "w64,pc16")
+    assert ops.gdfn_fused_plan((2, 96, 24, 128), 255, "train") == zeros
+    assert FF.instance_of(ops.gdfn_fused_plan((2, 96, 24, 128), 255, "inference")) == FF.tile(96, 8, 64, 16, 8)
+    out = (C.c_int64 * 20)()
+    s = lib.GdfnFusedShape(2, 96, 255, 24, 128, 1)
+    assert L.mi_gdfn_fused_plan(None, 0, out) == -1 and L.mi_gdfn_fused_plan(C.byref(s), 0, None) == -1
+    assert L.mi_gdfn_fused_plan(C.byref(s), 3, out) == -1 and b"bad entry 3" in L.mi_last_error()
+    assert L.mi_gdfn_fused_plan(C.byref(lib.GdfnFusedShape(0, 96, 255, 24, 128, 1)), 0, out) == -1 and b"bad shape" in L.mi_last_error()
+
+
+def test_mdta_fused_plan_sweep(lib, monkeypatch):
+    """ops.mdta_fused_plan over the same shapes under both MI_FM_CFG settings: covered agrees with mi_mdta_fused_ok, pays with
+    mi_mdta_fused_pays, the workspace and pack sizes with their entry points, and the partials' arena holds part_mult * S
+    partials per image."""
+    from image_restoration_amd import ops
+    import fused_forms as FF
+    L = lib.lib()
+    zeros = dict.fromkeys(ops.MDTA_FUSED_PLAN_FIELDS, 0)
+    zeros.update(covered=False, pays=False, kind=None, form=None)
+    for cfg in ("", "v2"):
+        FF.set_switches(monkeypatch, fm_cfg=cfg)
+        for C_, heads in ((48, 1), (96, 1), (96, 2), (96, 4), (48, 2), (192, 4)):
+            for H in FUSED_HS:
+                for W in FUSED_WS:
+                    for B in FUSED_BS:
+                        s = lib.MdtaShape(B, C_, heads, H, W, lib.MI_BF16, 3)
+                        p = ops.mdta_fused_plan((B, C_, H, W), heads)
+                        kind = {(48, 1): "48_1", (96, 2): "96_2", (96, 1): "96_1"}.get((C_, heads))
+                        assert p["covered"] == bool(L.mi_mdta_fused_ok(C.byref(s))) == (kind is not None and H % 8 == 0 and W % 64 == 0)
+                        assert p["pays"] == bool(L.mi_mdta_fused_pays(C.byref(s)))
+                        assert p["workspace"] == L.mi_mdta_fused_workspace(C.byref(s)) and p["pack_bytes"] == L.mi_mdta_fused_pack_bytes(C.byref(s))
+                        if not p["covered"]:
+                            assert p == zeros
+                            continue
+                        tiles = p["tiles_x"] * p["tiles_y"]
+                        assert p["kind"] == kind and p["form"] == ("fourth" if kind == "48_1" and not cfg else "round3")
+                        assert p["th"] == 8 and tiles == (H // 8) * (W // 32) and p["S"] == max(1, min(256 // B, tiles // 4))
+                        assert 1 <= p["S"] <= tiles and p["grid"] == B * p["S"] and p["block"] == 64 * p["waves"] == 512
+                        assert 0 < p["lds"] <= 160 * 1024 and p["pays"] == (p["grid"] >= 192)
+                        assert p["part_mult"] == (8 if p["form"] == "fourth" else 1)
+                        partial = 4 * (C_ * (C_ // heads) + 2 * C_)                  # heads x c x c Gram + 2 C sums of squares, fp32
+                        assert p["workspace"] > p["part_bytes"] >= B * p["S"] * p["part_mult"] * partial
+        for dt, ks in ((torch.float32, 3), (torch.bfloat16, 5)):                     # fp32 and 5x5 stay on the chain
+            assert ops.mdta_fused_plan((2, 48, 16, 64), 1, ks, dt) == zeros
+    monkeypatch.setenv("MI_NO_FUSED_MDTA", "1")                                      # the module paths' off switch answers _ok, not the plan
+    s = lib.MdtaShape(32, 48, 1, 128, 128, lib.MI_BF16, 3)
+    assert ops.mdta_fused_plan((32, 48, 128, 128), 1)["pays"] and not L.mi_mdta_fused_ok(C.byref(s)) and not L.mi_mdta_fused_pays(C.byref(s))
+    out = (C.c_int64 * 16)()
+    assert L.mi_mdta_fused_plan(None, out) == -1 and L.mi_mdta_fused_plan(C.byref(s), None) == -1
+    assert L.mi_mdta_fused_plan(C.byref(lib.MdtaShape(2, 48, 1, 0, 64, lib.MI_BF16, 3)), out) == -1 and b"bad shape" in L.mi_last_error()
+
+
+def test_fused_case_tables_reach_every_instance(lib, monkeypatch):
+    """The GPU case tables of tests/fused_forms.py, evaluated through the plan on the host, reach every instance the dispatch
+    lists of csrc/fused_gdfn.hip can select - each row of FG_INFER_ROWS, FG_TRAIN_ROWS and FG_F8_ROWS, the fourth form with SAVE on
+    and off at both widths - each with a ragged and an exact last chunk, bias on and off, both LayerNorm kinds; both MDTA forms
+    for every kind that has them; and the launch-plan branches (relabelling on / off, fg4 with S = 1, S = tiles / 2 and an uneven
+    capped S, uneven MDTA ranges).  A row added to a list without a case fails here."""
+    from image_restoration_amd import ops
+    import fused_forms as FF
+    want = {FF.tile(*r, SAVE=(e == "train"), F8=(e == "f8")) for e, rows in FF.ladder_rows().items() for r in rows}
+    want |= {FF.fourth(c, s) for c in (48, 96) for s in (False, True)}
+    seen, splits = {}, set()
+    for inst, entry, cfg, shape, pset in FF.GDFN_CASES:
+        FF.set_switches(monkeypatch, cfg)
+        chunk, bias, kind = FF.PARAMS[pset]
+        hidden = FF.HIDDEN[(shape[1], chunk)]
+        p = FF.reach(ops, inst, entry, shape, hidden)
+        width = 16 if inst[0] == "fourth" else p["pc"]
+        assert (hidden % width != 0) == (chunk == "ragged")
+        assert shape[0] == 2 or (inst, shape[0]) in ((FF.tile(96, 8, 32, 16, 4), 1),)
+        seen.setdefault(inst, set()).update({chunk, "bias" if bias else "no bias", kind})
+        if shape[0] == 2 and shape[2] > 8:
+            assert p["tiles_x"] >= 2 and p["tiles_y"] >= 2 and shape[3] == 2 * p["tw"] and shape[2] in ((24,) if p["th"] == 8 else (32, 48))
+        if inst[0] == "fourth":
+            tiles = p["tiles_x"] * p["tiles_y"]
+            splits.add("one" if p["S"] == 1 else "half" if p["S"] == tiles // 2 else "other")
+        elif p["tw"] == 32 and not cfg and p["grid"] % 16:
+            splits.add("no relabelling")
+    assert set(seen) == want, (want - set(seen), set(seen) - want)
+    for inst, tags in seen.items():
+        assert tags >= {"ragged", "exact", "bias", "no bias", "WithBias", "BiasFree"}, (inst, tags)
+    assert splits >= {"one", "half", "no relabelling"}
+    for inst, shape, pset in FF.XCD_CASES:
+        for noxcd in (False, True):
+            FF.set_switches(monkeypatch, "", noxcd=noxcd)
+            p = FF.reach(ops, inst, "train" if inst[6] else "inference", shape, FF.HIDDEN[(shape[1], FF.PARAMS[pset][0])])
+            assert p["xcd_pairs"] == (not noxcd) and p["grid"] % 16 == 0
+    assert {s[0] * (s[2] // i[2]) * (s[3] // i[3]) for i, s, _ in FF.XCD_CASES} >= {16, 32}
+    inst, cfg, shape, pset, S, tiles = FF.FG4_RANGES
+    FF.set_switches(monkeypatch, cfg)
+    p = FF.reach(ops, inst, "inference", shape, FF.HIDDEN[(shape[1], FF.PARAMS[pset][0])])
+    assert p["S"] == S == 256 // shape[0] < tiles // 2 and p["tiles_x"] * p["tiles_y"] == tiles and tiles % S
+    for entry, cfg, shape, hidden in FF.GDFN_REFUSALS:
+        FF.set_switches(monkeypatch, cfg)
+        assert not ops.gdfn_fused_plan(shape, hidden, entry)["covered"] and ops.gdfn_fused_plan(shape, hidden, "inference")["covered"]
+    assert {r[0] for r in FF.GDFN_REFUSALS} == {"train", "f8"}       # (inference has a kernel under every switch string: its refusals are shapes)
+    forms, uneven = set(), set()
+    for kind, c, heads, cfg, form, shape, bias, ln, (tiles, S) in FF.MDTA_CASES:
+        FF.set_switches(monkeypatch, fm_cfg=cfg)
+        p = ops.mdta_fused_plan(shape, heads)
+        assert (p["kind"], p["form"], p["tiles_x"] * p["tiles_y"], p["S"]) == (kind, form, tiles, S)
+        forms.add((kind, form))
+        if tiles % S:
+            uneven.add((kind, form))
+    assert forms == uneven == {("48_1", "fourth"), ("48_1", "round3"), ("96_2", "round3"), ("96_1", "round3")}
+    for shape, heads in FF.MDTA_REFUSALS:
+        assert not ops.mdta_fused_plan(shape, heads)["covered"]
+
+
+def test_fused_assertions_pass_on_bf16_arithmetic_and_catch_five_faults(lib):
+    """The assertion helper of the GPU tests (fused_forms.assert_half_block, assert_saved) on the CPU, for every distinct
+    (C, parameters, shape, tile) of the case tables:
+      * it passes on a CPU evaluation of the documented arithmetic (fused_forms.model_half_block, mode "fused") held against the
+        modelled chain, and that evaluation stays under HALF of each bar;
+      * it fails on each of five injected faults: an interior corner halo pixel dropped per tile, the right-halo column dropped,
+        the last hidden channel dropped from project_out, the padding holding b' = W' LN(0) + b instead of 0, the gate halves
+        swapped;
+      * the cap: every fault, evaluated in pure fp64, exceeds the bar it is meant to trip (fused_forms.FAULT_BAR) by at least 3 x.
+        This is what fused_forms.BIAS_SCALE / BETA are chosen for: with the stock 0.1 N biases and 0.2 N beta the padding fault
+        moves the branch by 5 - 7 % against its 4 % bar.
+    Reference-only figures (pure fp64, worst and best over the table) are in DESIGN.md next to the measured ones."""
+    import fused_forms as FF
+    figures = {f: [] for f in FF.FAULTS}
+    table = FF.fault_table()
+    assert len(table) >= 20
+    for C_, pset, shape, thw in table:
+        sd, kind, hidden = FF.gdfn_state(C_, pset)
+        y = FF.gdfn_input(shape)
+        ref = FF._oracle_half_block(y, sd, kind)
+        assert FF.rel(FF.model_half_block(y, sd, kind, "fp64", thw)[0], ref) < 1e-12       # the model states the oracle's operation
+        chain, h0_c, g_c = FF.model_half_block(y, sd, kind, "chain", thw)
+        clean, h0, g = FF.model_half_block(y, sd, kind, "fused", thw)
+        e_out, e_branch, _ = FF.assert_half_block(clean, chain, y, ref, f"model {C_} {pset} {shape}")
+        assert e_out < FF.BAR_OUT / 2 and e_branch < FF.BAR_BRANCH / 2, (C_, pset, shape, e_out, e_branch)
+        FF.assert_saved(h0, g, h0_c, g_c, FF.oracle_h0(y, sd, kind))     # (a bf16 ulp of the largest entry apart: inside the bars, not half)
+        for fault in FF.FAULTS:
+            if fault == "corner" and shape[2] <= thw[0]:
+                continue                                             # one tile row: no tile has a diagonal neighbour
+            pure = dict(zip(("out", "branch"), FF.errors(FF.model_half_block(y, sd, kind, "fp64", thw, fault)[0], y, ref)))
+            bar = {"out": FF.BAR_OUT, "branch": FF.BAR_BRANCH}[FF.FAULT_BAR[fault]]
+            figures[fault].append(pure[FF.FAULT_BAR[fault]])
+            assert pure[FF.FAULT_BAR[fault]] > 3 * bar, (fault, C_, pset, shape, thw, pure)
+            with pytest.raises(AssertionError, match="off the fp64 oracle"):
+                FF.assert_half_block(FF.model_half_block(y, sd, kind, "fused", thw, fault)[0], chain, y, ref, fault)
+    for fault, v in figures.items():
+        print(f"{fault}: {FF.FAULT_BAR[fault]} moved by {min(v):.3f} .. {max(v):.3f} (pure fp64)")

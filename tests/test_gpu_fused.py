@@ -388,7 +388,7 @@ FM_CASES = [
     (48, 1, True, "BiasFree", (1, 48, 8, 128)),
     (96, 2, False, "WithBias", (2, 96, 24, 64)),
     (96, 1, False, "WithBias", (2, 96, 16, 64)),
-    (96, 1, True, "WithBias", (3, 96, 40, 128)),       # 3 images x 20 tiles over 32 splits: uneven tile ranges, workgroups with one tile
+    (96, 1, True, "WithBias", (3, 96, 40, 128)),       # 3 images x 20 tiles over 5 persistent workgroups each (fm_splits: tiles / 4): even ranges of 4 tiles
     (96, 2, True, "BiasFree", (1, 96, 64, 64)),
 ]
 
