@@ -322,6 +322,9 @@ SIGNATURES = {
     "mi_gap_bwd": (C.c_int, [fp, vp, C.c_int, C.c_int, c_i64, C.c_int, vp]),
     "mi_cast": (C.c_int, [vp, C.c_int, vp, C.c_int, c_i64, vp]),
     "mi_l1_loss": (C.c_int, [vp, vp, vp, fp, c_i64, C.c_float, C.c_int, vp]),
+    "mi_fft_l1_workspace": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    "mi_fft_l1_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(c_i64)]),
+    "mi_fft_l1_loss": (C.c_int, [vp, vp, vp, fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, vp, vp]),
     "mi_prof_enable": (C.c_int, [C.c_int]),
     "mi_prof_kernel_count": (C.c_int, []),
     "mi_prof_kernel_name": (C.c_char_p, [C.c_int]),

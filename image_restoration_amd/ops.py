@@ -1440,6 +1440,42 @@ def l1_loss(a: Tensor, b: Tensor, want_grad: bool = True, scale: float = 1.0):
     return buf[:1], da
 
 
+_FFT_L1_SECTIONS = ("cos_w", "sin_w", "cos_wt", "sin_wt", "cos_h", "sin_h", "T", "S", "partials", "reduce_scratch")
+
+
+def fft_l1_plan(B: int, C: int, H: int, W: int, dtype: torch.dtype = torch.float32, want_grad: bool = True) -> dict:
+    """What fft_l1_loss launches for [B, C, H, W] (mi_fft_l1_plan: the plan the launcher itself follows; no GPU work).
+    ``sections`` maps each workspace section to its (byte offset, bytes); a grid of 0 means the stage is not launched."""
+    out = (L.c_i64 * 40)()
+    L.check(L.lib().mi_fft_l1_plan(B, C, H, W, _dtype_code(dtype), int(want_grad), out), "fft_l1_plan")
+    keys = ("planes", "K", "tile_m", "tile_k", "l_block", "l_blocks", "x_block", "x_blocks", "m_tiles_folded", "m_tiles_plane",
+            "grid_tables", "grid_stage1", "grid_stage2", "grid_stage3", "grid_stage4", "block", "partials", "reduce_launches",
+            "launches")
+    plan = {k: int(out[i]) for i, k in enumerate(keys)}
+    plan["sections"] = {n: (int(out[19 + 2 * i]), int(out[20 + 2 * i])) for i, n in enumerate(_FFT_L1_SECTIONS)}
+    plan["workspace"] = int(out[39])
+    return plan
+
+
+def fft_l1_loss(pred: Tensor, target: Tensor, loss_weight: float = 1.0, want_grad: bool = True):
+    """``loss_weight * mean(|Re| + |Im|)`` of ``rfft2(pred - target)`` over [B, C, H, W] and (optionally) its gradient w.r.t.
+    pred in pred's dtype, as dense-DFT GEMMs on the fp32 MFMA (mi_fft_l1_loss: no FFT library, bitwise reproducible).  The
+    loss comes back as a 1-element fp32 tensor.  2 <= H, W <= 512; anything else is an error."""
+    _gpu(pred, target)
+    if pred.dim() != 4 or pred.shape != target.shape:
+        raise ValueError(f"fft_l1_loss: pred and target must be [B, C, H, W] of one shape, got {tuple(pred.shape)} and "
+                         f"{tuple(target.shape)}")
+    if pred.dtype != target.dtype:
+        raise TypeError(f"fft_l1_loss: pred and target must share a dtype, got {pred.dtype} and {target.dtype}")
+    B, Cc, H, W = pred.shape
+    loss = torch.empty(1, dtype=torch.float32, device=pred.device)
+    dpred = torch.empty_like(pred) if want_grad else None
+    ws = _ws(L.lib().mi_fft_l1_workspace(B, Cc, H, W), pred.device)
+    L.check(L.lib().mi_fft_l1_loss(_p(pred), _p(target), _p(dpred), _p(loss), B, Cc, H, W, float(loss_weight), _dt(pred),
+                                   _p(ws), _stream()), "fft_l1_loss")
+    return loss, dpred
+
+
 # ----------------------------------------------------------------------------- profiler (bench.py roofline pass)
 _pw_cache_buf: Optional[Tensor] = None
 

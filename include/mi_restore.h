@@ -754,6 +754,25 @@ int mi_l1_loss(const void* a, const void* b, void* da, float* loss, int64_t n, f
                void* stream);
 
 /* ------------------------------------------------------------------------
+ * FFT loss (MoCE-IR-main/src/utils/loss_utils.py:139-152) without an FFT library (csrc/fftloss.hip):
+ *   loss[0] = loss_weight * mean(|Re Z| + |Im Z|),  Z = rfft2(pred - target) over the last two axes of [B,C,H,W]
+ *   dpred   = d loss / d pred, written in `dtype` (rounded once from fp32); may be NULL (the adjoint stages are skipped).
+ * The transform is a two-stage dense DFT on the fp32-input MFMA, fp32 throughout (inputs widened on load); the gradient is the
+ * adjoint applied to sign(Re Z) + i sign(Im Z) on the half spectrum, sign(0) = 0.  2 <= H, W <= 512, any B*C >= 1; anything
+ * else is refused.  Bitwise reproducible (no atomics, fixed-order sums).  loss: one device float, overwritten.
+ * ws: mi_fft_l1_workspace() bytes (twiddle tables, intermediates and loss partials, all rebuilt each call).
+ * mi_fft_l1_plan (host-only; the launcher takes every decision from the same plan) fills out[40]: planes B*C, K = W/2 + 1,
+ * tile rows, contraction depth per LDS stage, l block width, l blocks, x block width, x blocks, 64-row tiles over B*C*H,
+ * 64-row tiles over H, grid of the table fill, grids of stages 1..4 (0: not launched), threads per workgroup, loss partials,
+ * launches of their sum, launches in all; then (byte offset, bytes) of the ten workspace sections cos W, sin W, cos W^T,
+ * sin W^T, cos H, sin H, T (the gradient's gT reuses it), S, the partials, the sum's scratch; last, the workspace size.
+ * ------------------------------------------------------------------------ */
+size_t mi_fft_l1_workspace(int B, int C, int H, int W);
+int mi_fft_l1_plan(int B, int C, int H, int W, int dtype, int want_grad, int64_t* out);
+int mi_fft_l1_loss(const void* pred, const void* target, void* dpred, float* loss, int B, int C, int H, int W,
+                   float loss_weight, int dtype, void* ws, void* stream);
+
+/* ------------------------------------------------------------------------
  * Optional per-kernel profiler (measurement aid for bench.py's roofline object; nothing in the
  * reference corresponds to it).  When enabled every kernel launch is bracketed by two HIP events
  * recorded on the stream it is launched on, and its algorithmic HBM bytes / flops are booked.
