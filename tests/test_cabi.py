@@ -247,12 +247,11 @@ def test_ln_case_lists_reach_every_plan(lib, monkeypatch):
 
 
 # --------------------------------------------------------------------------- the 1x1 GEMM plan (mi_pw_plan)
-PW_SWITCHES = ("MI_PW_WAVE", "MI_PW_CHUNKED", "MI_PW_DMA", "MI_PW_XWIDE", "MI_PW_WAVE_WIDE", "MI_PW_LDS", "MI_NO_PW_LDS", "MI_PW_DIRECT",
-               "MI_PW_B16", "MI_PW_TM_EVEN", "MI_PW_TPB", "MI_PW_WAVE_TPW", "MI_PW_XCD")
+from pw_forms import PW_INSTANCES, PW_SWITCHES, PW_WAVE_FORMS, key as pw_key      # shared with tests/test_gpu_pw_forms.py
+
 PW_MS = (16, 48, 49, 64, 96, 97, 144, 192, 254, 256, 288, 510, 1021, 2042)
 PW_KS = (16, 33, 48, 96, 97, 128, 129, 192, 193, 384, 576, 1020)
 PW_NS = (35, 64, 256, 4096)
-PW_WAVE_FORMS = ("xres", "stream", "xwide")
 
 
 def _pw_switches(monkeypatch, **env):
@@ -342,26 +341,13 @@ def test_pw_predicates_and_workspace_follow_the_plan(lib, monkeypatch):
     assert n == 14 * 12 * 4 * 2 * 2 * 2 * 2
 
 
-# every instance the launchers can select: (family, tile rows / K chunks, ...).  The weight-resident kernel has a 48-row instance
-# that no shape takes: 48-row tiles need M <= 48, and M <= 64 stays chunked.
-PW_INSTANCES = (
-    {("chunked", dt, tm) for dt in ("f32", "bf16") for tm in (128, 96, 64, 48)} | {("resident", tm) for tm in (128, 96, 64)} |
-    {("dma", dt, tm) for dt in ("f32", "bf16") for tm in (128, 64)} | {("xres", kb, f8) for kb in (1, 2, 3) for f8 in (False, True)} |
-    {("stream", tm, f8) for tm in (96, 64, 48) for f8 in (False, True)} |
-    {("xwide", kb, f8, ln) for kb in (4, 5, 6) for f8 in (False, True) for ln in ((False, True) if kb == 4 else (False,))} |
-    {("lds", 256), ("lds", 128)})
-
-
 def test_pw_every_family_and_instance_is_reachable(lib, monkeypatch):
     """The sweep under the default switches and under each A/B switch reaches all seven families and every kernel instance (with
     fp8 operands and LayerNorm on load wherever the predicates allow them).  A threshold that strands an instance shows up here."""
     from image_restoration_amd import ops
 
     def key(dtype, d, p):
-        dt = "bf16" if dtype == torch.bfloat16 else "f32"
-        return {"chunked": (p["family"], dt, p["tm"]), "dma": (p["family"], dt, p["tm"]), "resident": (p["family"], p["tm"]),
-                "lds": (p["family"], p["tm"]), "xres": (p["family"], p["kb"], p["f8"]), "stream": (p["family"], p["tm"], p["f8"]),
-                "xwide": (p["family"], p["kb"], p["f8"], p["ln"])}[p["family"]]
+        return pw_key(dtype, p)
 
     reached = set()
     for env in ({}, {"MI_PW_WAVE": "0"}, {"MI_PW_CHUNKED": "1"}, {"MI_PW_DMA": "1"}, {"MI_PW_XWIDE": "0"}, {"MI_PW_WAVE_WIDE": "0"},
@@ -382,6 +368,71 @@ def test_pw_every_family_and_instance_is_reachable(lib, monkeypatch):
                 d.f8, d.ln_mode = 0, 0
     assert reached == PW_INSTANCES, (sorted(PW_INSTANCES - reached, key=str), sorted(reached - PW_INSTANCES, key=str))
     assert {k[0] for k in reached} == set(ops.PW_FAMILIES)
+
+
+def test_pw_case_tables_reach_every_instance_and_loop_state(lib, monkeypatch):
+    """The GPU case tables of tests/pw_forms.py, planned here on probe descriptors of the rows' shapes, strides and features: every
+    row reaches the instance and loop state it names (a row nobody can reach fails here, without a GPU), the union of the tables
+    is every kernel instance, and the loop states the default plans of small planes never take are each there at least once."""
+    import pw_forms as P
+    from image_restoration_amd import ops
+    reached, states, ids = set(), set(), set()
+    for table, rows in P.TABLES.items():
+        for r in rows:
+            assert (table, P.case_id(r)) not in ids, f"{table}: two rows named {P.case_id(r)}"
+            ids.add((table, P.case_id(r)))
+            P.set_switches(monkeypatch, r["env"])
+            p = P.reach(ops, r, P.probe(ops, r))
+            reached.add(P.key(P.DTYPES[r["dtype"]], p))
+            states |= P.loop_state(r, p)
+            if r["replaced"]:
+                P.set_switches(monkeypatch, r["replaced"])
+                assert ops.pw_plan(P.probe(ops, r))["family"] != r["key"][0], (P.case_id(r), r["replaced"])
+    assert reached == PW_INSTANCES, (sorted(PW_INSTANCES - reached, key=str), sorted(reached - PW_INSTANCES, key=str))
+    want = ({(s, f) for s in ("tpw_ragged", "tpw_idle") for f in ("xres", "stream")}             # the wave forms' tile loop
+            | {("tpb_ragged",), ("resident_partial_tile",), ("xcd_map",)}
+            | {("slabs", "one"), ("slabs", "some_ragged"), ("slabs", "all")}                     # the X-wide slab pipeline
+            | {("weights", src, f) for src in ops.PW_WEIGHTS for f in PW_WAVE_FORMS} | {("split", f) for f in PW_WAVE_FORMS}
+            | {("ln", inst, mode) for inst in (("xres", 1), ("xres", 2), ("xres", 3), ("xwide", 4)) for mode in (1, 2)}
+            | {("strided", f) for f in ops.PW_FAMILIES})
+    assert want <= states, sorted(want - states, key=str)
+
+
+def test_pw_ln_bar_admits_the_model_and_catches_four_faults(lib):
+    """The LayerNorm-on-load bar of tests/pw_forms.py (e_gpu <= 1.5 e_model + 2^-8) on the CPU, at every shape, mode and operand
+    type of the table: it passes the model of the kernel's roundings evaluated in the opposite summation order, and each of four
+    faults - the K tail counted in the statistics, gamma / beta one channel off, beta in the wrong mode, the statistics of the
+    previous pixel tile - lands at least 3 x over it.  Likewise the NaN guard: a store one row past M and a skipped tile are caught."""
+    import pw_forms as P
+    from image_restoration_amd import ops
+    seen = set()
+    for r in P.LN_CASES:
+        sig = (r["M"], r["K"], r["ln"], r["f8"])
+        if sig in seen:
+            continue
+        seen.add(sig)
+        h = P._host((r["B"], 1, r["M"], r["K"], 0, r["N"], False, True))
+        ref, mu, rstd = P.ln_model(h, r["ln"], "fp64")
+        bar = P.ln_bar(P.rel_err(P.ln_model(h, r["ln"], "kernel", f8=r["f8"])[0], ref))
+        other, mu32, rstd32 = P.ln_model(h, r["ln"], "kernel", f8=r["f8"], flip=True)
+        assert P.rel_err(other, ref) <= bar, (sig, P.rel_err(other, ref), bar)
+        assert P.rel_err(mu32, mu) < P.BAR_STATS and P.rel_err(rstd32, rstd) < P.BAR_STATS
+        for fault in P.LN_FAULTS:
+            if fault == "k_tail" and r["K"] % 32 == 0:          # no tail: not a fault
+                continue
+            e = P.rel_err(P.ln_model(h, r["ln"], "kernel", f8=r["f8"], fault=fault)[0], ref)
+            assert e >= 3 * bar, f"{sig}: fault {fault} at {e:.3e} is within 3 x the bar {bar:.3e}"
+    assert len(seen) == 11
+    r = next(r for r in P.WAVE_LOOP_CASES if r["key"] == ("xres", 2, False) and r["tpw"] == 2)
+    call = P.build(ops, r, "cpu")
+    P.fake_store(call)
+    call.check_guards()
+    assert torch.equal(call.result(), call.ref)
+    for fault, msg in (("row_past_m", "outside the output were written"), ("skipped_tile", "never written")):
+        call.reset_outputs()
+        P.fake_store(call, fault)
+        with pytest.raises(AssertionError, match=msg):
+            call.check_guards()
 
 
 def test_pw_plan_argument_errors(lib):
