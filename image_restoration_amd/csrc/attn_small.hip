@@ -38,7 +38,7 @@ __global__ __launch_bounds__(256) void attn_fold_kernel(const float* __restrict_
                                                         const float* __restrict__ temperature, const float* __restrict__ wo,
                                                         float* __restrict__ P, float* __restrict__ A, float* __restrict__ nrm,
                                                         float* __restrict__ M, bf16* __restrict__ Mb, bf16* __restrict__ Mtb, int C,
-                                                        int heads, int rpw) {
+                                                        int heads, int rpw, int tb_vec) {
   constexpr int CP = 16 * CT, LD = CP + 1;
   extern __shared__ float sm[];
   float* As = sm;                       // [CP][LD]; rows and columns >= c are zero
@@ -114,7 +114,6 @@ __global__ __launch_bounds__(256) void attn_fold_kernel(const float* __restrict_
   __syncthreads();
 
   const int wv = __builtin_amdgcn_readfirstlane(t >> 6), lane = t & 63, li = lane & 15, kq = lane >> 4;
-  const bool tb_vec = (C & 3) == 0;
   for (int tile = wv; tile < nrc * CT; tile += 4) {
     const int rr = tile / CT, nt = tile - rr * CT;
     const float* wp = Wt + (rr * ATT_RC + li) * LD + kq;
@@ -170,7 +169,7 @@ __global__ __launch_bounds__(256) void attn_bwd_kernel(const float* __restrict__
                                                        const float* __restrict__ P, const float* __restrict__ nrm,
                                                        const float* __restrict__ temperature, const float* __restrict__ wo,
                                                        float* __restrict__ dwo_part, float* __restrict__ dtemp_part,
-                                                       float* __restrict__ wd, bf16* __restrict__ wdb, int C, int heads) {
+                                                       float* __restrict__ wd, bf16* __restrict__ wdb, int C, int heads, int vec) {
   constexpr int CP = 16 * CT, LD = CP + 1, MB = (CT + 3) / 4;
   extern __shared__ float sm[];
   const int c = C / heads;
@@ -326,7 +325,7 @@ __global__ __launch_bounds__(256) void attn_bwd_kernel(const float* __restrict__
   float* wk = wq + (int64_t)c * 2 * c;            // rows of dk
   bf16* bq = wdb ? wdb + (int64_t)z * 2 * c * 2 * c : nullptr;
   bf16* bk = wdb ? bq + (int64_t)c * 2 * c : nullptr;
-  const bool vec = (c & 3) == 0;                  // 4 consecutive rows of a lane: one vector store into the transposed blocks
+  // vec (attn_small_plan: c % 4 == 0): 4 consecutive rows of a lane are one vector store into the transposed blocks
 #pragma unroll
   for (int mb = 0; mb < MB; ++mb) {
     const int mt = wv + 4 * mb;
@@ -377,7 +376,7 @@ __global__ __launch_bounds__(256) void attn_bwd_kernel(const float* __restrict__
 // images with one dependent load each this kernel took an HBM round trip per image (19 us per call at bs 8 on MoCE-IR's planes).
 template <typename T>
 __global__ __launch_bounds__(256) void chan_sum_kernel(const T* __restrict__ x, float* __restrict__ part, int B, int C,
-                                                       int64_t N, int64_t per_split) {
+                                                       int64_t N, int64_t per_split, int vec) {
   __shared__ float red[4];
   const int c = blockIdx.x, sp = blockIdx.y;
   const int64_t nb = (int64_t)sp * per_split;
@@ -385,9 +384,8 @@ __global__ __launch_bounds__(256) void chan_sum_kernel(const T* __restrict__ x, 
   if (ne > N) ne = N;
   float acc = 0.f;
   constexpr int V = 16 / (int)sizeof(T);                // elements per 16-byte load
-  // (vec: whole 16-byte vectors - N, the split bounds and the base pointer allow it; a 2-byte load per lane made this kernel
-  //  instruction-bound: 34 us per call on MoCE-IR's planes, 7 % of its step)
-  const bool vec = (N % V == 0) && (nb % V == 0) && (ne % V == 0) && ((reinterpret_cast<uintptr_t>(x) & 15) == 0);
+  // (vec, decided by chan_sum_plan: whole 16-byte vectors - N, the split bounds and the base pointer allow it; a 2-byte load per
+  //  lane made this kernel instruction-bound: 34 us per call on MoCE-IR's planes, 7 % of its step)
   if (vec && ne > nb) {
     const int64_t nvec = (ne - nb) / V, items = (int64_t)B * nvec;
     const T* base = x + (int64_t)c * N + nb;
@@ -422,30 +420,41 @@ __global__ __launch_bounds__(256) void chan_sum_kernel(const T* __restrict__ x, 
   if (threadIdx.x == 0) part[(int64_t)sp * C + c] = (red[0] + red[1]) + (red[2] + red[3]);
 }
 
-int chan_sum_splits(int C, int64_t N) {
+// What one chan_sum call runs: filled by chan_sum_plan, the ONE place that decides it; launch_chan_sum launches what it says,
+// chan_sum_workspace sizes from it, mi_chan_sum_plan reports it.
+struct ChanSumPlan {
+  int splits;        // pixel ranges (grid.y): about 512 workgroups, at least 1024 pixels each
+  int64_t per;       // pixels per split, a multiple of 8 (16-byte vectors of either dtype); the last split ends at N
+  int vec;           // whole 16-byte loads: every split bound is then a multiple of the vector, so N % V == 0 and a 16-byte base decide
+};
+static ChanSumPlan chan_sum_plan(int C, int64_t N, int dtype, bool aligned) {
+  ChanSumPlan p;
   int s = 512 / (C > 0 ? C : 1);
   if (s < 1) s = 1;
   const int maxs = cdiv(N, 1024);
   if (s > maxs) s = maxs;
-  return s < 1 ? 1 : s;
+  p.splits = s < 1 ? 1 : s;
+  p.per = (N + p.splits - 1) / p.splits;
+  p.per = (p.per + 7) / 8 * 8;
+  const int64_t V = 16 / (int64_t)dtype_size(dtype);
+  p.vec = (N % V == 0 && aligned) ? 1 : 0;
+  return p;
 }
-size_t chan_sum_workspace(int C, int64_t N) { return align_up((size_t)chan_sum_splits(C, N) * C * sizeof(float), 256); }
+size_t chan_sum_workspace(int C, int64_t N) { return align_up((size_t)chan_sum_plan(C, N, MI_F32, true).splits * C * sizeof(float), 256); }
 
 int launch_chan_sum(const void* x, float* out, int B, int C, int64_t N, int dtype, int accumulate, void* ws, hipStream_t st) {
   return with_dtype(dtype, "chan_sum", [&](auto tag) -> int {
     using T = decltype(tag);
-    const int splits = chan_sum_splits(C, N);
-    int64_t per = (N + splits - 1) / splits;
-    per = (per + 7) / 8 * 8;                              // split bounds on 16-byte vectors (the last split takes the remainder)
+    const ChanSumPlan p = chan_sum_plan(C, N, dtype, aligned16(x));
     float* part = (float*)ws;
     if (accumulate) {          // a parameter gradient accumulated in place: the split sum may wait for mi_deferred_flush (common.h)
-      float* arena = deferred_take((size_t)splits * C, st);
+      float* arena = deferred_take((size_t)p.splits * C, st);
       if (arena) part = arena;
     }
     ProfScope ps(st, K_CHAN_SUM, (double)B * C * N * sizeof(T), (double)B * C * N);
-    hipLaunchKernelGGL((chan_sum_kernel<T>), dim3(C, splits), dim3(256), 0, st, (const T*)x, part, B, C, N, per);
+    hipLaunchKernelGGL((chan_sum_kernel<T>), dim3(C, p.splits), dim3(256), 0, st, (const T*)x, part, B, C, N, p.per, p.vec);
     MI_LAUNCH_CHECK();
-    return launch_reduce_rows(part, out, splits, C, C, accumulate, 1.0f, st);
+    return launch_reduce_rows(part, out, p.splits, C, C, accumulate, 1.0f, st);
   });
 }
 
@@ -456,7 +465,7 @@ int launch_chan_sum(const void* x, float* out, int B, int C, int64_t N, int dtyp
       case 2: { constexpr int CT = 2; CALL; } break;                   \
       case 3: { constexpr int CT = 3; CALL; } break;                   \
       case 4: { constexpr int CT = 4; CALL; } break;                   \
-      case 5: case 6: { constexpr int CT = 6; CALL; } break;           \
+      case 6: { constexpr int CT = 6; CALL; } break;                   \
       default: { constexpr int CT = 8; CALL; } break;                  \
     }                                                                  \
   } while (0)
@@ -466,24 +475,58 @@ size_t attn_bwd_scratch_floats(int B, int C, int heads) {
   return 64;            // (the one-launch backward keeps dA in registers: nothing to stage; the carve stays for the ABI)
 }
 
-int launch_attn_fold(const float* graw, const float* ss, const float* temperature, const float* wo, float* P, float* A,
-                     float* nrm, float* M, int B, int C, int heads, hipStream_t st, void* Mb, void* Mtb) {
+// What the two launches of the c x c side run: filled by attn_small_plan, the ONE place that decides it; launch_attn_fold and
+// launch_attn_bwd_small launch what it says, mi_attn_small_plan reports it.
+struct AttnSmallPlan {
+  int ct, promoted, cp;                     // instance CT of both kernels (1, 2, 3, 4, 6, 8); ceil(c/16) of 5 / 7 runs the next one; 16 CT
+  int rpw, fold_gx, fold_gy, last_chunks;   // W_o row chunks per fold workgroup, its grid, chunks of the last row group
+  size_t fold_lds, bwd_lds;                 // dynamic LDS bytes
+  int fold_raise, bwd_raise;                // above 64 KiB: the kernel's limit is raised before the launch
+  int bwd_gx, bwd_gy, mb;                   // backward grid; row blocks of dA a wave owns
+  int tb_vec, wd_vec;                       // 4 consecutive rows of a lane are one vector store: into Mtb (C % 4 == 0), into wd / wdb (c % 4 == 0)
+};
+static int attn_small_plan(int B, int C, int heads, AttnSmallPlan* p) {
+  MI_CHECK_ARG(B >= 1 && C >= 1 && heads >= 1, "mdta: bad shape B=%d C=%d heads=%d in the attention c x c side", B, C, heads);
   const int c = C / heads;
   MI_CHECK_ARG(c >= 1 && c <= ATTN_MAX_C && c * heads == C, "mdta: channels per head %d unsupported (1..%d)", c, ATTN_MAX_C);
-  MI_CHECK_ARG(graw && ss && temperature && wo && P && A && nrm && M, "mdta: null pointer in the attention fold");
+  const int ct = attn_ct(c);
+  p->ct = ct == 5 ? 6 : (ct == 7 ? 8 : ct);
+  p->promoted = p->ct != ct;
+  p->cp = 16 * p->ct;
   // row chunks per workgroup: every workgroup redoes the softmax, so deep levels (many heads, many chunks) fold several chunks
-  // each; about 768 workgroups (3 per CU) are kept
-  const int Z = B * heads, rch = attn_rchunks(C);
-  int rpw = (int)(((int64_t)Z * rch) / 768);
-  rpw = rpw < 1 ? 1 : (rpw > rch ? rch : (rpw > 8 ? 8 : rpw));
-  dim3 grid(Z, cdiv(rch, rpw));
+  // each; about 768 workgroups (3 per CU) are kept.  At most 8, and no more than there are: the fold's LDS holds rpw chunks.
+  // (The cap at the chunk count used to come first and skip the 8: B heads > 768 with more than 8 chunks folded them all, up to
+  //  48: 160 images of C = 370 in 5 heads asked for 24 chunks and 183 KiB of LDS, a launch error.)
+  const int Z = B * heads, rch = attn_rchunks(C), cap = rch < 8 ? rch : 8;
+  const int64_t want = ((int64_t)Z * rch) / 768;
+  p->rpw = want < 1 ? 1 : (want > cap ? cap : (int)want);
+  p->fold_gx = Z;
+  p->fold_gy = cdiv(rch, p->rpw);
+  p->last_chunks = rch - (p->fold_gy - 1) * p->rpw;
+  p->fold_lds = attn_fold_lds_floats(p->ct, p->rpw) * sizeof(float);
+  p->fold_raise = p->fold_lds > 64 * 1024;
+  p->bwd_gx = Z;
+  p->bwd_gy = 1 + cdiv(C, ATT_RW);
+  p->bwd_lds = attn_bwd_lds_floats(p->ct) * sizeof(float);
+  p->bwd_raise = p->bwd_lds > 64 * 1024;
+  p->mb = (p->ct + 3) / 4;
+  p->tb_vec = (C & 3) == 0;
+  p->wd_vec = (c & 3) == 0;
+  return MI_OK;
+}
+
+int launch_attn_fold(const float* graw, const float* ss, const float* temperature, const float* wo, float* P, float* A,
+                     float* nrm, float* M, int B, int C, int heads, hipStream_t st, void* Mb, void* Mtb) {
+  AttnSmallPlan p;
+  MI_TRY(attn_small_plan(B, C, heads, &p));
+  MI_CHECK_ARG(graw && ss && temperature && wo && P && A && nrm && M, "mdta: null pointer in the attention fold");
+  const int c = C / heads;
   ProfScope ps(st, K_ATTN_FOLD, 4.0 * B * (3.0 * C * c + 2.0 * C * C), 2.0 * B * C * (double)c * C);
-  ATTN_CT_SWITCH(attn_ct(c), {
-    const size_t lds = attn_fold_lds_floats(CT, rpw) * sizeof(float);
-    if (lds > 64 * 1024)
-      MI_CHECK_HIP(hipFuncSetAttribute((const void*)attn_fold_kernel<CT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL((attn_fold_kernel<CT>), grid, dim3(256), lds, st, graw, ss, temperature, wo, P, A, nrm, M, (bf16*)Mb, (bf16*)Mtb, C,
-                       heads, rpw);
+  ATTN_CT_SWITCH(p.ct, {
+    if (p.fold_raise)
+      MI_CHECK_HIP(hipFuncSetAttribute((const void*)attn_fold_kernel<CT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.fold_lds));
+    hipLaunchKernelGGL((attn_fold_kernel<CT>), dim3(p.fold_gx, p.fold_gy), dim3(256), p.fold_lds, st, graw, ss, temperature, wo, P, A, nrm,
+                       M, (bf16*)Mb, (bf16*)Mtb, C, heads, p.rpw, p.tb_vec);
   });
   MI_LAUNCH_CHECK();
   return MI_OK;
@@ -493,16 +536,16 @@ int launch_attn_bwd_small(const float* dM, const float* A, const float* P, const
                           const float* wo, float* dwo_part, float* dtemp_part, float* wd, float* scratch,
                           int B, int C, int heads, hipStream_t st, void* wdb) {
   (void)scratch;
-  const int c = C / heads;
-  MI_CHECK_ARG(c >= 1 && c <= ATTN_MAX_C && c * heads == C, "mdta: channels per head %d unsupported (1..%d)", c, ATTN_MAX_C);
+  AttnSmallPlan p;
+  MI_TRY(attn_small_plan(B, C, heads, &p));
   MI_CHECK_ARG(dM && A && P && nrm && temperature && wo && dwo_part && dtemp_part && wd, "mdta: null pointer in the attention backward");
+  const int c = C / heads;
   ProfScope ps(st, K_ATTN_BWD_SMALL, 4.0 * B * (6.0 * C * c + 3.0 * C * C), 4.0 * B * C * (double)c * C);
-  ATTN_CT_SWITCH(attn_ct(c), {
-    const size_t lds = attn_bwd_lds_floats(CT) * sizeof(float);
-    if (lds > 64 * 1024)
-      MI_CHECK_HIP(hipFuncSetAttribute((const void*)attn_bwd_kernel<CT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL((attn_bwd_kernel<CT>), dim3(B * heads, 1 + cdiv(C, ATT_RW)), dim3(256), lds, st, dM, A, P, nrm, temperature, wo,
-                       dwo_part, dtemp_part, wd, (bf16*)wdb, C, heads);
+  ATTN_CT_SWITCH(p.ct, {
+    if (p.bwd_raise)
+      MI_CHECK_HIP(hipFuncSetAttribute((const void*)attn_bwd_kernel<CT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.bwd_lds));
+    hipLaunchKernelGGL((attn_bwd_kernel<CT>), dim3(p.bwd_gx, p.bwd_gy), dim3(256), p.bwd_lds, st, dM, A, P, nrm, temperature, wo,
+                       dwo_part, dtemp_part, wd, (bf16*)wdb, C, heads, p.wd_vec);
   });
   MI_LAUNCH_CHECK();
   return MI_OK;
@@ -510,9 +553,49 @@ int launch_attn_bwd_small(const float* dM, const float* A, const float* P, const
 
 }  // namespace mi
 
+// The c x c side of MDTA by itself (tests, and callers that build their own attention): thin wrappers over the two launchers.
+//  fwd: graw [Z,c,c] = q k^T, ss [Z,2c] = (|q_i|^2, |k_j|^2), Z = B heads -> P, A [Z,c,c], nrm [Z,2c], M [B,C,C] (fp32) and the
+//       bf16 copies Mb = M, Mtb = M^T per image (either may be NULL).
+//  bwd: dM [B,C,C] -> dwo_part [B,C,C] (summed over images: dW_o), dtemp_part [Z] (summed over images: d temperature),
+//       wd [Z,2c,2c] = [[G1, diag D1], [diag D2, G1^T]] and its bf16 copy wdb (may be NULL).
+extern "C" int mi_attn_small_fwd(const float* graw, const float* ss, const float* temperature, const float* wo, float* P, float* A,
+                                 float* nrm, float* M, void* Mb, void* Mtb, int B, int C, int heads, void* stream) {
+  return mi::launch_attn_fold(graw, ss, temperature, wo, P, A, nrm, M, B, C, heads, (hipStream_t)stream, Mb, Mtb);
+}
+extern "C" int mi_attn_small_bwd(const float* dM, const float* A, const float* P, const float* nrm, const float* temperature,
+                                 const float* wo, float* dwo_part, float* dtemp_part, float* wd, void* wdb, int B, int C, int heads,
+                                 void* stream) {
+  return mi::launch_attn_bwd_small(dM, A, P, nrm, temperature, wo, dwo_part, dtemp_part, wd, nullptr, B, C, heads, (hipStream_t)stream,
+                                   wdb);
+}
+// What the two launches run for B images of C channels in `heads` heads.  Host-side only: the same attn_small_plan.  out[16]:
+// instance CT, promoted (ceil(c/16) of 5 or 7 runs CT 6 or 8), padded width 16 CT, W_o row chunks per fold workgroup, fold grid x,
+// fold grid y, chunks in the last row group, fold LDS bytes, fold raises the 64 KiB limit, backward grid x, backward grid y,
+// backward LDS bytes, backward raises the limit, row blocks of dA per wave, Mtb stored as vectors, wd / wdb stored as vectors.
+extern "C" int mi_attn_small_plan(int B, int C, int heads, int64_t* out) {
+  MI_CHECK_ARG(out, "attn_small_plan: null pointer");
+  mi::AttnSmallPlan p;
+  MI_TRY(mi::attn_small_plan(B, C, heads, &p));
+  const int64_t v[16] = {p.ct, p.promoted, p.cp, p.rpw, p.fold_gx, p.fold_gy, p.last_chunks, (int64_t)p.fold_lds, p.fold_raise,
+                         p.bwd_gx, p.bwd_gy, (int64_t)p.bwd_lds, p.bwd_raise, p.mb, p.tb_vec, p.wd_vec};
+  memcpy(out, v, sizeof(v));
+  return MI_OK;
+}
+
 // Per-channel sum over batch and pixels - the bias gradient of any conv (nn.Conv2d(bias=True): Restormer.py:82-86 with bias,
 // moce_ir.py expert / decoder projections): out[c] (+)= sum_{b,n} x[b][c][n].  ws: mi_chan_sum_workspace(C, N) bytes.
 extern "C" size_t mi_chan_sum_workspace(int C, int64_t N) { return (C > 0 && N > 0) ? mi::chan_sum_workspace(C, N) : 0; }
+// What mi_chan_sum runs for x [B,C,N] of `dtype` whose base pointer is (aligned != 0) or is not on a 16-byte boundary.  Host-side
+// only: the same chan_sum_plan.  out[4]: splits, pixels per split, vector path, workspace bytes.
+extern "C" int mi_chan_sum_plan(int B, int C, int64_t N, int dtype, int aligned, int64_t* out) {
+  MI_CHECK_ARG(out, "chan_sum_plan: null pointer");
+  MI_CHECK_ARG(dtype == MI_F32 || dtype == MI_BF16, "chan_sum_plan: bad dtype %d", dtype);
+  MI_CHECK_ARG(B >= 1 && C >= 1 && N >= 1, "chan_sum_plan: bad shape B=%d C=%d N=%lld", B, C, (long long)N);
+  const mi::ChanSumPlan p = mi::chan_sum_plan(C, N, dtype, aligned != 0);
+  const int64_t v[4] = {p.splits, p.per, p.vec, (int64_t)mi::chan_sum_workspace(C, N)};
+  memcpy(out, v, sizeof(v));
+  return MI_OK;
+}
 extern "C" int mi_chan_sum(const void* x, float* out, int B, int C, int64_t N, int dtype, int accumulate, void* ws, void* stream) {
   MI_CHECK_ARG(x && out && ws && B >= 1 && C >= 1 && N >= 1, "chan_sum: null pointer / bad shape");
   return mi::launch_chan_sum(x, out, B, C, N, dtype, accumulate, ws, (hipStream_t)stream);

@@ -1150,6 +1150,87 @@ def chan_sum(x: Tensor, out: Optional[Tensor] = None, accumulate: bool = False) 
     return out
 
 
+CHAN_SUM_PLAN_FIELDS = ("splits", "per_split", "vector", "workspace")
+
+
+def chan_sum_plan(B: int, Cn: int, N: int, dtype: torch.dtype, aligned: bool = True) -> dict:
+    """What chan_sum launches for x [B, Cn, N] whose base pointer is / is not on a 16-byte boundary (mi_chan_sum_plan; no GPU
+    work)."""
+    out = (L.c_i64 * 4)()
+    L.check(L.lib().mi_chan_sum_plan(B, Cn, N, _dtype_code(dtype), int(aligned), out), "chan_sum_plan")
+    p = dict(zip(CHAN_SUM_PLAN_FIELDS, out))
+    p["vector"] = bool(p["vector"])
+    return p
+
+
+ATTN_SMALL_PLAN_FIELDS = ("instance", "promoted", "padded", "rpw", "fold_grid_x", "fold_grid_y", "last_chunks", "fold_lds",
+                          "fold_raised", "bwd_grid_x", "bwd_grid_y", "bwd_lds", "bwd_raised", "row_blocks", "mtb_vector",
+                          "wd_vector")
+
+
+def attn_small_plan(B: int, Cn: int, heads: int) -> dict:
+    """What the c x c side of MDTA launches for B images of Cn channels in `heads` heads (mi_attn_small_plan; no GPU work)."""
+    out = (L.c_i64 * 16)()
+    L.check(L.lib().mi_attn_small_plan(B, Cn, heads, out), "attn_small_plan")
+    p = dict(zip(ATTN_SMALL_PLAN_FIELDS, out))
+    for k in ("promoted", "fold_raised", "bwd_raised", "mtb_vector", "wd_vector"):
+        p[k] = bool(p[k])
+    return p
+
+
+def _attn_small_out(out: Optional[dict], name: str, shape, dtype, device, want: bool = True) -> Optional[Tensor]:
+    if out is not None:
+        t = out.get(name)
+        if t is not None and (tuple(t.shape) != tuple(shape) or t.dtype != dtype):
+            raise ValueError(f"attn_small: {name} must be {tuple(shape)} of {dtype}")
+        return t
+    return torch.empty(shape, dtype=dtype, device=device) if want else None
+
+
+def attn_small_fwd(graw: Tensor, ss: Tensor, temperature: Tensor, wo: Tensor, heads: int, mb: bool = True, mtb: bool = True,
+                   out: Optional[dict] = None) -> dict:
+    """The attention fold by itself (mi_attn_small_fwd): graw [Z,c,c], ss [Z,2c], temperature [heads], wo [C,C], all fp32.
+    Returns P, A [Z,c,c], nrm [Z,2c], M [B,C,C] (fp32) and the bf16 Mb = M, Mtb = M^T per image (None when not asked for).
+    out: the caller's buffers by these names instead (Mb / Mtb absent: not written)."""
+    Cn, c = wo.shape[0], wo.shape[0] // heads
+    Z = graw.shape[0]
+    B = Z // heads
+    f32, b16, dev = torch.float32, torch.bfloat16, graw.device
+    o = {"P": _attn_small_out(out, "P", (Z, c, c), f32, dev), "A": _attn_small_out(out, "A", (Z, c, c), f32, dev),
+         "nrm": _attn_small_out(out, "nrm", (Z, 2 * c), f32, dev), "M": _attn_small_out(out, "M", (B, Cn, Cn), f32, dev),
+         "Mb": _attn_small_out(out, "Mb", (B, Cn, Cn), b16, dev, mb), "Mtb": _attn_small_out(out, "Mtb", (B, Cn, Cn), b16, dev, mtb)}
+    _gpu(graw, ss, temperature, wo, *o.values())
+    for t, what in ((graw, "graw"), (ss, "ss"), (temperature, "temperature"), (wo, "wo")):
+        _f32(t, what)
+    if tuple(graw.shape) != (B * heads, c, c) or tuple(ss.shape) != (Z, 2 * c) or tuple(wo.shape) != (Cn, Cn) or temperature.numel() != heads:
+        raise ValueError("attn_small_fwd: graw [B heads, c, c], ss [B heads, 2c], temperature [heads], wo [C, C] with c = C / heads")
+    L.check(L.lib().mi_attn_small_fwd(_p(graw), _p(ss), _p(temperature), _p(wo), _p(o["P"]), _p(o["A"]), _p(o["nrm"]), _p(o["M"]),
+                                      _p(o["Mb"]), _p(o["Mtb"]), B, Cn, heads, _stream()), "attn_small_fwd")
+    return o
+
+
+def attn_small_bwd(dM: Tensor, A: Tensor, P: Tensor, nrm: Tensor, temperature: Tensor, wo: Tensor, heads: int, wdb: bool = True,
+                   out: Optional[dict] = None) -> dict:
+    """The attention backward's c x c side by itself (mi_attn_small_bwd): dM [B,C,C] and the forward's A, P, nrm.  Returns
+    dwo_part [B,C,C], dtemp_part [Z], wd [Z,2c,2c] (fp32) and the bf16 wdb = wd (None when not asked for).  out: as in
+    attn_small_fwd."""
+    B, Cn = dM.shape[0], dM.shape[1]
+    c, Z = Cn // heads, B * heads
+    f32, dev = torch.float32, dM.device
+    o = {"dwo_part": _attn_small_out(out, "dwo_part", (B, Cn, Cn), f32, dev), "dtemp_part": _attn_small_out(out, "dtemp_part", (Z,), f32, dev),
+         "wd": _attn_small_out(out, "wd", (Z, 2 * c, 2 * c), f32, dev),
+         "wdb": _attn_small_out(out, "wdb", (Z, 2 * c, 2 * c), torch.bfloat16, dev, wdb)}
+    _gpu(dM, A, P, nrm, temperature, wo, *o.values())
+    for t, what in ((dM, "dM"), (A, "A"), (P, "P"), (nrm, "nrm"), (temperature, "temperature"), (wo, "wo")):
+        _f32(t, what)
+    if (tuple(dM.shape) != (B, Cn, Cn) or tuple(A.shape) != (Z, c, c) or tuple(P.shape) != (Z, c, c) or tuple(nrm.shape) != (Z, 2 * c)
+            or tuple(wo.shape) != (Cn, Cn) or temperature.numel() != heads):
+        raise ValueError("attn_small_bwd: dM [B, C, C], A, P [B heads, c, c], nrm [B heads, 2c], temperature [heads], wo [C, C]")
+    L.check(L.lib().mi_attn_small_bwd(_p(dM), _p(A), _p(P), _p(nrm), _p(temperature), _p(wo), _p(o["dwo_part"]), _p(o["dtemp_part"]),
+                                      _p(o["wd"]), _p(o["wdb"]), B, Cn, heads, _stream()), "attn_small_bwd")
+    return o
+
+
 def conv3x3_ok(x: Tensor) -> bool:
     """The implicit-GEMM 3x3 convolution covers this activation (bf16, W % 8 == 0; csrc/conv3x3.hip)."""
     return bool(x.is_cuda and x.dim() == 4 and L.lib().mi_conv3x3_ok(x.shape[2], x.shape[3], _dt(x)))

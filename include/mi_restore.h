@@ -484,6 +484,26 @@ size_t mi_mdta_fused_workspace(const mi_mdta_shape* s);
 int mi_mdta_fused_plan(const mi_mdta_shape* s, int64_t* out);
 int mi_mdta_fused_fwd(const mi_mdta_shape* s, const mi_mdta_params* p, const void* pack, int ln_with_bias, const void* x,
                       const void* residual, void* out, float* mean, float* rstd, void* ws, void* stream);
+/* ------------------------------------------------------------------------
+ * The c x c side of MDTA by itself (csrc/attn_small.hip), c = C / heads in 1..128, Z = B * heads, everything fp32:
+ *   fwd : graw [Z,c,c] = q k^T and ss [Z,2c] = (|q_i|^2, |k_j|^2) over the pixels, temperature [heads], wo [C,C] ->
+ *         nrm [Z,2c] = max(sqrt(ss), 1e-12), P = graw / (|q_i||k_j|), A = softmax_row(temperature P) [Z,c,c], and the fold
+ *         M [B,C,C], M[b][:, head cols] = wo[:, head cols] A, with bf16 copies Mb = M and Mtb = M^T per image (each may be NULL).
+ *   bwd : dM [B,C,C] and the forward's A, P, nrm -> dwo_part [B,C,C] (its sum over images is dW_o), dtemp_part [Z] (its sum over
+ *         images is d temperature) and wd [Z,2c,2c] = [[G1, diag D1], [diag D2, G1^T]], which maps the stacked [k; q] to
+ *         [dq; dk]; wdb is its bf16 copy (may be NULL).
+ * mi_attn_small_plan (host-only) reports what both launch.  out[16]: kernel instance CT (1, 2, 3, 4, 6, 8), promoted (ceil(c/16)
+ * of 5 or 7 runs CT 6 or 8), padded width 16 CT, W_o row chunks of 16 per fold workgroup, fold grid x, fold grid y, chunks in
+ * the last row group, fold LDS bytes, fold raises the 64 KiB LDS limit, backward grid x, backward grid y, backward LDS bytes,
+ * backward raises the limit, row blocks of dA per wave, Mtb stored as vectors (C % 4 == 0), wd / wdb stored as vectors
+ * (c % 4 == 0).  All three return -1 on a null pointer, B, C, heads <= 0, C % heads != 0 or c > 128.
+ * ------------------------------------------------------------------------ */
+int mi_attn_small_plan(int B, int C, int heads, int64_t* out);
+int mi_attn_small_fwd(const float* graw, const float* ss, const float* temperature, const float* wo, float* P, float* A,
+                      float* nrm, float* M, void* Mb, void* Mtb, int B, int C, int heads, void* stream);
+int mi_attn_small_bwd(const float* dM, const float* A, const float* P, const float* nrm, const float* temperature,
+                      const float* wo, float* dwo_part, float* dtemp_part, float* wd, void* wdb, int B, int C, int heads,
+                      void* stream);
 int mi_bwd_tail_ok(int M, int C, int64_t N, int dtype);
 size_t mi_bwd_tail_workspace(int M, int C);
 /* What mi_bwd_tail launches for this call under the current MI_BT_WIDE (host-only).  out[12]: covered, pays (covered and
@@ -719,6 +739,11 @@ int mi_copy_rows(const void* src, int64_t src_rs, void* dst, int64_t dst_rs, int
 int mi_gap_fwd(const void* x, float* out, int B, int C, int64_t N, int dtype, void* stream);
 /* bias gradient of a conv (nn.Conv2d(bias=True)): out[c] (+)= sum over batch and pixels of x[b][c][n]; fixed summation order */
 size_t mi_chan_sum_workspace(int C, int64_t N);
+/* What mi_chan_sum launches for x [B,C,N] (host-only); aligned: whether the base pointer lies on a 16-byte boundary.  out[4]:
+ * splits of the pixel axis, pixels per split (a multiple of 8; the last split ends at N), whether the kernel loads whole
+ * 16-byte vectors (N a multiple of the vector and an aligned base), workspace bytes.  -1 on a null out, a bad dtype code or
+ * B, C, N <= 0. */
+int mi_chan_sum_plan(int B, int C, int64_t N, int dtype, int aligned, int64_t* out);
 int mi_chan_sum(const void* x, float* out, int B, int C, int64_t N, int dtype, int accumulate, void* ws, void* stream);
 int mi_gap_bwd(const float* dout, void* dx, int B, int C, int64_t N, int dtype, void* stream);
 

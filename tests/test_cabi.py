@@ -947,3 +947,192 @@ def test_fused_assertions_pass_on_bf16_arithmetic_and_catch_five_faults(lib):
                 FF.assert_half_block(FF.model_half_block(y, sd, kind, "fused", thw, fault)[0], chain, y, ref, fault)
     for fault, v in figures.items():
         print(f"{fault}: {FF.FAULT_BAR[fault]} moved by {min(v):.3f} .. {max(v):.3f} (pure fp64)")
+
+
+# --------------------------------------------------------------------------- the attention c x c side and chan_sum (mi_attn_small_plan, mi_chan_sum_plan)
+ATTN_BS = (1, 2, 8, 32, 160)
+
+
+def _attn_formulas(B, C_, heads):
+    """The launchers' decisions, read from csrc/attn_small.hip."""
+    c = C_ // heads
+    ct0 = -(-c // 16)
+    ct = {5: 6, 7: 8}.get(ct0, ct0)
+    cp, rch, Z = 16 * ct, -(-C_ // 16), B * heads
+    rpw = min(max(Z * rch // 768, 1), min(8, rch))
+    gy = -(-rch // rpw)
+    fold = 4 * (cp * (cp + 1) + 2 * cp + rpw * 16 * (cp + 1))
+    bwd = 4 * max(2 * 32 * (cp + 1) + 16 * cp + 2 * cp + 8, cp * (cp + 1) + 64 * (cp + 1))
+    return {"instance": ct, "promoted": ct != ct0, "padded": cp, "rpw": rpw, "fold_grid_x": Z, "fold_grid_y": gy,
+            "last_chunks": rch - (gy - 1) * rpw, "fold_lds": fold, "fold_raised": fold > 65536, "bwd_grid_x": Z,
+            "bwd_grid_y": 1 + -(-C_ // 64), "bwd_lds": bwd, "bwd_raised": bwd > 65536, "row_blocks": -(-ct // 4),
+            "mtb_vector": C_ % 4 == 0, "wd_vector": c % 4 == 0}
+
+
+def test_attn_small_plan_sweep(lib):
+    """ops.attn_small_plan over C = 1..768, every head count with c <= 128 and five batch sizes: each field is the launcher's
+    formula, the LDS fits the 160 KiB of a CU, rpw stays within 1..min(8, chunks), the fold's row groups cover the chunks with a
+    non-empty last group, and the instance holds c.  ops.chan_sum_plan likewise over a grid of C and N."""
+    from image_restoration_amd import ops
+    seen, n = set(), 0
+    for C_ in range(1, 769):
+        for heads in range(1, C_ + 1):
+            if C_ % heads or C_ // heads > 128:
+                continue
+            for B in ATTN_BS:
+                p = ops.attn_small_plan(B, C_, heads)
+                assert p == _attn_formulas(B, C_, heads), (B, C_, heads, p)
+                rch = -(-C_ // 16)
+                assert p["instance"] in (1, 2, 3, 4, 6, 8) and p["padded"] - (32 if p["promoted"] else 16) < C_ // heads <= p["padded"]
+                assert max(p["fold_lds"], p["bwd_lds"]) <= 160 * 1024
+                assert 1 <= p["rpw"] <= min(8, rch) and 1 <= p["last_chunks"] <= p["rpw"]
+                assert (p["fold_grid_y"] - 1) * p["rpw"] + p["last_chunks"] == rch and p["bwd_grid_y"] * 64 - 64 >= C_
+                seen.add((p["instance"], p["rpw"], p["fold_raised"], p["bwd_raised"]))
+                n += 1
+    assert n > 20000 and {s[0] for s in seen} == {1, 2, 3, 4, 6, 8} and {s[1] for s in seen} == set(range(1, 9))
+    assert (6, 5, True, False) in seen and (6, 4, False, False) in seen and not any(s[3] for s in seen if s[0] < 8)
+    for dt, V in ((torch.float32, 4), (torch.bfloat16, 8)):
+        for C_ in (1, 3, 48, 100, 511, 512, 513, 600):
+            for N in (1, 7, 1023, 1024, 1025, 4096, 4099, 5000, 5004, 65536, 1 << 20):
+                for aligned in (True, False):
+                    p = ops.chan_sum_plan(2, C_, N, dt, aligned)
+                    splits = max(1, min(512 // C_, -(-N // 1024)))
+                    per = -(-(-(-N // splits)) // 8) * 8
+                    assert p == {"splits": splits, "per_split": per, "vector": aligned and N % V == 0,
+                                 "workspace": lib.lib().mi_chan_sum_workspace(C_, N)}, (C_, N, dt, aligned, p)
+                    assert per % 8 == 0 and (splits - 1) * per < N <= splits * per and p["workspace"] >= 4 * splits * C_
+
+
+def test_attn_small_and_chan_sum_argument_errors(lib):
+    """c > 128, C % heads != 0, non-positive extents and null pointers: -1 with their message from the plan and from both entry
+    points, before anything touches a GPU (the buffers here are host memory, never read)."""
+    L, out = lib.lib(), (C.c_int64 * 16)()
+    buf = C.create_string_buffer(64)
+    ptr = C.cast(buf, C.c_void_p).value
+    assert L.mi_attn_small_plan(2, 48, 1, None) == -1 and b"attn_small_plan: null pointer" in L.mi_last_error()
+    for B, C_, heads, msg in ((1, 129, 1, b"channels per head 129 unsupported (1..128)"), (1, 774, 6, b"channels per head 129 unsupported"),
+                              (2, 50, 4, b"channels per head 12 unsupported"), (2, 3, 4, b"channels per head 0 unsupported"),
+                              (0, 48, 1, b"bad shape B=0 C=48 heads=1"), (2, 0, 1, b"bad shape"), (2, 48, 0, b"bad shape"),
+                              (2, 48, -2, b"bad shape"), (-1, 48, 1, b"bad shape")):
+        assert L.mi_attn_small_plan(B, C_, heads, out) == -1 and msg in L.mi_last_error(), (B, C_, heads, L.mi_last_error())
+        fwd = L.mi_attn_small_fwd(ptr, ptr, ptr, ptr, ptr, ptr, ptr, ptr, ptr, ptr, B, C_, heads, None)
+        assert fwd == -1 and msg in L.mi_last_error(), (B, C_, heads)
+        bwd = L.mi_attn_small_bwd(ptr, ptr, ptr, ptr, ptr, ptr, ptr, ptr, ptr, ptr, B, C_, heads, None)
+        assert bwd == -1 and msg in L.mi_last_error(), (B, C_, heads)
+    assert L.mi_attn_small_plan(1, 128, 1, out) == 0 and out[0] == 8 and L.mi_attn_small_plan(2, 48, 1, out) == 0 and out[0] == 3
+    for k in range(8):                                   # each required pointer of the fold; Mb and Mtb may be NULL
+        a = [ptr] * 10
+        a[k] = None
+        assert L.mi_attn_small_fwd(*a, 2, 48, 1, None) == -1 and b"mdta: null pointer in the attention fold" in L.mi_last_error(), k
+    for k in range(9):                                   # each required pointer of the backward; wdb may be NULL
+        a = [ptr] * 10
+        a[k] = None
+        assert L.mi_attn_small_bwd(*a, 2, 48, 1, None) == -1 and b"mdta: null pointer in the attention backward" in L.mi_last_error(), k
+    o4 = (C.c_int64 * 4)()
+    assert L.mi_chan_sum_plan(2, 48, 4096, lib.MI_F32, 1, None) == -1 and b"chan_sum_plan: null pointer" in L.mi_last_error()
+    assert L.mi_chan_sum_plan(2, 48, 4096, 7, 1, o4) == -1 and b"chan_sum_plan: bad dtype 7" in L.mi_last_error()
+    for B, C_, N in ((0, 48, 4096), (2, 0, 4096), (2, 48, 0), (-1, 48, 4096), (2, -48, 4096), (2, 48, -8)):
+        assert L.mi_chan_sum_plan(B, C_, N, lib.MI_BF16, 1, o4) == -1 and b"chan_sum_plan: bad shape" in L.mi_last_error(), (B, C_, N)
+    assert L.mi_chan_sum_plan(2, 48, 4096, lib.MI_BF16, 1, o4) == 0 and list(o4) == [4, 1024, 1, 768]
+    assert L.mi_chan_sum(None, ptr, 2, 48, 4096, lib.MI_F32, 0, ptr, None) == -1 and b"chan_sum: null pointer" in L.mi_last_error()
+
+
+def test_attn_case_tables_reach_every_plan(lib):
+    """The tables of tests/attn_forms.py together reach every instance at an exact and at a padded width and both promotions,
+    rpw 1, 2, 3, 5, 7, 8 with a partial last group and the cap at the chunk count, both raised-LDS fold launches and the raised
+    backward, both values of each vector-store flag, every row tail the issue names, clamped norms on every third row, and every
+    chan_sum plan for each dtype.  Each row names its plan: a threshold that moves in the launcher is a row that lost it."""
+    from image_restoration_amd import ops
+    import attn_forms as T
+    fit, rpws, promoted, raised, flags, partial = set(), set(), set(), set(), set(), set()
+    for case in T.ALL_CASES:
+        (B, C_, heads), _ = case
+        p, c = T.assert_plan(ops, case), C_ // heads
+        fit.add((p["instance"], "exact" if c == p["padded"] else "padded"))
+        rpws.add(p["rpw"])
+        if p["promoted"]:
+            promoted.add(p["instance"])
+        if p["fold_raised"]:
+            raised.add(("fold", p["instance"]))
+        if p["bwd_raised"]:
+            raised.add(("bwd", p["instance"]))
+        if p["last_chunks"] < p["rpw"]:
+            partial.add(p["rpw"])
+        flags |= {("mtb", p["mtb_vector"]), ("wd", p["wd_vector"])}
+    assert {C_ // h for (B, C_, h), _ in T.WIDTH_CASES} == {1, 10, 16, 17, 24, 32, 33, 40, 48, 49, 64, 65, 80, 81, 96, 97, 112, 120, 127, 128}
+    assert all(B <= 3 and 1 <= h <= 3 for (B, C_, h), _ in T.WIDTH_CASES)
+    assert fit == {(ct, f) for ct in (1, 2, 3, 4, 6, 8) for f in ("exact", "padded")} and promoted == {6, 8}
+    assert rpws == {1, 2, 3, 5, 7, 8} and partial >= {3, 5, 7}
+    assert raised == {("fold", 6), ("fold", 8), ("bwd", 8)}
+    assert flags == {("mtb", True), ("mtb", False), ("wd", True), ("wd", False)}
+    (B, C_, heads), _ = T.CHUNK_CASES[-1]                                          # the cap: more asked for than there are chunks
+    assert B * heads * -(-C_ // 16) // 768 > -(-C_ // 16) == ops.attn_small_plan(B, C_, heads)["rpw"]
+    assert T.CHUNK_CASES[3][0] == (32, 384, 8)                                     # the benchmark's deepest level, batch 32
+    cs = [C_ for (B, C_, h), _ in T.WIDTH_CASES]
+    assert any(x % 16 for x in cs) and any(x % 4 for x in cs) and any(x % 32 and not x % 4 for x in cs) and 72 in cs
+    assert any(T.is_clamp_case(k) and (k[0][1] // k[0][2]) % 16 for k in T.ALL_CASES)           # a clamped row inside a padded fragment
+    assert sum(map(T.is_clamp_case, T.ALL_CASES)) == 9 and any(T.is_clamp_case(k) for k in T.CHUNK_CASES)
+    assert all(v <= 5e-5 for v in T.BOUND.values()) and all(T.BOUND[k] == 8 * T.MEASURED[k] for k in T.BOUND)
+    plans = {}
+    for (B, C_, N), per_dtype in T.CHAN_SUM_CASES:
+        for dt in per_dtype:
+            for aligned in (True, False):
+                p = T.assert_chan_sum_plan(ops, B, C_, N, dt, aligned)
+                plans.setdefault(dt, set()).add((p["splits"] > 1, p["vector"]))
+    assert all(v == {(False, True), (False, False), (True, True), (True, False)} for v in plans.values()) and len(plans) == 2
+
+
+def test_attn_bounds_admit_a_correct_fp32_evaluation(lib):
+    """On every row of both tables: Reference 1 agrees with fp64 autograd (Reference 2) to 1e-10, and autograd rejects the
+    projection terms D1 / D2 on a clamped norm; the kernels' arithmetic evaluated in torch fp32 on the CPU, with every contraction
+    in a permuted order, passes Family B's assertions and Family A's bit for bit.  The bounds ask nothing that correct fp32
+    arithmetic cannot give, and Family A's expected values are what the formulas give."""
+    from image_restoration_amd import ops
+    import attn_forms as T
+    worst = {}
+    for n, case in enumerate(T.ALL_CASES):
+        plan, who = T.assert_plan(ops, case), T.case_id(case)
+        assert max(T.reference_gap(case).values()) <= T.REFERENCE_GAP, who
+        if T.is_clamp_case(case) and case[0][1] // case[0][2] >= 4:
+            assert max(T.reference_gap(case, d_on_clamp=True).values()) > 1e3 * T.REFERENCE_GAP, who
+        s = T.float_inputs(case)
+        got = T.evaluate_fp32(s, plan, seed=n)
+        for ratios, _ in (T.assert_float_fwd(got, s, who), T.assert_float_bwd(got, s, who)):
+            for k, v in ratios.items():
+                worst[k] = max(worst.get(k, 0.0), v)
+        e = T.exact_inputs(case)
+        got = T.evaluate_fp32(e, plan, seed=n)
+        T.assert_exact_fwd(got, e, who)
+        T.assert_exact_bwd(got, e, who)
+    assert set(worst) == set(T.BOUND) and max(worst.values()) <= 1.0, worst
+    assert max(worst.values()) >= 1.0 / 16, worst          # (and the bounds are of the arithmetic's own size, not idle)
+
+
+def test_attn_assertions_catch_five_deliberate_faults(lib):
+    """Five faults of the kind the kernels' padding, row groups, clamps and store tails can have, applied to the fp32 evaluation
+    on the CPU, on every row of the tables where each can occur: each fails its assertion.
+
+    Contrast with the bar that guarded these kernels before (test_attention_small_kernels_at_padded_and_wide_heads: one
+    max-over-tensor ratio of 5e-5 per tensor, behind two Grams, three GEMMs and LayerNorm, at rpw = 1 and unclamped norms only):
+    the partial row group and the clamp branch were never run, and the bf16 copies never read back."""
+    from image_restoration_amd import ops
+    import attn_forms as T
+    caught = dict.fromkeys(T.FAULTS, 0)
+    for case in T.ALL_CASES:
+        (B, C_, heads), _ = case
+        plan, who, c = T.assert_plan(ops, case), T.case_id(case), C_ // heads
+        s = T.float_inputs(case)
+        applicable = {"pad_in_softmax": c % 16 != 0, "partial_group_unwritten": plan["last_chunks"] < plan["rpw"],
+                      "d_on_clamp": s.clamp and c >= 4, "g1t_shift": c % 4 != 0 and c >= 4, "mtb_tail": C_ % 4 != 0}
+        match = {"pad_in_softmax": "A off", "partial_group_unwritten": "M has elements never written",
+                 "d_on_clamp": "D1 / D2 not zero on a clamped norm", "g1t_shift": "lower-right block is not G1 transposed",
+                 "mtb_tail": "Mtb is not Mb transposed"}
+        for fault in T.FAULTS:
+            if not applicable[fault]:
+                continue
+            got = T.evaluate_fp32(s, plan, fault=fault)
+            with pytest.raises(AssertionError, match=match[fault]):
+                T.assert_float_fwd(got, s, who)
+                T.assert_float_bwd(got, s, who)
+            caught[fault] += 1
+    assert min(caught.values()) >= 3, caught

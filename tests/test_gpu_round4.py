@@ -265,9 +265,10 @@ def test_forward_gelu_of_the_bf16_kernels_stays_within_its_stated_bound():
 def test_attention_small_kernels_at_padded_and_wide_heads(c, heads, shape):
     """The c x c side of MDTA (attn_fold: DPP-row softmax + fp32-MFMA fold; the one-launch attention backward) pads channels per
     head to a multiple of 16 in LDS and masks at the stores: channels per head that are NOT multiples of 16 (40, 24, 10), the
-    widest tiles (112, 120 -> 8 x 8 fragments), C not a multiple of 4 (scalar path of the transposed stores) and several W_o row
-    chunks per workgroup (384 / 8 heads at 3 images) against the fp64 oracle (Restormer.py:111-131), forward, dx and every
-    parameter gradient, bound 5e-5."""
+    widest tiles (112, 120 -> 8 x 8 fragments), C not a multiple of 4 (scalar path of the transposed stores) and 24 W_o row
+    chunks (384 / 8 heads at 3 images: 3 * 8 * 24 < 768, so still ONE chunk per workgroup - several chunks per workgroup, partial
+    row groups and clamped norms are run by tests/test_gpu_attn_small.py) against the fp64 oracle (Restormer.py:111-131), forward,
+    dx and every parameter gradient, bound 5e-5."""
     import image_restoration_amd as m
     from oracle import restormer_ref as R
     from oracle.fixtures import seeded_input
