@@ -12,6 +12,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MI_RESTORE_LIB") or os.path.join(HERE, "libmi_restore.so")   # (override: A/B builds)
 
 MI_F32, MI_BF16 = 0, 1
+MI_SSIM_TILE = 32   # include/mi_restore.h: the tile edge of the SSIM loss kernels (map tiles and image tiles)
 c_i64 = C.c_int64
 vp = C.c_void_p
 fp = C.c_void_p  # float* passed as raw addresses
@@ -329,6 +330,12 @@ SIGNATURES = {
     "mi_fft_l1_workspace": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "mi_fft_l1_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(c_i64)]),
     "mi_fft_l1_loss": (C.c_int, [vp, vp, vp, fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, vp, vp]),
+    "mi_ssim_loss_workspace": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    "mi_ssim_loss": (C.c_int, [vp, vp, vp, fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, vp, vp]),
+    "mi_edge_loss_workspace": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    "mi_edge_loss": (C.c_int, [vp, vp, vp, fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_int, vp, vp]),
+    "mi_focal_l1_workspace": (C.c_size_t, [c_i64]),
+    "mi_focal_l1_loss": (C.c_int, [vp, vp, vp, fp, c_i64, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int, vp, vp]),
     "mi_prof_enable": (C.c_int, [C.c_int]),
     "mi_prof_kernel_count": (C.c_int, []),
     "mi_prof_kernel_name": (C.c_char_p, [C.c_int]),

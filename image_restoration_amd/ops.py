@@ -1557,6 +1557,68 @@ def fft_l1_loss(pred: Tensor, target: Tensor, loss_weight: float = 1.0, want_gra
     return loss, dpred
 
 
+def _loss_pair(who: str, pred: Tensor, target: Tensor, planes: bool) -> None:
+    _gpu(pred, target)
+    if pred.shape != target.shape or (planes and pred.dim() != 4):
+        raise ValueError(f"{who}: pred and target must be {'[B, C, H, W]' if planes else 'tensors'} of one shape, got "
+                         f"{tuple(pred.shape)} and {tuple(target.shape)}")
+    if pred.dtype != target.dtype:
+        raise TypeError(f"{who}: pred and target must share a dtype, got {pred.dtype} and {target.dtype}")
+
+
+def ssim_loss(pred: Tensor, target: Tensor, loss_weight: float = 1.0, data_range: float = 1.0, want_grad: bool = True):
+    """``pytorch_msssim.ssim`` with its defaults, restated (11-tap Gaussian, sigma 1.5, valid correlation, per channel; see
+    include/mi_restore.h), over [B, C, H, W] with H, W >= 11.  Returns a 2-element fp32 tensor ``[loss_weight * (1 - m), m]``,
+    m the mean SSIM, and (optionally) the gradient of its first entry w.r.t. pred in pred's dtype (mi_ssim_loss)."""
+    _loss_pair("ssim_loss", pred, target, True)
+    B, Cc, H, W = pred.shape
+    if H < 11 or W < 11:
+        raise ValueError(f"ssim_loss: H and W must be at least the 11-pixel window, got {H} x {W}")
+    loss = torch.empty(2, dtype=torch.float32, device=pred.device)
+    dpred = torch.empty_like(pred) if want_grad else None
+    ws = _ws(L.lib().mi_ssim_loss_workspace(B, Cc, H, W), pred.device)
+    L.check(L.lib().mi_ssim_loss(_p(pred), _p(target), _p(dpred), _p(loss), B, Cc, H, W, float(loss_weight), float(data_range),
+                                 _dt(pred), _p(ws), _stream()), "ssim_loss")
+    return loss, dpred
+
+
+EDGE_CRITERIA = {"l2": 0, "l1": 1}
+
+
+def edge_loss(pred: Tensor, target: Tensor, loss_weight: float = 1.0, criterion: str = "l2", want_grad: bool = True):
+    """``loss_weight * mean(e^2)`` ('l2') or ``loss_weight * mean|e|`` ('l1') of e = Laplacian(pred - target), the Laplacian of
+    the reference's EdgeLoss (5x5 blur over the replicate-padded plane, even-grid upsampling), over [B, C, H, W] with H, W >= 2,
+    and (optionally) its gradient w.r.t. pred in pred's dtype (mi_edge_loss).  The loss is a 1-element fp32 tensor."""
+    _loss_pair("edge_loss", pred, target, True)
+    if criterion not in EDGE_CRITERIA:
+        raise NotImplementedError(f"edge_loss: unsupported criterion {criterion!r} ('l1' or 'l2')")
+    B, Cc, H, W = pred.shape
+    if H < 2 or W < 2:
+        raise ValueError(f"edge_loss: H and W must be at least 2, got {H} x {W}")
+    loss = torch.empty(1, dtype=torch.float32, device=pred.device)
+    dpred = torch.empty_like(pred) if want_grad else None
+    ws = _ws(L.lib().mi_edge_loss_workspace(B, Cc, H, W), pred.device)
+    L.check(L.lib().mi_edge_loss(_p(pred), _p(target), _p(dpred), _p(loss), B, Cc, H, W, float(loss_weight),
+                                 EDGE_CRITERIA[criterion], _dt(pred), _p(ws), _stream()), "edge_loss")
+    return loss, dpred
+
+
+def focal_l1_loss(pred: Tensor, target: Tensor, gamma: float = 2.0, epsilon: float = 1e-6, alpha: float = 0.1,
+                  scale: float = 1.0, want_grad: bool = True):
+    """``scale * mean(log1p(a + epsilon)^gamma * a)``, a = |pred - target| / alpha (the reference's FocalL1Loss), over tensors of
+    any shape, and (optionally) its gradient w.r.t. pred in pred's dtype, 0 at a tie (mi_focal_l1_loss).  1-element fp32 loss."""
+    _loss_pair("focal_l1_loss", pred, target, False)
+    if not alpha > 0:
+        raise ValueError(f"focal_l1_loss: alpha must be > 0, got {alpha}")
+    n = pred.numel()
+    loss = torch.empty(1, dtype=torch.float32, device=pred.device)
+    dpred = torch.empty_like(pred) if want_grad else None
+    ws = _ws(L.lib().mi_focal_l1_workspace(n), pred.device)
+    L.check(L.lib().mi_focal_l1_loss(_p(pred), _p(target), _p(dpred), _p(loss), n, float(gamma), float(epsilon), float(alpha),
+                                     float(scale), _dt(pred), _p(ws), _stream()), "focal_l1_loss")
+    return loss, dpred
+
+
 # ----------------------------------------------------------------------------- profiler (bench.py roofline pass)
 _pw_cache_buf: Optional[Tensor] = None
 

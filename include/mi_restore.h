@@ -798,6 +798,39 @@ int mi_fft_l1_loss(const void* pred, const void* target, void* dpred, float* los
                    float loss_weight, int dtype, void* ws, void* stream);
 
 /* ------------------------------------------------------------------------
+ * The other pixel-space loss terms of the reference's training steps (csrc/losses.hip), each with d loss / d pred from the same
+ * call.  Conventions of mi_fft_l1_loss: fp32 arithmetic on inputs widened on load; dpred written in `dtype`, rounded once, NULL
+ * skips every gradient stage; loss is device fp32 and overwritten; ws holds the matching *_workspace() bytes; no atomics,
+ * fixed-order sums (bitwise reproducible); no allocation, no host synchronisation; every refusal returns before any launch.
+ *
+ * mi_ssim_loss   SSIMloss / SSIM (MoCE-IR-main/src/utils/loss_utils.py:35-55), i.e. pytorch_msssim.ssim with its defaults,
+ *                restated (that library is not a dependency: this definition is the contract, unpinned like mi_psnr_ssim):
+ *                window g[i] = exp(-(i-5)^2 / (2 1.5^2)), i = 0..10, sum 1, separable, per channel, VALID correlation (the map
+ *                is (H-10) x (W-10));  C1 = (0.01 data_range)^2, C2 = (0.03 data_range)^2;  mu1 = g*x, mu2 = g*y,
+ *                s1 = g*x^2 - mu1^2, s2 = g*y^2 - mu2^2, s12 = g*xy - mu1 mu2,
+ *                S = (2 mu1 mu2 + C1)(2 s12 + C2) / ((mu1^2 + mu2^2 + C1)(s1 + s2 + C2)),  m = mean of S over B C (H-10)(W-10).
+ *                loss[0] = loss_weight (1 - m), loss[1] = m (loss holds TWO floats);  dpred = d loss[0] / d pred.
+ *                H, W >= 11, data_range > 0.  Kernels work on MI_SSIM_TILE x MI_SSIM_TILE tiles of the map / the image.
+ * mi_edge_loss   EdgeLoss (loss_utils.py:155-190) for any C >= 1, H, W >= 2:  e = L(pred - target),  L(c) = c - G(Z),
+ *                G the 5x5 blur [.05 .25 .4 .25 .05]^T [.05 .25 .4 .25 .05] over the replicate-padded plane, Z = 4 G(c) at
+ *                even (row, col) and 0 elsewhere.  criterion 0 ('l2'): loss = loss_weight mean(e^2), dpred = loss_weight
+ *                (2/N) L^T e;  criterion 1 ('l1'): loss = loss_weight mean|e|, dpred = loss_weight (1/N) L^T sign(e), sign(0) = 0.
+ * mi_focal_l1_loss  FocalL1Loss (loss_utils.py:100-136), flat over n elements:  a = |pred - target| / alpha,
+ *                loss = scale mean(log1p(a + epsilon)^gamma a),  dpred its gradient, sign(0) = 0 (exactly 0 at a tie).
+ *                alpha > 0, gamma >= 0, epsilon >= 0.
+ * ------------------------------------------------------------------------ */
+#define MI_SSIM_TILE 32
+size_t mi_ssim_loss_workspace(int B, int C, int H, int W);
+int mi_ssim_loss(const void* pred, const void* target, void* dpred, float* loss, int B, int C, int H, int W,
+                 float loss_weight, float data_range, int dtype, void* ws, void* stream);
+size_t mi_edge_loss_workspace(int B, int C, int H, int W);
+int mi_edge_loss(const void* pred, const void* target, void* dpred, float* loss, int B, int C, int H, int W,
+                 float loss_weight, int criterion, int dtype, void* ws, void* stream);
+size_t mi_focal_l1_workspace(int64_t n);
+int mi_focal_l1_loss(const void* pred, const void* target, void* dpred, float* loss, int64_t n, float gamma, float epsilon,
+                     float alpha, float scale, int dtype, void* ws, void* stream);
+
+/* ------------------------------------------------------------------------
  * Optional per-kernel profiler (measurement aid for bench.py's roofline object; nothing in the
  * reference corresponds to it).  When enabled every kernel launch is bracketed by two HIP events
  * recorded on the stream it is launched on, and its algorithmic HBM bytes / flops are booked.
