@@ -159,6 +159,33 @@ class MefcGrads(C.Structure):
                                                                                      ("accumulate", C.c_int)]
 
 
+class DilgateParams(C.Structure):
+    _fields_ = [("w", fp * 4), ("b", fp * 4)]
+
+
+class DilgateGrads(C.Structure):
+    _fields_ = [("w", fp * 4), ("b", fp * 4), ("accumulate", C.c_int)]
+
+
+class DblockShape(C.Structure):
+    _fields_ = [("B", C.c_int), ("C", C.c_int), ("H", C.c_int), ("W", C.c_int), ("dtype", C.c_int), ("n_dil", C.c_int),
+                ("dil", C.c_int * 4), ("extra", C.c_int)]
+
+
+# mi_dblock_params / mi_dblock_grads in field order; (name, 4): one pointer per branch
+DBLOCK_FIELDS = (("norm1_w", 1), ("norm1_b", 1), ("conv1_w", 1), ("conv1_b", 1), ("extra_w", 1), ("extra_b", 1), ("br_w", 4), ("br_b", 4),
+                 ("sca_w", 1), ("sca_b", 1), ("conv3_w", 1), ("conv3_b", 1), ("beta", 1), ("norm2_w", 1), ("norm2_b", 1),
+                 ("conv4_w", 1), ("conv4_b", 1), ("conv5_w", 1), ("conv5_b", 1), ("gamma", 1))
+
+
+class DblockParams(C.Structure):
+    _fields_ = [(n, fp * k) if k > 1 else (n, fp) for n, k in DBLOCK_FIELDS]
+
+
+class DblockGrads(C.Structure):
+    _fields_ = [(n, fp * k) if k > 1 else (n, fp) for n, k in DBLOCK_FIELDS] + [("accumulate", C.c_int)]
+
+
 # symbol -> (restype, argtypes); this table is also what tests/test_cabi.py checks against the header
 SIGNATURES = {
     "mi_version": (C.c_int, []),
@@ -171,6 +198,7 @@ SIGNATURES = {
     "mi_deferred_flush": (C.c_int, [vp]),
     "mi_deferred_end": (C.c_int, []),
     "mi_ln_fwd": (C.c_int, [vp, fp, fp, vp, fp, fp, C.c_int, C.c_int, c_i64, C.c_int, C.c_int, vp]),
+    "mi_ln_fwd_eps": (C.c_int, [vp, fp, fp, vp, fp, fp, C.c_int, C.c_int, c_i64, C.c_int, C.c_float, C.c_int, vp]),
     "mi_ln_bwd_workspace": (C.c_size_t, [C.c_int, C.c_int, c_i64]),
     "mi_ln_bwd": (C.c_int, [vp, vp, fp, fp, fp, vp, vp, fp, fp, C.c_int, C.c_int, c_i64, C.c_int, C.c_int, C.c_int,
                             vp, vp]),
@@ -267,6 +295,20 @@ SIGNATURES = {
     "mi_mefc_workspace": (C.c_size_t, [C.POINTER(MefcShape)]),
     "mi_mefc_fwd": (C.c_int, [C.POINTER(MefcShape), C.POINTER(MefcParams), vp, vp, vp, vp, vp]),
     "mi_mefc_bwd": (C.c_int, [C.POINTER(MefcShape), C.POINTER(MefcParams), vp, vp, vp, vp, C.POINTER(MefcGrads), vp, vp, vp]),
+    "mi_dilgate_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(c_i64)]),
+    "mi_dilgate_fwd_workspace": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    "mi_dilgate_fwd": (C.c_int, [vp, C.POINTER(DilgateParams), vp, fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int),
+                                 C.c_int, vp, vp]),
+    "mi_dilgate_bwd_workspace": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "mi_dilgate_bwd": (C.c_int, [vp, fp, vp, C.POINTER(DilgateParams), vp, C.POINTER(DilgateGrads), C.c_int, C.c_int, C.c_int, C.c_int,
+                                 C.c_int, C.POINTER(C.c_int), C.c_int, vp, vp]),
+    "mi_pairconv3x3_fwd": (C.c_int, [vp, fp, fp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
+    "mi_pairconv3x3_bwd_workspace": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    "mi_pairconv3x3_bwd": (C.c_int, [vp, vp, fp, vp, fp, fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]),
+    "mi_dblock_saved_bytes": (C.c_size_t, [C.POINTER(DblockShape)]),
+    "mi_dblock_workspace": (C.c_size_t, [C.POINTER(DblockShape)]),
+    "mi_dblock_fwd": (C.c_int, [C.POINTER(DblockShape), C.POINTER(DblockParams), vp, vp, vp, vp, vp]),
+    "mi_dblock_bwd": (C.c_int, [C.POINTER(DblockShape), C.POINTER(DblockParams), vp, vp, vp, C.POINTER(DblockGrads), vp, vp, vp]),
     "mi_gdfn_fused_ok": (C.c_int, [C.POINTER(GdfnFusedShape)]),
     "mi_gdfn_fused_pack_bytes": (C.c_size_t, [C.POINTER(GdfnFusedShape)]),
     "mi_gdfn_fused_pack": (C.c_int, [C.POINTER(GdfnFusedShape), fp, fp, C.POINTER(GdfnParams), vp, vp]),

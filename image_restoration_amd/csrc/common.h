@@ -328,7 +328,7 @@ enum KernelId {
   K_IM2COL, K_COL2IM, K_GDFN_FUSED_FWD, K_GDFN_FUSED_BWD, K_MDTA_FUSED_A, K_FUSED_PACK, K_MOE_ROUTE, K_CIRCCONV, K_EWISE, K_CONV3X3, K_GRAM_QK, K_PW_AV, K_BWD_TAIL, K_BWD_TAIL_FIN, K_ADAIR, K_SUMSQ, K_ADAMW_CLIP, K_ADAMW_EMA,
   K_TKSA_ATTN, K_TKSA_FOLD, K_TKSA_BWD, K_TKSA_DWO, K_MSFN_S1, K_MSFN_S2, K_MSFN_S1_BWD, K_MSFN_S2_BWD,
   K_MEFC_STA, K_MEFC_STB, K_MEFC_STA_BWD, K_MEFC_STB_BWD, K_MEFC_WGRAD, K_MEFC_FOLD, K_MEFC_FOLD_BWD, K_MEFC_HEAD, K_MEFC_HEAD_BWD,
-  K_MEFC_EW, K_COUNT
+  K_MEFC_EW, K_DK_GATE_FWD, K_DK_GATE_BWD_DZ, K_DK_GATE_BWD_DX, K_DK_PAIR, K_DK_PAIR_WGRAD, K_DK_FOLD, K_DK_FOLD_BWD, K_COUNT
 };
 // Brackets one kernel launch with two events on ITS stream and books its algorithmic bytes / flops.
 struct ProfScope {

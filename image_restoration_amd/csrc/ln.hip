@@ -8,7 +8,7 @@
 
 namespace mi {
 
-constexpr float LN_EPS = 1e-5f;
+constexpr float LN_EPS = 1e-5f;   // mi_ln_fwd; mi_ln_fwd_eps passes its own (the kernels take eps as an argument)
 
 // A lane's VEC pixels of one channel exactly as loaded: bf16 x 2 is ONE register (two floats after conversion), so
 // values that must survive between sweeps are kept raw and converted again where they are used.
@@ -37,7 +37,7 @@ template <typename T, int LN_WAVES, int CPT, int VEC, bool WITH_BIAS>
 __global__ __launch_bounds__(64 * LN_WAVES) void ln_fwd_kernel(const T* __restrict__ x, const float* __restrict__ w,
                                                                 const float* __restrict__ b, T* __restrict__ y,
                                                                 float* __restrict__ mean_out, float* __restrict__ rstd_out,
-                                                                int C, int64_t N) {
+                                                                int C, int64_t N, float eps) {
   constexpr int TILE = 64 * VEC;
   __shared__ float red[LN_WAVES][TILE];
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
@@ -94,7 +94,7 @@ __global__ __launch_bounds__(64 * LN_WAVES) void ln_fwd_kernel(const T* __restri
     float t = 0.f;
 #pragma unroll
     for (int k = 0; k < LN_WAVES; ++k) t += red[k][lane * VEC + j];
-    rs[j] = 1.0f / sqrtf(t * invC + LN_EPS);
+    rs[j] = 1.0f / sqrtf(t * invC + eps);
   }
   if (!valid) return;
 #pragma unroll
@@ -262,7 +262,7 @@ template <typename T, int CB, int VEC, bool WITH_BIAS, int WS>
 __global__ __launch_bounds__(256) void ln_fwd_wave_kernel(const T* __restrict__ x, const float* __restrict__ w,
                                                           const float* __restrict__ b, T* __restrict__ y,
                                                           float* __restrict__ mean_out, float* __restrict__ rstd_out,
-                                                          int C, int64_t N) {
+                                                          int C, int64_t N, float eps) {
   using RW = LnRaw<T, VEC>;
   constexpr int TILE = 64 * VEC;
   __shared__ float red[WS > 1 ? 4 : 1][WS > 1 ? TILE : 1];
@@ -319,7 +319,7 @@ __global__ __launch_bounds__(256) void ln_fwd_wave_kernel(const T* __restrict__ 
   }
   across(s);
 #pragma unroll
-  for (int j = 0; j < VEC; ++j) rs[j] = 1.0f / sqrtf(s[j] * invC + LN_EPS);
+  for (int j = 0; j < VEC; ++j) rs[j] = 1.0f / sqrtf(s[j] * invC + eps);
   if (!valid) return;
 #pragma unroll
   for (int c = 0; c < CB; ++c) {
@@ -540,7 +540,7 @@ static LnPlan ln_bwd_plan(int B, int C, int64_t N, bool f32, bool aligned) {
 
 template <typename T, bool WB>
 static int ln_fwd_dispatch(const T* x, const float* w, const float* b, T* y, float* mean, float* rstd, int B, int C,
-                           int64_t N, hipStream_t st) {
+                           int64_t N, float eps, hipStream_t st) {
   constexpr bool F32 = sizeof(T) == 4;
   constexpr int WVEC = F32 ? 1 : 2;
   if (C > 768) { set_error("ln_fwd: C=%d > 768 unsupported", C); return MI_ERR_ARG; }
@@ -550,7 +550,7 @@ static int ln_fwd_dispatch(const T* x, const float* w, const float* b, T* y, flo
   if (p.wave) {   // wave-owned form
 #define LN_FWDW_CASE(CB, WS_)                                                                                            \
     if (p.cb == CB && p.ws == WS_)                                                                                       \
-      hipLaunchKernelGGL((ln_fwd_wave_kernel<T, CB, WVEC, WB, WS_>), grid, dim3(256), 0, st, x, w, b, y, mean, rstd, C, N)
+      hipLaunchKernelGGL((ln_fwd_wave_kernel<T, CB, WVEC, WB, WS_>), grid, dim3(256), 0, st, x, w, b, y, mean, rstd, C, N, eps)
     LN_FWDW_CASE(16, 1); LN_FWDW_CASE(48, 1); LN_FWDW_CASE(96, 1); LN_FWDW_CASE(96, 2); LN_FWDW_CASE(96, 4);
 #undef LN_FWDW_CASE
     MI_LAUNCH_CHECK();
@@ -558,7 +558,7 @@ static int ln_fwd_dispatch(const T* x, const float* w, const float* b, T* y, flo
   }
 #define LN_FWD_CASE(WV, CPT, VEC)                                                                                   \
   if (p.waves == WV && p.cpt == CPT && p.vec == VEC)                                                                    \
-    hipLaunchKernelGGL((ln_fwd_kernel<T, WV, CPT, VEC, WB>), grid, dim3(64 * WV), 0, st, x, w, b, y, mean, rstd, C, N)
+    hipLaunchKernelGGL((ln_fwd_kernel<T, WV, CPT, VEC, WB>), grid, dim3(64 * WV), 0, st, x, w, b, y, mean, rstd, C, N, eps)
   if constexpr (!F32) {
     LN_FWD_CASE(8, 2, 2); LN_FWD_CASE(8, 6, 2); LN_FWD_CASE(8, 12, 2); LN_FWD_CASE(8, 24, 2); LN_FWD_CASE(16, 24, 2);
   }
@@ -609,19 +609,25 @@ static int ln_bwd_dispatch(const T* dy, const T* x, const float* w, const float*
 
 using namespace mi;
 
-extern "C" int mi_ln_fwd(const void* x, const float* w, const float* b, void* y, float* mean, float* rstd, int B, int C,
-                         int64_t N, int with_bias, int dtype, void* stream) {
+extern "C" int mi_ln_fwd_eps(const void* x, const float* w, const float* b, void* y, float* mean, float* rstd, int B, int C,
+                             int64_t N, int with_bias, float eps, int dtype, void* stream) {
   MI_CHECK_ARG(x && w && y, "ln_fwd: null pointer");
   MI_CHECK_ARG(B > 0 && C > 0 && N > 0, "ln_fwd: bad shape B=%d C=%d N=%lld", B, C, (long long)N);
   MI_CHECK_ARG((int64_t)C * N < (1ll << 31), "ln_fwd: C*H*W must be below 2^31");
   MI_CHECK_ARG(!with_bias || b, "ln_fwd: with_bias needs b");
   MI_CHECK_ARG((mean == nullptr) == (rstd == nullptr), "ln_fwd: mean/rstd must both be given or both NULL");
+  MI_CHECK_ARG(eps > 0.f && eps < 1.f, "ln_fwd: eps=%g outside (0, 1)", (double)eps);
   hipStream_t st = (hipStream_t)stream;
   return with_dtype(dtype, "ln_fwd", [&](auto tag) -> int {
     using T = decltype(tag);
-    return with_bias ? ln_fwd_dispatch<T, true>((const T*)x, w, b, (T*)y, mean, rstd, B, C, N, st)
-                     : ln_fwd_dispatch<T, false>((const T*)x, w, b, (T*)y, mean, rstd, B, C, N, st);
+    return with_bias ? ln_fwd_dispatch<T, true>((const T*)x, w, b, (T*)y, mean, rstd, B, C, N, eps, st)
+                     : ln_fwd_dispatch<T, false>((const T*)x, w, b, (T*)y, mean, rstd, B, C, N, eps, st);
   });
+}
+// the reference families' LayerNorm: eps 1e-5 (the same kernels and arithmetic: eps is a kernel argument)
+extern "C" int mi_ln_fwd(const void* x, const float* w, const float* b, void* y, float* mean, float* rstd, int B, int C,
+                         int64_t N, int with_bias, int dtype, void* stream) {
+  return mi_ln_fwd_eps(x, w, b, y, mean, rstd, B, C, N, with_bias, LN_EPS, dtype, stream);
 }
 
 extern "C" size_t mi_ln_bwd_workspace(int B, int C, int64_t N) {

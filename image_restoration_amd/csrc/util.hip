@@ -53,7 +53,9 @@ static const char* const g_kernel_names[K_COUNT] = {
     "pw_pack", "gap", "im2col3x3", "col2im3x3", "gdfn_fused_fwd", "gdfn_fused_bwd", "mdta_fused_a", "fused_pack", "moe_route", "patch_circconv", "ewise", "conv3x3", "mdta_qk", "mdta_av", "bwd_tail", "bwd_tail_finish", "adair_fre", "grad_sumsq",
     "adamw_clip", "adamw_clip_ema", "tksa_attn", "tksa_fold", "tksa_bwd", "tksa_dwo", "msfn_stencil1", "msfn_stencil2",
     "msfn_stencil1_bwd", "msfn_stencil2_bwd", "mefc_stencil_a", "mefc_stencil_b", "mefc_stencil_a_bwd", "mefc_stencil_b_bwd",
-    "mefc_dw_wgrad", "mefc_fold", "mefc_fold_bwd", "mefc_head", "mefc_head_bwd", "mefc_ewise"};
+    "mefc_dw_wgrad", "mefc_fold", "mefc_fold_bwd", "mefc_head", "mefc_head_bwd", "mefc_ewise",
+    "darkir_dilgate_fwd", "darkir_dilgate_bwd_dz", "darkir_dilgate_bwd_dx", "darkir_pairconv", "darkir_pairconv_wgrad", "darkir_fold",
+    "darkir_fold_bwd"};
 
 ProfScope::ProfScope(hipStream_t stream, int kernel_id, double bytes, double flops)
     : st(stream), kid(kernel_id), on(g_prof_on.load(std::memory_order_relaxed) != 0) {

@@ -781,6 +781,171 @@ def msfn_bwd(x: Tensor, dout: Tensor, params: Sequence[Optional[Tensor]], saved:
     return dx
 
 
+# ----------------------------------------------------------------------------- DarkIR: dilated gate, pair conv, DBlock
+DILGATE_MAX_BRANCHES, DILGATE_MAX_DILATION = 4, 16
+
+
+def ln_fwd_eps(x: Tensor, w: Tensor, b: Optional[Tensor], with_bias: bool, eps: float, want_stats: bool = True):
+    """ln_fwd with the caller's eps (DarkIR's LayerNorm2d: 1e-6).  -> (y, mean, rstd)."""
+    _gpu(x, w, b)
+    _f32(w, "LayerNorm weight"); _f32(b, "LayerNorm bias")
+    B, Cc, H, W = x.shape
+    y = torch.empty_like(x)
+    mean = rstd = None
+    if want_stats:
+        mean = torch.empty((B, H * W), dtype=torch.float32, device=x.device)
+        rstd = torch.empty_like(mean)
+    L.check(L.lib().mi_ln_fwd_eps(_p(x), _p(w), _p(b), _p(y), _p(mean), _p(rstd), B, Cc, H * W, int(with_bias), float(eps), _dt(x),
+                                  _stream()), "ln_fwd_eps")
+    return y, mean, rstd
+
+
+def _dil_array(dilations: Sequence[int]):
+    return (C.c_int * max(len(dilations), 1))(*[int(d) for d in dilations])
+
+
+def dilgate_plan(B: int, c: int, H: int, W: int, dtype: torch.dtype, dilations: Sequence[int]) -> dict:
+    """What dilgate_fwd / dilgate_bwd launch for x [B, 2c, H, W] (mi_dilgate_plan; no GPU work)."""
+    out = (L.c_i64 * 12)()
+    L.check(L.lib().mi_dilgate_plan(B, c, H, W, _dtype_code(dtype), len(dilations), _dil_array(dilations), out), "dilgate_plan")
+    names = ("tile_rows", "tile_cols", "halo", "lds_bytes", "grid_x", "grid_y", "grid_z", "pool_partials", "z_stored", "fwd_ws_bytes",
+             "bwd_splits", "bwd_ws_bytes")
+    plan = {n: int(v) for n, v in zip(names, out)}
+    plan["z_stored"] = bool(plan["z_stored"])
+    return plan
+
+
+def _dilgate_struct(cls, ws_: Sequence[Tensor], bs: Sequence[Optional[Tensor]], what: str, *tail):
+    st = cls()
+    for i, (w, b) in enumerate(zip(ws_, bs)):
+        st.w[i], st.b[i] = _p(_f32(w, what)), _p(_f32(b, what))
+    for name, v in zip(("accumulate",), tail):
+        setattr(st, name, v)
+    return st
+
+
+def dilgate_fwd(x: Tensor, weights: Sequence[Tensor], biases: Sequence[Optional[Tensor]], dilations: Sequence[int]):
+    """Sum of the dilated depthwise 3x3 convs (weights[i] [2c,1,3,3], biases[i] [2c] or None, dilation dilations[i]) on x
+    [B, 2c, H, W], SimpleGate and the pool sums.  -> (g [B, c, H, W], pool [B, c] fp32 = sum over the plane of g)."""
+    _gpu(x, *weights, *biases)
+    B, C2, H, W = x.shape
+    c = C2 // 2
+    lib = L.lib()
+    g = torch.empty((B, c, H, W), dtype=x.dtype, device=x.device)
+    pool = torch.empty((B, c), dtype=torch.float32, device=x.device)
+    ws = _ws(lib.mi_dilgate_fwd_workspace(B, c, H, W), x.device)
+    pp = _dilgate_struct(L.DilgateParams, weights, biases, "dilgate parameter")
+    L.check(lib.mi_dilgate_fwd(_p(x), C.byref(pp), _p(g), _p(pool), B, c, H, W, len(dilations), _dil_array(dilations), _dt(x), _p(ws),
+                               _stream()), "dilgate_fwd")
+    return g, pool
+
+
+def dilgate_bwd(dg: Tensor, dg_add: Optional[Tensor], x: Tensor, weights: Sequence[Tensor], biases: Sequence[Optional[Tensor]],
+                dilations: Sequence[int], gw: Sequence[Tensor], gb: Sequence[Optional[Tensor]], accumulate: bool) -> Tensor:
+    """Backward of dilgate_fwd: dx; the weight / bias gradients of every branch are written (accumulate: added) into gw / gb.
+    dg_add [B, c] fp32 or None: added to every pixel of dg's plane (the gradient through the pooled mean)."""
+    _gpu(dg, dg_add, x, *weights, *biases, *gw, *gb)
+    _f32(dg_add, "dg_add")
+    B, C2, H, W = x.shape
+    c = C2 // 2
+    lib = L.lib()
+    dx = torch.empty_like(x)
+    ws = _ws(lib.mi_dilgate_bwd_workspace(B, c, H, W, len(dilations), _dt(x)), x.device)
+    pp = _dilgate_struct(L.DilgateParams, weights, biases, "dilgate parameter")
+    gg = _dilgate_struct(L.DilgateGrads, gw, gb, "dilgate gradient", int(accumulate))
+    L.check(lib.mi_dilgate_bwd(_p(dg), _p(dg_add), _p(x), C.byref(pp), _p(dx), C.byref(gg), B, c, H, W, len(dilations),
+                               _dil_array(dilations), _dt(x), _p(ws), _stream()), "dilgate_bwd")
+    return dx
+
+
+def pairconv3x3_fwd(x: Tensor, w: Tensor, bias: Optional[Tensor]) -> Tensor:
+    """3x3 conv, padding 1, on 2c channels in c groups (w [2c,2,3,3]): DarkIR's extra_conv."""
+    _gpu(x, w, bias)
+    _f32(w, "pairconv3x3 weight"); _f32(bias, "pairconv3x3 bias")
+    B, C2, H, W = x.shape
+    y = torch.empty_like(x)
+    L.check(L.lib().mi_pairconv3x3_fwd(_p(x), _p(w), _p(bias), _p(y), B, C2 // 2, H, W, _dt(x), _stream()), "pairconv3x3_fwd")
+    return y
+
+
+def pairconv3x3_bwd(dy: Tensor, x: Tensor, w: Tensor, dw: Tensor, db: Optional[Tensor], accumulate: bool) -> Tensor:
+    _gpu(dy, x, w, dw, db)
+    _f32(w, "pairconv3x3 weight"); _f32(dw, "pairconv3x3 gradient"); _f32(db, "pairconv3x3 gradient")
+    B, C2, H, W = x.shape
+    lib = L.lib()
+    dx = torch.empty_like(x)
+    ws = _ws(lib.mi_pairconv3x3_bwd_workspace(B, C2 // 2, H, W), x.device)
+    L.check(lib.mi_pairconv3x3_bwd(_p(dy), _p(x), _p(w), _p(dx), _p(dw), _p(db), B, C2 // 2, H, W, int(accumulate), _dt(x), _p(ws),
+                                   _stream()), "pairconv3x3_bwd")
+    return dx
+
+
+def _dblock_shape(B: int, Cc: int, H: int, W: int, dtype_code: int, dilations: Sequence[int], extra: bool) -> L.DblockShape:
+    s = L.DblockShape(B, Cc, H, W, dtype_code, len(dilations))
+    for i, d in enumerate(dilations[:4]):
+        s.dil[i] = int(d)
+    s.extra = int(extra)
+    return s
+
+
+def dblock_sizes(B: int, Cc: int, H: int, W: int, dtype: torch.dtype, dilations: Sequence[int], extra: bool) -> Tuple[int, int]:
+    """(saved bytes, workspace bytes) of one DBlock; (0, 0) for a shape the kernels do not cover.  No GPU needed."""
+    s = _dblock_shape(B, Cc, H, W, _dtype_code(dtype), dilations, extra)
+    lib = L.lib()
+    return int(lib.mi_dblock_saved_bytes(C.byref(s))), int(lib.mi_dblock_workspace(C.byref(s)))
+
+
+def _dblock_struct(cls, ts: Sequence[Optional[Tensor]], n_dil: int, what: str, *tail):
+    """mi_dblock_params / mi_dblock_grads from the flat list: norm1 (2), conv1 (2), extra_conv (2, None without it), the
+    branches' weights (n_dil), their biases (n_dil), sca (2), conv3 (2), beta, norm2 (2), conv4 (2), conv5 (2), gamma."""
+    for t in ts:
+        _f32(t, what)
+    st = cls()
+    it = iter(ts)
+    for name, k in L.DBLOCK_FIELDS:
+        if k == 1:
+            setattr(st, name, _p(next(it)))
+        else:
+            arr = getattr(st, name)
+            for i in range(n_dil):
+                arr[i] = _p(next(it))
+    if tail:
+        st.accumulate = tail[0]
+    return st
+
+
+def dblock_fwd(x: Tensor, params: Sequence[Optional[Tensor]], dilations: Sequence[int], extra: bool, need_saved: bool):
+    """DarkIR DBlock.forward.  params: see _dblock_struct.  -> (out, saved)."""
+    _gpu(x, *params)
+    B, Cc, H, W = x.shape
+    s = _dblock_shape(B, Cc, H, W, _dt(x), dilations, extra)
+    lib = L.lib()
+    ws_bytes = lib.mi_dblock_workspace(C.byref(s))
+    if ws_bytes == 0:
+        L.check(-1, "dblock_workspace")
+    out = torch.empty_like(x)
+    saved = _blob(lib.mi_dblock_saved_bytes(C.byref(s)), x.device) if need_saved else None
+    ws = _ws(ws_bytes, x.device)
+    pp = _dblock_struct(L.DblockParams, params, len(dilations), "DBlock parameter")
+    L.check(lib.mi_dblock_fwd(C.byref(s), C.byref(pp), _p(x), _p(out), _p(saved), _p(ws), _stream()), "dblock_fwd")
+    return out, saved
+
+
+def dblock_bwd(x: Tensor, dout: Tensor, params: Sequence[Optional[Tensor]], dilations: Sequence[int], extra: bool, saved: Tensor,
+               grads: Sequence[Optional[Tensor]], accumulate: bool) -> Tensor:
+    """Backward of dblock_fwd: dx; the parameter gradients are written (accumulate: added) into ``grads``."""
+    _gpu(x, dout, saved, *params, *grads)
+    B, Cc, H, W = x.shape
+    s = _dblock_shape(B, Cc, H, W, _dt(x), dilations, extra)
+    lib = L.lib()
+    dx = torch.empty_like(x)
+    pp = _dblock_struct(L.DblockParams, params, len(dilations), "DBlock parameter")
+    gg = _dblock_struct(L.DblockGrads, grads, len(dilations), "DBlock gradient", int(accumulate))
+    ws = _ws(lib.mi_dblock_workspace(C.byref(s)), x.device)
+    L.check(lib.mi_dblock_bwd(C.byref(s), C.byref(pp), _p(x), _p(dout), _p(dx), C.byref(gg), _p(saved), _p(ws), _stream()), "dblock_bwd")
+    return dx
+
+
 # ----------------------------------------------------------------------------- DRSformer: MEFC (one OALayer + GroupOLs pair)
 MEFC_STEP_PARAMS = 23     # per OperationLayer: SepConv k = 1, 3, 5, 7 (op.0, op.1, op.3, op.4), DilConv k = 3, 5, 7 (op.0, op.1), _out.0
 

@@ -75,6 +75,10 @@ int mi_deferred_end(void);
  * ------------------------------------------------------------------------ */
 int mi_ln_fwd(const void* x, const float* w, const float* b, void* y, float* mean, float* rstd,
               int B, int C, int64_t N, int with_bias, int dtype, void* stream);
+/* The same with the caller's eps, 0 < eps < 1 (DarkIR's LayerNorm2d: 1e-6, arch_util.py:37).  mi_ln_fwd is this call with 1e-5:
+ * one set of kernels, eps a kernel argument.  The backward reads the saved rstd and needs no eps. */
+int mi_ln_fwd_eps(const void* x, const float* w, const float* b, void* y, float* mean, float* rstd,
+                  int B, int C, int64_t N, int with_bias, float eps, int dtype, void* stream);
 size_t mi_ln_bwd_workspace(int B, int C, int64_t N);
 int mi_ln_bwd(const void* dy, const void* x, const float* w, const float* mean, const float* rstd,
               const void* dres, void* dx, float* dw, float* db,
@@ -356,6 +360,77 @@ size_t mi_mefc_workspace(const mi_mefc_shape* s);
 int mi_mefc_fwd(const mi_mefc_shape* s, const mi_mefc_params* p, const void* x, void* out, void* saved, void* ws, void* stream);
 int mi_mefc_bwd(const mi_mefc_shape* s, const mi_mefc_params* p, const void* x, const void* out, const void* dout, void* dx,
                 const mi_mefc_grads* g, const void* saved, void* ws, void* stream);
+
+/* ------------------------------------------------------------------------
+ * DarkIR — the dilated-gate decoder block (DarkIR-main/archs/arch_model.py:72-139 DBlock; Branch :57-70; SimpleGate :12-15).
+ *
+ * dilgate: the n summed dilated depthwise 3x3 convs of the Branch list on the same 2c planes, SimpleGate and the SCA pool sums:
+ *   z = sum_i (dw3x3(x; w_i, dilation d_i, padding d_i) + b_i)   [B,2c,H,W];   g = z[:, :c] * z[:, c:]   [B,c,H,W]
+ *   pool[b, j] = sum_hw g[b, j]   (fp32, of the unrounded products; per-tile partials summed in a fixed order: no atomics)
+ * 1 <= n_dil <= 4, 1 <= d_i <= 16 (they may repeat), any H, W, c >= 1 (c <= 65535).  w_i [2c, 9], b_i [2c] (NULL: none).
+ * One workgroup forms both halves (j, j + c) of a 32-row tile from one LDS tile with a max(d_i) halo.  z is never stored: the
+ * backward recomputes it from x.  Its scratch dz is fp32 in either dtype.  fwd ws / bwd ws: mi_dilgate_fwd_workspace / mi_dilgate_bwd_workspace bytes.
+ *   bwd: dz[:, :c] = (dg + dg_add[b, j]) z[:, c:], dz[:, c:] = (dg + dg_add[b, j]) z[:, :c]  (dg_add [B, c] fp32 or NULL: the
+ *        gradient through the pooled mean, constant over a plane);  dx = sum_i dw_i^T dz;  dw_i, db_i fixed-order sums, added to
+ *        the buffers when accumulate != 0, else written (a NULL b[i] is skipped).
+ * mi_dilgate_plan (host-only; the launchers take every decision from the same plan) fills out[12]: tile rows, tile columns, halo,
+ * dynamic LDS bytes, forward grid x (tiles of a plane), y (c), z (B), pool partials per plane, 1 when z is stored (never), forward
+ * workspace bytes, workgroups per (image, channel pair) of the backward's weight-gradient pass, backward workspace bytes.
+ *
+ * pairconv3x3: DBlock.extra_conv (:83), a 3x3 conv with padding 1 on 2c channels in c groups: output channels 2g, 2g + 1 each read
+ * input channels 2g, 2g + 1.  w [2c, 2, 9], bias [2c] or NULL.  bwd: dx, dw, db (db may be NULL).
+ * ------------------------------------------------------------------------ */
+typedef struct { const float* w[4]; const float* b[4]; } mi_dilgate_params;
+typedef struct { float* w[4]; float* b[4]; int accumulate; } mi_dilgate_grads;
+int mi_dilgate_plan(int B, int c, int H, int W, int dtype, int n_dil, const int* dil, int64_t* out);
+size_t mi_dilgate_fwd_workspace(int B, int c, int H, int W);
+int mi_dilgate_fwd(const void* x, const mi_dilgate_params* p, void* g, float* pool, int B, int c, int H, int W, int n_dil,
+                   const int* dil, int dtype, void* ws, void* stream);
+size_t mi_dilgate_bwd_workspace(int B, int c, int H, int W, int n_dil, int dtype);
+int mi_dilgate_bwd(const void* dg, const float* dg_add, const void* x, const mi_dilgate_params* p, void* dx,
+                   const mi_dilgate_grads* gr, int B, int c, int H, int W, int n_dil, const int* dil, int dtype, void* ws,
+                   void* stream);
+int mi_pairconv3x3_fwd(const void* x, const float* w, const float* bias, void* y, int B, int c, int H, int W, int dtype,
+                       void* stream);
+size_t mi_pairconv3x3_bwd_workspace(int B, int c, int H, int W);
+int mi_pairconv3x3_bwd(const void* dy, const void* x, const float* w, void* dx, float* dw, float* db, int B, int c, int H, int W,
+                       int accumulate, int dtype, void* ws, void* stream);
+
+/* DBlock.forward / backward as one unit:
+ *   x0 = LayerNorm2d(inp; norm1, eps 1e-6);  x1 = conv1(x0) [2c];  x2 = extra_conv(x1) when `extra`, else x1;
+ *   g = dilgate(x2);  s[b] = sca_w . mean_hw(g[b]) + sca_b;  y = inp + beta (conv3(s g));
+ *   u = conv4(LayerNorm2d(y; norm2));  out = y + gamma conv5(u[:, :c] u[:, c:]).
+ * conv3 with the SCA scale, beta and the residual is ONE per-image 1x1 GEMM (M[b] = diag(beta) W3 diag(s[b]), bias beta b3,
+ * r = inp); conv5 with gamma and the residual likewise (diag(gamma) W5).  C <= 256 (DarkIR's widest level).
+ * With bf16 activations the four 1x1 products and their transposes run on SPLIT weights, [hi | lo] . [x ; x] with hi = w rounded to
+ * bf16 and lo = w - hi (two K panels of mi_pw_gemm): the MFMA path would otherwise round each weight to 8 mantissa bits, an error
+ * common to a channel that the bias gradients (pixel sums) keep whole.
+ * Parameters fp32 in the reference's layout: 1x1 [Cout, Cin], branch [2c, 9], extra_conv [2c, 2, 9], beta / gamma [c]; every bias
+ * is required (the reference's convs all have one); extra_w / extra_b are read only when `extra`.  saved == NULL: inference,
+ * nothing is kept.  The sizing calls return 0 for a shape that is not covered.
+ * ------------------------------------------------------------------------ */
+typedef struct { int B, C, H, W, dtype, n_dil; int dil[4]; int extra; } mi_dblock_shape;
+typedef struct {
+  const float* norm1_w; const float* norm1_b; const float* conv1_w; const float* conv1_b; const float* extra_w; const float* extra_b;
+  const float* br_w[4]; const float* br_b[4];
+  const float* sca_w; const float* sca_b; const float* conv3_w; const float* conv3_b; const float* beta;
+  const float* norm2_w; const float* norm2_b; const float* conv4_w; const float* conv4_b; const float* conv5_w; const float* conv5_b;
+  const float* gamma;
+} mi_dblock_params;
+typedef struct {
+  float* norm1_w; float* norm1_b; float* conv1_w; float* conv1_b; float* extra_w; float* extra_b;
+  float* br_w[4]; float* br_b[4];
+  float* sca_w; float* sca_b; float* conv3_w; float* conv3_b; float* beta;
+  float* norm2_w; float* norm2_b; float* conv4_w; float* conv4_b; float* conv5_w; float* conv5_b;
+  float* gamma;
+  int accumulate;
+} mi_dblock_grads;
+size_t mi_dblock_saved_bytes(const mi_dblock_shape* s);
+size_t mi_dblock_workspace(const mi_dblock_shape* s);
+int mi_dblock_fwd(const mi_dblock_shape* s, const mi_dblock_params* p, const void* inp, void* out, void* saved, void* ws,
+                  void* stream);
+int mi_dblock_bwd(const mi_dblock_shape* s, const mi_dblock_params* p, const void* inp, const void* dout, void* dinp,
+                  const mi_dblock_grads* g, const void* saved, void* ws, void* stream);
 
 /* ------------------------------------------------------------------------
  * GDFN — FeedForward.forward / backward (Restormer.py:76-93; moce_ir.py:255-276;
