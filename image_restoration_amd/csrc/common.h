@@ -297,6 +297,28 @@ __device__ __forceinline__ void gelu_parts(float x, float& cdf, float& pdf) {
   cdf = x >= 0.f ? 1.0f - q : q;
   pdf = 0.39894228040143267794f * e;
 }
+// gelu_parts of two values at once in packed fp32 (v_pk_mul_f32 / v_pk_fma_f32; one rcp and one exp per value stay).
+// Every step is the one gelu_parts compiles to - same order, fused where that is fused (the A-S denominator, the Horner
+// steps, 1 - q), unfused elsewhere - written out with contraction off, so each half rounds exactly as the scalar form.
+__device__ __forceinline__ void gelu_parts2(f32x2 x, f32x2& cdf, f32x2& pdf) {
+#pragma clang fp contract(off)
+  const f32x2 ax = {fabsf(x[0]), fabsf(x[1])};
+  const f32x2 z = ax * 0.70710678118654752440f;
+  const f32x2 den = __builtin_elementwise_fma(z, (f32x2){0.3275911f, 0.3275911f}, (f32x2){1.0f, 1.0f});
+  const f32x2 t = {__builtin_amdgcn_rcpf(den[0]), __builtin_amdgcn_rcpf(den[1])};
+  const f32x2 a = (z * -z) * 1.44269504088896340736f;       // __expf(v) = exp2(v * log2 e)
+  const f32x2 e = {__builtin_amdgcn_exp2f(a[0]), __builtin_amdgcn_exp2f(a[1])};
+  f32x2 p = __builtin_elementwise_fma(t, (f32x2){1.061405429f, 1.061405429f}, (f32x2){-1.453152027f, -1.453152027f});
+  p = __builtin_elementwise_fma(t, p, (f32x2){1.421413741f, 1.421413741f});
+  p = __builtin_elementwise_fma(t, p, (f32x2){-0.284496736f, -0.284496736f});
+  p = __builtin_elementwise_fma(t, p, (f32x2){0.254829592f, 0.254829592f});
+  const f32x2 hp = (t * p) * 0.5f;
+  const f32x2 q = hp * e;
+  const f32x2 omq = __builtin_elementwise_fma(-e, hp, (f32x2){1.0f, 1.0f});
+  cdf[0] = x[0] >= 0.f ? omq[0] : q[0];
+  cdf[1] = x[1] >= 0.f ? omq[1] : q[1];
+  pdf = e * 0.39894228040143267794f;
+}
 __device__ __forceinline__ float gelu_erf(float x) {
   float cdf, pdf;
   gelu_parts(x, cdf, pdf);

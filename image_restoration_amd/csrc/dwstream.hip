@@ -410,6 +410,22 @@ __device__ __forceinline__ void copy6x2(f32x2* d, const f32x2* s) {
   for (int i = 0; i < 6; ++i) d[i] = s[i];
 }
 
+// (d1, d2) of one pixel from y = (y1, y2), dg and the GELU parts of y1:  d1 = (dg y2) (cdf + y1 pdf),  d2 = (dg y1) cdf.
+// Two packed products; the sum is formed unfused, as the scalar form of this kernel formed it in its row loop.
+__device__ __forceinline__ f32x2 gate_grad2(f32x2 y, float dg, float cdf, float pdf) {
+#pragma clang fp contract(off)
+  const float m = y[0] * pdf;
+  const f32x2 g = {dg * y[1], dg * y[0]};
+  const f32x2 c = {cdf + m, cdf};
+  return g * c;
+}
+
+// The 3-row windows of x and of (d1, d2) live in three register sets that the row body names by phase (row mod 3), and
+// the raw prefetch slots go by the same phase: nothing is copied from row to row.  The row loop can end after any phase, so
+// a band runs exactly its rows whatever its height.
+constexpr int PFR = 3;   // rows in flight per plane = phases of the row body
+template <int K> struct Phase { static constexpr int k = K; };
+
 template <typename T, int LPR, bool UNI, bool WANT_DW>
 __global__ __launch_bounds__(256) void dws_gate_bwd_rc_kernel(DwArgs a, float* __restrict__ part, int planes, int nb,
                                                               int band_rows) {
@@ -417,23 +433,47 @@ __global__ __launch_bounds__(256) void dws_gate_bwd_rc_kernel(DwArgs a, float* _
   using RV = typename R::V;
   const Unit<LPR, UNI> u(planes, nb, band_rows);
   const int h = a.hidden;
-  const int b = u.active ? u.plane / h : 0, j = u.active ? u.plane - b * h : 0;
+  int b = u.active ? u.plane / h : 0, j = u.active ? u.plane - b * h : 0;
+  if (UNI) { b = __builtin_amdgcn_readfirstlane(b); j = __builtin_amdgcn_readfirstlane(j); }   // the division ran on the VALU
   const int64_t HW = (int64_t)a.H * a.W;
   const int x = 4 * u.lx;
   const bool first = u.lx == 0, last = u.lx == LPR - 1;
-  const T* dgp = (const T*)a.in + ((int64_t)b * h + j) * HW + x;          // dg [B, h, H, W]
-  const T* x1p = (const T*)a.gy + ((int64_t)b * a.Cc + j) * HW + x;       // conv input [B, 2h, H, W] (passed in a.gy)
+  // plane bases (in SGPRs when UNI); a lane adds a 32-bit byte offset (row, x) inside the plane, so a UNI wave addresses
+  // with scalar base + vector offset and holds no 64-bit pointers.  A plane (H * W elements, W <= 256) therefore has to stay
+  // below 2 GiB - four million rows.  The offset of a row above the plane wraps; ld() / ldu() never load from it.
+  const T* dgp = (const T*)a.in + ((int64_t)b * h + j) * HW;              // dg [B, h, H, W]
+  const T* x1p = (const T*)a.gy + ((int64_t)b * a.Cc + j) * HW;           // conv input [B, 2h, H, W] (passed in a.gy)
   const T* x2p = x1p + (int64_t)h * HW;
+  auto at = [&](const T* base, int y) -> const char* {
+    if constexpr (UNI) return reinterpret_cast<const char*>(base) + (uint32_t)((y * a.W + x) * (int)sizeof(T));
+    else return reinterpret_cast<const char*>(base + ((int64_t)y * a.W + x));
+  };
   f32x2 w[9], bias2 = {0.f, 0.f};                                          // (taps of plane j, taps of plane j+h)
 #pragma unroll
   for (int i = 0; i < 9; ++i) { w[i][0] = a.w[(int64_t)j * 9 + i]; w[i][1] = a.w[(int64_t)(j + h) * 9 + i]; }
   if (a.bias) { bias2[0] = a.bias[j]; bias2[1] = a.bias[j + h]; }
   const int yend = min(u.y0 + band_rows, a.H);
   auto ld = [&](const T* base, int y, int ymax) -> RV {
-    return (u.active && y >= 0 && y <= ymax && y < a.H) ? dws_ld<DWS_NT>(reinterpret_cast<const RV*>(base + (int64_t)y * a.W)) : R::zero();
+    return (u.active && y >= 0 && y <= ymax && y < a.H) ? dws_ld<DWS_NT>(reinterpret_cast<const RV*>(at(base, y))) : R::zero();
   };
-  f32x2 hA[6], hB[6], hC[6];            // x rows rho-1, rho, rho+1
-  f32x2 p0[6], p1[6], p2[6];            // (d1, d2) rows y-1, y, y+1
+  // The rows in flight of a UNI wave are loaded without a branch - from the nearest row the unit may read, so nothing new is
+  // fetched - and the guard zeroes them where they are used: with every load on every path the compiler counts the loads
+  // in flight and waits for the oldest row only (vmcnt(6)), where a guarded load in a block of its own made it drain them
+  // all (vmcnt(0)) once per loop trip.  Not UNI the guard is a lane mask that would live three rows: those waves keep the
+  // guarded load (measured at the 32-pixel rows: 112 us guarded, 117 us branch-free - profiles/gate_bwd_rc_valu.txt).
+  auto ldu = [&](const T* base, int y, int ymax, bool& ok) -> RV {
+    ok = u.active && y >= 0 && y <= ymax && y < a.H;
+    if constexpr (UNI) {
+      return dws_ld<DWS_NT>(reinterpret_cast<const RV*>(at(base, min(max(y, 0), min(ymax, a.H - 1)))));
+    } else {
+      const RV r = ok ? dws_ld<DWS_NT>(reinterpret_cast<const RV*>(at(base, y))) : R::zero();
+      ok = true;
+      return r;
+    }
+  };
+  auto use = [&](bool ok, const RV& r) -> RV { return ok ? r : R::zero(); };
+  f32x2 hw[3][6];                       // x rows y, y+1, y+2 at phases k, k+1, k+2 (mod 3)
+  f32x2 pw[3][6];                       // (d1, d2) rows y-1, y, y+1 likewise
   f32x2 acc[WANT_DW ? 10 : 1];
   const f32x2 zero2 = {0.f, 0.f};
   if (WANT_DW) {
@@ -446,27 +486,28 @@ __global__ __launch_bounds__(256) void dws_gate_bwd_rc_kernel(DwArgs a, float* _
 #pragma unroll
     for (int q = 0; q < 4; ++q) { out4[q][0] = v1[q]; out4[q][1] = v2[q]; }
   };
-  // d row rho from dg row rho and x rows rho-1 (hA), rho (hB), rho+1 (raw, becomes hC); rows outside the image give d = 0
-  auto d_row = [&](int rho, const RV& rdg, const RV& rx1, const RV& rx2, f32x2* pd) {
+  // d row rho from dg row rho and the window rows of x rows rho-1 (hA), rho (hB) and rho+1 (raw; its window row is left in
+  // hC).  A row outside the image has dg = 0 from its guarded load, and finite inputs give a finite y, so its d is +-0
+  // without a select.
+  auto d_row = [&](const RV& rdg, const RV& rx1, const RV& rx2, const f32x2* hA, const f32x2* hB, f32x2* hC, f32x2* pd) {
     f32x2 xv[4], y[4], d[4];
     float dg[4];
     pair_row(rx1, rx2, xv);
     window_row2(xv, first, last, hC);
     stencil2<false>(w, bias2, hA, hB, hC, y);       // (y1, y2) in fp32, exactly what the forward gated
-    R::expand(rdg, dg);                             // zero for rows outside the image / band halo limits
-    const bool inside = rho >= 0 && rho < a.H;
+    R::expand(rdg, dg);
 #pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      float cdf, pdf;
-      gelu_parts(y[q][0], cdf, pdf);
-      d[q][0] = inside ? dg[q] * y[q][1] * (cdf + y[q][0] * pdf) : 0.f;
-      d[q][1] = inside ? dg[q] * y[q][0] * cdf : 0.f;
+    for (int q = 0; q < 4; q += 2) {
+      f32x2 cdf, pdf;
+      gelu_parts2((f32x2){y[q][0], y[q + 1][0]}, cdf, pdf);
+      d[q] = gate_grad2(y[q], dg[q], cdf[0], pdf[0]);
+      d[q + 1] = gate_grad2(y[q + 1], dg[q + 1], cdf[1], pdf[1]);
     }
     window_row2(d, first, last, pd);
   };
-  auto h_shift = [&]() { copy6x2(hA, hB); copy6x2(hB, hC); };
 
-  RV cg[PFG], c1[PFG], c2[PFG];
+  RV cg[PFR], c1[PFR], c2[PFR];
+  bool og[PFR], ox[PFR];
   {
     f32x2 v[4];
     const RV ra1 = ld(x1p, u.y0 - 2, yend + 1), ra2 = ld(x2p, u.y0 - 2, yend + 1);
@@ -475,38 +516,67 @@ __global__ __launch_bounds__(256) void dws_gate_bwd_rc_kernel(DwArgs a, float* _
     const RV rd1 = ld(x1p, u.y0 + 1, yend + 1), rd2 = ld(x2p, u.y0 + 1, yend + 1);
     const RV g0 = ld(dgp, u.y0 - 1, yend), g1 = ld(dgp, u.y0, yend);
 #pragma unroll
-    for (int i = 0; i < PFG; ++i) {
-      cg[i] = ld(dgp, u.y0 + 1 + i, yend);
-      c1[i] = ld(x1p, u.y0 + 2 + i, yend + 1);
-      c2[i] = ld(x2p, u.y0 + 2 + i, yend + 1);
+    for (int i = 0; i < PFR; ++i) {
+      cg[i] = ldu(dgp, u.y0 + 1 + i, yend, og[i]);
+      c1[i] = ldu(x1p, u.y0 + 2 + i, yend + 1, ox[i]);
+      c2[i] = ldu(x2p, u.y0 + 2 + i, yend + 1, ox[i]);
     }
-    pair_row(ra1, ra2, v); window_row2(v, first, last, hA);
-    pair_row(rb1, rb2, v); window_row2(v, first, last, hB);
-    d_row(u.y0 - 1, g0, rc1, rc2, p0); h_shift();
-    d_row(u.y0, g1, rd1, rd2, p1); h_shift();
+    pair_row(ra1, ra2, v); window_row2(v, first, last, hw[1]);
+    pair_row(rb1, rb2, v); window_row2(v, first, last, hw[2]);
+    d_row(g0, rc1, rc2, hw[1], hw[2], hw[0], pw[0]);     // d row y0-1, x row y0
+    d_row(g1, rd1, rd2, hw[2], hw[0], hw[1], pw[1]);     // d row y0,   x row y0+1
   }
-  T* o1p = a.out ? (T*)a.out + ((int64_t)b * a.Cc + j) * HW + x : nullptr;
+  T* o1p = a.out ? (T*)a.out + ((int64_t)b * a.Cc + j) * HW : nullptr;
   T* o2p = o1p ? o1p + (int64_t)h * HW : nullptr;
-  for (int yy = 0; yy < band_rows; yy += PFG) {
-#pragma unroll
-    for (int i = 0; i < PFG; ++i) {
-      const int y = u.y0 + yy + i;
-      const bool st = u.active && y < yend;
-      // now hA = x row y, hB = x row y+1; the raw slots hold dg row y+1 and x row y+2
-      d_row(y + 1, cg[i], c1[i], c2[i], p2);
-      cg[i] = ld(dgp, y + PFG + 1, yend); c1[i] = ld(x1p, y + PFG + 2, yend + 1); c2[i] = ld(x2p, y + PFG + 2, yend + 1);
-      if (o1p) {
-        f32x2 o[4];
-        stencil2<true>(w, zero2, p0, p1, p2, o);
-        if (st) {
-          float oa[4] = {o[0][0], o[1][0], o[2][0], o[3][0]}, ob[4] = {o[0][1], o[1][1], o[2][1], o[3][1]};
-          store4<DWS_NT>(o1p + (int64_t)y * a.W, oa);
-          store4<DWS_NT>(o2p + (int64_t)y * a.W, ob);
-        }
+  // output row y at phase k: hw[k] = x row y, hw[k+1] = x row y+1, pw[k] = d row y-1, pw[k+1] = d row y; slot k holds dg
+  // row y+1 and x row y+2, which become pw[k+2] and hw[k+2]
+  auto out_row = [&](auto ph, int y) {
+    constexpr int k = decltype(ph)::k, k1 = (k + 1) % 3, k2 = (k + 2) % 3;
+    const bool live = LPR == 64 || y < yend;          // a wave of several bands runs the rows of its tallest
+    const bool st = u.active && live;
+    d_row(use(og[k], cg[k]), use(ox[k], c1[k]), use(ox[k], c2[k]), hw[k], hw[k1], hw[k2], pw[k2]);
+    cg[k] = ldu(dgp, y + PFR + 1, yend, og[k]); c1[k] = ldu(x1p, y + PFR + 2, yend + 1, ox[k]); c2[k] = ldu(x2p, y + PFR + 2, yend + 1, ox[k]);
+    if (o1p) {
+      f32x2 o[4];
+      stencil2<true>(w, zero2, pw[k], pw[k1], pw[k2], o);
+      if (st) {
+        float oa[4] = {o[0][0], o[1][0], o[2][0], o[3][0]}, ob[4] = {o[0][1], o[1][1], o[2][1], o[3][1]};
+        store4<DWS_NT>((T*)at(o1p, y), oa);
+        store4<DWS_NT>((T*)at(o2p, y), ob);
       }
-      if (WANT_DW && y < yend) wgrad_row2(&hA[1], p0, p1, p2, acc);    // x row y, own 4 pixels
-      h_shift();
-      copy6x2(p0, p1); copy6x2(p1, p2);
+    }
+    if (WANT_DW && live) wgrad_row2(&hw[k][1], pw[k], pw[k1], pw[k2], acc);    // x row y, own 4 pixels
+    // pin the sums to this row: left alone, the three rows' accumulation sinks to the end of the loop body, the windows
+    // stay alive across it and 14 register pairs are copied at the back edge (172 VGPRs at 256-pixel rows).  This and the
+    // two loop forms below steer one compiler version: after a compiler update re-check NumVgprs and the v_mov_b64 count of
+    // the row loop in `hipcc -O3 -S` of this file against profiles/gate_bwd_rc_valu.txt.
+    if (WANT_DW && UNI) {
+#pragma unroll
+      for (int i = 0; i < 10; ++i) asm volatile("" : "+v"(acc[i]));
+    }
+  };
+  // rows of this wave: its band's when the wave has one band, else a whole band (or the whole image, if shorter)
+  const int nrow = LPR == 64 ? yend - u.y0 : min(band_rows, a.H);
+  // One exit and the last rows written out where the wave is UNI; a loop that leaves after any phase elsewhere: each is the
+  // form that takes the fewest registers there (counts per instantiation: profiles/gate_bwd_rc_valu.txt)
+  if constexpr (UNI) {
+    int yy = 0;
+    for (; yy + 3 <= nrow; yy += 3) {
+      out_row(Phase<0>(), u.y0 + yy);
+      out_row(Phase<1>(), u.y0 + yy + 1);
+      out_row(Phase<2>(), u.y0 + yy + 2);
+    }
+    if (yy < nrow) {
+      out_row(Phase<0>(), u.y0 + yy);
+      if (yy + 1 < nrow) out_row(Phase<1>(), u.y0 + yy + 1);
+    }
+  } else {
+    for (int yy = 0; yy < nrow; yy += 3) {
+      out_row(Phase<0>(), u.y0 + yy);
+      if (yy + 1 >= nrow) break;
+      out_row(Phase<1>(), u.y0 + yy + 1);
+      if (yy + 2 >= nrow) break;
+      out_row(Phase<2>(), u.y0 + yy + 2);
     }
   }
   if (WANT_DW) {

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Per-shape kernel microbenchmarks (run on the GPU box): python tools/bench_kernels.py [pw|ln|dw|gram]
+"""Per-shape kernel microbenchmarks (run on the GPU box): python tools/bench_kernels.py [pw|ln|dw|gate|gram|dqk]
 Times each call with HIP events on the current stream, prints algorithmic GB/s."""
 import os
 import subprocess
@@ -89,6 +89,26 @@ def bench_dw():
             print(f"dw_gate_fwd(no y) C={C} {H}x{W}: {us:8.1f} us {1.5 * x.numel() * 2 / us / 1e3:7.0f} GB/s", flush=True)
 
 
+def bench_gate():
+    """The recomputing gate backward beside dwconv_bwd (its nearest HBM-bound sibling) on the planes of the bs-32 step; GB/s by
+    the bytes each really moves (2.5 and 3 passes over the 2h-channel tensor; dy and x are distinct tensors)."""
+    from image_restoration_amd import ops
+    B = int(os.environ.get("BK_BATCH", "8"))
+    for (C, H, W) in [(510, 256, 256), (254, 256, 256), (510, 128, 128), (1020, 64, 64), (2042, 32, 32)]:
+        x = torch.randn(B, C, H, W, device="cuda").bfloat16()
+        dy = torch.randn_like(x)
+        w = torch.randn(C, 1, 3, 3, device="cuda")
+        bias = torch.randn(C, device="cuda")
+        dg = x[:, : C // 2].contiguous()
+        pl = ops.dwconv_plan(B, C, H, W, 3, "gate_bwd")
+        us_b = timeit(lambda: ops.dwconv_bwd(dy, x, w, False))
+        us_g = timeit(lambda: ops.dwconv_gate_bwd_recompute(dg, x, w, bias))
+        gb_b, gb_g = 3 * x.numel() * 2 / us_b / 1e3, 2.5 * x.numel() * 2 / us_g / 1e3
+        print(f"2h={C} {H}x{W} band={pl['band']} uni={pl['uni']}: gate_bwd_rc {us_g:8.1f} us {gb_g:6.0f} GB/s | dwconv_bwd "
+              f"{us_b:8.1f} us {gb_b:6.0f} GB/s | ratio {gb_g / gb_b:.3f}", flush=True)
+        del x, dy, dg
+
+
 def bench_gram():
     from image_restoration_amd import ops
     for (ma, mb, H, W, g, sb) in [(48, 48, 256, 256, 1, False), (96, 96, 256, 256, 1, False), (144, 48, 256, 256, 1, True),
@@ -143,5 +163,5 @@ def bench_dqk():
 if __name__ == "__main__":
     which = sys.argv[1:] or ["pw", "ln", "dw", "gram"]
     for wname in which:
-        {"pw": bench_pw, "ln": bench_ln, "dw": bench_dw, "gram": bench_gram, "dqk": bench_dqk}[wname]()
+        {"pw": bench_pw, "ln": bench_ln, "dw": bench_dw, "gate": bench_gate, "gram": bench_gram, "dqk": bench_dqk}[wname]()
 
