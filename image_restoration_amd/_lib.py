@@ -186,6 +186,10 @@ class DblockGrads(C.Structure):
     _fields_ = [(n, fp * k) if k > 1 else (n, fp) for n, k in DBLOCK_FIELDS] + [("accumulate", C.c_int)]
 
 
+class FremlpShape(C.Structure):
+    _fields_ = [("B", C.c_int), ("nc", C.c_int), ("expand", C.c_int), ("H", C.c_int), ("W", C.c_int), ("dtype", C.c_int)]
+
+
 # symbol -> (restype, argtypes); this table is also what tests/test_cabi.py checks against the header
 SIGNATURES = {
     "mi_version": (C.c_int, []),
@@ -372,6 +376,14 @@ SIGNATURES = {
     "mi_fft_l1_workspace": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "mi_fft_l1_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(c_i64)]),
     "mi_fft_l1_loss": (C.c_int, [vp, vp, vp, fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, vp, vp]),
+    "mi_dft2_workspace": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    "mi_dft2_r2c": (C.c_int, [vp, fp, fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]),
+    "mi_dft2_c2r": (C.c_int, [fp, fp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]),
+    "mi_fremlp_workspace": (C.c_size_t, [C.POINTER(FremlpShape)]),
+    "mi_fremlp_saved_bytes": (C.c_size_t, [C.POINTER(FremlpShape)]),
+    "mi_fremlp_plan": (C.c_int, [C.POINTER(FremlpShape), C.POINTER(c_i64)]),
+    "mi_fremlp_fwd": (C.c_int, [C.POINTER(FremlpShape), fp, fp, fp, fp, vp, vp, vp, vp, vp]),
+    "mi_fremlp_bwd": (C.c_int, [C.POINTER(FremlpShape), fp, fp, fp, vp, vp, fp, fp, fp, fp, C.c_int, vp, vp, vp]),
     "mi_ssim_loss_workspace": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "mi_ssim_loss": (C.c_int, [vp, vp, vp, fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, vp, vp]),
     "mi_edge_loss_workspace": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),

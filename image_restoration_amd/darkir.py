@@ -1,5 +1,6 @@
-"""Drop-in replacement for DarkIR's dilated-gate decoder block (``DarkIR-main/archs/arch_model.py``: ``DBlock`` :72-139 with
-``SimpleGate`` :12-15 and ``Branch`` :57-70; ``archs/arch_util.py``: ``LayerNorm2d`` :35-44).
+"""Drop-in replacements for DarkIR's dilated-gate decoder block and its frequency MLP (``DarkIR-main/archs/arch_model.py``:
+``DBlock`` :72-139 with ``SimpleGate`` :12-15 and ``Branch`` :57-70, ``FreMLP`` :36-55; ``archs/arch_util.py``: ``LayerNorm2d``
+:35-44).
 
 The classes keep the reference's names, constructor signatures, parameter names and shapes (``state_dict`` interchangeable) and
 ``forward`` signatures; ``DBlock.forward`` runs the gfx950 kernels through the C-ABI (``mi_dblock_*``: the multi-dilation
@@ -12,7 +13,12 @@ over channels with a biased variance and ``eps = 1e-6`` (the other families' Lay
 :mod:`image_restoration_amd.restormer`.  CPU tensors are refused: there is no fallback.
 
 The kernels were built for ``DW_Expand = FFN_Expand = 2``, one to four branches with dilations 1..16 and c <= 256; anything else
-raises ``NotImplementedError``.  ``EBlock`` (with ``FreMLP``) and the whole ``DarkIR`` network are not part of this module yet.
+raises ``NotImplementedError``.
+
+``FreMLP.forward`` is one autograd node too (``mi_fremlp_*``): ``rfft2`` and ``irfft2`` as dense-DFT GEMMs on the fp32 MFMA (no
+FFT library), the polar form as ``|Z|`` and ``Z / |Z|`` (no ``atan2``, ``cos`` or ``sin``), the two 1x1 convs of ``process1`` per
+frequency bin in fp32.  Planes of 2..512 pixels a side, ``nc <= 256``, ``expand * nc <= 512``; larger images need tiling or a
+factored DFT, which is not built.  ``EBlock`` and the whole ``DarkIR`` network are not part of this module yet.
 """
 from __future__ import annotations
 
@@ -24,7 +30,7 @@ from ._autograd import module_op
 
 Tensor = torch.Tensor
 
-__all__ = ["SimpleGate", "LayerNorm2d", "Branch", "DBlock"]
+__all__ = ["SimpleGate", "LayerNorm2d", "Branch", "DBlock", "FreMLP"]
 
 LN_EPS = 1e-6
 
@@ -169,3 +175,38 @@ class DBlock(nn.Module):
             raise NotImplementedError(f"image_restoration_amd: DBlock's LayerNorm2d runs with eps = {LN_EPS} (the value the block "
                                       "kernels were built for)")
         return module_op(_DBlockOp(self._dilations, self._extra), (inp,), self._params())
+
+
+class _FreMlpOp:
+    """FreMLP.forward as one module op.  params: process1's two weights and biases; saved = [the kernels' blob]."""
+
+    def forward(self, acts, params, need):
+        out, blob = ops.fremlp_fwd(acts[0], params, need)
+        return out, [blob]
+
+    def backward(self, acts, saved, dout, params, grads, acc):
+        return (ops.fremlp_bwd(dout, params, saved[0], grads, acc),)
+
+
+class FreMLP(nn.Module):
+    """irfft2(process1(|Z|) * Z / |Z|), Z = rfft2(x) (arch_model.py:36-55), one autograd node.  ``process1`` holds the
+    parameters (a DarkIR checkpoint loads unchanged); its LeakyReLU(0.1) runs inside the kernels."""
+
+    def __init__(self, nc, expand=2):
+        super().__init__()
+        if not (isinstance(nc, int) and isinstance(expand, int) and 1 <= nc <= ops.FREMLP_MAX_NC and expand >= 1 and
+                expand * nc <= ops.FREMLP_MAX_HIDDEN):
+            raise NotImplementedError(f"image_restoration_amd: FreMLP(nc={nc!r}, expand={expand!r}) not covered; the kernels were "
+                                      f"built for 1 <= nc <= {ops.FREMLP_MAX_NC}, expand >= 1, expand * nc <= "
+                                      f"{ops.FREMLP_MAX_HIDDEN}")
+        self.process1 = nn.Sequential(
+            nn.Conv2d(nc, expand * nc, 1, 1, 0),
+            nn.LeakyReLU(0.1, inplace=True),
+            nn.Conv2d(expand * nc, nc, 1, 1, 0))
+
+    def forward(self, x):
+        if self.process1[1].negative_slope != 0.1:
+            raise NotImplementedError("image_restoration_amd: FreMLP's LeakyReLU runs with slope 0.1 (the value the kernels were "
+                                      "built for)")
+        c1, c2 = self.process1[0], self.process1[2]
+        return module_op(_FreMlpOp(), (x,), (c1.weight, c1.bias, c2.weight, c2.bias))

@@ -946,6 +946,122 @@ def dblock_bwd(x: Tensor, dout: Tensor, params: Sequence[Optional[Tensor]], dila
     return dx
 
 
+# ----------------------------------------------------------------------------- DarkIR: FreMLP and the real 2-D transforms
+FREMLP_MAX_HW, FREMLP_MAX_NC, FREMLP_MAX_HIDDEN = 512, 256, 512
+_FREMLP_PLAN_KEYS = ("planes", "K", "hidden", "tile_m", "tile_k", "l_block", "l_blocks", "x_block", "x_blocks", "m_tiles_folded",
+                     "m_tiles_plane", "grid_tables", "grid_rows_k", "grid_planes", "grid_rows_w", "grid_bins", "grid_hidden", "block",
+                     "kernels_fwd", "kernels_bwd", "lib_calls_fwd", "lib_calls_bwd")
+_FREMLP_SECTIONS = ("cos_w", "sin_w", "cos_wt", "sin_wt", "wcos_w", "wsin_w", "wcos_wt", "wsin_wt", "cos_h", "sin_h", "T", "U", "Z",
+                    "hidden", "m1", "m2", "pw_ws", "gram_ws", "chan_sum_ws")
+
+
+def _fremlp_shape(B: int, nc: int, expand: int, H: int, W: int, dtype_code: int) -> L.FremlpShape:
+    return L.FremlpShape(B, nc, expand, H, W, dtype_code)
+
+
+def fremlp_plan(B: int, nc: int, expand: int, H: int, W: int, dtype: torch.dtype = torch.float32) -> dict:
+    """What fremlp_fwd / fremlp_bwd launch for x [B, nc, H, W] (mi_fremlp_plan: the plan the launchers follow; no GPU work).
+    ``sections`` maps each workspace section to its (byte offset, bytes)."""
+    out = (L.c_i64 * 64)()
+    s = _fremlp_shape(B, nc, expand, H, W, _dtype_code(dtype))
+    L.check(L.lib().mi_fremlp_plan(C.byref(s), out), "fremlp_plan")
+    plan = {k: int(out[i]) for i, k in enumerate(_FREMLP_PLAN_KEYS)}
+    plan["sections"] = {n: (int(out[22 + 2 * i]), int(out[23 + 2 * i])) for i, n in enumerate(_FREMLP_SECTIONS)}
+    plan["workspace"], plan["saved_bytes"], plan["saved_hidden_offset"] = int(out[60]), int(out[61]), int(out[62])
+    return plan
+
+
+def fremlp_sizes(B: int, nc: int, expand: int, H: int, W: int, dtype: torch.dtype) -> Tuple[int, int]:
+    """(saved bytes, workspace bytes) of one FreMLP; (0, 0) for a shape the kernels do not cover.  No GPU needed."""
+    s = _fremlp_shape(B, nc, expand, H, W, _dtype_code(dtype))
+    return int(L.lib().mi_fremlp_saved_bytes(C.byref(s))), int(L.lib().mi_fremlp_workspace(C.byref(s)))
+
+
+def _fremlp_args(x: Tensor, params: Sequence[Tensor]):
+    w1, b1, w2, b2 = params
+    if x.dim() != 4:
+        raise ValueError(f"fremlp: x must be [B, nc, H, W], got {tuple(x.shape)}")
+    B, nc, H, W = x.shape
+    hc = w1.shape[0]
+    if hc % nc or tuple(w1.shape[:2]) != (hc, nc) or tuple(w2.shape[:2]) != (nc, hc) or b1.numel() != hc or b2.numel() != nc:
+        raise ValueError(f"fremlp: parameters {tuple(w1.shape)}, {tuple(b1.shape)}, {tuple(w2.shape)}, {tuple(b2.shape)} do not "
+                         f"fit nc = {nc}")
+    s = _fremlp_shape(B, nc, hc // nc, H, W, _dt(x))
+    ws_bytes = L.lib().mi_fremlp_workspace(C.byref(s))
+    if ws_bytes == 0:
+        raise NotImplementedError("image_restoration_amd: " + L.lib().mi_last_error().decode("utf-8", "replace"))
+    return s, ws_bytes
+
+
+def fremlp_fwd(x: Tensor, params: Sequence[Tensor], need_saved: bool):
+    """DarkIR FreMLP.forward: irfft2(MLP(|rfft2 x|) * rfft2 x / |rfft2 x|).  params: W1 [e nc, nc(, 1, 1)], b1, W2 [nc, e nc(, 1, 1)],
+    b2 (fp32).  -> (out, saved)."""
+    _gpu(x, *params)
+    for t in params:
+        _f32(t, "FreMLP parameter")
+    s, ws_bytes = _fremlp_args(x, params)
+    lib = L.lib()
+    out = torch.empty_like(x)
+    saved = _blob(lib.mi_fremlp_saved_bytes(C.byref(s)), x.device) if need_saved else None
+    ws = _ws(ws_bytes, x.device)
+    w1, b1, w2, b2 = params
+    L.check(lib.mi_fremlp_fwd(C.byref(s), _p(w1), _p(b1), _p(w2), _p(b2), _p(x), _p(out), _p(saved), _p(ws), _stream()), "fremlp_fwd")
+    return out, saved
+
+
+def fremlp_bwd(dout: Tensor, params: Sequence[Tensor], saved: Tensor, grads: Sequence[Tensor], accumulate: bool) -> Tensor:
+    """Backward of fremlp_fwd: dx; the four parameter gradients are written (accumulate: added) into ``grads``."""
+    _gpu(dout, saved, *params, *grads)
+    for t in (*params, *grads):
+        _f32(t, "FreMLP parameter / gradient")
+    s, ws_bytes = _fremlp_args(dout, params)
+    lib = L.lib()
+    dx = torch.empty_like(dout)
+    ws = _ws(ws_bytes, dout.device)
+    w1, _, w2, b2 = params
+    L.check(lib.mi_fremlp_bwd(C.byref(s), _p(w1), _p(w2), _p(b2), _p(dout), _p(dx), *[_p(g) for g in grads], int(accumulate),
+                              _p(saved), _p(ws), _stream()), "fremlp_bwd")
+    return dx
+
+
+def _dft2_ws(who: str, B: int, Cc: int, H: int, W: int, device) -> Tensor:
+    n = L.lib().mi_dft2_workspace(B, Cc, H, W)
+    if n == 0:
+        raise NotImplementedError(f"image_restoration_amd: {who}: [{B}, {Cc}, {H}, {W}] not covered; the dense-DFT kernels take "
+                                  f"2 <= H, W <= {FREMLP_MAX_HW}")
+    return _ws(n, device)
+
+
+def dft2_r2c(x: Tensor):
+    """rfft2 of x [B, C, H, W] (fp32 or bf16) as dense-DFT GEMMs (mi_dft2_r2c) -> (Re Z, Im Z), fp32 [B, C, H, W/2 + 1]."""
+    _gpu(x)
+    if x.dim() != 4:
+        raise ValueError(f"dft2_r2c: x must be [B, C, H, W], got {tuple(x.shape)}")
+    B, Cc, H, W = x.shape
+    dt = _dt(x)
+    ws = _dft2_ws("dft2_r2c", B, Cc, H, W, x.device)
+    zre = torch.empty(B, Cc, H, W // 2 + 1, dtype=torch.float32, device=x.device)
+    zim = torch.empty_like(zre)
+    L.check(L.lib().mi_dft2_r2c(_p(x), _p(zre), _p(zim), B, Cc, H, W, dt, _p(ws), _stream()), "dft2_r2c")
+    return zre, zim
+
+
+def dft2_c2r(yre: Tensor, yim: Tensor, W: int, dtype: torch.dtype = torch.float32) -> Tensor:
+    """irfft2(yre + i yim, s=(H, W), norm='backward') of fp32 [B, C, H, W/2 + 1] halves (mi_dft2_c2r) -> [B, C, H, W] in ``dtype``."""
+    _gpu(yre, yim)
+    _f32(yre, "dft2_c2r input")
+    _f32(yim, "dft2_c2r input")
+    if yre.dim() != 4 or yre.shape != yim.shape or yre.shape[3] != W // 2 + 1:
+        raise ValueError(f"dft2_c2r: the halves must be [B, C, H, {W // 2 + 1}] for W = {W}, got {tuple(yre.shape)} and "
+                         f"{tuple(yim.shape)}")
+    B, Cc, H, _ = yre.shape
+    dt = _dtype_code(dtype)
+    ws = _dft2_ws("dft2_c2r", B, Cc, H, W, yre.device)
+    out = torch.empty(B, Cc, H, W, dtype=dtype, device=yre.device)
+    L.check(L.lib().mi_dft2_c2r(_p(yre), _p(yim), _p(out), B, Cc, H, W, dt, _p(ws), _stream()), "dft2_c2r")
+    return out
+
+
 # ----------------------------------------------------------------------------- DRSformer: MEFC (one OALayer + GroupOLs pair)
 MEFC_STEP_PARAMS = 23     # per OperationLayer: SepConv k = 1, 3, 5, 7 (op.0, op.1, op.3, op.4), DilConv k = 3, 5, 7 (op.0, op.1), _out.0
 

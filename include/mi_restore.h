@@ -873,6 +873,53 @@ int mi_fft_l1_loss(const void* pred, const void* target, void* dpred, float* los
                    float loss_weight, int dtype, void* ws, void* stream);
 
 /* ------------------------------------------------------------------------
+ * The real 2-D transforms on their own and DarkIR's FreMLP (DarkIR-main/archs/arch_model.py:36-55), without an FFT library
+ * (csrc/fremlp.hip): the dense-DFT GEMMs of the FFT loss, fp32 between the input load and the output store.  K = W/2 + 1.
+ *   mi_dft2_r2c   x [B,C,H,W] in `dtype` -> Re Z, Im Z [B,C,H,K] fp32,  Z = rfft2(x):
+ *                 Z[k,l] = sum_y sum_x x[y,x] exp(-2 pi i (k y / H + l x / W)).
+ *   mi_dft2_c2r   Re Y, Im Y [B,C,H,K] fp32 -> out [B,C,H,W] in `dtype` (rounded once):
+ *                 out[y,x] = 1/(HW) sum_l w_l Re( exp(+2 pi i l x / W) sum_k exp(+2 pi i k y / H) Y[k,l] ),
+ *                 w_l = 1 at l = 0 and, for even W, at l = W/2 (odd W has no Nyquist column), 2 at every other l.  This IS
+ *                 irfft2(Y, s=(H,W), norm='backward') for ANY Y: the imaginary parts that a c2r transform drops in the edge
+ *                 columns are dropped here by the same formula; no Hermitian fix-up is needed or made.
+ *   ws: mi_dft2_workspace() bytes serve both (twiddle tables and one complex intermediate, rebuilt each call).
+ *
+ *   FreMLP        Z = rfft2(x);  mag = sqrt(Re Z^2 + Im Z^2);  u = Z / mag, and u = (1, 0) where mag == 0 (torch.angle(0) = 0);
+ *                 mag' = W2 LeakyReLU_0.1(W1 mag + b1) + b2 over the nc channels of each frequency bin
+ *                 (W1 [expand nc, nc], W2 [nc, expand nc], both biases required);  out = irfft2(mag' u, s=(H,W)).
+ *                 No atan2, cos or sin of data is taken.  x, out, dout, dx in `dtype` (widened on load, rounded once on store);
+ *                 spectra, the MLP, the saved blob, parameters and their gradients fp32.
+ *   backward      G = the adjoint of c2r applied to dout;  dmag' = G . u (real dot product),  du = mag' G;  the MLP backward
+ *                 gives dmag, dW1, db1, dW2, db2;  dZ = dmag u + (du - u (u . du)) / mag, and dZ = 0 where mag == 0 (abs and
+ *                 angle have zero gradient there);  dx = the adjoint of r2c applied to dZ (real, no column doubling).
+ *                 accumulate: the four parameter gradients are added to (1) or overwritten (0), as in mi_dblock_bwd.
+ *   saved         mi_fremlp_saved_bytes(): Z and the hidden activations, fp32 ((2 + expand) floats per bin and channel); mag, u
+ *                 and mag' are recomputed.  saved == NULL in mi_fremlp_fwd: inference, nothing is kept.
+ * Limits: 2 <= H, W <= 512 (larger images need tiling or a factored DFT: not built), 1 <= nc <= 256, expand >= 1 with
+ * expand nc <= 512, any B >= 1 (B nc H K and B expand nc H K below 2^31).  Anything else is refused before any launch; the
+ * sizing calls return 0.  Bitwise reproducible (no atomics, fixed-order sums).  No allocation, no host synchronisation.
+ * mi_fremlp_plan (host-only; the launchers and the sizing calls read the same plan) fills out[64]: planes B nc, K, hidden width,
+ * tile rows, contraction depth per LDS stage, l block width, l blocks, x block width, x blocks, 64-row tiles over B nc H, 64-row
+ * tiles over H, grids of the table fill, of the [B nc H] x K stages, of the per-plane stages, of the [B nc H] x W stages, of the
+ * per-bin passes, of the hidden passes, threads per workgroup, own kernel launches forward / backward, library calls (1x1
+ * product, Gram, channel sum) forward / backward; then (byte offset, bytes) of the 19 workspace sections: cos W, sin W, their
+ * transposes, the same four with w_l folded in, cos H, sin H, two complex intermediates, Z and the hidden plane (used when
+ * nothing is saved; the hidden plane also holds the hidden gradient), two real planes, the 1x1 / Gram / channel-sum
+ * workspaces [22..59]; the workspace size [60], the saved blob's size [61], the offset of the hidden activations in it [62]; 0.
+ * ------------------------------------------------------------------------ */
+typedef struct { int B, nc, expand, H, W, dtype; } mi_fremlp_shape;
+size_t mi_dft2_workspace(int B, int C, int H, int W);
+int mi_dft2_r2c(const void* x, float* zre, float* zim, int B, int C, int H, int W, int dtype, void* ws, void* stream);
+int mi_dft2_c2r(const float* yre, const float* yim, void* out, int B, int C, int H, int W, int dtype, void* ws, void* stream);
+size_t mi_fremlp_workspace(const mi_fremlp_shape* s);
+size_t mi_fremlp_saved_bytes(const mi_fremlp_shape* s);
+int mi_fremlp_plan(const mi_fremlp_shape* s, int64_t* out);
+int mi_fremlp_fwd(const mi_fremlp_shape* s, const float* w1, const float* b1, const float* w2, const float* b2, const void* x,
+                  void* out, void* saved, void* ws, void* stream);
+int mi_fremlp_bwd(const mi_fremlp_shape* s, const float* w1, const float* w2, const float* b2, const void* dout, void* dx,
+                  float* g_w1, float* g_b1, float* g_w2, float* g_b2, int accumulate, const void* saved, void* ws, void* stream);
+
+/* ------------------------------------------------------------------------
  * The other pixel-space loss terms of the reference's training steps (csrc/losses.hip), each with d loss / d pred from the same
  * call.  Conventions of mi_fft_l1_loss: fp32 arithmetic on inputs widened on load; dpred written in `dtype`, rounded once, NULL
  * skips every gradient stage; loss is device fp32 and overwritten; ws holds the matching *_workspace() bytes; no atomics,
