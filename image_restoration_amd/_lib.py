@@ -190,6 +190,24 @@ class FremlpShape(C.Structure):
     _fields_ = [("B", C.c_int), ("nc", C.c_int), ("expand", C.c_int), ("H", C.c_int), ("W", C.c_int), ("dtype", C.c_int)]
 
 
+class EblockShape(C.Structure):
+    _fields_ = DblockShape._fields_
+
+
+# mi_eblock_params / mi_eblock_grads in field order; (name, 4): one pointer per branch
+EBLOCK_FIELDS = (("norm1_w", 1), ("norm1_b", 1), ("extra_w", 1), ("extra_b", 1), ("conv1_w", 1), ("conv1_b", 1), ("br_w", 4), ("br_b", 4),
+                 ("sca_w", 1), ("sca_b", 1), ("conv3_w", 1), ("conv3_b", 1), ("beta", 1), ("norm2_w", 1), ("norm2_b", 1),
+                 ("fre_w1", 1), ("fre_b1", 1), ("fre_w2", 1), ("fre_b2", 1), ("gamma", 1))
+
+
+class EblockParams(C.Structure):
+    _fields_ = [(n, fp * k) if k > 1 else (n, fp) for n, k in EBLOCK_FIELDS]
+
+
+class EblockGrads(C.Structure):
+    _fields_ = [(n, fp * k) if k > 1 else (n, fp) for n, k in EBLOCK_FIELDS] + [("accumulate", C.c_int)]
+
+
 # symbol -> (restype, argtypes); this table is also what tests/test_cabi.py checks against the header
 SIGNATURES = {
     "mi_version": (C.c_int, []),
@@ -384,6 +402,14 @@ SIGNATURES = {
     "mi_fremlp_plan": (C.c_int, [C.POINTER(FremlpShape), C.POINTER(c_i64)]),
     "mi_fremlp_fwd": (C.c_int, [C.POINTER(FremlpShape), fp, fp, fp, fp, vp, vp, vp, vp, vp]),
     "mi_fremlp_bwd": (C.c_int, [C.POINTER(FremlpShape), fp, fp, fp, vp, vp, fp, fp, fp, fp, C.c_int, vp, vp, vp]),
+    "mi_fregate_fwd": (C.c_int, [vp, vp, fp, vp, C.c_int, C.c_int, c_i64, C.c_int, vp]),
+    "mi_fregate_bwd_workspace": (C.c_size_t, [C.c_int, C.c_int, c_i64]),
+    "mi_fregate_bwd": (C.c_int, [vp, vp, vp, fp, vp, vp, fp, C.c_int, C.c_int, c_i64, C.c_int, C.c_int, vp, vp]),
+    "mi_eblock_saved_bytes": (C.c_size_t, [C.POINTER(EblockShape)]),
+    "mi_eblock_workspace": (C.c_size_t, [C.POINTER(EblockShape)]),
+    "mi_eblock_plan": (C.c_int, [C.POINTER(EblockShape), C.POINTER(c_i64)]),
+    "mi_eblock_fwd": (C.c_int, [C.POINTER(EblockShape), C.POINTER(EblockParams), vp, vp, vp, vp, vp]),
+    "mi_eblock_bwd": (C.c_int, [C.POINTER(EblockShape), C.POINTER(EblockParams), vp, vp, vp, C.POINTER(EblockGrads), vp, vp, vp]),
     "mi_ssim_loss_workspace": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "mi_ssim_loss": (C.c_int, [vp, vp, vp, fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, vp, vp]),
     "mi_edge_loss_workspace": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),

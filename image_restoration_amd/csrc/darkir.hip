@@ -16,6 +16,8 @@
 // The c x c folds: M[b] = diag(beta) W3 diag(s[b]) (and diag(gamma) W5) feed ONE per-image mi_pw_gemm each with the residual in
 // its epilogue; their backward starts from the per-image Gram dY g^T (mi_gram, sum_batch = 0) and per-image channel sums of dY.
 // With bf16 activations the 1x1 products run on split weights ([hi | lo] . [x ; x], dk_split_kernel): see there.
+// The encoder block (EBlock, arch_model.py:141-204; mi_eblock_*) is a launch sequence over the same pieces with a plain depthwise
+// extra_conv in front of conv1, mi_fremlp_* behind norm2, and its own streaming tail out = y (1 + gamma f) (mi_fregate_*).
 #include "internal.h"
 
 namespace mi {
@@ -744,6 +746,252 @@ static int db_conv_bwd(const void* dy, int M, const void* x, int K, const float*
   return mi_pw_gemm(&d, pw_ws, st);
 }
 
+// ------------------------------------------------------------------ EBlock's tail: out = y (1 + gamma f)
+// Streaming kernels, grid (S, C, B): the workgroups (.., c, b) share plane (b, c), whose N elements are a scalar head up to the first
+// 16-byte boundary (`a0`: the element offset of the tensors' base inside its 16-byte line, the same for every tensor of a call),
+// nv vectors of V elements dealt to the S workgroups in turn (vector v to workgroup v / 256 mod S), and a scalar tail; workgroup 0
+// takes head and tail.  gamma[c] is one scalar load per workgroup: no index arithmetic per element.
+constexpr int FG_ITER = 4, FG_MAX_S = 64;
+template <typename T> struct FgVec { static constexpr int V = 16 / sizeof(T); };
+struct FgSpan { int64_t base; int head, tail; int64_t nv; };
+template <int V>
+__device__ __forceinline__ FgSpan fg_span(int64_t plane, int64_t N, int a0) {
+  FgSpan s;
+  s.base = plane * N;
+  const int mis = (int)((s.base + a0) % V);
+  const int64_t h = mis ? V - mis : 0;
+  s.head = (int)(h < N ? h : N);
+  s.nv = (N - s.head) / V;
+  s.tail = (int)(N - s.head - s.nv * V);
+  return s;
+}
+static int fg_slices(int64_t N, int dtype) { return cdiv_cap(N, (int64_t)256 * (16 / dtype_size(dtype)) * FG_ITER, FG_MAX_S); }
+
+template <typename T, int V>
+__global__ __launch_bounds__(256) void fregate_fwd_kernel(const T* __restrict__ y, const T* __restrict__ f, const float* __restrict__ gamma,
+                                                          T* __restrict__ out, int64_t N, int a0) {
+  const int c = blockIdx.y, C = gridDim.y;
+  const FgSpan sp = fg_span<V>((int64_t)blockIdx.z * C + c, N, a0);
+  const float gm = gamma[c];
+  const int64_t body = sp.base + sp.head;
+  for (int64_t v = (int64_t)blockIdx.x * 256 + threadIdx.x; v < sp.nv; v += (int64_t)gridDim.x * 256) {
+    float yy[V], ff[V], o[V];
+    Vec<T, V>::ld(y + body + v * V, yy);
+    Vec<T, V>::ld(f + body + v * V, ff);
+#pragma unroll
+    for (int i = 0; i < V; ++i) o[i] = yy[i] * fmaf(gm, ff[i], 1.0f);
+    Vec<T, V>::st(out + body + v * V, o);
+  }
+  if (blockIdx.x == 0 && (int)threadIdx.x < sp.head + sp.tail) {
+    const int t = threadIdx.x;
+    const int64_t e = sp.base + (t < sp.head ? t : sp.head + sp.nv * V + (t - sp.head));
+    st1(out + e, ld1(y + e) * fmaf(gm, ld1(f + e), 1.0f));
+  }
+}
+
+// part[(b S + blockIdx.x) C + c] = this workgroup's share of sum_p dout y f (its threads' sums, then the 4 waves in order)
+template <typename T, int V>
+__global__ __launch_bounds__(256) void fregate_bwd_kernel(const T* __restrict__ dout, const T* __restrict__ y, const T* __restrict__ f,
+                                                          const float* __restrict__ gamma, T* __restrict__ df, T* __restrict__ dyr,
+                                                          float* __restrict__ part, int64_t N, int a0) {
+  __shared__ float red[4];
+  const int c = blockIdx.y, C = gridDim.y;
+  const FgSpan sp = fg_span<V>((int64_t)blockIdx.z * C + c, N, a0);
+  const float gm = gamma[c];
+  const int64_t body = sp.base + sp.head;
+  float acc = 0.f;
+  for (int64_t v = (int64_t)blockIdx.x * 256 + threadIdx.x; v < sp.nv; v += (int64_t)gridDim.x * 256) {
+    float dd[V], yy[V], ff[V], o1[V], o2[V];
+    Vec<T, V>::ld(dout + body + v * V, dd);
+    Vec<T, V>::ld(y + body + v * V, yy);
+    Vec<T, V>::ld(f + body + v * V, ff);
+#pragma unroll
+    for (int i = 0; i < V; ++i) {
+      o1[i] = (dd[i] * gm) * yy[i];
+      o2[i] = dd[i] * fmaf(gm, ff[i], 1.0f);
+      acc = fmaf(dd[i] * yy[i], ff[i], acc);
+    }
+    Vec<T, V>::st(df + body + v * V, o1);
+    Vec<T, V>::st(dyr + body + v * V, o2);
+  }
+  if (blockIdx.x == 0 && (int)threadIdx.x < sp.head + sp.tail) {
+    const int t = threadIdx.x;
+    const int64_t e = sp.base + (t < sp.head ? t : sp.head + sp.nv * V + (t - sp.head));
+    const float d = ld1(dout + e), yv = ld1(y + e), fv = ld1(f + e);
+    st1(df + e, (d * gm) * yv);
+    st1(dyr + e, d * fmaf(gm, fv, 1.0f));
+    acc = fmaf(d * yv, fv, acc);
+  }
+  const float s = wave_sum(acc);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+  __syncthreads();
+  if (threadIdx.x == 0)
+    part[((int64_t)blockIdx.z * gridDim.x + blockIdx.x) * C + c] = (red[0] + red[1]) + (red[2] + red[3]);
+}
+
+static int fg_check(const char* who, int B, int C, int64_t N, int dtype) {
+  MI_CHECK_ARG(B > 0 && B <= 65535 && C > 0 && C <= 65535 && N > 0, "%s: bad shape B=%d C=%d N=%lld", who, B, C, (long long)N);
+  MI_CHECK_ARG(dtype == MI_F32 || dtype == MI_BF16, "%s: bad dtype %d", who, dtype);
+  MI_CHECK_ARG((int64_t)B * C <= ((int64_t)1 << 62) / N, "%s: tensor too large", who);
+  return MI_OK;
+}
+// the element offset inside a 16-byte line that every pointer shares, or -1 (the scalar form)
+static int fg_a0(std::initializer_list<const void*> ps, int dtype) {
+  const uintptr_t first = reinterpret_cast<uintptr_t>(*ps.begin()) & 15u;
+  for (const void* p : ps)
+    if ((reinterpret_cast<uintptr_t>(p) & 15u) != first) return -1;
+  return first % dtype_size(dtype) ? -1 : (int)(first / dtype_size(dtype));
+}
+
+static int launch_fregate_fwd(const void* y, const void* f, const float* gamma, void* out, int B, int C, int64_t N, int dtype,
+                              hipStream_t st) {
+  MI_TRY(fg_check("fregate_fwd", B, C, N, dtype));
+  MI_CHECK_ARG(y && f && gamma && out, "fregate_fwd: null pointer");
+  const int a0 = fg_a0({y, f, out}, dtype);
+  const dim3 grid(fg_slices(N, dtype), C, B);
+  const double n = (double)B * C * N;
+  ProfScope ps(st, K_EWISE, 3.0 * n * dtype_size(dtype), 3.0 * n);
+  return with_dtype(dtype, "fregate_fwd", [&](auto tag) {
+    using T = decltype(tag);
+    if (a0 >= 0)
+      hipLaunchKernelGGL((fregate_fwd_kernel<T, FgVec<T>::V>), grid, dim3(256), 0, st, (const T*)y, (const T*)f, gamma, (T*)out, N, a0);
+    else
+      hipLaunchKernelGGL((fregate_fwd_kernel<T, 1>), grid, dim3(256), 0, st, (const T*)y, (const T*)f, gamma, (T*)out, N, 0);
+  });
+}
+
+static size_t fg_bwd_ws(int B, int C, int64_t N) { return fbytes((size_t)B * FG_MAX_S * C); }
+
+static int launch_fregate_bwd(const void* dout, const void* y, const void* f, const float* gamma, void* df, void* dyr, float* dgamma,
+                              int B, int C, int64_t N, int accumulate, int dtype, void* ws, hipStream_t st) {
+  MI_TRY(fg_check("fregate_bwd", B, C, N, dtype));
+  MI_CHECK_ARG(dout && y && f && gamma && df && dyr && dgamma && ws, "fregate_bwd: null pointer");
+  const int a0 = fg_a0({dout, y, f, df, dyr}, dtype);
+  const int S = fg_slices(N, dtype);
+  const dim3 grid(S, C, B);
+  float* part = (float*)ws;
+  {
+    const double n = (double)B * C * N;
+    ProfScope ps(st, K_EWISE, 5.0 * n * dtype_size(dtype), 8.0 * n);
+    MI_TRY(with_dtype(dtype, "fregate_bwd", [&](auto tag) {
+      using T = decltype(tag);
+      if (a0 >= 0)
+        hipLaunchKernelGGL((fregate_bwd_kernel<T, FgVec<T>::V>), grid, dim3(256), 0, st, (const T*)dout, (const T*)y, (const T*)f, gamma,
+                           (T*)df, (T*)dyr, part, N, a0);
+      else
+        hipLaunchKernelGGL((fregate_bwd_kernel<T, 1>), grid, dim3(256), 0, st, (const T*)dout, (const T*)y, (const T*)f, gamma, (T*)df,
+                           (T*)dyr, part, N, 0);
+    }));
+  }
+  return launch_reduce_rows(part, dgamma, (int64_t)B * S, C, C, accumulate, 1.0f, st);
+}
+
+// ------------------------------------------------------------------ EBlock: layouts
+struct EbSaved {
+  void* x0; void* xe; void* x1; void* g; void* y; void* f;
+  float* mean1; float* rstd1; float* mean2; float* rstd2; float* pool; float* s; float* M3; float* b3f; float* M3s; float* M3ts;
+  void* blob;
+  size_t sec[9];     // bytes of x0, xe, x1, g, y, f, the statistics, the small tensors, the FreMLP blob
+  size_t bytes;
+};
+static mi_fremlp_shape eb_fre_shape(const mi_eblock_shape* s) { return mi_fremlp_shape{s->B, s->C, 2, s->H, s->W, s->dtype}; }
+// train: everything the backward reads; inference (blob = false, in the workspace): the same planes, nothing outlives the call
+static EbSaved eb_saved_layout(const mi_eblock_shape* s, void* base, bool blob) {
+  const size_t B = s->B, C = s->C, N = (size_t)s->H * s->W, cc = B * C * C;
+  const int dt = s->dtype;
+  Carver cv(base);
+  EbSaved r;
+  memset(&r, 0, sizeof(r));
+  size_t o = cv.off;
+  auto close = [&](int i) { r.sec[i] = cv.off - o; o = cv.off; };
+  r.x0 = cv.take(tbytes(B * C * N, dt)); close(0);
+  r.xe = s->extra ? cv.take(tbytes(B * C * N, dt)) : r.x0; close(1);
+  r.x1 = cv.take(tbytes(B * 2 * C * N, dt)); close(2);
+  r.g = cv.take(tbytes(B * C * N, dt)); close(3);
+  r.y = cv.take(tbytes(B * C * N, dt)); close(4);
+  r.f = cv.take(tbytes(B * C * N, dt)); close(5);
+  r.mean1 = cv.take<float>(fbytes(B * N));
+  r.rstd1 = cv.take<float>(fbytes(B * N));
+  r.mean2 = cv.take<float>(fbytes(B * N));
+  r.rstd2 = cv.take<float>(fbytes(B * N)); close(6);
+  r.pool = cv.take<float>(fbytes(B * C));
+  r.s = cv.take<float>(fbytes(B * C));
+  r.M3 = cv.take<float>(fbytes(cc));
+  r.b3f = cv.take<float>(fbytes(C));
+  r.M3s = cv.take<float>(fbytes(2 * cc));
+  r.M3ts = cv.take<float>(fbytes(2 * cc)); close(7);
+  if (blob) {
+    const mi_fremlp_shape fs = eb_fre_shape(s);
+    r.blob = cv.take(mi_fremlp_saved_bytes(&fs));
+  }
+  close(8);
+  r.bytes = cv.off;
+  return r;
+}
+
+struct EbWs {
+  void* pw_ws; void* gram_ws; void* cs_ws; void* ln_ws; void* dg_fwd_ws; void* dg_bwd_ws; void* dw_ws; void* fre_ws; void* fg_ws;
+  float* G; float* S; float* ds; float* dg_add; float* wsplit; void* y0;
+  EbSaved inf; void* t1; void* t2; void* t3; size_t bytes;
+};
+static EbWs eb_ws_layout(const mi_eblock_shape* s, void* base, int R) {
+  const int B = s->B, C = s->C, dt = s->dtype;
+  const int64_t N = (int64_t)s->H * s->W;
+  Carver cv(base);
+  EbWs w;
+  memset(&w, 0, sizeof(w));
+  const bool sp = dt == MI_BF16;
+  // c -> 2c, its transpose 2c -> c, the per-image c -> c and its transpose (bf16: all four as split products, none transposed)
+  w.pw_ws = cv.take(max_of({db_probe(C, 2 * C, sp, false, false, B, N, dt), db_probe(C, C, sp, true, false, B, N, dt),
+                            sp ? db_probe(2 * C, C, true, false, false, B, N, dt) : db_probe(2 * C, C, false, false, true, B, N, dt),
+                            sp ? (size_t)0 : db_probe(C, C, false, true, true, B, N, dt)}));
+  w.wsplit = cv.take<float>(fbytes((size_t)4 * C * C));
+  w.gram_ws = cv.take(max_of({gram_ws_bytes(probe_wgrad(C, C, B, N, dt, 0)), gram_ws_bytes(probe_wgrad(2 * C, C, B, N, dt, 1))}));
+  w.cs_ws = cv.take(chan_sum_workspace(B * C > 2 * C ? B * C : 2 * C, N));
+  w.ln_ws = cv.take(mi_ln_bwd_workspace(B, C, N));
+  const DgPlan pl = dg_plan(B, C, s->H, s->W, s->n_dil, R, dt);
+  w.dg_fwd_ws = cv.take(pl.fwd_ws);
+  w.dg_bwd_ws = cv.take(pl.bwd_ws);
+  w.dw_ws = cv.take(s->extra ? mi_dwconv_bwd_workspace(B, C, s->H, s->W, 3) : 0);
+  const mi_fremlp_shape fs = eb_fre_shape(s);
+  w.fre_ws = cv.take(mi_fremlp_workspace(&fs));
+  w.fg_ws = cv.take(fg_bwd_ws(B, C, N));
+  w.G = cv.take<float>(fbytes((size_t)B * C * C));
+  w.S = cv.take<float>(fbytes((size_t)B * C));
+  w.ds = cv.take<float>(fbytes((size_t)B * C));
+  w.dg_add = cv.take<float>(fbytes((size_t)B * C));
+  w.y0 = cv.take(tbytes((size_t)B * C * N, dt));       // LayerNorm2d(y): FreMLP's input, dead when the forward returns
+  const size_t mark = cv.off;
+  w.inf = eb_saved_layout(s, base ? (char*)base + mark : nullptr, false);
+  Carver big(base ? (char*)base + mark : nullptr);
+  const size_t plane2 = tbytes((size_t)B * 2 * C * N, dt);
+  w.t1 = big.take(plane2);
+  w.t2 = big.take(plane2);
+  w.t3 = big.take(plane2);
+  w.bytes = mark + max_of({w.inf.bytes, big.off});
+  return w;
+}
+
+constexpr int EB_MIN_HW = 2, EB_MAX_HW = 512;
+static int eb_check(const mi_eblock_shape* s, int* R) {
+  MI_CHECK_ARG(s, "eblock: null shape");
+  MI_CHECK_ARG(s->C >= 1 && s->C <= DB_MAX_C, "eblock: C=%d not covered (1 <= C <= %d)", s->C, DB_MAX_C);
+  MI_CHECK_ARG(s->H >= EB_MIN_HW && s->H <= EB_MAX_HW && s->W >= EB_MIN_HW && s->W <= EB_MAX_HW,
+               "eblock: plane %d x %d not covered (%d <= H, W <= %d: FreMLP's dense transforms)", s->H, s->W, EB_MIN_HW, EB_MAX_HW);
+  MI_TRY(dg_check(s->B, s->C, s->H, s->W, s->n_dil, s->dil, s->dtype, R));
+  MI_CHECK_ARG((int64_t)2 * s->C * s->H * s->W < (1ll << 31), "eblock: 2*C*H*W must be below 2^31");
+  const mi_fremlp_shape fs = eb_fre_shape(s);
+  if (mi_fremlp_workspace(&fs) == 0) return MI_ERR_ARG;      // (its message stands)
+  return MI_OK;
+}
+static int eb_check_params(const mi_eblock_shape* s, const mi_eblock_params* p) {
+  MI_CHECK_ARG(p && p->norm1_w && p->norm1_b && p->conv1_w && p->conv1_b && p->sca_w && p->sca_b && p->conv3_w && p->conv3_b && p->beta &&
+               p->norm2_w && p->norm2_b && p->fre_w1 && p->fre_b1 && p->fre_w2 && p->fre_b2 && p->gamma, "eblock: null parameter");
+  MI_CHECK_ARG(!s->extra || (p->extra_w && p->extra_b), "eblock: null extra_conv parameter");
+  for (int i = 0; i < s->n_dil; ++i) MI_CHECK_ARG(p->br_w[i] && p->br_b[i], "eblock: null parameter of branch %d", i);
+  return MI_OK;
+}
+
 }  // namespace mi
 
 using namespace mi;
@@ -903,5 +1151,144 @@ extern "C" int mi_dblock_bwd(const mi_dblock_shape* s, const mi_dblock_params* p
   }
   void* dx0 = s->extra ? w.t2 : w.t1;
   MI_TRY(db_conv_bwd(dx1, 2 * C, sv.x0, C, p->conv1_w, g->conv1_w, g->conv1_b, dx0, B, N, dt, acc, w.wsplit, w.gram_ws, w.cs_ws, w.pw_ws, st));
+  return mi_ln_bwd(dx0, inp, p->norm1_w, sv.mean1, sv.rstd1, dy, dinp, g->norm1_w, g->norm1_b, B, C, N, 1, acc, dt, w.ln_ws, stream);
+}
+
+// ------------------------------------------------------------------ EBlock (arch_model.py:141-204)
+extern "C" int mi_fregate_fwd(const void* y, const void* f, const float* gamma, void* out, int B, int C, int64_t N, int dtype,
+                              void* stream) {
+  return launch_fregate_fwd(y, f, gamma, out, B, C, N, dtype, (hipStream_t)stream);
+}
+extern "C" size_t mi_fregate_bwd_workspace(int B, int C, int64_t N) {
+  if (fg_check("fregate_bwd_workspace", B, C, N, MI_F32) != MI_OK) return 0;
+  return fg_bwd_ws(B, C, N);
+}
+extern "C" int mi_fregate_bwd(const void* dout, const void* y, const void* f, const float* gamma, void* df, void* dyr, float* dgamma,
+                              int B, int C, int64_t N, int accumulate, int dtype, void* ws, void* stream) {
+  return launch_fregate_bwd(dout, y, f, gamma, df, dyr, dgamma, B, C, N, accumulate, dtype, ws, (hipStream_t)stream);
+}
+
+extern "C" size_t mi_eblock_saved_bytes(const mi_eblock_shape* s) {
+  int R = 0;
+  if (eb_check(s, &R) != MI_OK) return 0;
+  return eb_saved_layout(s, nullptr, true).bytes;
+}
+extern "C" size_t mi_eblock_workspace(const mi_eblock_shape* s) {
+  int R = 0;
+  if (eb_check(s, &R) != MI_OK) return 0;
+  return eb_ws_layout(s, nullptr, R).bytes;
+}
+extern "C" int mi_eblock_plan(const mi_eblock_shape* s, int64_t* out) {
+  MI_CHECK_ARG(out, "eblock_plan: null pointer");
+  int R = 0;
+  MI_TRY(eb_check(s, &R));
+  const EbSaved sv = eb_saved_layout(s, nullptr, true);
+  const EbWs w = eb_ws_layout(s, nullptr, R);
+  const mi_fremlp_shape fs = eb_fre_shape(s);
+  int64_t fp[64];
+  MI_TRY(mi_fremlp_plan(&fs, fp));
+  const int b16 = s->dtype == MI_BF16 ? 1 : 0, ex = s->extra ? 1 : 0, n = s->n_dil;
+  // forward: norm1, [extra_conv], conv1 (bf16: the split first), the gate and its pool sum, the fold, conv3, norm2, FreMLP, the tail
+  const int64_t fwd = 1 + ex + (1 + b16) + 2 + 1 + 1 + 1 + (fp[18] + fp[20]) + 1;
+  // backward: the tail and its row sum, FreMLP, norm2; Gram, channel sums, three c x c kernels, conv3^T; the gate's two passes and
+  // 2n row sums; conv1 (Gram, channel sum, [split], product); [extra_conv and its two row sums]; norm1
+  const int64_t bwd = 2 + (fp[19] + fp[21]) + 1 + 2 + 3 + 1 + (2 + 2 * n) + (3 + b16) + 3 * ex + 1;
+  for (int i = 0; i < 9; ++i) out[i] = (int64_t)sv.sec[i];
+  out[9] = (int64_t)sv.bytes;
+  out[10] = (int64_t)w.bytes;
+  out[11] = fwd;
+  out[12] = bwd;
+  out[13] = fg_slices((int64_t)s->H * s->W, s->dtype);
+  out[14] = out[15] = 0;
+  return MI_OK;
+}
+
+extern "C" int mi_eblock_fwd(const mi_eblock_shape* s, const mi_eblock_params* p, const void* inp, void* out, void* saved, void* ws,
+                             void* stream) {
+  int R = 0;
+  MI_TRY(eb_check(s, &R));
+  MI_TRY(eb_check_params(s, p));
+  MI_CHECK_ARG(inp && out && ws, "eblock_fwd: null pointer");
+  hipStream_t st = (hipStream_t)stream;
+  const int B = s->B, C = s->C, H = s->H, W = s->W, dt = s->dtype;
+  const int64_t N = (int64_t)H * W;
+  const bool b16 = dt == MI_BF16;
+  EbWs w = eb_ws_layout(s, ws, R);
+  EbSaved sv = saved ? eb_saved_layout(s, saved, true) : w.inf;
+  mi_dilgate_params br;
+  for (int i = 0; i < DG_MAX_N; ++i) { br.w[i] = p->br_w[i]; br.b[i] = p->br_b[i]; }
+  // first half (arch_model.py:183-193)
+  MI_TRY(mi_ln_fwd_eps(inp, p->norm1_w, p->norm1_b, sv.x0, sv.mean1, sv.rstd1, B, C, N, 1, 1e-6f, dt, stream));
+  if (s->extra) MI_TRY(mi_dwconv_fwd(sv.x0, p->extra_w, p->extra_b, sv.xe, B, C, H, W, 3, dt, stream));
+  MI_TRY(db_conv(sv.xe, C, p->conv1_w, p->conv1_b, sv.x1, 2 * C, B, N, dt, w.wsplit, w.pw_ws, st));
+  MI_TRY(launch_dilgate_fwd(sv.x1, &br, sv.g, sv.pool, B, C, H, W, s->n_dil, s->dil, dt, w.dg_fwd_ws, st));
+  MI_TRY(db_fold(sv.pool, p->sca_w, p->sca_b, p->conv3_w, p->conv3_b, p->beta, sv.s, sv.M3, b16 ? sv.M3s : nullptr, b16 ? sv.M3ts : nullptr,
+                 sv.b3f, B, C, N, st));
+  mi_pw_desc d3 = db_gemm(sv.g, C, b16 ? sv.M3s : sv.M3, b16, true, sv.b3f, inp, sv.y, C, B, N, dt);
+  MI_TRY(mi_pw_gemm(&d3, w.pw_ws, stream));
+  // second half (:196-199)
+  MI_TRY(mi_ln_fwd_eps(sv.y, p->norm2_w, p->norm2_b, w.y0, sv.mean2, sv.rstd2, B, C, N, 1, 1e-6f, dt, stream));
+  const mi_fremlp_shape fs = eb_fre_shape(s);
+  MI_TRY(mi_fremlp_fwd(&fs, p->fre_w1, p->fre_b1, p->fre_w2, p->fre_b2, w.y0, sv.f, saved ? sv.blob : nullptr, w.fre_ws, stream));
+  return launch_fregate_fwd(sv.y, sv.f, p->gamma, out, B, C, N, dt, st);
+}
+
+extern "C" int mi_eblock_bwd(const mi_eblock_shape* s, const mi_eblock_params* p, const void* inp, const void* dout, void* dinp,
+                             const mi_eblock_grads* g, const void* saved, void* ws, void* stream) {
+  int R = 0;
+  MI_TRY(eb_check(s, &R));
+  MI_TRY(eb_check_params(s, p));
+  MI_CHECK_ARG(inp && dout && dinp && g && saved && ws, "eblock_bwd: null pointer");
+  MI_CHECK_ARG(g->norm1_w && g->norm1_b && g->conv1_w && g->conv1_b && g->sca_w && g->sca_b && g->conv3_w && g->conv3_b && g->beta &&
+               g->norm2_w && g->norm2_b && g->fre_w1 && g->fre_b1 && g->fre_w2 && g->fre_b2 && g->gamma, "eblock_bwd: null gradient buffer");
+  MI_CHECK_ARG(!s->extra || (g->extra_w && g->extra_b), "eblock_bwd: null extra_conv gradient buffer");
+  for (int i = 0; i < s->n_dil; ++i) MI_CHECK_ARG(g->br_w[i] && g->br_b[i], "eblock_bwd: null gradient buffer of branch %d", i);
+  hipStream_t st = (hipStream_t)stream;
+  const int B = s->B, C = s->C, H = s->H, W = s->W, dt = s->dtype, acc = g->accumulate;
+  const int64_t N = (int64_t)H * W;
+  const bool b16 = dt == MI_BF16;
+  const float inv_n = 1.0f / (float)N;
+  EbWs w = eb_ws_layout(s, ws, R);
+  EbSaved sv = eb_saved_layout(s, const_cast<void*>(saved), true);
+  // ---- second half: out = y (1 + gamma f), f = FreMLP(LN(y))
+  void* df = w.t3;
+  void* dyr = w.t2;    // the residual's share of the gradient at y
+  MI_TRY(launch_fregate_bwd(dout, sv.y, sv.f, p->gamma, df, dyr, g->gamma, B, C, N, acc, dt, w.fg_ws, st));
+  void* dy0 = w.t1;
+  const mi_fremlp_shape fs = eb_fre_shape(s);
+  MI_TRY(mi_fremlp_bwd(&fs, p->fre_w1, p->fre_w2, p->fre_b2, df, dy0, g->fre_w1, g->fre_b1, g->fre_w2, g->fre_b2, acc, sv.blob, w.fre_ws,
+                       stream));
+  void* dy = w.t3;     // (df is dead) the whole gradient at y: through norm2 plus the residual's share
+  MI_TRY(mi_ln_bwd(dy0, sv.y, p->norm2_w, sv.mean2, sv.rstd2, dyr, dy, g->norm2_w, g->norm2_b, B, C, N, 1, acc, dt, w.ln_ws, stream));
+  // ---- first half: y = inp + M3[b] g + b3f (mi_dblock_bwd's, with extra_conv in front of conv1)
+  mi_gram_desc g3 = wgrad_gram(dy, C, sv.g, C, B, N, dt, w.G, 0, 0);
+  MI_TRY(mi_gram(&g3, w.gram_ws, stream));
+  MI_TRY(launch_chan_sum(dy, w.S, 1, B * C, N, dt, 0, w.cs_ws, st));       // per image: [B][c]
+  {
+    ProfScope ps(st, K_DK_FOLD_BWD, 4.0 * (2.0 * B + 3) * C * C, 2.0 * (3.0 * B + 2) * C * C);
+    hipLaunchKernelGGL(dk_sca_ds_kernel, dim3(B), dim3(256), C * sizeof(float), st, w.G, p->conv3_w, p->beta, p->sca_w, w.ds, w.dg_add, C, inv_n);
+    MI_LAUNCH_CHECK();
+    hipLaunchKernelGGL(dk_fold_bwd_kernel, dim3(C), dim3(256), 0, st, w.G, sv.s, w.S, p->conv3_w, p->conv3_b, p->beta, g->conv3_w, g->conv3_b,
+                       g->beta, B, C, acc);
+    MI_LAUNCH_CHECK();
+    hipLaunchKernelGGL(dk_sca_w_kernel, dim3(C), dim3(256), 0, st, w.ds, sv.pool, g->sca_w, g->sca_b, B, C, inv_n, acc);
+    MI_LAUNCH_CHECK();
+  }
+  void* dgp = w.t1;    // (dy0 is dead)
+  mi_pw_desc e3 = b16 ? db_gemm(dy, C, sv.M3ts, true, true, nullptr, nullptr, dgp, C, B, N, dt) : db_gemm_t(dy, C, sv.M3, true, dgp, C, B, N, dt);
+  MI_TRY(mi_pw_gemm(&e3, w.pw_ws, stream));
+  mi_dilgate_params br;
+  mi_dilgate_grads bg;
+  for (int i = 0; i < DG_MAX_N; ++i) { br.w[i] = p->br_w[i]; br.b[i] = p->br_b[i]; bg.w[i] = g->br_w[i]; bg.b[i] = g->br_b[i]; }
+  bg.accumulate = acc;
+  void* dx1 = w.t2;    // (dyr is dead)
+  MI_TRY(launch_dilgate_bwd(dgp, w.dg_add, sv.x1, &br, dx1, &bg, B, C, H, W, s->n_dil, s->dil, dt, w.dg_bwd_ws, st));
+  void* dxe = w.t1;    // (dg is dead)
+  MI_TRY(db_conv_bwd(dx1, 2 * C, sv.xe, C, p->conv1_w, g->conv1_w, g->conv1_b, dxe, B, N, dt, acc, w.wsplit, w.gram_ws, w.cs_ws, w.pw_ws, st));
+  void* dx0 = dxe;
+  if (s->extra) {
+    dx0 = w.t2;        // (dx1 is dead)
+    MI_TRY(mi_dwconv_bwd(dxe, sv.x0, p->extra_w, dx0, g->extra_w, g->extra_b, B, C, H, W, 3, acc, dt, w.dw_ws, stream));
+  }
   return mi_ln_bwd(dx0, inp, p->norm1_w, sv.mean1, sv.rstd1, dy, dinp, g->norm1_w, g->norm1_b, B, C, N, 1, acc, dt, w.ln_ws, stream);
 }

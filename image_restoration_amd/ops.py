@@ -1024,6 +1024,130 @@ def fremlp_bwd(dout: Tensor, params: Sequence[Tensor], saved: Tensor, grads: Seq
     return dx
 
 
+# ----------------------------------------------------------------------------- DarkIR: EBlock and its tail
+EBLOCK_MAX_C, EBLOCK_MIN_HW, EBLOCK_MAX_HW = 256, 2, FREMLP_MAX_HW
+_EBLOCK_PLAN_KEYS = ("x0_bytes", "xe_bytes", "x1_bytes", "g_bytes", "y_bytes", "f_bytes", "stats_bytes", "small_bytes",
+                     "fremlp_blob_bytes", "saved_bytes", "workspace", "calls_fwd", "calls_bwd", "fregate_bwd_slices")
+
+
+def _fregate_check(y: Tensor, *others: Tensor):
+    if y.dim() != 4:
+        raise ValueError(f"fregate: y must be [B, C, H, W], got {tuple(y.shape)}")
+    for t in others:
+        if t.shape != y.shape or t.dtype != y.dtype:
+            raise ValueError(f"fregate: tensors differ in shape or dtype ({tuple(t.shape)} {t.dtype} against {tuple(y.shape)} {y.dtype})")
+    B, Cc, H, W = y.shape
+    return B, Cc, H * W
+
+
+def fregate_fwd(y: Tensor, f: Tensor, gamma: Tensor) -> Tensor:
+    """EBlock's tail: out = y * (1 + gamma[c] * f).  y, f [B, C, H, W]; gamma fp32 with C elements."""
+    _gpu(y, f, gamma)
+    _f32(gamma, "fregate gamma")
+    B, Cc, N = _fregate_check(y, f)
+    if gamma.numel() != Cc:
+        raise ValueError(f"fregate: gamma has {gamma.numel()} elements for {Cc} channels")
+    out = torch.empty_like(y)
+    L.check(L.lib().mi_fregate_fwd(_p(y), _p(f), _p(gamma), _p(out), B, Cc, N, _dt(y), _stream()), "fregate_fwd")
+    return out
+
+
+def fregate_bwd(dout: Tensor, y: Tensor, f: Tensor, gamma: Tensor, dgamma: Tensor, accumulate: bool):
+    """Backward of fregate_fwd in one pass -> (df, dyr): df = dout gamma y (FreMLP's cotangent), dyr = dout (1 + gamma f) (the
+    residual's share); dgamma (fp32, C elements) is written (accumulate: added to) with sum_{b,p} dout y f."""
+    _gpu(dout, y, f, gamma, dgamma)
+    _f32(gamma, "fregate gamma"); _f32(dgamma, "fregate gradient")
+    B, Cc, N = _fregate_check(y, f, dout)
+    if gamma.numel() != Cc or dgamma.numel() != Cc:
+        raise ValueError(f"fregate: gamma / dgamma have {gamma.numel()} / {dgamma.numel()} elements for {Cc} channels")
+    lib = L.lib()
+    df, dyr = torch.empty_like(y), torch.empty_like(y)
+    ws = _ws(lib.mi_fregate_bwd_workspace(B, Cc, N), y.device)
+    L.check(lib.mi_fregate_bwd(_p(dout), _p(y), _p(f), _p(gamma), _p(df), _p(dyr), _p(dgamma), B, Cc, N, int(accumulate), _dt(y), _p(ws),
+                               _stream()), "fregate_bwd")
+    return df, dyr
+
+
+def _eblock_shape(B: int, Cc: int, H: int, W: int, dtype_code: int, dilations: Sequence[int], extra: bool) -> L.EblockShape:
+    s = L.EblockShape(B, Cc, H, W, dtype_code, len(dilations))
+    for i, d in enumerate(dilations[:4]):
+        s.dil[i] = int(d)
+    s.extra = int(extra)
+    return s
+
+
+def eblock_sizes(B: int, Cc: int, H: int, W: int, dtype: torch.dtype, dilations: Sequence[int], extra: bool) -> Tuple[int, int]:
+    """(saved bytes, workspace bytes) of one EBlock; (0, 0) for a shape the kernels do not cover.  No GPU needed."""
+    s = _eblock_shape(B, Cc, H, W, _dtype_code(dtype), dilations, extra)
+    lib = L.lib()
+    return int(lib.mi_eblock_saved_bytes(C.byref(s))), int(lib.mi_eblock_workspace(C.byref(s)))
+
+
+def eblock_plan(B: int, Cc: int, H: int, W: int, dtype: torch.dtype, dilations: Sequence[int], extra: bool) -> dict:
+    """Section sizes of the saved blob, the two totals and the launch counts of one EBlock (mi_eblock_plan; no GPU work)."""
+    out = (L.c_i64 * 16)()
+    s = _eblock_shape(B, Cc, H, W, _dtype_code(dtype), dilations, extra)
+    L.check(L.lib().mi_eblock_plan(C.byref(s), out), "eblock_plan")
+    return {k: int(out[i]) for i, k in enumerate(_EBLOCK_PLAN_KEYS)}
+
+
+def _eblock_struct(cls, ts: Sequence[Optional[Tensor]], n_dil: int, what: str, *tail):
+    """mi_eblock_params / mi_eblock_grads from the flat list: norm1 (2), extra_conv (2, None without it), conv1 (2), the branches'
+    weights (n_dil), their biases (n_dil), sca (2), conv3 (2), beta, norm2 (2), freq.process1.0 (2), freq.process1.2 (2), gamma."""
+    for t in ts:
+        _f32(t, what)
+    st = cls()
+    it = iter(ts)
+    for name, k in L.EBLOCK_FIELDS:
+        if k == 1:
+            setattr(st, name, _p(next(it)))
+        else:
+            arr = getattr(st, name)
+            for i in range(n_dil):
+                arr[i] = _p(next(it))
+    if tail:
+        st.accumulate = tail[0]
+    return st
+
+
+def _eblock_args(x: Tensor, dilations: Sequence[int], extra: bool):
+    if x.dim() != 4:
+        raise ValueError(f"eblock: x must be [B, c, H, W], got {tuple(x.shape)}")
+    B, Cc, H, W = x.shape
+    s = _eblock_shape(B, Cc, H, W, _dt(x), dilations, extra)
+    ws_bytes = L.lib().mi_eblock_workspace(C.byref(s))
+    if ws_bytes == 0:
+        raise NotImplementedError("image_restoration_amd: " + L.lib().mi_last_error().decode("utf-8", "replace"))
+    return s, ws_bytes
+
+
+def eblock_fwd(x: Tensor, params: Sequence[Optional[Tensor]], dilations: Sequence[int], extra: bool, need_saved: bool):
+    """DarkIR EBlock.forward.  params: see _eblock_struct.  -> (out, saved)."""
+    _gpu(x, *params)
+    s, ws_bytes = _eblock_args(x, dilations, extra)
+    lib = L.lib()
+    out = torch.empty_like(x)
+    saved = _blob(lib.mi_eblock_saved_bytes(C.byref(s)), x.device) if need_saved else None
+    ws = _ws(ws_bytes, x.device)
+    pp = _eblock_struct(L.EblockParams, params, len(dilations), "EBlock parameter")
+    L.check(lib.mi_eblock_fwd(C.byref(s), C.byref(pp), _p(x), _p(out), _p(saved), _p(ws), _stream()), "eblock_fwd")
+    return out, saved
+
+
+def eblock_bwd(x: Tensor, dout: Tensor, params: Sequence[Optional[Tensor]], dilations: Sequence[int], extra: bool, saved: Tensor,
+               grads: Sequence[Optional[Tensor]], accumulate: bool) -> Tensor:
+    """Backward of eblock_fwd: dx; the parameter gradients are written (accumulate: added) into ``grads``."""
+    _gpu(x, dout, saved, *params, *grads)
+    s, ws_bytes = _eblock_args(x, dilations, extra)
+    lib = L.lib()
+    dx = torch.empty_like(x)
+    pp = _eblock_struct(L.EblockParams, params, len(dilations), "EBlock parameter")
+    gg = _eblock_struct(L.EblockGrads, grads, len(dilations), "EBlock gradient", int(accumulate))
+    ws = _ws(ws_bytes, x.device)
+    L.check(lib.mi_eblock_bwd(C.byref(s), C.byref(pp), _p(x), _p(dout), _p(dx), C.byref(gg), _p(saved), _p(ws), _stream()), "eblock_bwd")
+    return dx
+
+
 def _dft2_ws(who: str, B: int, Cc: int, H: int, W: int, device) -> Tensor:
     n = L.lib().mi_dft2_workspace(B, Cc, H, W)
     if n == 0:

@@ -920,6 +920,60 @@ int mi_fremlp_bwd(const mi_fremlp_shape* s, const float* w1, const float* w2, co
                   float* g_w1, float* g_b1, float* g_w2, float* g_b2, int accumulate, const void* saved, void* ws, void* stream);
 
 /* ------------------------------------------------------------------------
+ * DarkIR — the encoder block (DarkIR-main/archs/arch_model.py:141-204 EBlock) and its tail (csrc/darkir.hip).
+ *
+ * fregate: the block's last line, y + gamma (y f), as one streaming pass.  y, f, out [B,C,N] in `dtype`, gamma [C] fp32, fp32
+ * arithmetic:   out = y (1 + gamma[c] f).
+ *   bwd (one pass over dout, y, f):  df = (dout gamma[c]) y;  dyr = dout (1 + gamma[c] f);  dgamma[c] (+)= sum_{b,p} (dout y) f
+ *   (per-workgroup partial rows summed in a fixed order: no atomics, bitwise reproducible; accumulate != 0 adds to dgamma).
+ * 16-byte vector access over the aligned interior of every plane, scalar head and tail; any N >= 1, any alignment the dtype has
+ * (pointers that disagree modulo 16 bytes take the scalar form).  B, C <= 65535.  ws: mi_fregate_bwd_workspace() bytes.
+ *
+ * EBlock.forward / backward as one unit:
+ *   x0 = LayerNorm2d(inp; norm1, eps 1e-6);  xe = extra_conv(x0) when `extra` (plain depthwise 3x3, w [c, 9]), else x0;
+ *   x1 = conv1(xe) [2c];  g = dilgate(x1);  s[b] = sca_w . mean_hw(g[b]) + sca_b;  y = inp + beta (conv3(s g));
+ *   f = FreMLP(LayerNorm2d(y; norm2)) (nc = c, expand = 2: fre_w1 [2c, c], fre_w2 [c, 2c]);  out = fregate(y, f, gamma).
+ * The pieces are mi_ln_fwd_eps, mi_dwconv_*, the split-weight 1x1 products and the per-image fold of DBlock, mi_dilgate_*,
+ * mi_fremlp_* and mi_fregate_*.  Parameters fp32 in the reference's layout, every bias required; extra_w / extra_b are read only
+ * when `extra`.  saved == NULL: inference, nothing is kept.  Kept for the backward: x0, xe (with `extra`), x1, g, y, f, the
+ * LayerNorm statistics, pool, s, the folded conv3 matrices and the FreMLP blob; LayerNorm2d(y) is not (FreMLP's backward reads
+ * its blob only).
+ * Limits: 1 <= C <= 256, 2 <= H, W <= 512, 1..4 dilations of 1..16, fp32 or bf16, 2 C H W < 2^31 and FreMLP's own size
+ * conditions; anything else is refused before any launch and the sizing calls return 0.
+ * mi_eblock_plan (host-only; the sizing calls and the launchers read the same layout) fills out[16]: bytes of x0, xe (0 without
+ * `extra`), x1, g, y, f, of the four LayerNorm statistics, of the small tensors (pool, s, the conv3 folds), of the FreMLP blob;
+ * saved bytes; workspace bytes; calls of the forward's / the backward's launch sequence (a library entry point counts as one,
+ * FreMLP as its own launches and library calls); workgroups per plane of the fregate backward; 0; 0.
+ * ------------------------------------------------------------------------ */
+typedef struct { int B, C, H, W, dtype, n_dil; int dil[4]; int extra; } mi_eblock_shape;
+typedef struct {
+  const float* norm1_w; const float* norm1_b; const float* extra_w; const float* extra_b; const float* conv1_w; const float* conv1_b;
+  const float* br_w[4]; const float* br_b[4];
+  const float* sca_w; const float* sca_b; const float* conv3_w; const float* conv3_b; const float* beta;
+  const float* norm2_w; const float* norm2_b; const float* fre_w1; const float* fre_b1; const float* fre_w2; const float* fre_b2;
+  const float* gamma;
+} mi_eblock_params;
+typedef struct {
+  float* norm1_w; float* norm1_b; float* extra_w; float* extra_b; float* conv1_w; float* conv1_b;
+  float* br_w[4]; float* br_b[4];
+  float* sca_w; float* sca_b; float* conv3_w; float* conv3_b; float* beta;
+  float* norm2_w; float* norm2_b; float* fre_w1; float* fre_b1; float* fre_w2; float* fre_b2;
+  float* gamma;
+  int accumulate;
+} mi_eblock_grads;
+int mi_fregate_fwd(const void* y, const void* f, const float* gamma, void* out, int B, int C, int64_t N, int dtype, void* stream);
+size_t mi_fregate_bwd_workspace(int B, int C, int64_t N);
+int mi_fregate_bwd(const void* dout, const void* y, const void* f, const float* gamma, void* df, void* dyr, float* dgamma, int B,
+                   int C, int64_t N, int accumulate, int dtype, void* ws, void* stream);
+size_t mi_eblock_saved_bytes(const mi_eblock_shape* s);
+size_t mi_eblock_workspace(const mi_eblock_shape* s);
+int mi_eblock_plan(const mi_eblock_shape* s, int64_t* out);
+int mi_eblock_fwd(const mi_eblock_shape* s, const mi_eblock_params* p, const void* inp, void* out, void* saved, void* ws,
+                  void* stream);
+int mi_eblock_bwd(const mi_eblock_shape* s, const mi_eblock_params* p, const void* inp, const void* dout, void* dinp,
+                  const mi_eblock_grads* g, const void* saved, void* ws, void* stream);
+
+/* ------------------------------------------------------------------------
  * The other pixel-space loss terms of the reference's training steps (csrc/losses.hip), each with d loss / d pred from the same
  * call.  Conventions of mi_fft_l1_loss: fp32 arithmetic on inputs widened on load; dpred written in `dtype`, rounded once, NULL
  * skips every gradient stage; loss is device fp32 and overwritten; ws holds the matching *_workspace() bytes; no atomics,
