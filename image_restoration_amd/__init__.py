@@ -10,6 +10,7 @@ from .darkir import DarkIR, DBlock, EBlock, FreMLP  # noqa: F401
 from .ops import reload_env  # noqa: F401
 from .restormer import (Attention, Downsample, FeedForward, LayerNorm, OverlapPatchEmbed, Restormer,  # noqa: F401
                         TransformerBlock, Upsample)
+from .sfhformer import FourierUnit  # noqa: F401
 
-__all__ = ["Attention", "DarkIR", "DBlock", "Downsample", "EBlock", "FeedForward", "FreMLP", "LayerNorm", "OverlapPatchEmbed", "Restormer",
+__all__ = ["Attention", "DarkIR", "DBlock", "Downsample", "EBlock", "FeedForward", "FourierUnit", "FreMLP", "LayerNorm", "OverlapPatchEmbed", "Restormer",
            "TransformerBlock", "Upsample", "reload_env"]

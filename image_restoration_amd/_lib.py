@@ -190,6 +190,23 @@ class FremlpShape(C.Structure):
     _fields_ = [("B", C.c_int), ("nc", C.c_int), ("expand", C.c_int), ("H", C.c_int), ("W", C.c_int), ("dtype", C.c_int)]
 
 
+class FourierUnitShape(C.Structure):
+    _fields_ = [("B", C.c_int), ("c", C.c_int), ("groups", C.c_int), ("H", C.c_int), ("W", C.c_int), ("dtype", C.c_int),
+                ("training", C.c_int), ("eps", C.c_float), ("momentum", C.c_float)]
+
+
+# mi_fourier_unit_params / mi_fourier_unit_grads in field order
+FOURIER_UNIT_FIELDS = ("bn_w", "bn_b", "fdc_w", "fdc_b", "gate_w", "gate_b", "fpe_w", "fpe_b")
+
+
+class FourierUnitParams(C.Structure):
+    _fields_ = [(n, fp) for n in FOURIER_UNIT_FIELDS]
+
+
+class FourierUnitGrads(C.Structure):
+    _fields_ = [(n, fp) for n in FOURIER_UNIT_FIELDS] + [("accumulate", C.c_int)]
+
+
 class EblockShape(C.Structure):
     _fields_ = DblockShape._fields_
 
@@ -402,6 +419,12 @@ SIGNATURES = {
     "mi_fremlp_plan": (C.c_int, [C.POINTER(FremlpShape), C.POINTER(c_i64)]),
     "mi_fremlp_fwd": (C.c_int, [C.POINTER(FremlpShape), fp, fp, fp, fp, vp, vp, vp, vp, vp]),
     "mi_fremlp_bwd": (C.c_int, [C.POINTER(FremlpShape), fp, fp, fp, vp, vp, fp, fp, fp, fp, C.c_int, vp, vp, vp]),
+    "mi_fourier_unit_workspace": (C.c_size_t, [C.POINTER(FourierUnitShape)]),
+    "mi_fourier_unit_saved_bytes": (C.c_size_t, [C.POINTER(FourierUnitShape)]),
+    "mi_fourier_unit_plan": (C.c_int, [C.POINTER(FourierUnitShape), C.POINTER(c_i64)]),
+    "mi_fourier_unit_fwd": (C.c_int, [C.POINTER(FourierUnitShape), C.POINTER(FourierUnitParams), vp, vp, fp, fp, vp, vp, vp]),
+    "mi_fourier_unit_bwd": (C.c_int, [C.POINTER(FourierUnitShape), C.POINTER(FourierUnitParams), vp, vp, C.POINTER(FourierUnitGrads),
+                                      vp, vp, vp]),
     "mi_fregate_fwd": (C.c_int, [vp, vp, fp, vp, C.c_int, C.c_int, c_i64, C.c_int, vp]),
     "mi_fregate_bwd_workspace": (C.c_size_t, [C.c_int, C.c_int, c_i64]),
     "mi_fregate_bwd": (C.c_int, [vp, vp, vp, fp, vp, vp, fp, C.c_int, C.c_int, c_i64, C.c_int, C.c_int, vp, vp]),

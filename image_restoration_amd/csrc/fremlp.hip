@@ -258,6 +258,49 @@ int dft2_check(const char* who, int B, int C, int H, int W, int dtype, FrePlan* 
 }
 
 }  // namespace
+
+// ---- the four transform directions for other modules (internal.h): the launchers above, on a mi_dft2_workspace() blob ----
+size_t dft2_tables_bytes(int B, int C, int H, int W) {
+  FrePlan p;
+  return fre_plan(B, C, 1, H, W, false, &p) ? p.off[FS_T] : 0;
+}
+int dft2_tables(int B, int C, int H, int W, void* ws, hipStream_t st) {
+  FrePlan p;
+  MI_TRY(dft2_check("dft2_tables", B, C, H, W, MI_F32, &p));
+  return fre_tables(FreWs{p, (char*)ws}, st);
+}
+int dft2_r2c_run(const void* x, float* zre, float* zim, int B, int C, int H, int W, int dtype, void* ws, hipStream_t st) {
+  FrePlan p;
+  MI_TRY(dft2_check("dft2_r2c", B, C, H, W, dtype, &p));
+  const FreWs w = {p, (char*)ws};
+  float* tre = w.sec(FS_T); float* tim = tre + p.bins;
+  MI_TRY(fre_rows_fwd(w, x, w.sec(FS_CW), w.sec(FS_SW), tre, tim, dtype, st));
+  return fre_cols(w, -1.f, tre, tim, zre, zim, st);
+}
+int dft2_c2r_run(const float* yre, const float* yim, void* out, int B, int C, int H, int W, int dtype, void* ws, hipStream_t st) {
+  FrePlan p;
+  MI_TRY(dft2_check("dft2_c2r", B, C, H, W, dtype, &p));
+  const FreWs w = {p, (char*)ws};
+  float* tre = w.sec(FS_T); float* tim = tre + p.bins;
+  MI_TRY(fre_cols(w, 1.f, yre, yim, tre, tim, st));
+  return fre_rows_bwd(w, tre, tim, w.sec(FS_WCWT), w.sec(FS_WSWT), out, (float)(1.0 / ((double)H * W)), dtype, st);
+}
+int dft2_c2r_adj(const void* dout, float* gre, float* gim, int B, int C, int H, int W, int dtype, void* ws, hipStream_t st) {
+  FrePlan p;
+  MI_TRY(dft2_check("dft2_c2r_adj", B, C, H, W, dtype, &p));
+  const FreWs w = {p, (char*)ws};
+  float* tre = w.sec(FS_T); float* tim = tre + p.bins;
+  MI_TRY(fre_rows_fwd(w, dout, w.sec(FS_WCW), w.sec(FS_WSW), tre, tim, dtype, st));
+  return fre_cols(w, -1.f, tre, tim, gre, gim, st);
+}
+int dft2_r2c_adj(const float* dre, const float* dim, void* dx, int B, int C, int H, int W, int dtype, void* ws, hipStream_t st) {
+  FrePlan p;
+  MI_TRY(dft2_check("dft2_r2c_adj", B, C, H, W, dtype, &p));
+  const FreWs w = {p, (char*)ws};
+  float* tre = w.sec(FS_T); float* tim = tre + p.bins;
+  MI_TRY(fre_cols(w, 1.f, dre, dim, tre, tim, st));
+  return fre_rows_bwd(w, tre, tim, w.sec(FS_CWT), w.sec(FS_SWT), dx, 1.f, dtype, st);
+}
 }  // namespace mi
 
 using namespace mi;

@@ -1024,6 +1024,89 @@ def fremlp_bwd(dout: Tensor, params: Sequence[Tensor], saved: Tensor, grads: Seq
     return dx
 
 
+# ----------------------------------------------------------------------------- SFHformer: FourierUnit
+FOURIER_UNIT_MAX_C, FOURIER_UNIT_MAX_GROUPS = 256, 8
+_FU_PLAN_KEYS = ("planes", "K", "channels", "groups", "group_width", "elements", "bins", "block", "bn_chunk", "chunks_per_plane",
+                 "partials_per_channel", "grid_elements", "grid_bins", "kernels_fwd", "kernels_bwd", "lib_calls_fwd", "lib_calls_bwd")
+_FU_SECTIONS = ("dft_tables", "dft_T", "Z", "U", "t", "ts", "pre", "q", "s", "dlogit", "stat", "bn_partials", "w_fold", "grad_tmp", "bwd_partials",
+                "pw_ws", "gram_ws", "chan_sum_ws")
+
+
+def _fu_shape(B: int, c: int, groups: int, H: int, W: int, dtype_code: int, training: bool = True, eps: float = 1e-5,
+              momentum: float = 0.1) -> L.FourierUnitShape:
+    return L.FourierUnitShape(B, c, groups, H, W, dtype_code, int(training), eps, momentum)
+
+
+def fourier_unit_plan(B: int, c: int, groups: int, H: int, W: int, dtype: torch.dtype = torch.float32) -> dict:
+    """What fourier_unit_fwd / fourier_unit_bwd launch for x [B, c, H, W] (mi_fourier_unit_plan; no GPU work).  ``sections`` maps
+    each workspace section to its (byte offset, bytes)."""
+    out = (L.c_i64 * 64)()
+    s = _fu_shape(B, c, groups, H, W, _dtype_code(dtype))
+    L.check(L.lib().mi_fourier_unit_plan(C.byref(s), out), "fourier_unit_plan")
+    plan = {k: int(out[i]) for i, k in enumerate(_FU_PLAN_KEYS)}
+    plan["sections"] = {n: (int(out[18 + 2 * i]), int(out[19 + 2 * i])) for i, n in enumerate(_FU_SECTIONS)}
+    plan["workspace"], plan["saved_bytes"], plan["saved_stat_offset"] = int(out[60]), int(out[61]), int(out[62])
+    return plan
+
+
+def fourier_unit_sizes(B: int, c: int, groups: int, H: int, W: int, dtype: torch.dtype) -> Tuple[int, int]:
+    """(saved bytes, workspace bytes) of one FourierUnit; (0, 0) for a shape the kernels do not cover.  No GPU needed."""
+    s = _fu_shape(B, c, groups, H, W, _dtype_code(dtype))
+    return int(L.lib().mi_fourier_unit_saved_bytes(C.byref(s))), int(L.lib().mi_fourier_unit_workspace(C.byref(s)))
+
+
+def _fu_args(x: Tensor, params: Sequence[Tensor], training: bool, eps: float, momentum: float):
+    """params: bn.weight, bn.bias, fdc.weight, fdc.bias, the gate conv's weight and bias, fpe.weight, fpe.bias."""
+    bn_w, bn_b, fdc_w, fdc_b, gate_w, gate_b, fpe_w, fpe_b = params
+    if x.dim() != 4:
+        raise ValueError(f"fourier_unit: x must be [B, c, H, W], got {tuple(x.shape)}")
+    B, c, H, W = x.shape
+    G, C2 = gate_w.shape[0], 2 * c
+    if G < 1 or C2 % G or (bn_w.numel(), bn_b.numel(), fdc_b.numel(), gate_b.numel(), fpe_b.numel()) != (C2, C2, G * C2, G, C2) or \
+            tuple(fdc_w.shape[:2]) != (G * C2, C2 // G) or gate_w.numel() != G * C2 or fpe_w.numel() != 9 * C2:
+        raise ValueError(f"fourier_unit: parameters {[tuple(p.shape) for p in params]} do not fit c = {c}")
+    s = _fu_shape(B, c, G, H, W, _dt(x), training, eps, momentum)
+    ws_bytes = L.lib().mi_fourier_unit_workspace(C.byref(s))
+    if ws_bytes == 0:
+        raise NotImplementedError("image_restoration_amd: " + L.lib().mi_last_error().decode("utf-8", "replace"))
+    return s, ws_bytes
+
+
+def fourier_unit_fwd(x: Tensor, params: Sequence[Tensor], running_mean: Tensor, running_var: Tensor, training: bool,
+                     need_saved: bool, eps: float = 1e-5, momentum: float = 0.1):
+    """SFHformer FourierUnit.forward (see mi_restore.h).  ``running_mean`` / ``running_var`` [2c] fp32 are updated in place when
+    ``training``.  -> (out, saved)."""
+    _gpu(x, running_mean, running_var, *params)
+    for t in (*params, running_mean, running_var):
+        _f32(t, "FourierUnit parameter / running statistic")
+    s, ws_bytes = _fu_args(x, params, training, eps, momentum)
+    if running_mean.numel() != 2 * x.shape[1] or running_var.numel() != 2 * x.shape[1]:
+        raise ValueError("fourier_unit: the running statistics must hold 2c values")
+    lib = L.lib()
+    out = torch.empty_like(x)
+    saved = _blob(lib.mi_fourier_unit_saved_bytes(C.byref(s)), x.device) if need_saved else None
+    ws = _ws(ws_bytes, x.device)
+    pp = _f32_struct(L.FourierUnitParams, params, "FourierUnit parameter")
+    L.check(lib.mi_fourier_unit_fwd(C.byref(s), C.byref(pp), _p(x), _p(out), _p(running_mean), _p(running_var), _p(saved), _p(ws),
+                                    _stream()), "fourier_unit_fwd")
+    return out, saved
+
+
+def fourier_unit_bwd(dout: Tensor, params: Sequence[Tensor], saved: Tensor, grads: Sequence[Tensor], accumulate: bool,
+                     training: bool, eps: float = 1e-5, momentum: float = 0.1) -> Tensor:
+    """Backward of fourier_unit_fwd: dx; the eight parameter gradients are written (accumulate: added) into ``grads``."""
+    _gpu(dout, saved, *params, *grads)
+    s, ws_bytes = _fu_args(dout, params, training, eps, momentum)
+    lib = L.lib()
+    dx = torch.empty_like(dout)
+    ws = _ws(ws_bytes, dout.device)
+    pp = _f32_struct(L.FourierUnitParams, params, "FourierUnit parameter")
+    gg = _f32_struct(L.FourierUnitGrads, grads, "FourierUnit gradient", int(accumulate))
+    L.check(lib.mi_fourier_unit_bwd(C.byref(s), C.byref(pp), _p(dout), _p(dx), C.byref(gg), _p(saved), _p(ws), _stream()),
+            "fourier_unit_bwd")
+    return dx
+
+
 # ----------------------------------------------------------------------------- DarkIR: EBlock and its tail
 EBLOCK_MAX_C, EBLOCK_MIN_HW, EBLOCK_MAX_HW = 256, 2, FREMLP_MAX_HW
 _EBLOCK_PLAN_KEYS = ("x0_bytes", "xe_bytes", "x1_bytes", "g_bytes", "y_bytes", "f_bytes", "stats_bytes", "small_bytes",

@@ -1,0 +1,75 @@
+"""SFHformer's spectral token mixer core on the MI355X: ``FourierUnit`` (``SFHformer.py:143-180``) with the reference's constructor
+arguments and ``state_dict`` keys (``bn.*``, ``fdc.*``, ``weight.0.*``, ``fpe.*``), so a checkpoint slice loads with
+``strict=True``.
+
+``FourierUnit.forward`` is ONE autograd node over ``mi_fourier_unit_*`` (``csrc/sfh.hip``): ``rfft2`` and ``irfft2`` (``norm='ortho'``)
+as the dense-DFT GEMMs of ``csrc/fremlp.hip``, and between them BatchNorm over the interleaved real / imaginary channels (training
+or eval mode, running statistics updated on the device), the depthwise 3x3 with its residual, the softmax gate over the groups and
+the grouped 1x1 folded into one dense product, then GELU.  The submodules are parameter containers only.
+
+Limits: ``in_channels == out_channels`` (the reference's ``view`` and ``bn`` only work then; anything else raises
+``NotImplementedError``), 1 <= c <= 256, 1 <= groups <= 8 with 2c % groups == 0, planes of 2..512 pixels a side, fp32 or bf16
+activations; BatchNorm with running statistics and a fixed momentum.  CPU tensors are refused (``RuntimeError``).
+"""
+from __future__ import annotations
+
+import torch
+import torch.nn as nn
+
+from . import ops
+from ._autograd import module_op
+
+Tensor = torch.Tensor
+
+__all__ = ["FourierUnit"]
+
+
+class _FourierUnitOp:
+    """FourierUnit.forward as one module op.  params: bn, fdc, gate and fpe weights and biases; saved = [the kernels' blob]."""
+
+    def __init__(self, bn: nn.BatchNorm2d, training: bool):
+        self.rm, self.rv, self.training, self.eps, self.momentum = bn.running_mean, bn.running_var, training, bn.eps, bn.momentum
+
+    def forward(self, acts, params, need):
+        out, blob = ops.fourier_unit_fwd(acts[0], params, self.rm, self.rv, self.training, need, self.eps, self.momentum)
+        return out, [blob]
+
+    def backward(self, acts, saved, dout, params, grads, acc):
+        return (ops.fourier_unit_bwd(dout, params, saved[0], grads, acc, self.training, self.eps, self.momentum),)
+
+
+class FourierUnit(nn.Module):
+    """irfft2(gelu(sum_g softmax_g(weight(t)) fdc_g(t))), t = fpe(bn(Z)) + bn(Z), Z = rfft2(x) with its real and imaginary parts
+    as interleaved channels (both transforms ``norm='ortho'``)."""
+
+    def __init__(self, in_channels, out_channels, groups=4):
+        super().__init__()
+        if in_channels != out_channels:
+            raise NotImplementedError(f"image_restoration_amd: FourierUnit(in_channels={in_channels!r}, out_channels={out_channels!r}) "
+                                      "not covered: the unit is defined for in_channels == out_channels only")
+        c = in_channels
+        if not (isinstance(c, int) and isinstance(groups, int) and 1 <= c <= ops.FOURIER_UNIT_MAX_C and
+                1 <= groups <= ops.FOURIER_UNIT_MAX_GROUPS and (2 * c) % groups == 0):
+            raise NotImplementedError(f"image_restoration_amd: FourierUnit(in_channels={c!r}, groups={groups!r}) not covered; the "
+                                      f"kernels were built for 1 <= channels <= {ops.FOURIER_UNIT_MAX_C}, 1 <= groups <= "
+                                      f"{ops.FOURIER_UNIT_MAX_GROUPS}, 2 * channels a multiple of groups")
+        self.groups = groups
+        self.bn = nn.BatchNorm2d(2 * c)
+        self.fdc = nn.Conv2d(2 * c, 2 * c * groups, 1, 1, 0, groups=groups, bias=True)
+        self.weight = nn.Sequential(nn.Conv2d(2 * c, groups, 1, 1, 0), nn.Softmax(dim=1))
+        self.fpe = nn.Conv2d(2 * c, 2 * c, 3, 1, 1, groups=2 * c, bias=True)
+
+    def forward(self, x):
+        bn = self.bn
+        if not (bn.track_running_stats and bn.affine and bn.momentum is not None and bn.running_mean is not None):
+            raise NotImplementedError("image_restoration_amd: FourierUnit's BatchNorm runs affine, with running statistics and a "
+                                      "fixed momentum (the form the kernels were built for)")
+        ops._gpu(x)
+        training = bool(bn.training)
+        gate = self.weight[0]
+        out = module_op(_FourierUnitOp(bn, training), (x,), (bn.weight, bn.bias, self.fdc.weight, self.fdc.bias, gate.weight, gate.bias,
+                                                             self.fpe.weight, self.fpe.bias))
+        if training:
+            with torch.no_grad():
+                bn.num_batches_tracked += 1
+        return out

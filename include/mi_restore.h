@@ -920,6 +920,58 @@ int mi_fremlp_bwd(const mi_fremlp_shape* s, const float* w1, const float* w2, co
                   float* g_w1, float* g_b1, float* g_w2, float* g_b2, int accumulate, const void* saved, void* ws, void* stream);
 
 /* ------------------------------------------------------------------------
+ * SFHformer's FourierUnit (SFHformer.py:143-180; csrc/sfh.hip): BatchNorm, a depthwise 3x3 with residual, a softmax gate over G
+ * groups, a grouped 1x1 and GELU, all on the half spectrum between rfft2 and irfft2 (norm='ortho'), fp32 between the input load
+ * and the output store.  c = in_channels = out_channels, C2 = 2c, K = W/2 + 1, S = C2 / G; the reference's interleaved spectral
+ * channel j = 2i + d is Re Z_i (d = 0) / Im Z_i (d = 1): pure indexing on the planar spectra of mi_dft2_r2c, no copy is made.
+ *   t1 = BatchNorm(Z / sqrt(HW))   bn_w, bn_b, running_mean, running_var [C2].  Training: the batch mean and biased variance over
+ *        the B H K bins of each channel normalise, and running_mean <- (1 - momentum) rm + momentum mean, running_var <-
+ *        (1 - momentum) rv + momentum var n / (n - 1), in place, on the device, in the same launch sequence (num_batches_tracked is
+ *        the caller's).  Eval: the running statistics normalise, nothing is updated.  The ortho scale is folded in exactly: with
+ *        mu, var of the unscaled Z,  xhat = (z - mu) alpha / sqrt(alpha^2 var + eps), alpha = 1 / sqrt(HW): eps is not rescaled.
+ *        The variance is a fixed-order merge of per-chunk (mean, sum of squared deviations from that mean) pairs: no difference of
+ *        large sums, no atomics.
+ *   t  = fpe(t1) + t1              fpe_w [C2, 9], fpe_b [C2]: depthwise 3x3, zero padding 1, over the (H, K) plane
+ *   s  = softmax_g(gate_w t + gate_b)   gate_w [G, C2], gate_b [G]  (the reference's `weight.0`)
+ *   pre[k] = sum_j W'[k, j] s_{j / S} t[j] + sum_g s_g fdc_b[g C2 + k],  W'[k, g S + jl] = fdc_w[g C2 + k, jl]   (fdc_w [G C2, S]):
+ *        the grouped 1x1 and the gate-weighted sum over groups as ONE C2 x C2 product on the gate-scaled input (mi_pw_gemm at
+ *        fp32); the [B, G C2, H, K] tensor is never formed, forward or backward.
+ *   out = irfft2(gelu_erf(pre), s=(H,W), norm='ortho')   (mi_dft2_c2r's formula: the parts irfft2 drops are dropped)
+ *   backward   dx and all eight parameter gradients (added to when g->accumulate, else overwritten); BatchNorm's backward in the
+ *        full training form (mean(dy), mean(dy xhat)) when `training`, the plain affine form otherwise.
+ *   saved      mi_fourier_unit_saved_bytes(): Z (fp32, 2 floats per bin and channel) and the per-channel (mu, r); t, s, the gate-
+ *        scaled input and pre are recomputed by the forward's own kernels.  saved == NULL in _fwd: inference or no_grad, nothing is
+ *        kept (the running statistics are still updated when `training`).
+ * Limits: 2 <= H, W <= 512, 1 <= c <= 256, 1 <= groups <= 8 with 2c % groups == 0 (c % groups != 0 is fine), fp32 or bf16,
+ * B 2c H K below 2^31, eps > 0, 0 <= momentum <= 1.  Anything else is refused before any launch; the sizing calls return 0.
+ * Bitwise reproducible (no atomics, fixed-order sums).  No allocation, no host synchronisation.
+ * mi_fourier_unit_plan (host-only; the launchers and the sizing calls read the same plan) fills out[64]: planes B c, K, 2c, groups,
+ * S, elements B 2c H K, bins B H K, threads per workgroup, bins per BatchNorm chunk, chunks per plane, partials per channel, grids
+ * of the per-element and the per-bin passes, own kernel launches forward / backward, library calls (1x1 product, Gram, channel
+ * sum) forward / backward, 0; then (byte offset, bytes) of the 18 workspace sections [18..53]: the transforms' tables and their complex intermediate, Z (used
+ * when nothing is saved), the complex plane the transforms read / write, t, the gate-scaled input (later dt1), pre (later dpre),
+ * W'^T dpre (later dt), s, dlogit, the statistics, the BatchNorm partials, W', the three gradient matrices, the fpe / BatchNorm
+ * backward partials, the 1x1 / Gram / channel-sum workspaces; the workspace size [60], the saved blob's size [61], the offset of
+ * (mu, r) in it [62]; 0.
+ * ------------------------------------------------------------------------ */
+typedef struct { int B, c, groups, H, W, dtype, training; float eps, momentum; } mi_fourier_unit_shape;
+typedef struct {
+  const float* bn_w; const float* bn_b; const float* fdc_w; const float* fdc_b; const float* gate_w; const float* gate_b;
+  const float* fpe_w; const float* fpe_b;
+} mi_fourier_unit_params;
+typedef struct {
+  float* bn_w; float* bn_b; float* fdc_w; float* fdc_b; float* gate_w; float* gate_b; float* fpe_w; float* fpe_b;
+  int accumulate;
+} mi_fourier_unit_grads;
+size_t mi_fourier_unit_workspace(const mi_fourier_unit_shape* s);
+size_t mi_fourier_unit_saved_bytes(const mi_fourier_unit_shape* s);
+int mi_fourier_unit_plan(const mi_fourier_unit_shape* s, int64_t* out);
+int mi_fourier_unit_fwd(const mi_fourier_unit_shape* s, const mi_fourier_unit_params* p, const void* x, void* out,
+                        float* running_mean, float* running_var, void* saved, void* ws, void* stream);
+int mi_fourier_unit_bwd(const mi_fourier_unit_shape* s, const mi_fourier_unit_params* p, const void* dout, void* dx,
+                        const mi_fourier_unit_grads* g, const void* saved, void* ws, void* stream);
+
+/* ------------------------------------------------------------------------
  * DarkIR — the encoder block (DarkIR-main/archs/arch_model.py:141-204 EBlock) and its tail (csrc/darkir.hip).
  *
  * fregate: the block's last line, y + gamma (y f), as one streaming pass.  y, f, out [B,C,N] in `dtype`, gamma [C] fp32, fp32
