@@ -207,6 +207,35 @@ class FourierUnitGrads(C.Structure):
     _fields_ = [(n, fp) for n in FOURIER_UNIT_FIELDS] + [("accumulate", C.c_int)]
 
 
+class SfhFfnShape(C.Structure):
+    _fields_ = [("B", C.c_int), ("dim", C.c_int), ("H", C.c_int), ("W", C.c_int), ("dtype", C.c_int)]
+
+
+# mi_sfh_ffn_params / mi_sfh_ffn_grads and mi_sfh_local_params / mi_sfh_local_grads in field order
+SFH_FFN_FIELDS = ("init_w", "init_b", "c1_w", "c1_b", "c2_w", "c2_b", "c3_w", "c3_b", "fina_w", "fina_b")
+SFH_LOCAL_FIELDS = ("cd1_w", "cd1_b", "cd2_w", "cd2_b")
+
+
+class SfhFfnParams(C.Structure):
+    _fields_ = [(n, fp) for n in SFH_FFN_FIELDS]
+
+
+class SfhFfnGrads(C.Structure):
+    _fields_ = [(n, fp) for n in SFH_FFN_FIELDS] + [("accumulate", C.c_int)]
+
+
+class SfhLocalShape(C.Structure):
+    _fields_ = SfhFfnShape._fields_
+
+
+class SfhLocalParams(C.Structure):
+    _fields_ = [(n, fp) for n in SFH_LOCAL_FIELDS]
+
+
+class SfhLocalGrads(C.Structure):
+    _fields_ = [(n, fp) for n in SFH_LOCAL_FIELDS] + [("accumulate", C.c_int)]
+
+
 class EblockShape(C.Structure):
     _fields_ = DblockShape._fields_
 
@@ -425,6 +454,15 @@ SIGNATURES = {
     "mi_fourier_unit_fwd": (C.c_int, [C.POINTER(FourierUnitShape), C.POINTER(FourierUnitParams), vp, vp, fp, fp, vp, vp, vp]),
     "mi_fourier_unit_bwd": (C.c_int, [C.POINTER(FourierUnitShape), C.POINTER(FourierUnitParams), vp, vp, C.POINTER(FourierUnitGrads),
                                       vp, vp, vp]),
+    "mi_sfh_ffn_workspace": (C.c_size_t, [C.POINTER(SfhFfnShape)]),
+    "mi_sfh_ffn_saved_bytes": (C.c_size_t, [C.POINTER(SfhFfnShape)]),
+    "mi_sfh_ffn_plan": (C.c_int, [C.POINTER(SfhFfnShape), C.POINTER(c_i64)]),
+    "mi_sfh_ffn_fwd": (C.c_int, [C.POINTER(SfhFfnShape), C.POINTER(SfhFfnParams), vp, vp, vp, vp, vp]),
+    "mi_sfh_ffn_bwd": (C.c_int, [C.POINTER(SfhFfnShape), C.POINTER(SfhFfnParams), vp, vp, vp, C.POINTER(SfhFfnGrads), vp, vp, vp]),
+    "mi_sfh_local_workspace": (C.c_size_t, [C.POINTER(SfhLocalShape)]),
+    "mi_sfh_local_plan": (C.c_int, [C.POINTER(SfhLocalShape), C.POINTER(c_i64)]),
+    "mi_sfh_local_fwd": (C.c_int, [C.POINTER(SfhLocalShape), C.POINTER(SfhLocalParams), vp, vp, vp, vp]),
+    "mi_sfh_local_bwd": (C.c_int, [C.POINTER(SfhLocalShape), C.POINTER(SfhLocalParams), vp, vp, vp, C.POINTER(SfhLocalGrads), vp, vp]),
     "mi_fregate_fwd": (C.c_int, [vp, vp, fp, vp, C.c_int, C.c_int, c_i64, C.c_int, vp]),
     "mi_fregate_bwd_workspace": (C.c_size_t, [C.c_int, C.c_int, c_i64]),
     "mi_fregate_bwd": (C.c_int, [vp, vp, vp, fp, vp, vp, fp, C.c_int, C.c_int, c_i64, C.c_int, C.c_int, vp, vp]),

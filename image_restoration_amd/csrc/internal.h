@@ -90,6 +90,22 @@ int launch_msfn_s1_bwd(const void* dza, const void* dzb, const void* h0, const f
                        hipStream_t st);
 size_t chan_sum_workspace(int C, int64_t N);
 int launch_chan_sum(const void* x, float* out, int B, int C, int64_t N, int dtype, int accumulate, void* ws, hipStream_t st);
+#if defined(__HIPCC__)
+// Sums NV per-thread values over a workgroup of 256 threads (wave DPP sums, then the 4 waves in order: a fixed order, bitwise
+// reproducible); thread n < NV gets total n.  red: 4 * NV floats of LDS.  Used by the stencil backwards (msfn.hip, sfh_ffn.hip).
+template <int NV>
+__device__ __forceinline__ float block_sum4(const float (&v)[NV], float* red) {
+  const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
+#pragma unroll
+  for (int n = 0; n < NV; ++n) {
+    const float s = wave_sum(v[n]);
+    if (lane == 0) red[wv * NV + n] = s;
+  }
+  __syncthreads();
+  const int n = threadIdx.x;
+  return n < NV ? (red[n] + red[NV + n]) + (red[2 * NV + n] + red[3 * NV + n]) : 0.f;
+}
+#endif
 
 // ---- depthwise convolution (dwconv.hip: LDS-tiled k x k; dwstream.hip: register-streaming 3x3) ----
 enum { IN_PLAIN = 0, IN_GATE_BWD = 1 };

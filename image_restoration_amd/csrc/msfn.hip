@@ -45,20 +45,6 @@ __device__ __forceinline__ int64_t ms_src(int br, int k, int hd, int b, int64_t 
   return ((int64_t)b * C2 + br * hd + (from_b ? k - hd : k)) * N;
 }
 
-// Sums NV per-thread values over the workgroup (wave DPP sums, then the 4 waves in order); thread n < NV gets total n.
-template <int NV>
-__device__ __forceinline__ float ms_block_sum(const float (&v)[NV], float* red) {
-  const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
-#pragma unroll
-  for (int n = 0; n < NV; ++n) {
-    const float s = wave_sum(v[n]);
-    if (lane == 0) red[wv * NV + n] = s;
-  }
-  __syncthreads();
-  const int n = threadIdx.x;
-  return n < NV ? (red[n] + red[NV + n]) + (red[2 * NV + n] + red[3 * NV + n]) : 0.f;
-}
-
 // ------------------------------------------------------------------ stage 1
 template <typename T>
 __global__ __launch_bounds__(256) void msfn_s1_fwd_kernel(const T* __restrict__ h0, const float* __restrict__ w3,
@@ -139,7 +125,7 @@ __global__ __launch_bounds__(256) void msfn_s1_bwd_kernel(const T* __restrict__ 
       st1(dh0 + po + (int64_t)y * W + x, dh);
     }
   }
-  const float tot = ms_block_sum<36>(acc, red);
+  const float tot = block_sum4<36>(acc, red);
   const int n = threadIdx.x;
   const int64_t row = (int64_t)b * splits + split;
   if (n < 9) p3[row * C2 * 9 + ch * 9 + n] = tot;
@@ -228,7 +214,7 @@ __device__ __forceinline__ void ms_s2_bwd_body(float* L, float* red, const T* __
       }
     }
   }
-  const float tot = ms_block_sum<NV>(acc, red);
+  const float tot = block_sum4<NV>(acc, red);
   const int n = threadIdx.x;
   if (n < 2 * K2) pw[n] = tot;
   else if (n == 2 * K2) pb[0] = tot;

@@ -1107,6 +1107,112 @@ def fourier_unit_bwd(dout: Tensor, params: Sequence[Tensor], saved: Tensor, grad
     return dx
 
 
+# ----------------------------------------------------------------------------- SFHformer: FFN and TokenMixer_For_Local
+SFH_FFN_MAX_DIM = 256
+_SF_PLAN_KEYS = ("tile_w", "tile_h", "segments", "segment_width", "halo0", "halo1", "halo2", "halo3", "tiles_x", "tiles_y", "grid_x",
+                 "grid_y", "grid_z", "splits", "partial_rows", "partial_cols", "kernels_fwd", "kernels_bwd", "lib_calls_fwd",
+                 "lib_calls_bwd", "lds_fwd", "lds_bwd", "block")
+_SF_SECTIONS = ("pw_ws", "gram_ws", "chan_sum_ws", "partials", "g", "dg", "dh")
+
+
+def _sf_plan(fn, shape, who: str) -> dict:
+    out = (L.c_i64 * 64)()
+    L.check(fn(C.byref(shape), out), who)
+    plan = {k: int(out[i]) for i, k in enumerate(_SF_PLAN_KEYS)}
+    plan["halo"] = tuple(plan.pop(f"halo{k}") for k in range(4))[:plan["segments"]]
+    plan["sections"] = {n: (int(out[24 + 2 * i]), int(out[25 + 2 * i])) for i, n in enumerate(_SF_SECTIONS)}
+    plan["workspace"], plan["saved_bytes"], plan["saved_u_offset"] = int(out[60]), int(out[61]), int(out[62])
+    return plan
+
+
+def sfh_ffn_plan(B: int, dim: int, H: int, W: int, dtype: torch.dtype = torch.float32) -> dict:
+    """What sfh_ffn_fwd / sfh_ffn_bwd launch for x [B, dim, H, W] (mi_sfh_ffn_plan; no GPU work): the tile, the halo per segment,
+    grids, backward splits, partial rows, launch counts; ``sections`` maps each workspace section to its (byte offset, bytes)."""
+    return _sf_plan(L.lib().mi_sfh_ffn_plan, L.SfhFfnShape(B, dim, H, W, _dtype_code(dtype)), "sfh_ffn_plan")
+
+
+def sfh_local_plan(B: int, dim: int, H: int, W: int, dtype: torch.dtype = torch.float32) -> dict:
+    """The same for sfh_local_fwd / sfh_local_bwd (mi_sfh_local_plan); its workspace holds the partial rows only."""
+    return _sf_plan(L.lib().mi_sfh_local_plan, L.SfhLocalShape(B, dim, H, W, _dtype_code(dtype)), "sfh_local_plan")
+
+
+def sfh_ffn_sizes(B: int, dim: int, H: int, W: int, dtype: torch.dtype) -> Tuple[int, int]:
+    """(saved bytes, workspace bytes) of one SFHformer FFN; (0, 0) for a shape the kernels do not cover.  No GPU needed."""
+    s = L.SfhFfnShape(B, dim, H, W, _dtype_code(dtype))
+    return int(L.lib().mi_sfh_ffn_saved_bytes(C.byref(s))), int(L.lib().mi_sfh_ffn_workspace(C.byref(s)))
+
+
+def _sf_args(x: Tensor, params: Sequence[Tensor], local: bool):
+    if x.dim() != 4:
+        raise ValueError(f"sfh: x must be [B, dim, H, W], got {tuple(x.shape)}")
+    B, dim, H, W = x.shape
+    s = dim // 2
+    if local:
+        want = [(s, 1, 3, 3), (s,), (s, 1, 3, 3), (s,)]
+    else:
+        want = [(2 * dim, dim, 1, 1), (2 * dim,), (s, 1, 3, 3), (s,), (s, 1, 5, 5), (s,), (s, 1, 7, 7), (s,), (dim, 2 * dim, 1, 1), (dim,)]
+    if dim % 2 == 0 and [tuple(p.shape) for p in params] != want:
+        raise ValueError(f"sfh: parameters {[tuple(p.shape) for p in params]} do not fit dim = {dim}")
+    lib = L.lib()
+    shape = (L.SfhLocalShape if local else L.SfhFfnShape)(B, dim, H, W, _dt(x))
+    ws_bytes = (lib.mi_sfh_local_workspace if local else lib.mi_sfh_ffn_workspace)(C.byref(shape))
+    if ws_bytes == 0:
+        raise NotImplementedError("image_restoration_amd: " + lib.mi_last_error().decode("utf-8", "replace"))
+    return shape, ws_bytes
+
+
+def sfh_ffn_fwd(x: Tensor, params: Sequence[Tensor], need_saved: bool):
+    """SFHformer FFN.forward (see mi_restore.h).  params: conv_init, conv1_1, conv1_2, conv1_3, conv_fina weights and biases.
+    -> (out, saved): the blob holds h and u in x's dtype."""
+    _gpu(x, *params)
+    s, ws_bytes = _sf_args(x, params, False)
+    lib = L.lib()
+    out = torch.empty_like(x)
+    saved = _blob(lib.mi_sfh_ffn_saved_bytes(C.byref(s)), x.device) if need_saved else None
+    ws = _ws(ws_bytes, x.device)
+    pp = _f32_struct(L.SfhFfnParams, params, "SFHformer FFN parameter")
+    L.check(lib.mi_sfh_ffn_fwd(C.byref(s), C.byref(pp), _p(x), _p(out), _p(saved), _p(ws), _stream()), "sfh_ffn_fwd")
+    return out, saved
+
+
+def sfh_ffn_bwd(x: Tensor, dout: Tensor, params: Sequence[Tensor], saved: Tensor, grads: Sequence[Tensor], accumulate: bool) -> Tensor:
+    """Backward of sfh_ffn_fwd: dx; the ten parameter gradients are written (accumulate: added) into ``grads``."""
+    _gpu(x, dout, saved, *params, *grads)
+    s, ws_bytes = _sf_args(x, params, False)
+    lib = L.lib()
+    dx = torch.empty_like(x)
+    ws = _ws(ws_bytes, x.device)
+    pp = _f32_struct(L.SfhFfnParams, params, "SFHformer FFN parameter")
+    gg = _f32_struct(L.SfhFfnGrads, grads, "SFHformer FFN gradient", int(accumulate))
+    L.check(lib.mi_sfh_ffn_bwd(C.byref(s), C.byref(pp), _p(x), _p(dout), _p(dx), C.byref(gg), _p(saved), _p(ws), _stream()),
+            "sfh_ffn_bwd")
+    return dx
+
+
+def sfh_local_fwd(x: Tensor, params: Sequence[Tensor]) -> Tensor:
+    """SFHformer TokenMixer_For_Local.forward.  params: CDilated_1 and CDilated_2 weights and biases.  Saves nothing but x."""
+    _gpu(x, *params)
+    s, ws_bytes = _sf_args(x, params, True)
+    out = torch.empty_like(x)
+    ws = _ws(ws_bytes, x.device)
+    pp = _f32_struct(L.SfhLocalParams, params, "SFHformer local mixer parameter")
+    L.check(L.lib().mi_sfh_local_fwd(C.byref(s), C.byref(pp), _p(x), _p(out), _p(ws), _stream()), "sfh_local_fwd")
+    return out
+
+
+def sfh_local_bwd(x: Tensor, dout: Tensor, params: Sequence[Tensor], grads: Sequence[Tensor], accumulate: bool) -> Tensor:
+    """Backward of sfh_local_fwd: dx; the four parameter gradients are written (accumulate: added) into ``grads``."""
+    _gpu(x, dout, *params, *grads)
+    s, ws_bytes = _sf_args(x, params, True)
+    dx = torch.empty_like(x)
+    ws = _ws(ws_bytes, x.device)
+    pp = _f32_struct(L.SfhLocalParams, params, "SFHformer local mixer parameter")
+    gg = _f32_struct(L.SfhLocalGrads, grads, "SFHformer local mixer gradient", int(accumulate))
+    L.check(L.lib().mi_sfh_local_bwd(C.byref(s), C.byref(pp), _p(x), _p(dout), _p(dx), C.byref(gg), _p(ws), _stream()),
+            "sfh_local_bwd")
+    return dx
+
+
 # ----------------------------------------------------------------------------- DarkIR: EBlock and its tail
 EBLOCK_MAX_C, EBLOCK_MIN_HW, EBLOCK_MAX_HW = 256, 2, FREMLP_MAX_HW
 _EBLOCK_PLAN_KEYS = ("x0_bytes", "xe_bytes", "x1_bytes", "g_bytes", "y_bytes", "f_bytes", "stats_bytes", "small_bytes",

@@ -1,4 +1,7 @@
-"""SFHformer's spectral token mixer core on the MI355X: ``FourierUnit`` (``SFHformer.py:143-180``) with the reference's constructor
+"""SFHformer on the MI355X, the pieces built so far: the spectral token mixer core ``FourierUnit``, the feed-forward ``FFN`` and the
+local token mixer ``TokenMixer_For_Local`` (below).
+
+``FourierUnit`` (``SFHformer.py:143-180``) with the reference's constructor
 arguments and ``state_dict`` keys (``bn.*``, ``fdc.*``, ``weight.0.*``, ``fpe.*``), so a checkpoint slice loads with
 ``strict=True``.
 
@@ -10,6 +13,12 @@ the grouped 1x1 folded into one dense product, then GELU.  The submodules are pa
 Limits: ``in_channels == out_channels`` (the reference's ``view`` and ``bn`` only work then; anything else raises
 ``NotImplementedError``), 1 <= c <= 256, 1 <= groups <= 8 with 2c % groups == 0, planes of 2..512 pixels a side, fp32 or bf16
 activations; BatchNorm with running statistics and a fixed momentum.  CPU tensors are refused (``RuntimeError``).
+
+``FFN(dim)`` (``SFHformer.py:76-119``, keys ``conv_init.0.*``, ``conv1_1.0.*``, ``conv1_2.0.*``, ``conv1_3.0.*``, ``conv_fina.0.*``) and
+``TokenMixer_For_Local(dim)`` (``:122-140``, keys ``CDilated_1.*``, ``CDilated_2.*``) are each ONE autograd node over ``mi_sfh_ffn_*`` /
+``mi_sfh_local_*`` (``csrc/sfh_ffn.hip``): the channel axis in segments of ``dim / 2`` channels, each with its own depthwise stencil
+(identity, 3x3, 5x5, 7x7 and erf-GELU between two biased 1x1 products; 3x3 at dilation 1 and 2).  Limits: ``dim`` even (an odd
+``dim`` changes the reference's chunk count: ``NotImplementedError``), 2 <= dim <= 256, any plane, fp32 or bf16 activations.
 """
 from __future__ import annotations
 
@@ -21,7 +30,7 @@ from ._autograd import module_op
 
 Tensor = torch.Tensor
 
-__all__ = ["FourierUnit"]
+__all__ = ["FFN", "FourierUnit", "TokenMixer_For_Local"]
 
 
 class _FourierUnitOp:
@@ -73,3 +82,67 @@ class FourierUnit(nn.Module):
             with torch.no_grad():
                 bn.num_batches_tracked += 1
         return out
+
+
+def _check_dim(name, dim):
+    if not (isinstance(dim, int) and 2 <= dim <= ops.SFH_FFN_MAX_DIM and dim % 2 == 0):
+        raise NotImplementedError(f"image_restoration_amd: {name}(dim={dim!r}) not covered; the kernels were built for even "
+                                  f"2 <= dim <= {ops.SFH_FFN_MAX_DIM} (an odd dim changes the reference's chunk count)")
+
+
+class _FfnOp:
+    """FFN.forward as one module op.  params: ops.sfh_ffn_fwd; saved = [the kernels' blob (h, u)]."""
+
+    def forward(self, acts, params, need):
+        out, blob = ops.sfh_ffn_fwd(acts[0], params, need)
+        return out, [blob]
+
+    def backward(self, acts, saved, dout, params, grads, acc):
+        return (ops.sfh_ffn_bwd(acts[0], dout, params, saved[0], grads, acc),)
+
+
+class _LocalOp:
+    """TokenMixer_For_Local.forward as one module op.  params: ops.sfh_local_fwd; nothing is saved beyond the input."""
+
+    def forward(self, acts, params, need):
+        return ops.sfh_local_fwd(acts[0], params), []
+
+    def backward(self, acts, saved, dout, params, grads, acc):
+        return (ops.sfh_local_bwd(acts[0], dout, params, grads, acc),)
+
+
+class FFN(nn.Module):
+    """conv_fina(gelu(cat(h_0, conv1_1(h_1), conv1_2(h_2), conv1_3(h_3)))), h = conv_init(x) split into four dim/2-wide segments."""
+
+    def __init__(self, dim):
+        super().__init__()
+        _check_dim("FFN", dim)
+        self.dim, self.dim_sp = dim, dim // 2
+        sp = self.dim_sp
+        self.conv_init = nn.Sequential(nn.Conv2d(dim, dim * 2, 1))
+        self.conv1_1 = nn.Sequential(nn.Conv2d(sp, sp, kernel_size=3, padding=1, groups=sp))
+        self.conv1_2 = nn.Sequential(nn.Conv2d(sp, sp, kernel_size=5, padding=2, groups=sp))
+        self.conv1_3 = nn.Sequential(nn.Conv2d(sp, sp, kernel_size=7, padding=3, groups=sp))
+        self.gelu = nn.GELU()
+        self.conv_fina = nn.Sequential(nn.Conv2d(dim * 2, dim, 1))
+
+    def forward(self, x):
+        ops._gpu(x)
+        convs = (self.conv_init[0], self.conv1_1[0], self.conv1_2[0], self.conv1_3[0], self.conv_fina[0])
+        return module_op(_FfnOp(), (x,), tuple(t for c in convs for t in (c.weight, c.bias)))
+
+
+class TokenMixer_For_Local(nn.Module):
+    """cat(CDilated_1(x[:, :dim/2]), CDilated_2(x[:, dim/2:])): depthwise 3x3 at dilation 1 and at dilation 2."""
+
+    def __init__(self, dim):
+        super().__init__()
+        _check_dim("TokenMixer_For_Local", dim)
+        self.dim, self.dim_sp = dim, dim // 2
+        sp = self.dim_sp
+        self.CDilated_1 = nn.Conv2d(sp, sp, 3, stride=1, padding=1, dilation=1, groups=sp)
+        self.CDilated_2 = nn.Conv2d(sp, sp, 3, stride=1, padding=2, dilation=2, groups=sp)
+
+    def forward(self, x):
+        ops._gpu(x)
+        return module_op(_LocalOp(), (x,), (self.CDilated_1.weight, self.CDilated_1.bias, self.CDilated_2.weight, self.CDilated_2.bias))

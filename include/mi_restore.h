@@ -972,6 +972,56 @@ int mi_fourier_unit_bwd(const mi_fourier_unit_shape* s, const mi_fourier_unit_pa
                         const mi_fourier_unit_grads* g, const void* saved, void* ws, void* stream);
 
 /* ------------------------------------------------------------------------
+ * SFHformer — FFN (SFHformer.py:76-119) and TokenMixer_For_Local (:122-140) over one "segmented depthwise" kernel family
+ * (csrc/sfh_ffn.hip): the channel axis is cut into equal segments of s = dim/2 channels, each with its own depthwise stencil
+ * (zero padding dil (ks - 1) / 2, weights [s,1,ks,ks], biases [s], fp32) or none.
+ *   FFN    x [B,dim,H,W] -> h = conv_init(x) [B,2dim,H,W] (biased 1x1) -> u = (identity | 3x3 | 5x5 | 7x7)(h) over four segments
+ *          -> g = gelu_erf(u) -> out = conv_fina(g) [B,dim,H,W] (biased 1x1).
+ *          saved: mi_sfh_ffn_saved_bytes(): h and u in the activation dtype, nothing else; saved == NULL in _fwd (inference,
+ *          no_grad): nothing is kept and u is never written.  g, dg = W2^T dout and dh live in the workspace; the backward's
+ *          stencil kernel multiplies dg by gelu_erf'(u) while staging it, and writes g again for the weight gradient of conv_fina.
+ *   local  x [B,dim,H,W] -> cat(3x3 dilation 1 (x[:, :s]), 3x3 dilation 2 (x[:, s:])); no activation; it saves nothing but x.
+ * Backward: dx and every parameter gradient (added to when g->accumulate, else overwritten); the stencil gradients are
+ * per-workgroup partial rows summed in a fixed order: no atomics, bitwise reproducible.  No allocation, no host synchronisation.
+ * Limits: dim even, 2 <= dim <= 256 (an odd dim changes the reference's chunk count: not covered), B, H, W >= 1, B <= 65535,
+ * B 2dim H W below 2^31, fp32 or bf16.  Anything else is refused before any launch; the sizing calls return 0.
+ * The plan calls (host-only; the launchers and the sizing calls read the same plan) fill out[64]: tile width, tile height,
+ * segments, segment width s, the halo of segments 0..3 [4..7], tiles across, tiles down, forward grid x / y / z [10..12],
+ * backward splits (workgroups per plane, each walks every splits-th tile), partial rows B splits, partial columns, own kernel
+ * launches forward / backward [16, 17], library calls (1x1 product, Gram, channel sum) forward / backward [18, 19], static LDS
+ * bytes forward / backward [20, 21], threads per workgroup [22], 0; then (byte offset, bytes) of the workspace sections
+ * [24..37]: the 1x1, Gram and channel-sum workspaces, the partial rows, g, dg (inference: h), dh (the local mixer: the partial
+ * rows only, the others 0, 0); the workspace size [60], the saved blob's size [61], the offset of u in it [62] (h sits at 0); 0.
+ * ------------------------------------------------------------------------ */
+typedef struct { int B, dim, H, W, dtype; } mi_sfh_ffn_shape;
+typedef struct {
+  const float* init_w; const float* init_b;   /* conv_init.0  [2dim,dim], [2dim] */
+  const float* c1_w; const float* c1_b;       /* conv1_1.0    [s,1,3,3], [s] */
+  const float* c2_w; const float* c2_b;       /* conv1_2.0    [s,1,5,5], [s] */
+  const float* c3_w; const float* c3_b;       /* conv1_3.0    [s,1,7,7], [s] */
+  const float* fina_w; const float* fina_b;   /* conv_fina.0  [dim,2dim], [dim] */
+} mi_sfh_ffn_params;
+typedef struct {
+  float* init_w; float* init_b; float* c1_w; float* c1_b; float* c2_w; float* c2_b; float* c3_w; float* c3_b; float* fina_w;
+  float* fina_b; int accumulate;
+} mi_sfh_ffn_grads;
+size_t mi_sfh_ffn_workspace(const mi_sfh_ffn_shape* s);
+size_t mi_sfh_ffn_saved_bytes(const mi_sfh_ffn_shape* s);
+int mi_sfh_ffn_plan(const mi_sfh_ffn_shape* s, int64_t* out);
+int mi_sfh_ffn_fwd(const mi_sfh_ffn_shape* s, const mi_sfh_ffn_params* p, const void* x, void* out, void* saved, void* ws,
+                   void* stream);
+int mi_sfh_ffn_bwd(const mi_sfh_ffn_shape* s, const mi_sfh_ffn_params* p, const void* x, const void* dout, void* dx,
+                   const mi_sfh_ffn_grads* g, const void* saved, void* ws, void* stream);
+typedef struct { int B, dim, H, W, dtype; } mi_sfh_local_shape;
+typedef struct { const float* cd1_w; const float* cd1_b; const float* cd2_w; const float* cd2_b; } mi_sfh_local_params;   /* [s,1,3,3], [s] */
+typedef struct { float* cd1_w; float* cd1_b; float* cd2_w; float* cd2_b; int accumulate; } mi_sfh_local_grads;
+size_t mi_sfh_local_workspace(const mi_sfh_local_shape* s);
+int mi_sfh_local_plan(const mi_sfh_local_shape* s, int64_t* out);
+int mi_sfh_local_fwd(const mi_sfh_local_shape* s, const mi_sfh_local_params* p, const void* x, void* out, void* ws, void* stream);
+int mi_sfh_local_bwd(const mi_sfh_local_shape* s, const mi_sfh_local_params* p, const void* x, const void* dout, void* dx,
+                     const mi_sfh_local_grads* g, void* ws, void* stream);
+
+/* ------------------------------------------------------------------------
  * DarkIR — the encoder block (DarkIR-main/archs/arch_model.py:141-204 EBlock) and its tail (csrc/darkir.hip).
  *
  * fregate: the block's last line, y + gamma (y f), as one streaming pass.  y, f, out [B,C,N] in `dtype`, gamma [C] fp32, fp32
