@@ -1,6 +1,6 @@
 // DarkIR's FreMLP (DarkIR-main/archs/arch_model.py:36-55) and the two real 2-D transforms it stands on, without an FFT library:
-// the dense-DFT GEMMs of the FFT loss (fl_gemm.h: exact fp32-input MFMA, exact quarter-turn twiddles), fp32 between the input
-// load and the output store.
+// the dense-DFT GEMMs of dft2.hip (dft2.h: exact fp32-input MFMA, exact quarter-turn twiddles), fp32 between the input load
+// and the output store.
 //
 //   K = W/2 + 1,  P = B*nc planes,  hc = expand*nc,  E_N[a][b] = exp(-2 pi i ((a b) mod N) / N)
 //   r2c   T = x . E_W  (planes folded into the rows);   Z = E_H . T per plane                          = rfft2(x)
@@ -12,27 +12,27 @@
 // (mi_gram, the channel sum, W^T dY) gives dmag and the parameter gradients;  dZ = dmag u + (du - u (u . du)) / mag, 0 where
 // mag == 0;  dx = Re(conj(E_H) . dZ . conj(E_W)^T)  (the adjoint of r2c: stages 3 and 4 of the FFT loss).
 // Saved for the backward: Z and a (fp32); mag, u and mag' are recomputed from them.
-// fre_plan is the ONE place that decides tiles, grids, workspace sections and launch counts: the launchers launch what it says,
-// mi_fremlp_workspace / mi_fremlp_saved_bytes / mi_dft2_workspace size from it, mi_fremlp_plan reports it.
+// The transforms' tiles and grids are dft2_geom's.  fre_plan adds what is FreMLP's own, the grids of the per-bin passes, the
+// workspace sections and the launch counts: the launchers launch what it says, mi_fremlp_workspace / mi_fremlp_saved_bytes size
+// from it, mi_fremlp_plan reports it.
 #include <limits.h>
 
-#include "fl_gemm.h"
+#include "dft2.h"
 
 namespace mi {
 namespace {
 
 constexpr int FRE_MAX_NC = 256, FRE_MAX_HC = 512;
 constexpr float FRE_SLOPE = 0.1f;
-// cos | sin of E_W [W][K], their transposes [K][W], the same four with the c2r column weights w_l folded in, cos | sin of
-// E_H [H][H]; T and U: two complex [P*H][K] intermediates (re | im); Z and A: the blob's two parts when the caller keeps none
-// (A also holds the hidden gradient in the backward); M1, M2: two real [P*H][K] planes; the three library workspaces.
-enum { FS_CW = 0, FS_SW, FS_CWT, FS_SWT, FS_WCW, FS_WSW, FS_WCWT, FS_WSWT, FS_CH, FS_SH, FS_T, FS_U, FS_Z, FS_A, FS_M1, FS_M2,
-       FS_PW, FS_GRAM, FS_CS, FRE_SECTIONS };
+// The transforms' blob (dft2.h: the ten DT_* tables, then T, its complex [P*H][K] intermediate); U: a second complex [P*H][K]
+// (re | im); Z and A: the saved blob's two parts when the caller keeps none (A also holds the hidden gradient in the backward);
+// M1, M2: two real [P*H][K] planes; the three library workspaces.
+enum { FS_T = DFT2_TABLES, FS_U, FS_Z, FS_A, FS_M1, FS_M2, FS_PW, FS_GRAM, FS_CS, FRE_SECTIONS };
 
 struct FrePlan {
-  int B, nc, hc, P, H, W, K;
-  int nf_l, nf_x, l_blocks, x_blocks, m_tiles_fold, m_tiles_plane;
-  int grid_tab, grid_fold_l, grid_plane, grid_fold_x;   // table fill; [P*H] x K tiles; per-plane H x K tiles; [P*H] x W tiles
+  int B, nc, hc;
+  Dft2Geom g;                                           // the transforms' tiles and grids
+  Dft2Blob dft;                                         // ... and their blob, which opens the workspace
   int grid_bins, grid_hidden;                           // elementwise passes over P*H*K bins / over B*hc*H*K hidden values
   int kernels_fwd, kernels_bwd, lib_calls_fwd, lib_calls_bwd;   // own launches; mi_pw_gemm / mi_gram / channel-sum calls
   int64_t bins, hidden;
@@ -40,73 +40,35 @@ struct FrePlan {
   size_t saved_a_off, saved_bytes;                      // the blob: Z (re | im) at 0, a at saved_a_off
 };
 
-// mlp = false: the transforms alone (tables and T only: mi_dft2_*)
-bool fre_plan(int B, int nc, int expand, int H, int W, bool mlp, FrePlan* p) {
+bool fre_plan(int B, int nc, int expand, int H, int W, FrePlan* p) {
   *p = FrePlan{};
-  if (B <= 0 || nc <= 0 || expand <= 0 || H < FL_MIN || W < FL_MIN || H > FL_MAX || W > FL_MAX) return false;
-  if (mlp && (nc > FRE_MAX_NC || (int64_t)expand * nc > FRE_MAX_HC)) return false;
-  const int64_t P = (int64_t)B * nc;
-  if (P * H > (1 << 30)) return false;
-  const int K = W / 2 + 1;
-  const int hc = mlp ? expand * nc : 1;
-  const int64_t bins = P * H * K, hidden = (int64_t)B * hc * H * K;
-  if (bins > INT_MAX || hidden > INT_MAX) return false;
-  p->B = B; p->nc = nc; p->hc = hc; p->P = (int)P; p->H = H; p->W = W; p->K = K;
+  if (B <= 0 || nc <= 0 || expand <= 0 || nc > FRE_MAX_NC || (int64_t)expand * nc > FRE_MAX_HC) return false;
+  if (!dft2_geom((int64_t)B * nc, H, W, &p->g) || !dft2_blob(p->g, &p->dft)) return false;
+  const int K = p->g.K, hc = expand * nc;
+  const int64_t bins = p->dft.bins, hidden = (int64_t)B * hc * H * K, N = (int64_t)H * K;
+  if (hidden > INT_MAX) return false;
+  p->B = B; p->nc = nc; p->hc = hc;
   p->bins = bins; p->hidden = hidden;
-  p->nf_l = fl_pick_nf(K); p->nf_x = fl_pick_nf(W);
-  p->l_blocks = cdiv(K, 16 * p->nf_l); p->x_blocks = cdiv(W, 16 * p->nf_x);
-  p->m_tiles_fold = cdiv(P * H, FL_TM); p->m_tiles_plane = cdiv(H, FL_TM);
-  const int64_t g1 = (int64_t)p->m_tiles_fold * p->l_blocks, g2 = P * p->m_tiles_plane * p->l_blocks,
-                g4 = (int64_t)p->m_tiles_fold * p->x_blocks;
-  if (g1 > INT_MAX || g2 > INT_MAX || g4 > INT_MAX) return false;
-  p->grid_tab = cdiv((int64_t)W * K + (int64_t)H * H, FL_THREADS);
-  p->grid_fold_l = (int)g1; p->grid_plane = (int)g2; p->grid_fold_x = (int)g4;
   p->grid_bins = cdiv(bins, FL_THREADS); p->grid_hidden = cdiv(hidden, FL_THREADS);
   // forward: tables, r2c (2), |Z|, LeakyReLU, Y = mag' u, c2r (2); two 1x1 products
   // backward: tables, GV, G, (dmag', du), LeakyReLU', |Z|, dZ, the r2c adjoint (2); mag' again, and per 1x1 conv a Gram, a
   // channel sum and W^T dY
-  p->kernels_fwd = mlp ? 8 : 3; p->kernels_bwd = mlp ? 9 : 0;
-  p->lib_calls_fwd = mlp ? 2 : 0; p->lib_calls_bwd = mlp ? 7 : 0;
-  const size_t wk = (size_t)W * K * 4, hh = (size_t)H * H * 4, cplx = (size_t)bins * 2 * 4, real = (size_t)bins * 4;
-  size_t sz[FRE_SECTIONS] = {wk, wk, wk, wk, wk, wk, wk, wk, hh, hh, cplx};
-  if (mlp) {
-    const int64_t N = (int64_t)H * K;
-    sz[FS_U] = cplx; sz[FS_Z] = cplx; sz[FS_A] = (size_t)hidden * 4; sz[FS_M1] = real; sz[FS_M2] = real;
-    sz[FS_PW] = max_of({pw_ws_bytes(probe1x1(nc, hc, false, B, N, MI_F32)), pw_ws_bytes(probe1x1(hc, nc, false, B, N, MI_F32)),
-                        pw_ws_bytes(probe1x1(nc, hc, true, B, N, MI_F32)), pw_ws_bytes(probe1x1(hc, nc, true, B, N, MI_F32))});
-    sz[FS_GRAM] = max_of({gram_ws_bytes(probe_wgrad(nc, hc, B, N, MI_F32)), gram_ws_bytes(probe_wgrad(hc, nc, B, N, MI_F32))});
-    sz[FS_CS] = max_of({chan_sum_workspace(hc, N), chan_sum_workspace(nc, N)});
-  }
-  size_t o = 0;
-  for (int i = 0; i < FRE_SECTIONS; ++i) { p->off[i] = o; p->bytes[i] = sz[i]; o = align_up(o + sz[i], 256); }
+  p->kernels_fwd = 8; p->kernels_bwd = 9; p->lib_calls_fwd = 2; p->lib_calls_bwd = 7;
+  const size_t cplx = (size_t)bins * 2 * 4, real = (size_t)bins * 4;
+  size_t* sz = p->bytes;
+  for (int i = 0; i < DFT2_TABLES; ++i) { p->off[i] = p->dft.tab[i]; sz[i] = dft2_table_bytes(p->g, i); }
+  p->off[FS_T] = p->dft.t; sz[FS_T] = cplx;
+  sz[FS_U] = cplx; sz[FS_Z] = cplx; sz[FS_A] = (size_t)hidden * 4; sz[FS_M1] = real; sz[FS_M2] = real;
+  sz[FS_PW] = max_of({pw_ws_bytes(probe1x1(nc, hc, false, B, N, MI_F32)), pw_ws_bytes(probe1x1(hc, nc, false, B, N, MI_F32)),
+                      pw_ws_bytes(probe1x1(nc, hc, true, B, N, MI_F32)), pw_ws_bytes(probe1x1(hc, nc, true, B, N, MI_F32))});
+  sz[FS_GRAM] = max_of({gram_ws_bytes(probe_wgrad(nc, hc, B, N, MI_F32)), gram_ws_bytes(probe_wgrad(hc, nc, B, N, MI_F32))});
+  sz[FS_CS] = max_of({chan_sum_workspace(hc, N), chan_sum_workspace(nc, N)});
+  size_t o = p->dft.total;   // the sections after the transforms' blob
+  for (int i = FS_U; i < FRE_SECTIONS; ++i) { p->off[i] = o; o = align_up(o + sz[i], 256); }
   p->total = o;
-  p->saved_a_off = mlp ? align_up(cplx, 256) : 0;
-  p->saved_bytes = mlp ? p->saved_a_off + align_up((size_t)hidden * 4, 256) : 0;
+  p->saved_a_off = align_up(cplx, 256);
+  p->saved_bytes = p->saved_a_off + align_up((size_t)hidden * 4, 256);
   return true;
-}
-
-__global__ __launch_bounds__(FL_THREADS) void fre_tables_kernel(float* __restrict__ cw, float* __restrict__ sw,
-                                                                float* __restrict__ cwt, float* __restrict__ swt,
-                                                                float* __restrict__ wcw, float* __restrict__ wsw,
-                                                                float* __restrict__ wcwt, float* __restrict__ wswt,
-                                                                float* __restrict__ ch, float* __restrict__ sh, int H, int W,
-                                                                int K) {
-  const int idx = blockIdx.x * FL_THREADS + threadIdx.x;
-  float c, s;
-  if (idx < W * K) {
-    const int x = idx / K, l = idx - x * K;
-    fl_twiddle((x * l) % W, W, &c, &s);
-    const float wl = (l == 0 || 2 * l == W) ? 1.f : 2.f;      // odd W has no Nyquist column
-    cw[idx] = c; sw[idx] = s;
-    cwt[l * W + x] = c; swt[l * W + x] = s;
-    wcw[idx] = wl * c; wsw[idx] = wl * s;
-    wcwt[l * W + x] = wl * c; wswt[l * W + x] = wl * s;
-  } else if (idx < W * K + H * H) {
-    const int j = idx - W * K;
-    const int k = j / H, y = j - k * H;
-    fl_twiddle((k * y) % H, H, &c, &s);
-    ch[j] = c; sh[j] = s;
-  }
 }
 
 // The polar form of one bin, the same arithmetic wherever it is (re)computed.  mag == 0 (both parts zero, or so small that their
@@ -185,55 +147,6 @@ struct FreWs {
   float* sec(int i) const { return (float*)(base + p.off[i]); }
 };
 
-int fre_tables(const FreWs& w, hipStream_t st) {
-  const FrePlan& p = w.p;
-  hipLaunchKernelGGL(fre_tables_kernel, dim3(p.grid_tab), dim3(FL_THREADS), 0, st, w.sec(FS_CW), w.sec(FS_SW), w.sec(FS_CWT),
-                     w.sec(FS_SWT), w.sec(FS_WCW), w.sec(FS_WSW), w.sec(FS_WCWT), w.sec(FS_WSWT), w.sec(FS_CH), w.sec(FS_SH), p.H,
-                     p.W, p.K);
-  MI_LAUNCH_CHECK();
-  return MI_OK;
-}
-
-// [P*H x W] real (activation dtype) . [W x K] complex table (cos - i sin) -> re | im [P*H][K]
-int fre_rows_fwd(const FreWs& w, const void* x, const float* tc, const float* ts, float* ore, float* oim, int dtype,
-                 hipStream_t st) {
-  const FrePlan& p = w.p;
-  FlGemm g = {};
-  g.a0 = x; g.lda = p.W;
-  g.b0 = tc; g.b1 = ts; g.ldb = p.K; g.b_sign = -1.f;
-  g.c0 = ore; g.c1 = oim; g.ldc = p.K;
-  g.M = p.P * p.H; g.N = p.K; g.Kd = p.W; g.m_tiles = p.m_tiles_fold; g.n_tiles = p.l_blocks;
-  return with_dtype(dtype, "fremlp", [&](auto tag) -> int {
-    return fl_launch<A_REAL, E_CPLX, decltype(tag)>(p.nf_l, g, p.grid_fold_l, st);
-  });
-}
-
-// per plane: (cos H + i sign sin H) . in -> out; sign -1: E_H, +1: conj(E_H)
-int fre_cols(const FreWs& w, float sign, const float* ire, const float* iim, float* ore, float* oim, hipStream_t st) {
-  const FrePlan& p = w.p;
-  const int64_t plane = (int64_t)p.H * p.K;
-  FlGemm g = {};
-  g.a0 = w.sec(FS_CH); g.a1 = w.sec(FS_SH); g.lda = p.H; g.a_sign = sign;
-  g.b0 = ire; g.b1 = iim; g.ldb = p.K; g.b_zs = plane; g.b_sign = 1.f;
-  g.c0 = ore; g.c1 = oim; g.ldc = p.K; g.c_zs = plane;
-  g.M = p.H; g.N = p.K; g.Kd = p.H; g.m_tiles = p.m_tiles_plane; g.n_tiles = p.l_blocks;
-  return fl_launch<A_CPLX, E_CPLX, float>(p.nf_l, g, p.grid_plane, st);
-}
-
-// out = scale * Re([P*H x K] complex . [K x W] complex table (cos + i sin)), rounded once to the activation dtype
-int fre_rows_bwd(const FreWs& w, const float* ire, const float* iim, const float* tc, const float* ts, void* out, float scale,
-                 int dtype, hipStream_t st) {
-  const FrePlan& p = w.p;
-  FlGemm g = {};
-  g.a0 = ire; g.a1 = iim; g.lda = p.K; g.a_sign = 1.f;
-  g.b0 = tc; g.b1 = ts; g.ldb = p.W; g.b_sign = 1.f;
-  g.c0 = out; g.ldc = p.W; g.scale = scale;
-  g.M = p.P * p.H; g.N = p.W; g.Kd = p.K; g.m_tiles = p.m_tiles_fold; g.n_tiles = p.x_blocks;
-  return with_dtype(dtype, "fremlp", [&](auto tag) -> int {
-    return fl_launch<A_CPLX, E_REAL, decltype(tag)>(p.nf_x, g, p.grid_fold_x, st);
-  });
-}
-
 int fre_check(const char* who, const mi_fremlp_shape* s, FrePlan* p) {
   MI_CHECK_ARG(s, "%s: null shape", who);
   MI_CHECK_ARG(s->dtype == MI_F32 || s->dtype == MI_BF16, "%s: bad dtype %d", who, s->dtype);
@@ -243,97 +156,15 @@ int fre_check(const char* who, const mi_fremlp_shape* s, FrePlan* p) {
                FRE_MAX_NC, FRE_MAX_HC);
   MI_CHECK_ARG(s->H >= FL_MIN && s->W >= FL_MIN && s->H <= FL_MAX && s->W <= FL_MAX,
                "%s: H=%d W=%d outside the supported %d..%d (there is no fallback)", who, s->H, s->W, FL_MIN, FL_MAX);
-  MI_CHECK_ARG(fre_plan(s->B, s->nc, s->expand, s->H, s->W, true, p), "%s: too many bins (B=%d nc=%d expand=%d H=%d W=%d)", who, s->B,
+  MI_CHECK_ARG(fre_plan(s->B, s->nc, s->expand, s->H, s->W, p), "%s: too many bins (B=%d nc=%d expand=%d H=%d W=%d)", who, s->B,
                s->nc, s->expand, s->H, s->W);
   return MI_OK;
 }
 
-int dft2_check(const char* who, int B, int C, int H, int W, int dtype, FrePlan* p) {
-  MI_CHECK_ARG(dtype == MI_F32 || dtype == MI_BF16, "%s: bad dtype %d", who, dtype);
-  MI_CHECK_ARG(B > 0 && C > 0, "%s: bad shape B=%d C=%d", who, B, C);
-  MI_CHECK_ARG(H >= FL_MIN && W >= FL_MIN && H <= FL_MAX && W <= FL_MAX,
-               "%s: H=%d W=%d outside the supported %d..%d (there is no fallback)", who, H, W, FL_MIN, FL_MAX);
-  MI_CHECK_ARG(fre_plan(B, C, 1, H, W, false, p), "%s: too many planes (B=%d C=%d H=%d)", who, B, C, H);
-  return MI_OK;
-}
-
 }  // namespace
-
-// ---- the four transform directions for other modules (internal.h): the launchers above, on a mi_dft2_workspace() blob ----
-size_t dft2_tables_bytes(int B, int C, int H, int W) {
-  FrePlan p;
-  return fre_plan(B, C, 1, H, W, false, &p) ? p.off[FS_T] : 0;
-}
-int dft2_tables(int B, int C, int H, int W, void* ws, hipStream_t st) {
-  FrePlan p;
-  MI_TRY(dft2_check("dft2_tables", B, C, H, W, MI_F32, &p));
-  return fre_tables(FreWs{p, (char*)ws}, st);
-}
-int dft2_r2c_run(const void* x, float* zre, float* zim, int B, int C, int H, int W, int dtype, void* ws, hipStream_t st) {
-  FrePlan p;
-  MI_TRY(dft2_check("dft2_r2c", B, C, H, W, dtype, &p));
-  const FreWs w = {p, (char*)ws};
-  float* tre = w.sec(FS_T); float* tim = tre + p.bins;
-  MI_TRY(fre_rows_fwd(w, x, w.sec(FS_CW), w.sec(FS_SW), tre, tim, dtype, st));
-  return fre_cols(w, -1.f, tre, tim, zre, zim, st);
-}
-int dft2_c2r_run(const float* yre, const float* yim, void* out, int B, int C, int H, int W, int dtype, void* ws, hipStream_t st) {
-  FrePlan p;
-  MI_TRY(dft2_check("dft2_c2r", B, C, H, W, dtype, &p));
-  const FreWs w = {p, (char*)ws};
-  float* tre = w.sec(FS_T); float* tim = tre + p.bins;
-  MI_TRY(fre_cols(w, 1.f, yre, yim, tre, tim, st));
-  return fre_rows_bwd(w, tre, tim, w.sec(FS_WCWT), w.sec(FS_WSWT), out, (float)(1.0 / ((double)H * W)), dtype, st);
-}
-int dft2_c2r_adj(const void* dout, float* gre, float* gim, int B, int C, int H, int W, int dtype, void* ws, hipStream_t st) {
-  FrePlan p;
-  MI_TRY(dft2_check("dft2_c2r_adj", B, C, H, W, dtype, &p));
-  const FreWs w = {p, (char*)ws};
-  float* tre = w.sec(FS_T); float* tim = tre + p.bins;
-  MI_TRY(fre_rows_fwd(w, dout, w.sec(FS_WCW), w.sec(FS_WSW), tre, tim, dtype, st));
-  return fre_cols(w, -1.f, tre, tim, gre, gim, st);
-}
-int dft2_r2c_adj(const float* dre, const float* dim, void* dx, int B, int C, int H, int W, int dtype, void* ws, hipStream_t st) {
-  FrePlan p;
-  MI_TRY(dft2_check("dft2_r2c_adj", B, C, H, W, dtype, &p));
-  const FreWs w = {p, (char*)ws};
-  float* tre = w.sec(FS_T); float* tim = tre + p.bins;
-  MI_TRY(fre_cols(w, 1.f, dre, dim, tre, tim, st));
-  return fre_rows_bwd(w, tre, tim, w.sec(FS_CWT), w.sec(FS_SWT), dx, 1.f, dtype, st);
-}
 }  // namespace mi
 
 using namespace mi;
-
-extern "C" size_t mi_dft2_workspace(int B, int C, int H, int W) {
-  FrePlan p;
-  return fre_plan(B, C, 1, H, W, false, &p) ? p.total : 0;
-}
-
-extern "C" int mi_dft2_r2c(const void* x, float* zre, float* zim, int B, int C, int H, int W, int dtype, void* ws, void* stream) {
-  MI_CHECK_ARG(x && zre && zim && ws, "dft2_r2c: null pointer");
-  FrePlan p;
-  MI_TRY(dft2_check("dft2_r2c", B, C, H, W, dtype, &p));
-  hipStream_t st = (hipStream_t)stream;
-  const FreWs w = {p, (char*)ws};
-  float* tre = w.sec(FS_T); float* tim = tre + p.bins;
-  MI_TRY(fre_tables(w, st));
-  MI_TRY(fre_rows_fwd(w, x, w.sec(FS_CW), w.sec(FS_SW), tre, tim, dtype, st));
-  return fre_cols(w, -1.f, tre, tim, zre, zim, st);
-}
-
-extern "C" int mi_dft2_c2r(const float* yre, const float* yim, void* out, int B, int C, int H, int W, int dtype, void* ws,
-                           void* stream) {
-  MI_CHECK_ARG(yre && yim && out && ws, "dft2_c2r: null pointer");
-  FrePlan p;
-  MI_TRY(dft2_check("dft2_c2r", B, C, H, W, dtype, &p));
-  hipStream_t st = (hipStream_t)stream;
-  const FreWs w = {p, (char*)ws};
-  float* tre = w.sec(FS_T); float* tim = tre + p.bins;
-  MI_TRY(fre_tables(w, st));
-  MI_TRY(fre_cols(w, 1.f, yre, yim, tre, tim, st));
-  return fre_rows_bwd(w, tre, tim, w.sec(FS_WCWT), w.sec(FS_WSWT), out, (float)(1.0 / ((double)H * W)), dtype, st);
-}
 
 extern "C" size_t mi_fremlp_workspace(const mi_fremlp_shape* s) {
   FrePlan p;
@@ -349,14 +180,15 @@ extern "C" size_t mi_fremlp_saved_bytes(const mi_fremlp_shape* s) {
 // x block width, x blocks, 64-row tiles over P*H, 64-row tiles over H, grid of the table fill, of the [P*H] x K stages, of the
 // per-plane stages, of the [P*H] x W stages, of the per-bin passes, of the hidden passes, threads per workgroup, own kernel
 // launches forward / backward, library calls (1x1 product, Gram, channel sum) forward / backward [22]; then (byte offset, bytes)
-// of the 19 workspace sections in the order of the FS_* list [22..59]; the workspace size [60], the saved blob's size [61], the
+// of the 19 workspace sections, the ten DT_* tables and then the FS_* list [22..59]; the workspace size [60], the saved blob's size [61], the
 // offset of `a` in it [62] (Z sits at 0), 0 [63].
 extern "C" int mi_fremlp_plan(const mi_fremlp_shape* s, int64_t* out) {
   MI_CHECK_ARG(out, "fremlp_plan: null pointer");
   FrePlan p;
   MI_TRY(fre_check("fremlp_plan", s, &p));
-  int64_t v[64] = {p.P, p.K, p.hc, FL_TM, FL_KC, 16 * p.nf_l, p.l_blocks, 16 * p.nf_x, p.x_blocks, p.m_tiles_fold, p.m_tiles_plane,
-                   p.grid_tab, p.grid_fold_l, p.grid_plane, p.grid_fold_x, p.grid_bins, p.grid_hidden, FL_THREADS, p.kernels_fwd,
+  const Dft2Geom& g = p.g;
+  int64_t v[64] = {g.P, g.K, p.hc, FL_TM, FL_KC, 16 * g.nf_l, g.l_blocks, 16 * g.nf_x, g.x_blocks, g.m_tiles_fold, g.m_tiles_plane,
+                   g.grid_tab, g.grid_fold_l, g.grid_plane, g.grid_fold_x, p.grid_bins, p.grid_hidden, FL_THREADS, p.kernels_fwd,
                    p.kernels_bwd, p.lib_calls_fwd, p.lib_calls_bwd};
   for (int i = 0; i < FRE_SECTIONS; ++i) { v[22 + 2 * i] = (int64_t)p.off[i]; v[23 + 2 * i] = (int64_t)p.bytes[i]; }
   v[60] = (int64_t)p.total; v[61] = (int64_t)p.saved_bytes; v[62] = (int64_t)p.saved_a_off;
@@ -371,17 +203,16 @@ extern "C" int mi_fremlp_fwd(const mi_fremlp_shape* s, const float* w1, const fl
   MI_CHECK_ARG(w1 && b1 && w2 && b2 && x && out && ws, "fremlp_fwd: null pointer");
   hipStream_t st = (hipStream_t)stream;
   const FreWs w = {p, (char*)ws};
+  const Dft2Ws dft = dft2_blob_ws(p.dft, ws);   // the tables and T
   const int n = (int)p.bins, nh = (int)p.hidden;
-  const int64_t N = (int64_t)p.H * p.K;
-  float* tre = w.sec(FS_T); float* tim = tre + n;
+  const int64_t N = (int64_t)p.g.H * p.g.K;
   float* ure = w.sec(FS_U); float* uim = ure + n;
   float* zre = saved ? (float*)saved : w.sec(FS_Z); float* zim = zre + n;
   float* a = saved ? (float*)((char*)saved + p.saved_a_off) : w.sec(FS_A);
   float* mag = w.sec(FS_M1); float* mag2 = w.sec(FS_M2);
 
-  MI_TRY(fre_tables(w, st));
-  MI_TRY(fre_rows_fwd(w, x, w.sec(FS_CW), w.sec(FS_SW), tre, tim, s->dtype, st));
-  MI_TRY(fre_cols(w, -1.f, tre, tim, zre, zim, st));
+  MI_TRY(dft2_tables(p.g, dft, st));
+  MI_TRY(dft2_r2c_run(p.g, dft, x, zre, zim, s->dtype, st));
   hipLaunchKernelGGL(fre_mag_kernel, dim3(p.grid_bins), dim3(FL_THREADS), 0, st, zre, zim, mag, n);
   MI_LAUNCH_CHECK();
   const mi_pw_desc d1 = conv1x1(mag, p.nc, w1, false, p.nc, b1, nullptr, a, p.hc, p.B, N, MI_F32);
@@ -390,10 +221,11 @@ extern "C" int mi_fremlp_fwd(const mi_fremlp_shape* s, const float* w1, const fl
   MI_LAUNCH_CHECK();
   const mi_pw_desc d2 = conv1x1(a, p.hc, w2, false, p.hc, b2, nullptr, mag2, p.nc, p.B, N, MI_F32);
   MI_TRY(mi_pw_gemm(&d2, w.sec(FS_PW), stream));
-  hipLaunchKernelGGL(fre_compose_kernel, dim3(p.grid_bins), dim3(FL_THREADS), 0, st, zre, zim, mag2, tre, tim, n);
+  hipLaunchKernelGGL(fre_compose_kernel, dim3(p.grid_bins), dim3(FL_THREADS), 0, st, zre, zim, mag2, dft.tre, dft.tim, n);
   MI_LAUNCH_CHECK();
-  MI_TRY(fre_cols(w, 1.f, tre, tim, ure, uim, st));
-  return fre_rows_bwd(w, ure, uim, w.sec(FS_WCWT), w.sec(FS_WSWT), out, (float)(1.0 / ((double)p.H * p.W)), s->dtype, st);
+  Dft2Ws via = dft;   // Y sits in T, which r2c is done with, so c2r passes through U
+  via.tre = ure; via.tim = uim;
+  return dft2_c2r_run(p.g, via, dft.tre, dft.tim, out, s->dtype, st);
 }
 
 extern "C" int mi_fremlp_bwd(const mi_fremlp_shape* s, const float* w1, const float* w2, const float* b2, const void* dout,
@@ -404,21 +236,20 @@ extern "C" int mi_fremlp_bwd(const mi_fremlp_shape* s, const float* w1, const fl
   MI_CHECK_ARG(w1 && w2 && b2 && dout && dx && g_w1 && g_b1 && g_w2 && g_b2 && saved && ws, "fremlp_bwd: null pointer");
   hipStream_t st = (hipStream_t)stream;
   const FreWs w = {p, (char*)ws};
+  const Dft2Ws dft = dft2_blob_ws(p.dft, ws);   // the tables and T
   const int n = (int)p.bins, nh = (int)p.hidden;
-  const int64_t N = (int64_t)p.H * p.K;
-  float* tre = w.sec(FS_T); float* tim = tre + n;
+  const int64_t N = (int64_t)p.g.H * p.g.K;
   float* ure = w.sec(FS_U); float* uim = ure + n;
   const float* zre = (const float*)saved; const float* zim = zre + n;
   const float* a = (const float*)((const char*)saved + p.saved_a_off);
   float* da = w.sec(FS_A); float* m1 = w.sec(FS_M1); float* m2 = w.sec(FS_M2);
 
-  MI_TRY(fre_tables(w, st));
-  MI_TRY(fre_rows_fwd(w, dout, w.sec(FS_WCW), w.sec(FS_WSW), tre, tim, s->dtype, st));     // GV
-  MI_TRY(fre_cols(w, -1.f, tre, tim, ure, uim, st));                                        // G (unscaled)
+  MI_TRY(dft2_tables(p.g, dft, st));
+  MI_TRY(dft2_c2r_adj(p.g, dft, dout, ure, uim, s->dtype, st));                             // G (unscaled), through GV
   const mi_pw_desc d2 = conv1x1(a, p.hc, w2, false, p.hc, b2, nullptr, m2, p.nc, p.B, N, MI_F32);   // mag' again
   MI_TRY(mi_pw_gemm(&d2, w.sec(FS_PW), stream));
   hipLaunchKernelGGL(fre_bwd_g_kernel, dim3(p.grid_bins), dim3(FL_THREADS), 0, st, zre, zim, (const float*)m2, ure, uim, m1,
-                     (float)(1.0 / ((double)p.H * p.W)), n);                                 // m1 = dmag', U = du
+                     (float)(1.0 / ((double)p.g.H * p.g.W)), n);                                 // m1 = dmag', U = du
   MI_LAUNCH_CHECK();
   MI_TRY(conv1x1_bwd_input(m1, p.nc, a, p.hc, w2, g_w2, g_b2, da, p.B, N, MI_F32, accumulate, w.sec(FS_GRAM), w.sec(FS_CS),
                            w.sec(FS_PW), st, false));
@@ -430,6 +261,5 @@ extern "C" int mi_fremlp_bwd(const mi_fremlp_shape* s, const float* w1, const fl
                            w.sec(FS_PW), st, false));                                        // m1 = dmag
   hipLaunchKernelGGL(fre_bwd_dz_kernel, dim3(p.grid_bins), dim3(FL_THREADS), 0, st, zre, zim, (const float*)m1, ure, uim, n);
   MI_LAUNCH_CHECK();
-  MI_TRY(fre_cols(w, 1.f, ure, uim, tre, tim, st));
-  return fre_rows_bwd(w, tre, tim, w.sec(FS_CWT), w.sec(FS_SWT), dx, 1.f, s->dtype, st);
+  return dft2_r2c_adj(p.g, dft, ure, uim, dx, s->dtype, st);
 }

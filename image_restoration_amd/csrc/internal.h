@@ -151,15 +151,7 @@ int launch_bwd_tail(const void* dy, int M, const void* x, int C, const void* dre
 MI_HIDDEN int pw_lds_tm(int M);                 // its tile height (256 / 128 rows)
 MI_HIDDEN size_t pw_lds_lds_bytes(int tm);      // dynamic LDS of the instance with that tile height
 MI_HIDDEN int pw_lds_launch(const mi_pw_desc* d, const PwPlan& pl, void* ws, hipStream_t st);   // packs its image into ws, then launches
-// ---- the real 2-D transforms (fremlp.hip) for other modules.  ws: mi_dft2_workspace(B, C, H, W) bytes; dft2_tables fills its
-// twiddle tables once per launch sequence, the four directions read them and use its one complex intermediate.  Spectra are
-// planar fp32 Re | Im [B,C,H,K]; x / out / dout / dx [B,C,H,W] in `dtype`.
-MI_HIDDEN size_t dft2_tables_bytes(int B, int C, int H, int W);   // the tables' share of that blob; the complex intermediate follows
-MI_HIDDEN int dft2_tables(int B, int C, int H, int W, void* ws, hipStream_t st);
-MI_HIDDEN int dft2_r2c_run(const void* x, float* zre, float* zim, int B, int C, int H, int W, int dtype, void* ws, hipStream_t st);   // Z = rfft2(x)
-MI_HIDDEN int dft2_c2r_run(const float* yre, const float* yim, void* out, int B, int C, int H, int W, int dtype, void* ws, hipStream_t st);   // irfft2(Y, norm='backward')
-MI_HIDDEN int dft2_c2r_adj(const void* dout, float* gre, float* gim, int B, int C, int H, int W, int dtype, void* ws, hipStream_t st);   // H W x the adjoint of c2r
-MI_HIDDEN int dft2_r2c_adj(const float* dre, const float* dim, void* dx, int B, int C, int H, int W, int dtype, void* ws, hipStream_t st);   // the adjoint of r2c
+// ---- the real 2-D transforms (dft2.hip) have a header of their own, dft2.h: geometry, tables, stages and the four directions ----
 // ---- fused GDFN forward, training form (fused_gdfn.hip): also writes h0 [B][2h][H][W] and g [B][h][H][W] ----
 int fused_gdfn_fwd_save(const mi_gdfn_fused_shape* s, const void* pack, const void* y, void* out, float* mean, float* rstd,
                         void* h0, void* g, hipStream_t st);

@@ -1,4 +1,4 @@
-// SFHformer's FourierUnit (SFHformer.py:143-180): what sits between the two real 2-D transforms of fremlp.hip.  fp32 between the
+// SFHformer's FourierUnit (SFHformer.py:143-180): what sits between the two real 2-D transforms of dft2.hip.   fp32 between the
 // input load and the output store.
 //
 //   c channels, C2 = 2c, K = W/2 + 1, N = H K bins per plane, G groups, S = C2 / G, alpha = 1/sqrt(HW)
@@ -28,7 +28,7 @@
 // sfh_plan is the ONE place that decides sections, grids and launch counts.
 #include <limits.h>
 
-#include "internal.h"
+#include "dft2.h"
 
 namespace mi {
 namespace {
@@ -51,6 +51,7 @@ enum { SS_DFT = 0, SS_T, SS_Z, SS_U, SS_A, SS_B, SS_P, SS_Q, SS_S, SS_DL, SS_STA
 
 struct SfhPlan {
   int B, c, C2, G, S, H, W, K, N;
+  Dft2Geom dft; Dft2Blob dft_blob;    // the transforms' tiles and grids; their blob (SS_DFT: its tables, SS_T: its intermediate)
   int nchunk, nparts;                 // chunks of a plane; partials per channel (B * nchunk)
   int64_t elems, bins;                // B C2 N; B N
   int nblk, grid_elems, grid_bins, grid_chan, grid_w, grid_scatter, grid_fin;
@@ -67,9 +68,7 @@ bool sfh_plan(int B, int c, int G, int H, int W, SfhPlan* p) {
   const int K = W / 2 + 1, C2 = 2 * c, N = H * K;
   const int64_t elems = (int64_t)B * C2 * N;
   if (elems > INT_MAX || (int64_t)B * C2 * cdiv(N, SFH_EW) > INT_MAX) return false;
-  const size_t dft = mi_dft2_workspace(B, c, H, W);
-  const size_t dft_tab = dft2_tables_bytes(B, c, H, W);
-  if (!dft || !dft_tab || dft_tab + align_up((size_t)elems * 4, 256) != dft) return false;
+  if (!dft2_geom((int64_t)B * c, H, W, &p->dft) || !dft2_blob(p->dft, &p->dft_blob)) return false;
   p->B = B; p->c = c; p->C2 = C2; p->G = G; p->S = C2 / G; p->H = H; p->W = W; p->K = K; p->N = N;
   p->nchunk = cdiv(N, SFH_CHUNK); p->nparts = B * p->nchunk;
   p->elems = elems; p->bins = (int64_t)B * N;
@@ -84,7 +83,7 @@ bool sfh_plan(int B, int c, int G, int H, int W, SfhPlan* p) {
   p->kernels_fwd = 11; p->kernels_bwd = 14; p->lib_calls_fwd = 1; p->lib_calls_bwd = 6;
   const size_t spec = (size_t)elems * 4, gate = (size_t)p->bins * G * 4;
   size_t sz[SFH_SECTIONS] = {};
-  sz[SS_DFT] = dft_tab; sz[SS_T] = spec;   // together the transforms' blob: its tables, then its complex intermediate
+  sz[SS_DFT] = p->dft_blob.t; sz[SS_T] = spec;   // together the transforms' blob: its tables, then its complex intermediate
   sz[SS_Z] = spec; sz[SS_U] = spec; sz[SS_A] = spec; sz[SS_B] = spec; sz[SS_P] = spec; sz[SS_Q] = spec;
   sz[SS_S] = gate; sz[SS_DL] = gate;
   sz[SS_STAT] = (size_t)4 * C2 * 4;
@@ -539,13 +538,14 @@ extern "C" int mi_fourier_unit_fwd(const mi_fourier_unit_shape* s, const mi_four
                out && running_mean && running_var && ws, "fourier_unit_fwd: null pointer");
   hipStream_t st = (hipStream_t)stream;
   const SfhWs w = {p, (char*)ws};
+  const Dft2Ws dft = dft2_blob_ws(p.dft_blob, w.sec(SS_DFT));
   float* z = saved ? (float*)saved : w.sec(SS_Z);
   float* stat = saved ? (float*)((char*)saved + p.saved_stat_off) : w.sec(SS_STAT);
   float* o = w.sec(SS_U);
   const int64_t half = (int64_t)p.B * p.c * p.N;
   const double hw = (double)p.H * p.W;
-  MI_TRY(dft2_tables(p.B, p.c, p.H, p.W, w.sec(SS_DFT), st));
-  MI_TRY(dft2_r2c_run(x, z, z + half, p.B, p.c, p.H, p.W, s->dtype, w.sec(SS_DFT), st));
+  MI_TRY(dft2_tables(p.dft, dft, st));
+  MI_TRY(dft2_r2c_run(p.dft, dft, x, z, z + half, s->dtype, st));
   if (s->training) {
     hipLaunchKernelGGL(bn_partial_kernel, dim3(p.nparts, p.C2), dim3(SFH_THREADS), 0, st, (const float*)z, p.map, p.N, p.nchunk,
                        w.sec(SS_BNP));
@@ -558,7 +558,7 @@ extern "C" int mi_fourier_unit_fwd(const mi_fourier_unit_shape* s, const mi_four
   hipLaunchKernelGGL(sfh_gelu_kernel, dim3(p.grid_elems), dim3(SFH_THREADS), 0, st, (const float*)w.sec(SS_P),
                      (const float*)w.sec(SS_S), pr->fdc_b, p.map, p.G, o, (float)sqrt(hw), p.N, p.nblk);
   MI_LAUNCH_CHECK();
-  return dft2_c2r_run(o, o + half, out, p.B, p.c, p.H, p.W, s->dtype, w.sec(SS_DFT), st);
+  return dft2_c2r_run(p.dft, dft, o, o + half, out, s->dtype, st);
 }
 
 extern "C" int mi_fourier_unit_bwd(const mi_fourier_unit_shape* s, const mi_fourier_unit_params* pr, const void* dout, void* dx,
@@ -570,6 +570,7 @@ extern "C" int mi_fourier_unit_bwd(const mi_fourier_unit_shape* s, const mi_four
                "fourier_unit_bwd: null pointer");
   hipStream_t st = (hipStream_t)stream;
   const SfhWs w = {p, (char*)ws};
+  const Dft2Ws dft = dft2_blob_ws(p.dft_blob, w.sec(SS_DFT));
   const int bins = (int)p.bins, acc = g->accumulate ? 1 : 0;
   const float* z = (const float*)saved;
   const float* stat = (const float*)((const char*)saved + p.saved_stat_off);
@@ -580,8 +581,8 @@ extern "C" int mi_fourier_unit_bwd(const mi_fourier_unit_shape* s, const mi_four
   float* sg = w.sec(SS_S); float* dl = w.sec(SS_DL); float* tmp = w.sec(SS_GT); float* means = w.sec(SS_STAT) + 2 * p.C2;
   float* tmp_b = tmp + (size_t)p.C2 * p.C2; float* tmp_w = tmp_b + (size_t)p.G * p.C2;
 
-  MI_TRY(dft2_tables(p.B, p.c, p.H, p.W, w.sec(SS_DFT), st));
-  MI_TRY(dft2_c2r_adj(dout, u, u + half, p.B, p.c, p.H, p.W, s->dtype, w.sec(SS_DFT), st));    // H W x the adjoint
+  MI_TRY(dft2_tables(p.dft, dft, st));
+  MI_TRY(dft2_c2r_adj(p.dft, dft, dout, u, u + half, s->dtype, st));    // H W x the adjoint
   MI_TRY(sfh_middle(w, pr, z, stat, st));
   hipLaunchKernelGGL(sfh_gelu_bwd_kernel, dim3(p.grid_elems), dim3(SFH_THREADS), 0, st, dpre, (const float*)sg, pr->fdc_b, p.map, p.G,
                      (const float*)u, (float)(1.0 / sqrt(hw)), p.N, p.nblk);
@@ -611,5 +612,5 @@ extern "C" int mi_fourier_unit_bwd(const mi_fourier_unit_shape* s, const mi_four
   hipLaunchKernelGGL(sfh_scatter_kernel, dim3(p.grid_scatter), dim3(SFH_THREADS), 0, st, (const float*)tmp, p.map, p.G, p.S, acc,
                      g->fdc_w, g->fdc_b, g->gate_w);
   MI_LAUNCH_CHECK();
-  return dft2_r2c_adj(u, u + half, dx, p.B, p.c, p.H, p.W, s->dtype, w.sec(SS_DFT), st);
+  return dft2_r2c_adj(p.dft, dft, u, u + half, dx, s->dtype, st);
 }

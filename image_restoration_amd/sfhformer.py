@@ -6,7 +6,7 @@ arguments and ``state_dict`` keys (``bn.*``, ``fdc.*``, ``weight.0.*``, ``fpe.*`
 ``strict=True``.
 
 ``FourierUnit.forward`` is ONE autograd node over ``mi_fourier_unit_*`` (``csrc/sfh.hip``): ``rfft2`` and ``irfft2`` (``norm='ortho'``)
-as the dense-DFT GEMMs of ``csrc/fremlp.hip``, and between them BatchNorm over the interleaved real / imaginary channels (training
+as the dense-DFT GEMMs of ``csrc/dft2.hip``, and between them BatchNorm over the interleaved real / imaginary channels (training
 or eval mode, running statistics updated on the device), the depthwise 3x3 with its residual, the softmax gate over the groups and
 the grouped 1x1 folded into one dense product, then GELU.  The submodules are parameter containers only.
 

@@ -65,7 +65,8 @@ def test_symbols_exist_with_their_signatures(lib):
     # shape, parameters, x, out, the two running statistics, saved, ws, stream / shape, parameters, dout, dx, gradients, saved, ws, stream
     assert len(lib.SIGNATURES["mi_fourier_unit_fwd"][1]) == 9 and len(lib.SIGNATURES["mi_fourier_unit_bwd"][1]) == 8
     # the transform launchers shared with FreMLP stay internal
-    assert not any("dft2_r2c_run" in n or "dft2_tables" in n or "dft2_c2r_adj" in n for n in dynsym)
+    internal = ("dft2_r2c_run", "dft2_tables", "dft2_c2r_adj", "dft2_geom", "dft2_blob", "dft2_rows_fwd", "dft2_cols")
+    assert not any(name in n for name in internal for n in dynsym)
 
 
 # B, c, groups, H, W
