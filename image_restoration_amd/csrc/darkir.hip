@@ -16,8 +16,9 @@
 // The c x c folds: M[b] = diag(beta) W3 diag(s[b]) (and diag(gamma) W5) feed ONE per-image mi_pw_gemm each with the residual in
 // its epilogue; their backward starts from the per-image Gram dY g^T (mi_gram, sum_batch = 0) and per-image channel sums of dY.
 // With bf16 activations the 1x1 products run on split weights ([hi | lo] . [x ; x], dk_split_kernel): see there.
-// The encoder block (EBlock, arch_model.py:141-204; mi_eblock_*) is a launch sequence over the same pieces with a plain depthwise
-// extra_conv in front of conv1, mi_fremlp_* behind norm2, and its own streaming tail out = y (1 + gamma f) (mi_fregate_*).
+// The encoder block (EBlock, arch_model.py:141-204; mi_eblock_*) shares DBlock's first half: one layout, one forward and one
+// backward (gh_*, "gated half") run for both, around each block's own extra_conv (EBlock's is a plain depthwise one in front of
+// conv1).  Its second half is mi_fremlp_* behind norm2 and its own streaming tail out = y (1 + gamma f) (mi_fregate_*).
 #include "internal.h"
 
 namespace mi {
@@ -593,51 +594,43 @@ static int launch_pairconv_bwd(const void* dy, const void* x, const float* w, vo
   return MI_OK;
 }
 
-// ------------------------------------------------------------------ the block: layouts
-struct DbSaved {
-  void* x0; void* x1; void* x2; void* g; void* y; void* y0; void* u; void* h;
-  float* mean1; float* rstd1; float* mean2; float* rstd2; float* pool; float* s; float* M3; float* b3f; float* M5; float* b5f;
-  float* M3s; float* M3ts; float* M5s; float* M5ts;   // split images (bf16 activations)
-  size_t bytes;
+// ------------------------------------------------------------------ the gated half: one description for both blocks
+// LayerNorm2d -> conv1 -> dilated gate -> SCA fold -> per-image conv3 with beta and the residual is the first half of DBlock and of
+// EBlock alike, and so is its backward; only extra_conv differs (DBlock: pair-grouped, behind conv1; EBlock: plain depthwise, in
+// front of it).  What the chain stores and what it needs as scratch is laid out once, here; a block adds its own sections.
+// (S, P and G below: either block's mi_*_shape, mi_*_params and mi_*_grads, which name the chain's fields alike.)
+
+// cin: conv1's input, x0 or an extra_conv in front of conv1 applied to it; gin: the gate's input, x1 or an extra_conv behind conv1
+// applied to it.  M3s / M3ts: split images (bf16 activations).  A block has at most one extra_conv: cin or gin is a plane of its own.
+struct GhSaved {
+  void* x0; void* cin; void* x1; void* gin; void* g; void* y;
+  float* mean1; float* rstd1; float* pool; float* s; float* M3; float* b3f; float* M3s; float* M3ts;
+  size_t sec[8];     // bytes, as carved, of x0, cin, x1, gin, g, y (0 where a plane is shared), the statistics, the small tensors
 };
-// train: everything the backward reads; inference (in the workspace): the same planes, nothing outlives the call
-static DbSaved db_saved_layout(const mi_dblock_shape* s, void* base) {
+template <typename S>
+static GhSaved gh_saved_carve(Carver& cv, const S* s, bool extra_front, bool extra_behind) {
   const size_t B = s->B, C = s->C, N = (size_t)s->H * s->W, cc = B * C * C;
   const int dt = s->dtype;
-  Carver cv(base);
-  DbSaved r;
-  memset(&r, 0, sizeof(r));
-  r.x0 = cv.take(tbytes(B * C * N, dt));
-  r.x1 = cv.take(tbytes(B * 2 * C * N, dt));
-  r.x2 = s->extra ? cv.take(tbytes(B * 2 * C * N, dt)) : r.x1;
-  r.g = cv.take(tbytes(B * C * N, dt));
-  r.y = cv.take(tbytes(B * C * N, dt));
-  r.y0 = cv.take(tbytes(B * C * N, dt));
-  r.u = cv.take(tbytes(B * 2 * C * N, dt));
-  r.h = cv.take(tbytes(B * C * N, dt));
+  GhSaved r;
+  size_t o = cv.off;
+  auto close = [&](int i) { r.sec[i] = cv.off - o; o = cv.off; };
+  r.x0 = cv.take(tbytes(B * C * N, dt)); close(0);
+  r.cin = extra_front ? cv.take(tbytes(B * C * N, dt)) : r.x0; close(1);
+  r.x1 = cv.take(tbytes(B * 2 * C * N, dt)); close(2);
+  r.gin = extra_behind ? cv.take(tbytes(B * 2 * C * N, dt)) : r.x1; close(3);
+  r.g = cv.take(tbytes(B * C * N, dt)); close(4);
+  r.y = cv.take(tbytes(B * C * N, dt)); close(5);
   r.mean1 = cv.take<float>(fbytes(B * N));
-  r.rstd1 = cv.take<float>(fbytes(B * N));
-  r.mean2 = cv.take<float>(fbytes(B * N));
-  r.rstd2 = cv.take<float>(fbytes(B * N));
+  r.rstd1 = cv.take<float>(fbytes(B * N)); close(6);
   r.pool = cv.take<float>(fbytes(B * C));
   r.s = cv.take<float>(fbytes(B * C));
   r.M3 = cv.take<float>(fbytes(cc));
   r.b3f = cv.take<float>(fbytes(C));
-  r.M5 = cv.take<float>(fbytes(cc));
-  r.b5f = cv.take<float>(fbytes(C));
   r.M3s = cv.take<float>(fbytes(2 * cc));
-  r.M3ts = cv.take<float>(fbytes(2 * cc));
-  r.M5s = cv.take<float>(fbytes(2 * cc));
-  r.M5ts = cv.take<float>(fbytes(2 * cc));
-  r.bytes = cv.off;
+  r.M3ts = cv.take<float>(fbytes(2 * cc)); close(7);
   return r;
 }
 
-struct DbWs {
-  void* pw_ws; void* gram_ws; void* cs_ws; void* ln_ws; void* dg_fwd_ws; void* dg_bwd_ws; void* pc_ws;
-  float* G; float* S; float* ds; float* dg_add; float* wsplit;
-  DbSaved inf; void* t1; void* t2; void* t3; size_t bytes;
-};
 // y[B][M] = W x (+ bias) (+ res).  split: w is a split image [M][2K] and x enters as both K panels; per_img: one matrix per image
 static mi_pw_desc db_gemm(const void* x, int K, const float* w, bool split, bool per_img, const float* bias, const void* res, void* y, int M,
                           int B, int64_t N, int dt) {
@@ -657,38 +650,111 @@ static size_t db_probe(int K, int M, bool split, bool per_img, bool t, int B, in
                          : db_gemm(PROBE_PTR, K, (const float*)PROBE_PTR, split, per_img, nullptr, nullptr, PROBE_PTR, M, B, N, dt);
   return pw_ws_bytes(d);
 }
-static DbWs db_ws_layout(const mi_dblock_shape* s, void* base, int R) {
+
+// The scratch of the chain and of the 1x1 products and Grams of a block's second half, which are of the same shapes.  t1..t3: the
+// backward's three [B][2c] planes (gh_ws_tail).
+struct GhWs {
+  void* pw_ws; void* gram_ws; void* cs_ws; void* ln_ws; void* dg_fwd_ws; void* dg_bwd_ws;
+  float* G; float* S; float* ds; float* dg_add; float* wsplit;
+  void* t1; void* t2; void* t3;
+};
+// own_gram: the workspace of a Gram that only the block's second half runs (0: none)
+template <typename S>
+static GhWs gh_ws_carve(Carver& cv, const S* s, int R, size_t own_gram) {
   const int B = s->B, C = s->C, dt = s->dtype;
   const int64_t N = (int64_t)s->H * s->W;
-  Carver cv(base);
-  DbWs w;
-  memset(&w, 0, sizeof(w));
+  GhWs w;
   const bool sp = dt == MI_BF16;
   // c -> 2c, its transpose 2c -> c, the per-image c -> c and its transpose (bf16: all four as split products, none transposed)
   w.pw_ws = cv.take(max_of({db_probe(C, 2 * C, sp, false, false, B, N, dt), db_probe(C, C, sp, true, false, B, N, dt),
                             sp ? db_probe(2 * C, C, true, false, false, B, N, dt) : db_probe(2 * C, C, false, false, true, B, N, dt),
                             sp ? (size_t)0 : db_probe(C, C, false, true, true, B, N, dt)}));
   w.wsplit = cv.take<float>(fbytes((size_t)4 * C * C));
-  w.gram_ws = cv.take(max_of({gram_ws_bytes(probe_wgrad(C, C, B, N, dt, 0)), gram_ws_bytes(probe_wgrad(C, C, B, N, dt, 1)),
-                              gram_ws_bytes(probe_wgrad(2 * C, C, B, N, dt, 1))}));
+  w.gram_ws = cv.take(max_of({gram_ws_bytes(probe_wgrad(C, C, B, N, dt, 0)), gram_ws_bytes(probe_wgrad(2 * C, C, B, N, dt, 1)), own_gram}));
   w.cs_ws = cv.take(chan_sum_workspace(B * C > 2 * C ? B * C : 2 * C, N));
   w.ln_ws = cv.take(mi_ln_bwd_workspace(B, C, N));
   const DgPlan pl = dg_plan(B, C, s->H, s->W, s->n_dil, R, dt);
   w.dg_fwd_ws = cv.take(pl.fwd_ws);
   w.dg_bwd_ws = cv.take(pl.bwd_ws);
-  w.pc_ws = cv.take(fbytes(pc_part_floats(B, C, s->H, s->W)));
   w.G = cv.take<float>(fbytes((size_t)B * C * C));
   w.S = cv.take<float>(fbytes((size_t)B * C));
   w.ds = cv.take<float>(fbytes((size_t)B * C));
   w.dg_add = cv.take<float>(fbytes((size_t)B * C));
-  const size_t mark = cv.off;
-  w.inf = db_saved_layout(s, base ? (char*)base + mark : nullptr);
-  Carver big(base ? (char*)base + mark : nullptr);
-  const size_t plane2 = tbytes((size_t)B * 2 * C * N, dt);
+  return w;
+}
+static void* ws_at(void* base, size_t off) { return base ? (char*)base + off : nullptr; }
+// Behind every other section and overlaid on one another: the inference copy of the saved planes (inf_bytes at `over`; a forward
+// without a blob keeps nothing) and the backward's t1..t3.  -> the bytes of the overlay
+template <typename S>
+static size_t gh_ws_tail(GhWs& w, void* over, size_t inf_bytes, const S* s) {
+  Carver big(over);
+  const size_t plane2 = tbytes((size_t)s->B * 2 * s->C * s->H * s->W, s->dtype);
   w.t1 = big.take(plane2);
   w.t2 = big.take(plane2);
   w.t3 = big.take(plane2);
-  w.bytes = mark + max_of({w.inf.bytes, big.off});
+  return max_of({inf_bytes, big.off});
+}
+
+// The null checks of a block's parameters (what = "parameter") or gradient buffers ("gradient buffer").  own: the fields of the
+// block's second half are all set.
+template <typename P>
+static int gh_check_par(const char* who, const char* what, const P* p, bool own, int extra, int n_dil) {
+  MI_CHECK_ARG(p->norm1_w && p->norm1_b && p->conv1_w && p->conv1_b && p->sca_w && p->sca_b && p->conv3_w && p->conv3_b && p->beta && own,
+               "%s: null %s", who, what);
+  MI_CHECK_ARG(!extra || (p->extra_w && p->extra_b), "%s: null extra_conv %s", who, what);
+  for (int i = 0; i < n_dil; ++i) MI_CHECK_ARG(p->br_w[i] && p->br_b[i], "%s: null %s of branch %d", who, what, i);
+  return MI_OK;
+}
+template <typename P>
+static mi_dilgate_params db_branches(const P* p) {
+  mi_dilgate_params q;
+  for (int i = 0; i < DG_MAX_N; ++i) { q.w[i] = p->br_w[i]; q.b[i] = p->br_b[i]; }
+  return q;
+}
+template <typename G>
+static mi_dilgate_grads db_branch_grads(const G* g) {
+  mi_dilgate_grads q;
+  for (int i = 0; i < DG_MAX_N; ++i) { q.w[i] = g->br_w[i]; q.b[i] = g->br_b[i]; }
+  q.accumulate = g->accumulate;
+  return q;
+}
+
+// ------------------------------------------------------------------ DBlock: layouts
+struct DbSaved {
+  GhSaved gh;
+  void* y0; void* u; void* h;
+  float* mean2; float* rstd2; float* M5; float* b5f; float* M5s; float* M5ts;
+  size_t bytes;
+};
+// train: everything the backward reads; inference (in the workspace): the same planes, nothing outlives the call
+static DbSaved db_saved_layout(const mi_dblock_shape* s, void* base) {
+  const size_t B = s->B, C = s->C, N = (size_t)s->H * s->W, cc = B * C * C;
+  const int dt = s->dtype;
+  Carver cv(base);
+  DbSaved r;
+  r.gh = gh_saved_carve(cv, s, false, s->extra != 0);
+  r.y0 = cv.take(tbytes(B * C * N, dt));
+  r.u = cv.take(tbytes(B * 2 * C * N, dt));
+  r.h = cv.take(tbytes(B * C * N, dt));
+  r.mean2 = cv.take<float>(fbytes(B * N));
+  r.rstd2 = cv.take<float>(fbytes(B * N));
+  r.M5 = cv.take<float>(fbytes(cc));
+  r.b5f = cv.take<float>(fbytes(C));
+  r.M5s = cv.take<float>(fbytes(2 * cc));
+  r.M5ts = cv.take<float>(fbytes(2 * cc));
+  r.bytes = cv.off;
+  return r;
+}
+
+struct DbWs { GhWs gh; void* pc_ws; DbSaved inf; size_t bytes; };
+static DbWs db_ws_layout(const mi_dblock_shape* s, void* base, int R) {
+  Carver cv(base);
+  DbWs w;
+  // (conv5's Gram is summed over the batch)
+  w.gh = gh_ws_carve(cv, s, R, gram_ws_bytes(probe_wgrad(s->C, s->C, s->B, (int64_t)s->H * s->W, s->dtype, 1)));
+  w.pc_ws = cv.take(fbytes(pc_part_floats(s->B, s->C, s->H, s->W)));
+  w.inf = db_saved_layout(s, ws_at(base, cv.off));
+  w.bytes = cv.off + gh_ws_tail(w.gh, ws_at(base, cv.off), w.inf.bytes, s);
   return w;
 }
 
@@ -699,17 +765,11 @@ static int db_check(const mi_dblock_shape* s, int* R) {
   MI_CHECK_ARG((int64_t)2 * s->C * s->H * s->W < (1ll << 31), "dblock: 2*C*H*W must be below 2^31");
   return MI_OK;
 }
-static int db_check_params(const mi_dblock_shape* s, const mi_dblock_params* p) {
-  MI_CHECK_ARG(p && p->norm1_w && p->norm1_b && p->conv1_w && p->conv1_b && p->sca_w && p->sca_b && p->conv3_w && p->conv3_b && p->beta &&
-               p->norm2_w && p->norm2_b && p->conv4_w && p->conv4_b && p->conv5_w && p->conv5_b && p->gamma, "dblock: null parameter");
-  MI_CHECK_ARG(!s->extra || (p->extra_w && p->extra_b), "dblock: null extra_conv parameter");
-  for (int i = 0; i < s->n_dil; ++i) MI_CHECK_ARG(p->br_w[i] && p->br_b[i], "dblock: null parameter of branch %d", i);
-  return MI_OK;
-}
-static mi_dilgate_params db_branches(const mi_dblock_params* p) {
-  mi_dilgate_params q;
-  for (int i = 0; i < DG_MAX_N; ++i) { q.w[i] = p->br_w[i]; q.b[i] = p->br_b[i]; }
-  return q;
+template <typename P>   // P = mi_dblock_params or mi_dblock_grads
+static int db_check_par(const char* who, const char* what, const mi_dblock_shape* s, const P* p) {
+  MI_CHECK_ARG(p, "%s: null %s", who, what);
+  return gh_check_par(who, what, p, p->norm2_w && p->norm2_b && p->conv4_w && p->conv4_b && p->conv5_w && p->conv5_b && p->gamma, s->extra,
+                      s->n_dil);
 }
 
 static int db_fold(const float* pool, const float* wsca, const float* bsca, const float* w, const float* bias, const float* scale, float* s_out,
@@ -744,6 +804,65 @@ static int db_conv_bwd(const void* dy, int M, const void* x, int K, const float*
   MI_TRY(db_split(w, scratch, M, K, true, st));
   const mi_pw_desc d = db_gemm(dy, M, scratch, true, false, nullptr, nullptr, dx, K, B, N, dt);
   return mi_pw_gemm(&d, pw_ws, st);
+}
+
+// ------------------------------------------------------------------ the gated half: forward and backward
+// y = inp + M3[b] g + b3f from inp (arch_model.py:118-129 and :183-193).  extra() runs the block's extra_conv, at the place the
+// storage gives it: x0 -> cin in front of conv1, or x1 -> gin behind it (never both: a block has one extra_conv, so one callable).
+template <typename S, typename P, typename Extra>
+static int gh_fwd(const S* s, const P* p, const void* inp, const GhSaved& sv, const GhWs& w, hipStream_t st, Extra extra) {
+  const int B = s->B, C = s->C, dt = s->dtype;
+  const int64_t N = (int64_t)s->H * s->W;
+  const bool b16 = dt == MI_BF16;
+  MI_TRY(mi_ln_fwd_eps(inp, p->norm1_w, p->norm1_b, sv.x0, sv.mean1, sv.rstd1, B, C, N, 1, 1e-6f, dt, st));
+  if (sv.cin != sv.x0) MI_TRY(extra());
+  MI_TRY(db_conv(sv.cin, C, p->conv1_w, p->conv1_b, sv.x1, 2 * C, B, N, dt, w.wsplit, w.pw_ws, st));
+  if (sv.gin != sv.x1) MI_TRY(extra());
+  const mi_dilgate_params br = db_branches(p);
+  MI_TRY(launch_dilgate_fwd(sv.gin, &br, sv.g, sv.pool, B, C, s->H, s->W, s->n_dil, s->dil, dt, w.dg_fwd_ws, st));
+  MI_TRY(db_fold(sv.pool, p->sca_w, p->sca_b, p->conv3_w, p->conv3_b, p->beta, sv.s, sv.M3, b16 ? sv.M3s : nullptr, b16 ? sv.M3ts : nullptr,
+                 sv.b3f, B, C, N, st));
+  mi_pw_desc d3 = db_gemm(sv.g, C, b16 ? sv.M3s : sv.M3, b16, true, sv.b3f, inp, sv.y, C, B, N, dt);
+  return mi_pw_gemm(&d3, w.pw_ws, st);
+}
+
+// dinp and the chain's parameter gradients from the whole gradient at y, which the block's second half left in w.t3.  w.t1 and
+// w.t2 are a ping-pong: a plane is written only once its content is dead, and on entry both hold dead planes of the second half
+// (t1: the gradient at norm2's output; t2: DBlock's du, EBlock's dyr).  extra(d_out, d_in) is extra_conv's backward.
+template <typename S, typename P, typename G, typename Extra>
+static int gh_bwd(const S* s, const P* p, const G* g, const void* inp, void* dinp, const GhSaved& sv, const GhWs& w, hipStream_t st,
+                  Extra extra) {
+  const int B = s->B, C = s->C, dt = s->dtype, acc = g->accumulate;
+  const int64_t N = (int64_t)s->H * s->W;
+  const bool b16 = dt == MI_BF16;
+  const float inv_n = 1.0f / (float)N;
+  const void* dy = w.t3;
+  mi_gram_desc g3 = wgrad_gram(dy, C, sv.g, C, B, N, dt, w.G, 0, 0);
+  MI_TRY(mi_gram(&g3, w.gram_ws, st));
+  MI_TRY(launch_chan_sum(dy, w.S, 1, B * C, N, dt, 0, w.cs_ws, st));       // per image: [B][c]
+  {
+    ProfScope ps(st, K_DK_FOLD_BWD, 4.0 * (2.0 * B + 3) * C * C, 2.0 * (3.0 * B + 2) * C * C);
+    hipLaunchKernelGGL(dk_sca_ds_kernel, dim3(B), dim3(256), C * sizeof(float), st, w.G, p->conv3_w, p->beta, p->sca_w, w.ds, w.dg_add, C, inv_n);
+    MI_LAUNCH_CHECK();
+    hipLaunchKernelGGL(dk_fold_bwd_kernel, dim3(C), dim3(256), 0, st, w.G, sv.s, w.S, p->conv3_w, p->conv3_b, p->beta, g->conv3_w, g->conv3_b,
+                       g->beta, B, C, acc);
+    MI_LAUNCH_CHECK();
+    hipLaunchKernelGGL(dk_sca_w_kernel, dim3(C), dim3(256), 0, st, w.ds, sv.pool, g->sca_w, g->sca_b, B, C, inv_n, acc);
+    MI_LAUNCH_CHECK();
+  }
+  void* dgp = w.t1;    // (the gradient at norm2's output is dead)
+  mi_pw_desc e3 = b16 ? db_gemm(dy, C, sv.M3ts, true, true, nullptr, nullptr, dgp, C, B, N, dt) : db_gemm_t(dy, C, sv.M3, true, dgp, C, B, N, dt);
+  MI_TRY(mi_pw_gemm(&e3, w.pw_ws, st));
+  const mi_dilgate_params br = db_branches(p);
+  const mi_dilgate_grads bg = db_branch_grads(g);
+  void* cur = w.t2;    // (du / dyr is dead) the gradient at the gate's input
+  void* dead = w.t1;   // (dg is dead once the gate's backward returns)
+  MI_TRY(launch_dilgate_bwd(dgp, w.dg_add, sv.gin, &br, cur, &bg, B, C, s->H, s->W, s->n_dil, s->dil, dt, w.dg_bwd_ws, st));
+  if (sv.gin != sv.x1) { MI_TRY(extra(cur, dead)); std::swap(cur, dead); }     // -> the gradient at x1 (the one at the gate's input is dead)
+  MI_TRY(db_conv_bwd(cur, 2 * C, sv.cin, C, p->conv1_w, g->conv1_w, g->conv1_b, dead, B, N, dt, acc, w.wsplit, w.gram_ws, w.cs_ws, w.pw_ws, st));
+  std::swap(cur, dead);      // the gradient at conv1's input (the one at x1 is dead)
+  if (sv.cin != sv.x0) { MI_TRY(extra(cur, dead)); std::swap(cur, dead); }     // -> the gradient at x0
+  return mi_ln_bwd(cur, inp, p->norm1_w, sv.mean1, sv.rstd1, dy, dinp, g->norm1_w, g->norm1_b, B, C, N, 1, acc, dt, w.ln_ws, st);
 }
 
 // ------------------------------------------------------------------ EBlock's tail: out = y (1 + gamma f)
@@ -888,87 +1007,44 @@ static int launch_fregate_bwd(const void* dout, const void* y, const void* f, co
 
 // ------------------------------------------------------------------ EBlock: layouts
 struct EbSaved {
-  void* x0; void* xe; void* x1; void* g; void* y; void* f;
-  float* mean1; float* rstd1; float* mean2; float* rstd2; float* pool; float* s; float* M3; float* b3f; float* M3s; float* M3ts;
-  void* blob;
+  GhSaved gh;
+  void* f; float* mean2; float* rstd2; void* blob;
   size_t sec[9];     // bytes of x0, xe, x1, g, y, f, the statistics, the small tensors, the FreMLP blob
   size_t bytes;
 };
 static mi_fremlp_shape eb_fre_shape(const mi_eblock_shape* s) { return mi_fremlp_shape{s->B, s->C, 2, s->H, s->W, s->dtype}; }
 // train: everything the backward reads; inference (blob = false, in the workspace): the same planes, nothing outlives the call
 static EbSaved eb_saved_layout(const mi_eblock_shape* s, void* base, bool blob) {
-  const size_t B = s->B, C = s->C, N = (size_t)s->H * s->W, cc = B * C * C;
-  const int dt = s->dtype;
+  const size_t N = (size_t)s->H * s->W;
   Carver cv(base);
   EbSaved r;
-  memset(&r, 0, sizeof(r));
-  size_t o = cv.off;
-  auto close = [&](int i) { r.sec[i] = cv.off - o; o = cv.off; };
-  r.x0 = cv.take(tbytes(B * C * N, dt)); close(0);
-  r.xe = s->extra ? cv.take(tbytes(B * C * N, dt)) : r.x0; close(1);
-  r.x1 = cv.take(tbytes(B * 2 * C * N, dt)); close(2);
-  r.g = cv.take(tbytes(B * C * N, dt)); close(3);
-  r.y = cv.take(tbytes(B * C * N, dt)); close(4);
-  r.f = cv.take(tbytes(B * C * N, dt)); close(5);
-  r.mean1 = cv.take<float>(fbytes(B * N));
-  r.rstd1 = cv.take<float>(fbytes(B * N));
-  r.mean2 = cv.take<float>(fbytes(B * N));
-  r.rstd2 = cv.take<float>(fbytes(B * N)); close(6);
-  r.pool = cv.take<float>(fbytes(B * C));
-  r.s = cv.take<float>(fbytes(B * C));
-  r.M3 = cv.take<float>(fbytes(cc));
-  r.b3f = cv.take<float>(fbytes(C));
-  r.M3s = cv.take<float>(fbytes(2 * cc));
-  r.M3ts = cv.take<float>(fbytes(2 * cc)); close(7);
-  if (blob) {
-    const mi_fremlp_shape fs = eb_fre_shape(s);
-    r.blob = cv.take(mi_fremlp_saved_bytes(&fs));
-  }
-  close(8);
+  r.gh = gh_saved_carve(cv, s, s->extra != 0, false);
+  const size_t* gs = r.gh.sec;      // x0, xe, x1, (no plane behind conv1,) g, y, mean1 / rstd1, the small tensors
+  size_t o = cv.off, own[3];        // f, mean2 / rstd2, the FreMLP blob
+  auto close = [&](int i) { own[i] = cv.off - o; o = cv.off; };
+  r.f = cv.take(tbytes(s->B * s->C * N, s->dtype)); close(0);
+  r.mean2 = cv.take<float>(fbytes(s->B * N));
+  r.rstd2 = cv.take<float>(fbytes(s->B * N)); close(1);
+  const mi_fremlp_shape fs = eb_fre_shape(s);
+  r.blob = blob ? cv.take(mi_fremlp_saved_bytes(&fs)) : nullptr; close(2);
   r.bytes = cv.off;
+  const size_t sec[9] = {gs[0], gs[1], gs[2], gs[4], gs[5], own[0], gs[6] + own[1], gs[7], own[2]};
+  memcpy(r.sec, sec, sizeof(sec));
   return r;
 }
 
-struct EbWs {
-  void* pw_ws; void* gram_ws; void* cs_ws; void* ln_ws; void* dg_fwd_ws; void* dg_bwd_ws; void* dw_ws; void* fre_ws; void* fg_ws;
-  float* G; float* S; float* ds; float* dg_add; float* wsplit; void* y0;
-  EbSaved inf; void* t1; void* t2; void* t3; size_t bytes;
-};
+struct EbWs { GhWs gh; void* dw_ws; void* fre_ws; void* fg_ws; void* y0; EbSaved inf; size_t bytes; };
 static EbWs eb_ws_layout(const mi_eblock_shape* s, void* base, int R) {
-  const int B = s->B, C = s->C, dt = s->dtype;
-  const int64_t N = (int64_t)s->H * s->W;
   Carver cv(base);
   EbWs w;
-  memset(&w, 0, sizeof(w));
-  const bool sp = dt == MI_BF16;
-  // c -> 2c, its transpose 2c -> c, the per-image c -> c and its transpose (bf16: all four as split products, none transposed)
-  w.pw_ws = cv.take(max_of({db_probe(C, 2 * C, sp, false, false, B, N, dt), db_probe(C, C, sp, true, false, B, N, dt),
-                            sp ? db_probe(2 * C, C, true, false, false, B, N, dt) : db_probe(2 * C, C, false, false, true, B, N, dt),
-                            sp ? (size_t)0 : db_probe(C, C, false, true, true, B, N, dt)}));
-  w.wsplit = cv.take<float>(fbytes((size_t)4 * C * C));
-  w.gram_ws = cv.take(max_of({gram_ws_bytes(probe_wgrad(C, C, B, N, dt, 0)), gram_ws_bytes(probe_wgrad(2 * C, C, B, N, dt, 1))}));
-  w.cs_ws = cv.take(chan_sum_workspace(B * C > 2 * C ? B * C : 2 * C, N));
-  w.ln_ws = cv.take(mi_ln_bwd_workspace(B, C, N));
-  const DgPlan pl = dg_plan(B, C, s->H, s->W, s->n_dil, R, dt);
-  w.dg_fwd_ws = cv.take(pl.fwd_ws);
-  w.dg_bwd_ws = cv.take(pl.bwd_ws);
-  w.dw_ws = cv.take(s->extra ? mi_dwconv_bwd_workspace(B, C, s->H, s->W, 3) : 0);
+  w.gh = gh_ws_carve(cv, s, R, 0);
+  w.dw_ws = cv.take(s->extra ? mi_dwconv_bwd_workspace(s->B, s->C, s->H, s->W, 3) : 0);
   const mi_fremlp_shape fs = eb_fre_shape(s);
   w.fre_ws = cv.take(mi_fremlp_workspace(&fs));
-  w.fg_ws = cv.take(fg_bwd_ws(B, C, N));
-  w.G = cv.take<float>(fbytes((size_t)B * C * C));
-  w.S = cv.take<float>(fbytes((size_t)B * C));
-  w.ds = cv.take<float>(fbytes((size_t)B * C));
-  w.dg_add = cv.take<float>(fbytes((size_t)B * C));
-  w.y0 = cv.take(tbytes((size_t)B * C * N, dt));       // LayerNorm2d(y): FreMLP's input, dead when the forward returns
-  const size_t mark = cv.off;
-  w.inf = eb_saved_layout(s, base ? (char*)base + mark : nullptr, false);
-  Carver big(base ? (char*)base + mark : nullptr);
-  const size_t plane2 = tbytes((size_t)B * 2 * C * N, dt);
-  w.t1 = big.take(plane2);
-  w.t2 = big.take(plane2);
-  w.t3 = big.take(plane2);
-  w.bytes = mark + max_of({w.inf.bytes, big.off});
+  w.fg_ws = cv.take(fg_bwd_ws(s->B, s->C, (int64_t)s->H * s->W));
+  w.y0 = cv.take(tbytes((size_t)s->B * s->C * s->H * s->W, s->dtype));       // LayerNorm2d(y): FreMLP's input, dead when the forward returns
+  w.inf = eb_saved_layout(s, ws_at(base, cv.off), false);
+  w.bytes = cv.off + gh_ws_tail(w.gh, ws_at(base, cv.off), w.inf.bytes, s);
   return w;
 }
 
@@ -984,12 +1060,11 @@ static int eb_check(const mi_eblock_shape* s, int* R) {
   if (mi_fremlp_workspace(&fs) == 0) return MI_ERR_ARG;      // (its message stands)
   return MI_OK;
 }
-static int eb_check_params(const mi_eblock_shape* s, const mi_eblock_params* p) {
-  MI_CHECK_ARG(p && p->norm1_w && p->norm1_b && p->conv1_w && p->conv1_b && p->sca_w && p->sca_b && p->conv3_w && p->conv3_b && p->beta &&
-               p->norm2_w && p->norm2_b && p->fre_w1 && p->fre_b1 && p->fre_w2 && p->fre_b2 && p->gamma, "eblock: null parameter");
-  MI_CHECK_ARG(!s->extra || (p->extra_w && p->extra_b), "eblock: null extra_conv parameter");
-  for (int i = 0; i < s->n_dil; ++i) MI_CHECK_ARG(p->br_w[i] && p->br_b[i], "eblock: null parameter of branch %d", i);
-  return MI_OK;
+template <typename P>   // P = mi_eblock_params or mi_eblock_grads
+static int eb_check_par(const char* who, const char* what, const mi_eblock_shape* s, const P* p) {
+  MI_CHECK_ARG(p, "%s: null %s", who, what);
+  return gh_check_par(who, what, p, p->norm2_w && p->norm2_b && p->fre_w1 && p->fre_b1 && p->fre_w2 && p->fre_b2 && p->gamma, s->extra,
+                      s->n_dil);
 }
 
 }  // namespace mi
@@ -1054,32 +1129,26 @@ extern "C" int mi_dblock_fwd(const mi_dblock_shape* s, const mi_dblock_params* p
                              void* stream) {
   int R = 0;
   MI_TRY(db_check(s, &R));
-  MI_TRY(db_check_params(s, p));
+  MI_TRY(db_check_par("dblock", "parameter", s, p));
   MI_CHECK_ARG(inp && out && ws, "dblock_fwd: null pointer");
   hipStream_t st = (hipStream_t)stream;
   const int B = s->B, C = s->C, H = s->H, W = s->W, dt = s->dtype;
   const int64_t N = (int64_t)H * W;
   const bool b16 = dt == MI_BF16;
-  DbWs w = db_ws_layout(s, ws, R);
-  DbSaved sv = saved ? db_saved_layout(s, saved) : w.inf;
-  const mi_dilgate_params br = db_branches(p);
+  const DbWs ws_ = db_ws_layout(s, ws, R);
+  const GhWs& w = ws_.gh;
+  const DbSaved sv = saved ? db_saved_layout(s, saved) : ws_.inf;
   // first half (arch_model.py:118-129)
-  MI_TRY(mi_ln_fwd_eps(inp, p->norm1_w, p->norm1_b, sv.x0, sv.mean1, sv.rstd1, B, C, N, 1, 1e-6f, dt, stream));
-  MI_TRY(db_conv(sv.x0, C, p->conv1_w, p->conv1_b, sv.x1, 2 * C, B, N, dt, w.wsplit, w.pw_ws, st));
-  if (s->extra) MI_TRY(launch_pairconv<1>(sv.x1, p->extra_w, p->extra_b, sv.x2, B, C, H, W, dt, st));
-  MI_TRY(launch_dilgate_fwd(sv.x2, &br, sv.g, sv.pool, B, C, H, W, s->n_dil, s->dil, dt, w.dg_fwd_ws, st));
-  MI_TRY(db_fold(sv.pool, p->sca_w, p->sca_b, p->conv3_w, p->conv3_b, p->beta, sv.s, sv.M3, b16 ? sv.M3s : nullptr, b16 ? sv.M3ts : nullptr,
-                 sv.b3f, B, C, N, st));
-  mi_pw_desc d3 = db_gemm(sv.g, C, b16 ? sv.M3s : sv.M3, b16, true, sv.b3f, inp, sv.y, C, B, N, dt);
-  MI_TRY(mi_pw_gemm(&d3, w.pw_ws, stream));
+  MI_TRY(gh_fwd(s, p, inp, sv.gh, w, st,
+                [&] { return launch_pairconv<1>(sv.gh.x1, p->extra_w, p->extra_b, sv.gh.gin, B, C, H, W, dt, st); }));
   // second half (:131-134)
-  MI_TRY(mi_ln_fwd_eps(sv.y, p->norm2_w, p->norm2_b, sv.y0, sv.mean2, sv.rstd2, B, C, N, 1, 1e-6f, dt, stream));
+  MI_TRY(mi_ln_fwd_eps(sv.gh.y, p->norm2_w, p->norm2_b, sv.y0, sv.mean2, sv.rstd2, B, C, N, 1, 1e-6f, dt, stream));
   MI_TRY(db_conv(sv.y0, C, p->conv4_w, p->conv4_b, sv.u, 2 * C, B, N, dt, w.wsplit, w.pw_ws, st));
   const size_t half = (size_t)C * N * dtype_size(dt);
   MI_TRY(mi_ewise_fwd(sv.u, 2 * C * N, (const char*)sv.u + half, 2 * C * N, sv.h, B, C * N, 0, dt, stream));
   MI_TRY(db_fold(nullptr, nullptr, nullptr, p->conv5_w, p->conv5_b, p->gamma, nullptr, sv.M5, b16 ? sv.M5s : nullptr,
                  b16 ? sv.M5ts : nullptr, sv.b5f, B, C, N, st));
-  mi_pw_desc d5 = db_gemm(sv.h, C, b16 ? sv.M5s : sv.M5, b16, true, sv.b5f, sv.y, out, C, B, N, dt);
+  mi_pw_desc d5 = db_gemm(sv.h, C, b16 ? sv.M5s : sv.M5, b16, true, sv.b5f, sv.gh.y, out, C, B, N, dt);
   return mi_pw_gemm(&d5, w.pw_ws, stream);
 }
 
@@ -1087,19 +1156,16 @@ extern "C" int mi_dblock_bwd(const mi_dblock_shape* s, const mi_dblock_params* p
                              const mi_dblock_grads* g, const void* saved, void* ws, void* stream) {
   int R = 0;
   MI_TRY(db_check(s, &R));
-  MI_TRY(db_check_params(s, p));
+  MI_TRY(db_check_par("dblock", "parameter", s, p));
   MI_CHECK_ARG(inp && dout && dinp && g && saved && ws, "dblock_bwd: null pointer");
-  MI_CHECK_ARG(g->norm1_w && g->norm1_b && g->conv1_w && g->conv1_b && g->sca_w && g->sca_b && g->conv3_w && g->conv3_b && g->beta &&
-               g->norm2_w && g->norm2_b && g->conv4_w && g->conv4_b && g->conv5_w && g->conv5_b && g->gamma, "dblock_bwd: null gradient buffer");
-  MI_CHECK_ARG(!s->extra || (g->extra_w && g->extra_b), "dblock_bwd: null extra_conv gradient buffer");
-  for (int i = 0; i < s->n_dil; ++i) MI_CHECK_ARG(g->br_w[i] && g->br_b[i], "dblock_bwd: null gradient buffer of branch %d", i);
+  MI_TRY(db_check_par("dblock_bwd", "gradient buffer", s, g));
   hipStream_t st = (hipStream_t)stream;
   const int B = s->B, C = s->C, H = s->H, W = s->W, dt = s->dtype, acc = g->accumulate;
   const int64_t N = (int64_t)H * W;
   const bool b16 = dt == MI_BF16;
-  const float inv_n = 1.0f / (float)N;
-  DbWs w = db_ws_layout(s, ws, R);
-  DbSaved sv = db_saved_layout(s, const_cast<void*>(saved));
+  const DbWs ws_ = db_ws_layout(s, ws, R);
+  const GhWs& w = ws_.gh;
+  const DbSaved sv = db_saved_layout(s, const_cast<void*>(saved));
   const size_t half = (size_t)C * N * dtype_size(dt);
   // ---- second half: out = y + M5 h + b5f
   void* dh = w.t1;
@@ -1120,38 +1186,11 @@ extern "C" int mi_dblock_bwd(const mi_dblock_shape* s, const mi_dblock_params* p
   void* dy0 = w.t1;    // (dh is dead)
   MI_TRY(db_conv_bwd(du, 2 * C, sv.y0, C, p->conv4_w, g->conv4_w, g->conv4_b, dy0, B, N, dt, acc, w.wsplit, w.gram_ws, w.cs_ws, w.pw_ws, st));
   void* dy = w.t3;     // the whole gradient at y: through norm2 plus the residual's dout
-  MI_TRY(mi_ln_bwd(dy0, sv.y, p->norm2_w, sv.mean2, sv.rstd2, dout, dy, g->norm2_w, g->norm2_b, B, C, N, 1, acc, dt, w.ln_ws, stream));
-  // ---- first half: y = inp + M3[b] g + b3f
-  mi_gram_desc g3 = wgrad_gram(dy, C, sv.g, C, B, N, dt, w.G, 0, 0);
-  MI_TRY(mi_gram(&g3, w.gram_ws, stream));
-  MI_TRY(launch_chan_sum(dy, w.S, 1, B * C, N, dt, 0, w.cs_ws, st));       // per image: [B][c]
-  {
-    ProfScope ps(st, K_DK_FOLD_BWD, 4.0 * (2.0 * B + 3) * C * C, 2.0 * (3.0 * B + 2) * C * C);
-    hipLaunchKernelGGL(dk_sca_ds_kernel, dim3(B), dim3(256), C * sizeof(float), st, w.G, p->conv3_w, p->beta, p->sca_w, w.ds, w.dg_add, C, inv_n);
-    MI_LAUNCH_CHECK();
-    hipLaunchKernelGGL(dk_fold_bwd_kernel, dim3(C), dim3(256), 0, st, w.G, sv.s, w.S, p->conv3_w, p->conv3_b, p->beta, g->conv3_w, g->conv3_b,
-                       g->beta, B, C, acc);
-    MI_LAUNCH_CHECK();
-    hipLaunchKernelGGL(dk_sca_w_kernel, dim3(C), dim3(256), 0, st, w.ds, sv.pool, g->sca_w, g->sca_b, B, C, inv_n, acc);
-    MI_LAUNCH_CHECK();
-  }
-  void* dgp = w.t1;    // (dy0 is dead)
-  mi_pw_desc e3 = b16 ? db_gemm(dy, C, sv.M3ts, true, true, nullptr, nullptr, dgp, C, B, N, dt) : db_gemm_t(dy, C, sv.M3, true, dgp, C, B, N, dt);
-  MI_TRY(mi_pw_gemm(&e3, w.pw_ws, stream));
-  const mi_dilgate_params br = db_branches(p);
-  mi_dilgate_grads bg;
-  for (int i = 0; i < DG_MAX_N; ++i) { bg.w[i] = g->br_w[i]; bg.b[i] = g->br_b[i]; }
-  bg.accumulate = acc;
-  void* dx2 = w.t2;    // (du is dead)
-  MI_TRY(launch_dilgate_bwd(dgp, w.dg_add, sv.x2, &br, dx2, &bg, B, C, H, W, s->n_dil, s->dil, dt, w.dg_bwd_ws, st));
-  void* dx1 = dx2;
-  if (s->extra) {
-    dx1 = w.t1;        // (dg is dead)
-    MI_TRY(launch_pairconv_bwd(dx2, sv.x1, p->extra_w, dx1, g->extra_w, g->extra_b, B, C, H, W, acc, dt, w.pc_ws, st));
-  }
-  void* dx0 = s->extra ? w.t2 : w.t1;
-  MI_TRY(db_conv_bwd(dx1, 2 * C, sv.x0, C, p->conv1_w, g->conv1_w, g->conv1_b, dx0, B, N, dt, acc, w.wsplit, w.gram_ws, w.cs_ws, w.pw_ws, st));
-  return mi_ln_bwd(dx0, inp, p->norm1_w, sv.mean1, sv.rstd1, dy, dinp, g->norm1_w, g->norm1_b, B, C, N, 1, acc, dt, w.ln_ws, stream);
+  MI_TRY(mi_ln_bwd(dy0, sv.gh.y, p->norm2_w, sv.mean2, sv.rstd2, dout, dy, g->norm2_w, g->norm2_b, B, C, N, 1, acc, dt, w.ln_ws, stream));
+  // ---- first half: y = inp + M3[b] g + b3f (dy0 and du are dead)
+  return gh_bwd(s, p, g, inp, dinp, sv.gh, w, st, [&](const void* dx2, void* dx1) {
+    return launch_pairconv_bwd(dx2, sv.gh.x1, p->extra_w, dx1, g->extra_w, g->extra_b, B, C, H, W, acc, dt, ws_.pc_ws, st);
+  });
 }
 
 // ------------------------------------------------------------------ EBlock (arch_model.py:141-204)
@@ -1207,88 +1246,47 @@ extern "C" int mi_eblock_fwd(const mi_eblock_shape* s, const mi_eblock_params* p
                              void* stream) {
   int R = 0;
   MI_TRY(eb_check(s, &R));
-  MI_TRY(eb_check_params(s, p));
+  MI_TRY(eb_check_par("eblock", "parameter", s, p));
   MI_CHECK_ARG(inp && out && ws, "eblock_fwd: null pointer");
   hipStream_t st = (hipStream_t)stream;
   const int B = s->B, C = s->C, H = s->H, W = s->W, dt = s->dtype;
   const int64_t N = (int64_t)H * W;
-  const bool b16 = dt == MI_BF16;
-  EbWs w = eb_ws_layout(s, ws, R);
-  EbSaved sv = saved ? eb_saved_layout(s, saved, true) : w.inf;
-  mi_dilgate_params br;
-  for (int i = 0; i < DG_MAX_N; ++i) { br.w[i] = p->br_w[i]; br.b[i] = p->br_b[i]; }
+  const EbWs w = eb_ws_layout(s, ws, R);
+  const EbSaved sv = saved ? eb_saved_layout(s, saved, true) : w.inf;
   // first half (arch_model.py:183-193)
-  MI_TRY(mi_ln_fwd_eps(inp, p->norm1_w, p->norm1_b, sv.x0, sv.mean1, sv.rstd1, B, C, N, 1, 1e-6f, dt, stream));
-  if (s->extra) MI_TRY(mi_dwconv_fwd(sv.x0, p->extra_w, p->extra_b, sv.xe, B, C, H, W, 3, dt, stream));
-  MI_TRY(db_conv(sv.xe, C, p->conv1_w, p->conv1_b, sv.x1, 2 * C, B, N, dt, w.wsplit, w.pw_ws, st));
-  MI_TRY(launch_dilgate_fwd(sv.x1, &br, sv.g, sv.pool, B, C, H, W, s->n_dil, s->dil, dt, w.dg_fwd_ws, st));
-  MI_TRY(db_fold(sv.pool, p->sca_w, p->sca_b, p->conv3_w, p->conv3_b, p->beta, sv.s, sv.M3, b16 ? sv.M3s : nullptr, b16 ? sv.M3ts : nullptr,
-                 sv.b3f, B, C, N, st));
-  mi_pw_desc d3 = db_gemm(sv.g, C, b16 ? sv.M3s : sv.M3, b16, true, sv.b3f, inp, sv.y, C, B, N, dt);
-  MI_TRY(mi_pw_gemm(&d3, w.pw_ws, stream));
+  MI_TRY(gh_fwd(s, p, inp, sv.gh, w.gh, st,
+                [&] { return mi_dwconv_fwd(sv.gh.x0, p->extra_w, p->extra_b, sv.gh.cin, B, C, H, W, 3, dt, stream); }));
   // second half (:196-199)
-  MI_TRY(mi_ln_fwd_eps(sv.y, p->norm2_w, p->norm2_b, w.y0, sv.mean2, sv.rstd2, B, C, N, 1, 1e-6f, dt, stream));
+  MI_TRY(mi_ln_fwd_eps(sv.gh.y, p->norm2_w, p->norm2_b, w.y0, sv.mean2, sv.rstd2, B, C, N, 1, 1e-6f, dt, stream));
   const mi_fremlp_shape fs = eb_fre_shape(s);
   MI_TRY(mi_fremlp_fwd(&fs, p->fre_w1, p->fre_b1, p->fre_w2, p->fre_b2, w.y0, sv.f, saved ? sv.blob : nullptr, w.fre_ws, stream));
-  return launch_fregate_fwd(sv.y, sv.f, p->gamma, out, B, C, N, dt, st);
+  return launch_fregate_fwd(sv.gh.y, sv.f, p->gamma, out, B, C, N, dt, st);
 }
 
 extern "C" int mi_eblock_bwd(const mi_eblock_shape* s, const mi_eblock_params* p, const void* inp, const void* dout, void* dinp,
                              const mi_eblock_grads* g, const void* saved, void* ws, void* stream) {
   int R = 0;
   MI_TRY(eb_check(s, &R));
-  MI_TRY(eb_check_params(s, p));
+  MI_TRY(eb_check_par("eblock", "parameter", s, p));
   MI_CHECK_ARG(inp && dout && dinp && g && saved && ws, "eblock_bwd: null pointer");
-  MI_CHECK_ARG(g->norm1_w && g->norm1_b && g->conv1_w && g->conv1_b && g->sca_w && g->sca_b && g->conv3_w && g->conv3_b && g->beta &&
-               g->norm2_w && g->norm2_b && g->fre_w1 && g->fre_b1 && g->fre_w2 && g->fre_b2 && g->gamma, "eblock_bwd: null gradient buffer");
-  MI_CHECK_ARG(!s->extra || (g->extra_w && g->extra_b), "eblock_bwd: null extra_conv gradient buffer");
-  for (int i = 0; i < s->n_dil; ++i) MI_CHECK_ARG(g->br_w[i] && g->br_b[i], "eblock_bwd: null gradient buffer of branch %d", i);
+  MI_TRY(eb_check_par("eblock_bwd", "gradient buffer", s, g));
   hipStream_t st = (hipStream_t)stream;
   const int B = s->B, C = s->C, H = s->H, W = s->W, dt = s->dtype, acc = g->accumulate;
   const int64_t N = (int64_t)H * W;
-  const bool b16 = dt == MI_BF16;
-  const float inv_n = 1.0f / (float)N;
-  EbWs w = eb_ws_layout(s, ws, R);
-  EbSaved sv = eb_saved_layout(s, const_cast<void*>(saved), true);
+  const EbWs w = eb_ws_layout(s, ws, R);
+  const EbSaved sv = eb_saved_layout(s, const_cast<void*>(saved), true);
   // ---- second half: out = y (1 + gamma f), f = FreMLP(LN(y))
-  void* df = w.t3;
-  void* dyr = w.t2;    // the residual's share of the gradient at y
-  MI_TRY(launch_fregate_bwd(dout, sv.y, sv.f, p->gamma, df, dyr, g->gamma, B, C, N, acc, dt, w.fg_ws, st));
-  void* dy0 = w.t1;
+  void* df = w.gh.t3;
+  void* dyr = w.gh.t2;    // the residual's share of the gradient at y
+  MI_TRY(launch_fregate_bwd(dout, sv.gh.y, sv.f, p->gamma, df, dyr, g->gamma, B, C, N, acc, dt, w.fg_ws, st));
+  void* dy0 = w.gh.t1;
   const mi_fremlp_shape fs = eb_fre_shape(s);
   MI_TRY(mi_fremlp_bwd(&fs, p->fre_w1, p->fre_w2, p->fre_b2, df, dy0, g->fre_w1, g->fre_b1, g->fre_w2, g->fre_b2, acc, sv.blob, w.fre_ws,
                        stream));
-  void* dy = w.t3;     // (df is dead) the whole gradient at y: through norm2 plus the residual's share
-  MI_TRY(mi_ln_bwd(dy0, sv.y, p->norm2_w, sv.mean2, sv.rstd2, dyr, dy, g->norm2_w, g->norm2_b, B, C, N, 1, acc, dt, w.ln_ws, stream));
-  // ---- first half: y = inp + M3[b] g + b3f (mi_dblock_bwd's, with extra_conv in front of conv1)
-  mi_gram_desc g3 = wgrad_gram(dy, C, sv.g, C, B, N, dt, w.G, 0, 0);
-  MI_TRY(mi_gram(&g3, w.gram_ws, stream));
-  MI_TRY(launch_chan_sum(dy, w.S, 1, B * C, N, dt, 0, w.cs_ws, st));       // per image: [B][c]
-  {
-    ProfScope ps(st, K_DK_FOLD_BWD, 4.0 * (2.0 * B + 3) * C * C, 2.0 * (3.0 * B + 2) * C * C);
-    hipLaunchKernelGGL(dk_sca_ds_kernel, dim3(B), dim3(256), C * sizeof(float), st, w.G, p->conv3_w, p->beta, p->sca_w, w.ds, w.dg_add, C, inv_n);
-    MI_LAUNCH_CHECK();
-    hipLaunchKernelGGL(dk_fold_bwd_kernel, dim3(C), dim3(256), 0, st, w.G, sv.s, w.S, p->conv3_w, p->conv3_b, p->beta, g->conv3_w, g->conv3_b,
-                       g->beta, B, C, acc);
-    MI_LAUNCH_CHECK();
-    hipLaunchKernelGGL(dk_sca_w_kernel, dim3(C), dim3(256), 0, st, w.ds, sv.pool, g->sca_w, g->sca_b, B, C, inv_n, acc);
-    MI_LAUNCH_CHECK();
-  }
-  void* dgp = w.t1;    // (dy0 is dead)
-  mi_pw_desc e3 = b16 ? db_gemm(dy, C, sv.M3ts, true, true, nullptr, nullptr, dgp, C, B, N, dt) : db_gemm_t(dy, C, sv.M3, true, dgp, C, B, N, dt);
-  MI_TRY(mi_pw_gemm(&e3, w.pw_ws, stream));
-  mi_dilgate_params br;
-  mi_dilgate_grads bg;
-  for (int i = 0; i < DG_MAX_N; ++i) { br.w[i] = p->br_w[i]; br.b[i] = p->br_b[i]; bg.w[i] = g->br_w[i]; bg.b[i] = g->br_b[i]; }
-  bg.accumulate = acc;
-  void* dx1 = w.t2;    // (dyr is dead)
-  MI_TRY(launch_dilgate_bwd(dgp, w.dg_add, sv.x1, &br, dx1, &bg, B, C, H, W, s->n_dil, s->dil, dt, w.dg_bwd_ws, st));
-  void* dxe = w.t1;    // (dg is dead)
-  MI_TRY(db_conv_bwd(dx1, 2 * C, sv.xe, C, p->conv1_w, g->conv1_w, g->conv1_b, dxe, B, N, dt, acc, w.wsplit, w.gram_ws, w.cs_ws, w.pw_ws, st));
-  void* dx0 = dxe;
-  if (s->extra) {
-    dx0 = w.t2;        // (dx1 is dead)
-    MI_TRY(mi_dwconv_bwd(dxe, sv.x0, p->extra_w, dx0, g->extra_w, g->extra_b, B, C, H, W, 3, acc, dt, w.dw_ws, stream));
-  }
-  return mi_ln_bwd(dx0, inp, p->norm1_w, sv.mean1, sv.rstd1, dy, dinp, g->norm1_w, g->norm1_b, B, C, N, 1, acc, dt, w.ln_ws, stream);
+  void* dy = w.gh.t3;     // (df is dead) the whole gradient at y: through norm2 plus the residual's share
+  MI_TRY(mi_ln_bwd(dy0, sv.gh.y, p->norm2_w, sv.mean2, sv.rstd2, dyr, dy, g->norm2_w, g->norm2_b, B, C, N, 1, acc, dt, w.gh.ln_ws, stream));
+  // ---- first half: y = inp + M3[b] g + b3f (dy0 and dyr are dead)
+  return gh_bwd(s, p, g, inp, dinp, sv.gh, w.gh, st, [&](const void* dxe, void* dx0) {
+    return mi_dwconv_bwd(dxe, sv.gh.x0, p->extra_w, dx0, g->extra_w, g->extra_b, B, C, H, W, 3, acc, dt, w.dw_ws, stream);
+  });
 }

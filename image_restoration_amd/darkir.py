@@ -20,8 +20,9 @@ FFT library), the polar form as ``|Z|`` and ``Z / |Z|`` (no ``atan2``, ``cos`` o
 frequency bin in fp32.  Planes of 2..512 pixels a side, ``nc <= 256``, ``expand * nc <= 512``; larger images need tiling or a
 factored DFT, which is not built.
 
-``EBlock.forward`` is one autograd node (``mi_eblock_*``): DBlock's first half with a plain depthwise ``extra_conv`` in front of
-``conv1``, then ``norm2``, FreMLP and the streaming tail ``y * (1 + gamma * f)`` (``mi_fregate_*``).  1 <= c <= 256, planes of
+``EBlock.forward`` is one autograd node (``mi_eblock_*``): DBlock's first half (the library runs one launch sequence for both,
+and one op class and one constructor check serve both here) with a plain depthwise ``extra_conv`` in front of ``conv1``, then
+``norm2``, FreMLP and the streaming tail ``y * (1 + gamma * f)`` (``mi_fregate_*``).  1 <= c <= 256, planes of
 2..512 pixels a side.  ``DarkIR`` assembles the U-Net with the reference's attribute names and ``state_dict``; its glue convolutions
 run on the native 1x1 / 3x3 kernels (split weights with bf16 activations).  Width 32 (DarkIR-m) runs; width 64 reaches c = 512 and
 is refused at construction; a padded input above 512 pixels a side is refused in ``forward``.
@@ -112,18 +113,37 @@ class Branch(nn.Module):
                                   "mi_dilgate_* stencil pass); the module holds the parameters")
 
 
-class _DBlockOp:
-    """DBlock.forward as one module op.  params: ops._dblock_struct's flat list; saved = [the kernels' blob]."""
+class _BlockOp:
+    """DBlock.forward or EBlock.forward as one module op: ``fwd`` / ``bwd`` are ops.dblock_fwd / _bwd or ops.eblock_fwd / _bwd.
+    params: the flat list of ops._dblock_struct / ops._eblock_struct; saved = [the kernels' blob]."""
 
-    def __init__(self, dilations, extra):
-        self.dilations, self.extra = dilations, extra
+    def __init__(self, fwd, bwd, dilations, extra):
+        self.fwd, self.bwd, self.dilations, self.extra = fwd, bwd, dilations, extra
 
     def forward(self, acts, params, need):
-        out, blob = ops.dblock_fwd(acts[0], params, self.dilations, self.extra, need)
+        out, blob = self.fwd(acts[0], params, self.dilations, self.extra, need)
         return out, [blob]
 
     def backward(self, acts, saved, dout, params, grads, acc):
-        return (ops.dblock_bwd(acts[0], dout, params, self.dilations, self.extra, saved[0], grads, acc),)
+        return (self.bwd(acts[0], dout, params, self.dilations, self.extra, saved[0], grads, acc),)
+
+
+def _block_args(name, dilations=None, **expand):
+    """The constructor checks that DBlock and EBlock share.  ``expand``: the block's expansion factors (DW_Expand, and DBlock's
+    FFN_Expand), which the kernels take as 2; ``dilations``: checked and returned as a list.  (EBlock calls it once for each, with
+    its own check of c between the two, which is where that check has always stood.)"""
+    if any(v != 2 for v in expand.values()):
+        raise NotImplementedError(f"image_restoration_amd: {name} with {', '.join(f'{k}={v}' for k, v in expand.items())} not "
+                                  f"covered; the kernels were built for {' = '.join(expand)} = 2")
+    if dilations is None:
+        return None
+    dilations = list(dilations)
+    if not 1 <= len(dilations) <= ops.DILGATE_MAX_BRANCHES:
+        raise NotImplementedError(f"image_restoration_amd: {name} with {len(dilations)} branches not covered; the kernels "
+                                  f"were built for 1..{ops.DILGATE_MAX_BRANCHES} dilations")
+    for d in dilations:
+        _check_dilation(d)
+    return dilations
 
 
 class DBlock(nn.Module):
@@ -132,15 +152,7 @@ class DBlock(nn.Module):
 
     def __init__(self, c, DW_Expand=2, FFN_Expand=2, dilations=[1], extra_depth_wise=False):  # noqa: B006 (the reference's signature)
         super().__init__()
-        if DW_Expand != 2 or FFN_Expand != 2:
-            raise NotImplementedError(f"image_restoration_amd: DBlock with DW_Expand={DW_Expand}, FFN_Expand={FFN_Expand} not "
-                                      "covered; the kernels were built for DW_Expand = FFN_Expand = 2")
-        dilations = list(dilations)
-        if not 1 <= len(dilations) <= ops.DILGATE_MAX_BRANCHES:
-            raise NotImplementedError(f"image_restoration_amd: DBlock with {len(dilations)} branches not covered; the kernels "
-                                      f"were built for 1..{ops.DILGATE_MAX_BRANCHES} dilations")
-        for d in dilations:
-            _check_dilation(d)
+        dilations = _block_args("DBlock", dilations, DW_Expand=DW_Expand, FFN_Expand=FFN_Expand)
         self.dw_channel = DW_Expand * c
         self.conv1 = nn.Conv2d(in_channels=c, out_channels=self.dw_channel, kernel_size=1, padding=0, stride=1, groups=1, bias=True,
                                dilation=1)
@@ -181,7 +193,7 @@ class DBlock(nn.Module):
         if self.norm1.eps != LN_EPS or self.norm2.eps != LN_EPS:
             raise NotImplementedError(f"image_restoration_amd: DBlock's LayerNorm2d runs with eps = {LN_EPS} (the value the block "
                                       "kernels were built for)")
-        return module_op(_DBlockOp(self._dilations, self._extra), (inp,), self._params())
+        return module_op(_BlockOp(ops.dblock_fwd, ops.dblock_bwd, self._dilations, self._extra), (inp,), self._params())
 
 
 class _FreMlpOp:
@@ -219,20 +231,6 @@ class FreMLP(nn.Module):
         return module_op(_FreMlpOp(), (x,), (c1.weight, c1.bias, c2.weight, c2.bias))
 
 
-class _EBlockOp:
-    """EBlock.forward as one module op.  params: ops._eblock_struct's flat list; saved = [the kernels' blob]."""
-
-    def __init__(self, dilations, extra):
-        self.dilations, self.extra = dilations, extra
-
-    def forward(self, acts, params, need):
-        out, blob = ops.eblock_fwd(acts[0], params, self.dilations, self.extra, need)
-        return out, [blob]
-
-    def backward(self, acts, saved, dout, params, grads, acc):
-        return (ops.eblock_bwd(acts[0], dout, params, self.dilations, self.extra, saved[0], grads, acc),)
-
-
 class EBlock(nn.Module):
     """norm1 -> extra_conv -> conv1 -> summed dilated branches -> SimpleGate -> SCA -> conv3 -> + beta; norm2 -> FreMLP ->
     y + gamma (y * f) (arch_model.py:141-204), one autograd node.  ``extra_conv`` is a plain depthwise 3x3 in FRONT of ``conv1``
@@ -240,18 +238,11 @@ class EBlock(nn.Module):
 
     def __init__(self, c, DW_Expand=2, dilations=[1], extra_depth_wise=False):  # noqa: B006 (the reference's signature)
         super().__init__()
-        if DW_Expand != 2:
-            raise NotImplementedError(f"image_restoration_amd: EBlock with DW_Expand={DW_Expand} not covered; the kernels were "
-                                      "built for DW_Expand = 2")
+        _block_args("EBlock", DW_Expand=DW_Expand)
         if not (isinstance(c, int) and 1 <= c <= ops.EBLOCK_MAX_C):
             raise NotImplementedError(f"image_restoration_amd: EBlock(c={c!r}) not covered; the block kernels were built for "
                                       f"1 <= c <= {ops.EBLOCK_MAX_C}")
-        dilations = list(dilations)
-        if not 1 <= len(dilations) <= ops.DILGATE_MAX_BRANCHES:
-            raise NotImplementedError(f"image_restoration_amd: EBlock with {len(dilations)} branches not covered; the kernels "
-                                      f"were built for 1..{ops.DILGATE_MAX_BRANCHES} dilations")
-        for d in dilations:
-            _check_dilation(d)
+        dilations = _block_args("EBlock", dilations)
         self.dw_channel = DW_Expand * c
         self.extra_conv = nn.Conv2d(c, c, kernel_size=3, padding=1, stride=1, groups=c, bias=True,
                                     dilation=1) if extra_depth_wise else nn.Identity()
@@ -291,7 +282,7 @@ class EBlock(nn.Module):
         if self.freq.process1[1].negative_slope != 0.1:
             raise NotImplementedError("image_restoration_amd: FreMLP's LeakyReLU runs with slope 0.1 (the value the kernels were "
                                       "built for)")
-        return module_op(_EBlockOp(self._dilations, self._extra), (inp,), self._params())
+        return module_op(_BlockOp(ops.eblock_fwd, ops.eblock_bwd, self._dilations, self._extra), (inp,), self._params())
 
 
 def _split_weight(w2):

@@ -7,6 +7,7 @@ All compute happens in ``libmi_restore.so``.  CPU tensors are rejected: there is
 from __future__ import annotations
 
 import ctypes as C
+import functools
 import os
 from typing import Optional, Sequence, Tuple
 
@@ -815,13 +816,28 @@ def dilgate_plan(B: int, c: int, H: int, W: int, dtype: torch.dtype, dilations: 
     return plan
 
 
-def _dilgate_struct(cls, ws_: Sequence[Tensor], bs: Sequence[Optional[Tensor]], what: str, *tail):
+def _table_struct(fields, cls, ts: Sequence[Optional[Tensor]], n_dil: int, what: str, *tail):
+    """Struct ``cls`` (parameters, or their gradients with ``accumulate`` as ``tail``) from the flat list ``ts`` over a field table
+    like L.DBLOCK_FIELDS: (name, 1) takes one tensor, (name, 4) one per branch (n_dil of them).  Each is checked to be fp32."""
+    for t in ts:
+        _f32(t, what)
     st = cls()
-    for i, (w, b) in enumerate(zip(ws_, bs)):
-        st.w[i], st.b[i] = _p(_f32(w, what)), _p(_f32(b, what))
-    for name, v in zip(("accumulate",), tail):
-        setattr(st, name, v)
+    it = iter(ts)
+    for name, k in fields:
+        if k == 1:
+            setattr(st, name, _p(next(it)))
+        else:
+            arr = getattr(st, name)
+            for i in range(n_dil):
+                arr[i] = _p(next(it))
+    if tail:
+        st.accumulate = tail[0]
     return st
+
+
+def _dilgate_struct(cls, ws_: Sequence[Tensor], bs: Sequence[Optional[Tensor]], what: str, *tail):
+    n = min(len(ws_), len(bs))
+    return _table_struct((("w", 4), ("b", 4)), cls, (*ws_[:n], *bs[:n]), n, what, *tail)
 
 
 def dilgate_fwd(x: Tensor, weights: Sequence[Tensor], biases: Sequence[Optional[Tensor]], dilations: Sequence[int]):
@@ -880,12 +896,16 @@ def pairconv3x3_bwd(dy: Tensor, x: Tensor, w: Tensor, dw: Tensor, db: Optional[T
     return dx
 
 
-def _dblock_shape(B: int, Cc: int, H: int, W: int, dtype_code: int, dilations: Sequence[int], extra: bool) -> L.DblockShape:
-    s = L.DblockShape(B, Cc, H, W, dtype_code, len(dilations))
+def _block_shape(cls, B: int, Cc: int, H: int, W: int, dtype_code: int, dilations: Sequence[int], extra: bool):
+    """mi_dblock_shape / mi_eblock_shape (``cls``: L.DblockShape / L.EblockShape; the same fields)."""
+    s = cls(B, Cc, H, W, dtype_code, len(dilations))
     for i, d in enumerate(dilations[:4]):
         s.dil[i] = int(d)
     s.extra = int(extra)
     return s
+
+
+_dblock_shape = functools.partial(_block_shape, L.DblockShape)
 
 
 def dblock_sizes(B: int, Cc: int, H: int, W: int, dtype: torch.dtype, dilations: Sequence[int], extra: bool) -> Tuple[int, int]:
@@ -895,23 +915,9 @@ def dblock_sizes(B: int, Cc: int, H: int, W: int, dtype: torch.dtype, dilations:
     return int(lib.mi_dblock_saved_bytes(C.byref(s))), int(lib.mi_dblock_workspace(C.byref(s)))
 
 
-def _dblock_struct(cls, ts: Sequence[Optional[Tensor]], n_dil: int, what: str, *tail):
-    """mi_dblock_params / mi_dblock_grads from the flat list: norm1 (2), conv1 (2), extra_conv (2, None without it), the
-    branches' weights (n_dil), their biases (n_dil), sca (2), conv3 (2), beta, norm2 (2), conv4 (2), conv5 (2), gamma."""
-    for t in ts:
-        _f32(t, what)
-    st = cls()
-    it = iter(ts)
-    for name, k in L.DBLOCK_FIELDS:
-        if k == 1:
-            setattr(st, name, _p(next(it)))
-        else:
-            arr = getattr(st, name)
-            for i in range(n_dil):
-                arr[i] = _p(next(it))
-    if tail:
-        st.accumulate = tail[0]
-    return st
+# mi_dblock_params / mi_dblock_grads from the flat list: norm1 (2), conv1 (2), extra_conv (2, None without it), the branches'
+# weights (n_dil), their biases (n_dil), sca (2), conv3 (2), beta, norm2 (2), conv4 (2), conv5 (2), gamma
+_dblock_struct = functools.partial(_table_struct, L.DBLOCK_FIELDS)
 
 
 def dblock_fwd(x: Tensor, params: Sequence[Optional[Tensor]], dilations: Sequence[int], extra: bool, need_saved: bool):
@@ -1257,12 +1263,7 @@ def fregate_bwd(dout: Tensor, y: Tensor, f: Tensor, gamma: Tensor, dgamma: Tenso
     return df, dyr
 
 
-def _eblock_shape(B: int, Cc: int, H: int, W: int, dtype_code: int, dilations: Sequence[int], extra: bool) -> L.EblockShape:
-    s = L.EblockShape(B, Cc, H, W, dtype_code, len(dilations))
-    for i, d in enumerate(dilations[:4]):
-        s.dil[i] = int(d)
-    s.extra = int(extra)
-    return s
+_eblock_shape = functools.partial(_block_shape, L.EblockShape)
 
 
 def eblock_sizes(B: int, Cc: int, H: int, W: int, dtype: torch.dtype, dilations: Sequence[int], extra: bool) -> Tuple[int, int]:
@@ -1280,23 +1281,9 @@ def eblock_plan(B: int, Cc: int, H: int, W: int, dtype: torch.dtype, dilations: 
     return {k: int(out[i]) for i, k in enumerate(_EBLOCK_PLAN_KEYS)}
 
 
-def _eblock_struct(cls, ts: Sequence[Optional[Tensor]], n_dil: int, what: str, *tail):
-    """mi_eblock_params / mi_eblock_grads from the flat list: norm1 (2), extra_conv (2, None without it), conv1 (2), the branches'
-    weights (n_dil), their biases (n_dil), sca (2), conv3 (2), beta, norm2 (2), freq.process1.0 (2), freq.process1.2 (2), gamma."""
-    for t in ts:
-        _f32(t, what)
-    st = cls()
-    it = iter(ts)
-    for name, k in L.EBLOCK_FIELDS:
-        if k == 1:
-            setattr(st, name, _p(next(it)))
-        else:
-            arr = getattr(st, name)
-            for i in range(n_dil):
-                arr[i] = _p(next(it))
-    if tail:
-        st.accumulate = tail[0]
-    return st
+# mi_eblock_params / mi_eblock_grads from the flat list: norm1 (2), extra_conv (2, None without it), conv1 (2), the branches'
+# weights (n_dil), their biases (n_dil), sca (2), conv3 (2), beta, norm2 (2), freq.process1.0 (2), freq.process1.2 (2), gamma
+_eblock_struct = functools.partial(_table_struct, L.EBLOCK_FIELDS)
 
 
 def _eblock_args(x: Tensor, dilations: Sequence[int], extra: bool):

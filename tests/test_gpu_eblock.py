@@ -251,6 +251,33 @@ def test_no_grad_output_equals_grad_mode_and_zero_sample_is_finite():
         mod(torch.zeros(1, c, 1, 8, device=DEV))
 
 
+FIRST_HALF = ("norm1.", "conv1.", "branches.", "sca.1.", "conv3.", "beta")
+
+
+@DTYPES
+@pytest.mark.parametrize("name", ["tiny", "max_dil"])
+def test_first_half_is_dblocks_first_half_bitwise(name, dtype):
+    """The two blocks' first halves are one function (csrc/darkir.hip runs one launch sequence for both).  Without extra_conv and
+    with gamma = 0 both tails are the identity on y and hand dout back unchanged as the gradient at y: DBlock's 0 . W5 gives exact
+    zeros and 0 + dres is exact; EBlock's fma(0, f, 1) is 1 and a zero cotangent through FreMLP above its spectral floor stays
+    zero.  So out, dinp and the gradient of every first-half parameter of an EBlock and of a DBlock that shares its first-half
+    parameters (norm2 / conv4 / conv5 random) are equal bit for bit."""
+    (B, c, H, W), dil, extra, seed = E.PARITY_CASES[name]
+    assert not extra
+    sd, x, cot, _ = E.parity_io(name)
+    sd = dict(sd, gamma=torch.zeros_like(sd["gamma"]))
+    dsd = D.make_state(D.dblock_shapes(c, len(dil), False), seed + 60)
+    dsd.update({k: v for k, v in sd.items() if k.startswith(FIRST_HALF)}, gamma=sd["gamma"])
+    e = run_native(build(c, dil, False, sd), x, cot, dtype)
+    dmod = N().DBlock(c, dilations=list(dil), extra_depth_wise=False)
+    dmod.load_state_dict(dsd)
+    d = run_native(dmod.to(DEV), x, cot, dtype)
+    keys = ["y", "dx"] + ["g." + k for k in sd if k.startswith(FIRST_HALF)]
+    assert len(keys) == 2 + 9 + 2 * len(dil)
+    diff = [k for k in keys if not torch.equal(e[k], d[k])]
+    assert not diff, diff
+
+
 # ------------------------------------------------------------------ 5. the network
 def _run_net_native(net, x, cots, dtype):
     net.zero_grad(set_to_none=True)
