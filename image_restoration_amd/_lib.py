@@ -410,6 +410,7 @@ SIGNATURES = {
     "mi_conv3x3_fwd": (C.c_int, [vp, vp, C.c_int64, fp, vp, C.c_int64, vp, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
     "mi_conv3x3_wgrad_workspace": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     "mi_conv3x3_wgrad": (C.c_int, [vp, C.c_int64, vp, C.c_int64, fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]),
+    "mi_conv3x3_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(c_i64)]),
     "mi_chan_sum_workspace": (C.c_size_t, [C.c_int, C.c_int64]),
     "mi_chan_sum": (C.c_int, [vp, fp, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_int, vp, vp]),
     "mi_chan_sum_plan": (C.c_int, [C.c_int, C.c_int, C.c_int64, C.c_int, C.c_int, C.POINTER(c_i64)]),
@@ -418,6 +419,7 @@ SIGNATURES = {
     "mi_attn_small_bwd": (C.c_int, [fp, fp, fp, fp, fp, fp, fp, fp, fp, vp, C.c_int, C.c_int, C.c_int, vp]),
     "mi_im2col3x3": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
     "mi_col2im3x3": (C.c_int, [vp, fp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
+    "mi_glue3x3_plan": (C.c_int, [c_i64, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(c_i64)]),
     "mi_grouped_pw_gemm": (C.c_int, [C.POINTER(GroupedProblem), C.c_int, vp, vp, C.c_int, c_i64, C.c_int, vp]),
     "mi_moe_route_fwd": (C.c_int, [fp, fp, fp, fp, fp, fp, fp, fp, vp, fp, fp, vp, vp, vp, fp, vp, vp, C.c_int, C.c_int, C.c_int,
                                    C.c_int, C.c_int, C.c_int, vp]),
@@ -430,6 +432,8 @@ SIGNATURES = {
     "mi_ewise_bwd": (C.c_int, [vp, c_i64, vp, c_i64, vp, vp, c_i64, vp, c_i64, c_i64, c_i64, C.c_int, C.c_int, vp]),
     "mi_pixel_shuffle2": (C.c_int, [vp, c_i64, vp, c_i64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
     "mi_copy_rows": (C.c_int, [vp, c_i64, vp, c_i64, c_i64, c_i64, C.c_int, vp]),
+    "mi_pixel_shuffle2_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, c_i64, c_i64, C.c_int, C.c_int, C.POINTER(c_i64)]),
+    "mi_copy_rows_plan": (C.c_int, [c_i64, c_i64, c_i64, c_i64, C.c_int, C.c_int, C.POINTER(c_i64)]),
     "mi_patch_batch": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, fp, fp, vp, vp, C.c_int, C.c_int, C.c_int, vp]),
     "mi_psnr_ssim_workspace": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "mi_psnr_ssim": (C.c_int, [vp, vp, fp, fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]),

@@ -360,18 +360,42 @@ __global__ __launch_bounds__(256) void c3_wgrad_kernel(C3WArgs a) {
     }
 }
 
-static int c3w_splits(int B, int M, int K, int H, int W, int TWP) {
-  const int64_t tiles = (int64_t)B * cdiv(W, TWP) * cdiv(H, 256 / TWP);
-  const int64_t groups = (int64_t)cdiv(K, 16) * cdiv(M, 64);
+static int c3_mt(int M) { return M <= 16 ? 1 : (M <= 32 ? 2 : 4); }
+static int c3_twp(int W) { return W > 32 ? 64 : (W > 16 ? 32 : 16); }
+
+// What one forward / data-gradient call runs: filled by c3_plan, the ONE place that decides it; mi_conv3x3_pack, mi_conv3x3_fwd
+// and mi_conv3x3_pack_bytes launch and size from it, mi_conv3x3_plan reports it.
+struct C3Plan { int mt, twp, tr, tiles_x, tiles_y, co_tiles, chunks; size_t pack_bytes; };
+static C3Plan c3_plan(int M, int K, int H, int W) {
+  C3Plan p;
+  p.mt = c3_mt(M); p.twp = c3_twp(W); p.tr = 256 / p.twp;
+  p.tiles_x = cdiv(W, p.twp); p.tiles_y = cdiv(H, p.tr);
+  p.co_tiles = cdiv(M, 16 * p.mt); p.chunks = cdiv(K, 16);
+  p.pack_bytes = (size_t)p.co_tiles * p.chunks * C3_KS * p.mt * 512 * 2;
+  return p;
+}
+
+// The weight gradient likewise (c3w_plan; mi_conv3x3_wgrad, mi_conv3x3_wgrad_workspace, mi_conv3x3_plan).  Either operand can
+// take the 64-row role: the one that wastes less of the 64-row x 16-column tile.  rows / cols: the M and K the kernel sees.
+struct C3WPlan { bool swap; int rows, cols, twp, tiles_x, tiles_y, splits, grid_x, grid_y; size_t workspace; };
+static C3WPlan c3w_plan(int B, int M, int K, int H, int W) {
+  C3WPlan p;
+  const int64_t normal = (int64_t)cdiv(M, 64) * 64 * cdiv(K, 16) * 16, swapped = (int64_t)cdiv(K, 64) * 64 * cdiv(M, 16) * 16;
+  p.swap = swapped < normal;
+  p.rows = p.swap ? K : M; p.cols = p.swap ? M : K;
+  p.twp = c3_twp(W);
+  p.tiles_x = cdiv(W, p.twp); p.tiles_y = cdiv(H, 256 / p.twp);
+  p.grid_x = cdiv(p.cols, 16); p.grid_y = cdiv(p.rows, 64);
+  const int64_t tiles = (int64_t)B * p.tiles_x * p.tiles_y;
+  const int64_t groups = (int64_t)p.grid_x * p.grid_y;
   int64_t S = cdiv(1024, groups);                       // ~4 workgroups per CU in flight over the whole grid
   if (S > tiles / 2) S = tiles / 2;
   if (S < 1) S = 1;
   if (S > 4096) S = 4096;
-  return (int)S;
+  p.splits = (int)S;
+  p.workspace = (size_t)p.splits * M * K * 9 * sizeof(float);
+  return p;
 }
-
-static int c3_mt(int M) { return M <= 16 ? 1 : (M <= 32 ? 2 : 4); }
-static int c3_twp(int W) { return W > 32 ? 64 : (W > 16 ? 32 : 16); }
 
 }  // namespace mi
 
@@ -383,15 +407,15 @@ extern "C" int mi_conv3x3_ok(int H, int W, int dtype) {
 
 extern "C" size_t mi_conv3x3_pack_bytes(int M, int K) {
   if (M < 1 || K < 1) return 0;
-  const int MT = c3_mt(M);
-  return (size_t)cdiv(M, 16 * MT) * cdiv(K, 16) * C3_KS * MT * 512 * 2;
+  return c3_plan(M, K, 1, 8).pack_bytes;
 }
 
 extern "C" int mi_conv3x3_pack(const float* w, int M, int K, int transpose_flip, void* pack, void* stream) {
   MI_CHECK_ARG(w && pack && M >= 1 && K >= 1, "conv3x3_pack: null pointer / bad shape");
   MI_CHECK_ARG(aligned16(pack), "conv3x3_pack: pack buffer must be 16-byte aligned");
   C3PackArgs a;
-  a.w = w; a.wp = (bf16*)pack; a.M = M; a.K = K; a.MT = c3_mt(M); a.ncot = cdiv(M, 16 * a.MT); a.nchunk = cdiv(K, 16);
+  const C3Plan p = c3_plan(M, K, 1, 8);                 // (the pack depends on M and K alone)
+  a.w = w; a.wp = (bf16*)pack; a.M = M; a.K = K; a.MT = p.mt; a.ncot = p.co_tiles; a.nchunk = p.chunks;
   a.flip = transpose_flip ? 1 : 0;
   // forward: w is [M][K][9]; data gradient: the conv's own weight is [K][M][9] and this op's output channels are its inputs
   a.s_m = transpose_flip ? 9 : (int64_t)K * 9;
@@ -415,15 +439,16 @@ extern "C" int mi_conv3x3_fwd(const void* pack, const void* x, int64_t x_bs, con
   a.x = (const bf16*)x; a.wp = (const bf16*)pack; a.bias = bias; a.res = (const bf16*)residual; a.y = (bf16*)y;
   a.xbs = x_bs ? x_bs : (int64_t)K * HW; a.ybs = y_bs ? y_bs : (int64_t)M * HW; a.rbs = r_bs ? r_bs : (int64_t)M * HW;
   MI_CHECK_ARG(a.xbs % 8 == 0 && a.ybs % 8 == 0 && a.rbs % 8 == 0, "conv3x3_fwd: batch strides must keep 16-byte alignment");
-  a.B = B; a.M = M; a.K = K; a.H = H; a.W = W; a.nchunk = cdiv(K, 16);
-  const int MT = c3_mt(M), TWP = c3_twp(W), TR = 256 / TWP;
-  a.tiles_x = cdiv(W, TWP); a.tiles_y = cdiv(H, TR);
+  const C3Plan p = c3_plan(M, K, H, W);
+  a.B = B; a.M = M; a.K = K; a.H = H; a.W = W; a.nchunk = p.chunks;
+  const int MT = p.mt, TWP = p.twp;
+  a.tiles_x = p.tiles_x; a.tiles_y = p.tiles_y;
   const int64_t tiles = (int64_t)a.tiles_x * a.tiles_y;
-  MI_CHECK_ARG(tiles < (1ll << 31) && B <= 65535 && cdiv(M, 16 * MT) <= 65535, "conv3x3_fwd: grid too large");
+  MI_CHECK_ARG(tiles < (1ll << 31) && B <= 65535 && p.co_tiles <= 65535, "conv3x3_fwd: grid too large");
   hipStream_t st = (hipStream_t)stream;
   const double N = (double)HW * B;
   ProfScope ps(st, K_CONV3X3, (double)(K + M + (residual ? M : 0)) * N * 2.0, 2.0 * 9.0 * M * K * N);
-  const dim3 grid((unsigned)tiles, (unsigned)cdiv(M, 16 * MT), (unsigned)B);
+  const dim3 grid((unsigned)tiles, (unsigned)p.co_tiles, (unsigned)B);
 #define C3_CASE(MT_, TWP_) \
   if (MT == MT_ && TWP == TWP_) { hipLaunchKernelGGL((c3_kernel<MT_, TWP_>), grid, dim3(256), 0, st, a); MI_LAUNCH_CHECK(); return MI_OK; }
   C3_CASE(1, 64) C3_CASE(2, 64) C3_CASE(4, 64)
@@ -434,16 +459,9 @@ extern "C" int mi_conv3x3_fwd(const void* pack, const void* x, int64_t x_bs, con
   return MI_ERR_ARG;
 }
 
-// which operand takes the row role: the one that wastes less of the 64-row x 16-column tile
-static bool c3w_swap(int M, int K) {
-  const int64_t normal = (int64_t)cdiv(M, 64) * 64 * cdiv(K, 16) * 16, swapped = (int64_t)cdiv(K, 64) * 64 * cdiv(M, 16) * 16;
-  return swapped < normal;
-}
-
 extern "C" size_t mi_conv3x3_wgrad_workspace(int B, int M, int K, int H, int W) {
   if (B < 1 || M < 1 || K < 1 || !mi_conv3x3_ok(H, W, MI_BF16)) return 0;
-  const bool sw = c3w_swap(M, K);
-  return (size_t)c3w_splits(B, sw ? K : M, sw ? M : K, H, W, c3_twp(W)) * M * K * 9 * sizeof(float);
+  return c3w_plan(B, M, K, H, W).workspace;
 }
 
 extern "C" int mi_conv3x3_wgrad(const void* dy, int64_t dy_bs, const void* x, int64_t x_bs, float* dw, int accumulate, int B, int M,
@@ -452,17 +470,18 @@ extern "C" int mi_conv3x3_wgrad(const void* dy, int64_t dy_bs, const void* x, in
   MI_CHECK_ARG(mi_conv3x3_ok(H, W, MI_BF16), "conv3x3_wgrad: plane not covered (bf16, W %% 8 == 0)");
   MI_CHECK_ARG(aligned16(dy) && aligned16(x), "conv3x3_wgrad: pointers must be 16-byte aligned");
   const int64_t HW = (int64_t)H * W;
-  const int TWP = c3_twp(W), TR = 256 / TWP;
+  const C3WPlan p = c3w_plan(B, M, K, H, W);
+  const int TWP = p.twp;
   if (!dy_bs) dy_bs = (int64_t)M * HW;
   if (!x_bs) x_bs = (int64_t)K * HW;
   MI_CHECK_ARG(dy_bs % 8 == 0 && x_bs % 8 == 0, "conv3x3_wgrad: batch strides must keep 16-byte alignment");
-  const bool sw = c3w_swap(M, K);
+  const bool sw = p.swap;
   C3WArgs a;
   if (!sw) { a.dy = (const bf16*)dy; a.dybs = dy_bs; a.M = M; a.x = (const bf16*)x; a.xbs = x_bs; a.K = K; a.s_r = (int64_t)K * 9; a.s_c = 9; }
   else     { a.dy = (const bf16*)x; a.dybs = x_bs; a.M = K; a.x = (const bf16*)dy; a.xbs = dy_bs; a.K = M; a.s_r = 9; a.s_c = (int64_t)K * 9; }
   a.flip = sw ? 1 : 0;
-  a.B = B; a.H = H; a.W = W; a.tiles_x = cdiv(W, TWP); a.tiles_y = cdiv(H, TR);
-  a.S = c3w_splits(B, a.M, a.K, H, W, TWP);
+  a.B = B; a.H = H; a.W = W; a.tiles_x = p.tiles_x; a.tiles_y = p.tiles_y;
+  a.S = p.splits;
   const size_t cols = (size_t)M * K * 9;
   a.cols = (int64_t)cols;
   // partials: the deferred arena when the sum accumulates into a trainer's gradient buffer (one table-driven launch at the end of
@@ -475,7 +494,7 @@ extern "C" int mi_conv3x3_wgrad(const void* dy, int64_t dy_bs, const void* x, in
   a.part = part;
   hipStream_t st = (hipStream_t)stream;
   constexpr int LDSB = 3 * 16 * C3_XSW * 2 + 64 * C3_DS * 2;
-  const dim3 grid((unsigned)cdiv(a.K, 16), (unsigned)cdiv(a.M, 64), (unsigned)a.S);
+  const dim3 grid((unsigned)p.grid_x, (unsigned)p.grid_y, (unsigned)a.S);
   MI_CHECK_ARG(grid.y <= 65535 && grid.z <= 65535, "conv3x3_wgrad: grid too large");
   {
     const double N = (double)HW * B;
@@ -490,4 +509,19 @@ extern "C" int mi_conv3x3_wgrad(const void* dy, int64_t dy_bs, const void* x, in
     MI_LAUNCH_CHECK();
   }
   return launch_reduce_rows(part, dw, a.S, (int64_t)cols, (int64_t)cols, accumulate, 1.0f, st, nullptr, nullptr, 0);
+}
+
+// What the forward / data-gradient kernel and the weight-gradient kernel launch for y[B,M,H,W] = conv(x[B,K,H,W]); host
+// only: the same c3_plan / c3w_plan.  out[15]: mt, twp, tr, tiles_x, tiles_y, co_tiles, chunks, pack_bytes, w_swap, w_rows, w_cols,
+// w_splits, w_grid_x, w_grid_y, w_workspace.
+extern "C" int mi_conv3x3_plan(int B, int M, int K, int H, int W, int64_t* out) {
+  MI_CHECK_ARG(out, "conv3x3_plan: null pointer");
+  MI_CHECK_ARG(B >= 1 && M >= 1 && K >= 1, "conv3x3_plan: bad shape B=%d M=%d K=%d", B, M, K);
+  MI_CHECK_ARG(mi_conv3x3_ok(H, W, MI_BF16), "conv3x3_plan: plane not covered (H=%d W=%d; bf16, W %% 8 == 0)", H, W);
+  const C3Plan p = c3_plan(M, K, H, W);
+  const C3WPlan w = c3w_plan(B, M, K, H, W);
+  const int64_t v[15] = {p.mt, p.twp, p.tr, p.tiles_x, p.tiles_y, p.co_tiles, p.chunks, (int64_t)p.pack_bytes,
+                         w.swap ? 1 : 0, w.rows, w.cols, w.splits, w.grid_x, w.grid_y, (int64_t)w.workspace};
+  for (int i = 0; i < 15; ++i) out[i] = v[i];
+  return MI_OK;
 }

@@ -248,6 +248,45 @@ static GPlan g_plan(int H, int W, int64_t planes) {
 static bool g_fast(int H, int W) { return H >= 1 && (W == 16 || W == 32 || W == 64 || W == 128 || W == 256); }   // wave-streaming forms
 static bool g_ok(int H, int W) { return H >= 1 && W >= 1; }
 
+// What one im2col3x3 / col2im3x3 call runs: filled by g3_plan, the ONE place that decides it; both launchers launch what it says,
+// mi_glue3x3_plan reports it.  aligned: every activation pointer of the call lies on a 16-byte boundary.  The general form has
+// lpr = band = bands = 0 and a capped grid-stride grid.
+struct G3Plan { bool fast; int lpr, band, bands; unsigned blocks_im2col, blocks_col2im; };
+static G3Plan g3_plan(int64_t planes, int H, int W, bool aligned) {
+  G3Plan p;
+  p.fast = g_fast(H, W) && aligned;
+  if (p.fast) {
+    const GPlan g = g_plan(H, W, planes);
+    p.lpr = W / 4; p.band = g.band; p.bands = g.nb;
+    p.blocks_im2col = p.blocks_col2im = g.blocks;
+    return p;
+  }
+  p.lpr = p.band = p.bands = 0;
+  const int64_t total = planes * H * W;                  // outputs of col2im; im2col writes nine times as many
+  p.blocks_im2col = (unsigned)(total * 9 / 256 + 1 > 65536 ? 65536 : total * 9 / 256 + 1);
+  p.blocks_col2im = (unsigned)(total / 256 + 1 > 65536 ? 65536 : total / 256 + 1);
+  return p;
+}
+
+// pixel_shuffle2 and copy_rows: elements per access (16 bytes, or 1 in the element-wise general form), threads' work items, grid
+struct VecPlan { int vector; int64_t total; int blocks; };
+static VecPlan ps_plan(int B, int c, int H, int W, int64_t ibs, int64_t obs, int dtype, bool aligned) {
+  const int VW = 16 / (int)dtype_size(dtype);            // 16-byte accesses on the planar side ...
+  VecPlan p;
+  p.vector = (W % VW != 0 || !aligned || ibs % VW != 0 || obs % VW != 0) ? 1 : VW;   // ... or the element-wise general form
+  p.total = (int64_t)B * c * 2 * H * (W / p.vector);
+  p.blocks = cdiv_cap(p.total, 256, 16384);
+  return p;
+}
+static VecPlan cr_plan(int64_t rows, int64_t L, int64_t src_rs, int64_t dst_rs, int dtype, bool aligned) {
+  const int VW = 16 / (int)dtype_size(dtype);
+  VecPlan p;
+  p.vector = (L % VW != 0 || src_rs % VW != 0 || dst_rs % VW != 0 || !aligned) ? 1 : VW;   // element-wise general form
+  p.total = rows * (L / p.vector);
+  p.blocks = cdiv_cap(p.total, 256, 16384);
+  return p;
+}
+
 #define G_LPR_SWITCH(W_, ...)                                      \
   switch ((W_) / 4) {                                              \
     case 64: { constexpr int LPR = 64; __VA_ARGS__; } break;       \
@@ -271,16 +310,15 @@ extern "C" int mi_im2col3x3(const void* x, void* out, int B, int C, int H, int W
   return with_dtype(dtype, "im2col3x3", [&](auto tag) {
     using T = decltype(tag);
     ProfScope ps(st, K_IM2COL, 10.0 * planes * H * W * sizeof(T), 0.0);
-    if (!(g_fast(H, W) && aligned16(x) && aligned16(out))) {             // general form
-      const int64_t total = planes * 9 * H * W;
-      const unsigned blocks = (unsigned)(total / 256 + 1 > 65536 ? 65536 : total / 256 + 1);
-      if (flip) hipLaunchKernelGGL((im2col3x3_any_kernel<T, true>), dim3(blocks), dim3(256), 0, st, (const T*)x, (T*)out, planes, H, W);
-      else hipLaunchKernelGGL((im2col3x3_any_kernel<T, false>), dim3(blocks), dim3(256), 0, st, (const T*)x, (T*)out, planes, H, W);
+    const G3Plan p = g3_plan(planes, H, W, aligned16(x) && aligned16(out));
+    const dim3 grid(p.blocks_im2col);
+    if (!p.fast) {                                                        // general form
+      if (flip) hipLaunchKernelGGL((im2col3x3_any_kernel<T, true>), grid, dim3(256), 0, st, (const T*)x, (T*)out, planes, H, W);
+      else hipLaunchKernelGGL((im2col3x3_any_kernel<T, false>), grid, dim3(256), 0, st, (const T*)x, (T*)out, planes, H, W);
       return;
     }
-    const GPlan p = g_plan(H, W, planes);
-    if (flip) { G_LPR_SWITCH(W, hipLaunchKernelGGL((im2col3x3_kernel<T, LPR, true>), dim3(p.blocks), dim3(256), 0, st, (const T*)x, (T*)out, (int)planes, H, W, p.nb, p.band)); }
-    else { G_LPR_SWITCH(W, hipLaunchKernelGGL((im2col3x3_kernel<T, LPR, false>), dim3(p.blocks), dim3(256), 0, st, (const T*)x, (T*)out, (int)planes, H, W, p.nb, p.band)); }
+    if (flip) { G_LPR_SWITCH(W, hipLaunchKernelGGL((im2col3x3_kernel<T, LPR, true>), grid, dim3(256), 0, st, (const T*)x, (T*)out, (int)planes, H, W, p.bands, p.band)); }
+    else { G_LPR_SWITCH(W, hipLaunchKernelGGL((im2col3x3_kernel<T, LPR, false>), grid, dim3(256), 0, st, (const T*)x, (T*)out, (int)planes, H, W, p.bands, p.band)); }
   });
 }
 
@@ -292,14 +330,13 @@ extern "C" int mi_col2im3x3(const void* z, const float* bias, const void* residu
   return with_dtype(dtype, "col2im3x3", [&](auto tag) {
     using T = decltype(tag);
     ProfScope ps(st, K_COL2IM, (10.0 + (residual ? 1.0 : 0.0)) * planes * H * W * sizeof(T), 9.0 * planes * H * W);
-    if (!(g_fast(H, W) && aligned16(z) && aligned16(y) && aligned16(residual))) {   // general form
-      const int64_t total = planes * H * W;
-      const unsigned blocks = (unsigned)(total / 256 + 1 > 65536 ? 65536 : total / 256 + 1);
-      hipLaunchKernelGGL((col2im3x3_any_kernel<T>), dim3(blocks), dim3(256), 0, st, (const T*)z, bias, (const T*)residual, (T*)y, planes, M, H, W, flip);
+    const G3Plan p = g3_plan(planes, H, W, aligned16(z) && aligned16(y) && aligned16(residual));
+    const dim3 grid(p.blocks_col2im);
+    if (!p.fast) {                                                        // general form
+      hipLaunchKernelGGL((col2im3x3_any_kernel<T>), grid, dim3(256), 0, st, (const T*)z, bias, (const T*)residual, (T*)y, planes, M, H, W, flip);
       return;
     }
-    const GPlan p = g_plan(H, W, planes);
-    G_LPR_SWITCH(W, hipLaunchKernelGGL((col2im3x3_kernel<T, LPR>), dim3(p.blocks), dim3(256), 0, st, (const T*)z, bias, (const T*)residual, (T*)y, (int)planes, M, H, W, p.nb, p.band, flip));
+    G_LPR_SWITCH(W, hipLaunchKernelGGL((col2im3x3_kernel<T, LPR>), grid, dim3(256), 0, st, (const T*)z, bias, (const T*)residual, (T*)y, (int)planes, M, H, W, p.bands, p.band, flip));
   });
 }
 
@@ -310,11 +347,11 @@ extern "C" int mi_pixel_shuffle2(const void* in, int64_t in_bs, void* out, int64
   const int64_t ibs = in_bs ? in_bs : dense_lo, obs = out_bs ? out_bs : dense_lo;
   return with_dtype(dtype, "pixel_shuffle2", [&](auto tag) {
     using T = decltype(tag);
-    constexpr int VW = 16 / sizeof(T);               // 16-byte accesses on the planar side ...
-    const int V = (W % VW != 0 || !aligned16(in) || !aligned16(out) || ibs % VW != 0 || obs % VW != 0) ? 1 : VW;   // ... or the element-wise general form
+    constexpr int VW = 16 / sizeof(T);
+    const VecPlan p = ps_plan(B, c, H, W, ibs, obs, dtype, aligned16(in) && aligned16(out));
+    const int V = p.vector, blocks = p.blocks;
+    const int64_t total = p.total;
     hipStream_t st = (hipStream_t)stream;
-    const int64_t total = (int64_t)B * c * 2 * H * (W / V);
-    const int blocks = cdiv_cap(total, 256, 16384);
     ProfScope ps(st, K_COL2IM, 2.0 * B * dense_lo * sizeof(T), 0.0);
 #define PS_LAUNCH(VV, UN) hipLaunchKernelGGL((pixel_shuffle_kernel<T, VV, UN>), dim3(blocks), dim3(256), 0, st, (const T*)in, (T*)out, c, H, W, ibs, obs, total)
     if (V == VW) { if (unshuffle) PS_LAUNCH(VW, true); else PS_LAUNCH(VW, false); }
@@ -331,12 +368,45 @@ extern "C" int mi_copy_rows(const void* src, int64_t src_rs, void* dst, int64_t 
   return with_dtype(dtype, "copy_rows", [&](auto tag) {
     using T = decltype(tag);
     constexpr int VW = 16 / sizeof(T);
-    const int V = (L % VW != 0 || src_rs % VW != 0 || dst_rs % VW != 0 || !aligned16(src) || !aligned16(dst)) ? 1 : VW;   // element-wise general form
+    const VecPlan p = cr_plan(rows, L, src_rs, dst_rs, dtype, aligned16(src) && aligned16(dst));
+    const int V = p.vector, blocks = p.blocks;
+    const int64_t total = p.total;
     hipStream_t st = (hipStream_t)stream;
-    const int64_t total = rows * (L / V);
-    const int blocks = cdiv_cap(total, 256, 16384);
     ProfScope ps(st, K_CAST, 2.0 * rows * L * sizeof(T), 0.0);
     if (V == VW) hipLaunchKernelGGL((copy_rows_kernel<T, VW>), dim3(blocks), dim3(256), 0, st, (const T*)src, src_rs, (T*)dst, dst_rs, L, total);
     else hipLaunchKernelGGL((copy_rows_kernel<T, 1>), dim3(blocks), dim3(256), 0, st, (const T*)src, src_rs, (T*)dst, dst_rs, L, total);
   });
+}
+
+// What mi_im2col3x3 / mi_col2im3x3 launch for `planes` planes (B * C, B * M) of H x W; host only: the same g3_plan.  out[6]: fast
+// (the wave-streaming form), lpr (lanes per row), band (rows per lane group), bands per plane, blocks of the im2col grid, blocks of
+// the col2im grid.
+extern "C" int mi_glue3x3_plan(int64_t planes, int H, int W, int dtype, int aligned, int64_t* out) {
+  MI_CHECK_ARG(out, "glue3x3_plan: null pointer");
+  MI_CHECK_ARG(dtype == MI_F32 || dtype == MI_BF16, "glue3x3_plan: bad dtype %d", dtype);
+  MI_CHECK_ARG(planes >= 1 && g_ok(H, W), "glue3x3_plan: bad shape planes=%lld H=%d W=%d", (long long)planes, H, W);
+  const G3Plan p = g3_plan(planes, H, W, aligned != 0);
+  out[0] = p.fast ? 1 : 0; out[1] = p.lpr; out[2] = p.band; out[3] = p.bands; out[4] = p.blocks_im2col; out[5] = p.blocks_col2im;
+  return MI_OK;
+}
+
+// What mi_pixel_shuffle2 launches (batch strides 0 = dense, as there); out[3]: vector (elements per access), total work items, blocks.
+extern "C" int mi_pixel_shuffle2_plan(int B, int c, int H, int W, int64_t in_bs, int64_t out_bs, int dtype, int aligned, int64_t* out) {
+  MI_CHECK_ARG(out, "pixel_shuffle2_plan: null pointer");
+  MI_CHECK_ARG(dtype == MI_F32 || dtype == MI_BF16, "pixel_shuffle2_plan: bad dtype %d", dtype);
+  MI_CHECK_ARG(B > 0 && c > 0 && H > 0 && W > 0 && in_bs >= 0 && out_bs >= 0, "pixel_shuffle2_plan: bad shape B=%d c=%d H=%d W=%d", B, c, H, W);
+  const int64_t dense_lo = (int64_t)4 * c * H * W;
+  const VecPlan p = ps_plan(B, c, H, W, in_bs ? in_bs : dense_lo, out_bs ? out_bs : dense_lo, dtype, aligned != 0);
+  out[0] = p.vector; out[1] = p.total; out[2] = p.blocks;
+  return MI_OK;
+}
+
+// What mi_copy_rows launches (row strides 0 = L, as there); out[3] as above.
+extern "C" int mi_copy_rows_plan(int64_t rows, int64_t L, int64_t src_rs, int64_t dst_rs, int dtype, int aligned, int64_t* out) {
+  MI_CHECK_ARG(out, "copy_rows_plan: null pointer");
+  MI_CHECK_ARG(dtype == MI_F32 || dtype == MI_BF16, "copy_rows_plan: bad dtype %d", dtype);
+  MI_CHECK_ARG(rows > 0 && L > 0 && src_rs >= 0 && dst_rs >= 0, "copy_rows_plan: bad shape rows=%lld L=%lld", (long long)rows, (long long)L);
+  const VecPlan p = cr_plan(rows, L, src_rs ? src_rs : L, dst_rs ? dst_rs : L, dtype, aligned != 0);
+  out[0] = p.vector; out[1] = p.total; out[2] = p.blocks;
+  return MI_OK;
 }

@@ -1716,6 +1716,19 @@ def col2im3x3(z: Tensor, bias: Optional[Tensor] = None, residual: Optional[Tenso
     return y
 
 
+GLUE3X3_PLAN_FIELDS = ("fast", "lpr", "band", "bands", "blocks_im2col", "blocks_col2im")
+
+
+def glue3x3_plan(planes: int, H: int, W: int, dtype: torch.dtype, aligned: bool = True) -> dict:
+    """What im2col3x3 / col2im3x3 launch for `planes` planes (B * C, B * M) of H x W whose pointers all are / are not on a 16-byte
+    boundary (mi_glue3x3_plan; no GPU work)."""
+    out = (L.c_i64 * 6)()
+    L.check(L.lib().mi_glue3x3_plan(planes, H, W, _dtype_code(dtype), int(aligned), out), "glue3x3_plan")
+    p = dict(zip(GLUE3X3_PLAN_FIELDS, out))
+    p["fast"] = bool(p["fast"])
+    return p
+
+
 def chan_sum(x: Tensor, out: Optional[Tensor] = None, accumulate: bool = False) -> Tensor:
     """Bias gradient of a conv: out[c] (+)= sum over batch and pixels of x[b, c] (fp32, fixed order)."""
     _gpu(x, out)
@@ -1893,6 +1906,36 @@ def copy_rows(src: Tensor, dst: Tensor) -> Tensor:
     B = src.shape[0]
     L.check(L.lib().mi_copy_rows(_p(src), _bstride(src), _p(dst), _bstride(dst), B, src[0].numel(), _dt(src), _stream()), "copy_rows")
     return dst
+
+
+CONV3X3_PLAN_FIELDS = ("mt", "twp", "tr", "tiles_x", "tiles_y", "co_tiles", "chunks", "pack_bytes", "w_swap", "w_rows", "w_cols",
+                       "w_splits", "w_grid_x", "w_grid_y", "w_workspace")
+VEC_PLAN_FIELDS = ("vector", "total", "blocks")
+
+
+def conv3x3_plan(B: int, M: int, K: int, H: int, W: int) -> dict:
+    """What conv3x3 (M planes written, K read: for the data gradient pass them as that call sees them) and conv3x3_wgrad launch
+    for a [B, K, H, W] bf16 input (mi_conv3x3_plan; no GPU work)."""
+    out = (L.c_i64 * 15)()
+    L.check(L.lib().mi_conv3x3_plan(B, M, K, H, W, out), "conv3x3_plan")
+    p = dict(zip(CONV3X3_PLAN_FIELDS, out))
+    p["w_swap"] = bool(p["w_swap"])
+    return p
+
+
+def pixel_shuffle2_plan(B: int, c: int, H: int, W: int, in_bs: int, out_bs: int, dtype: torch.dtype, aligned: bool = True) -> dict:
+    """What pixel_shuffle2 launches; c, H, W are the low-resolution side's, the batch strides in elements (0 = dense)
+    (mi_pixel_shuffle2_plan; no GPU work)."""
+    out = (L.c_i64 * 3)()
+    L.check(L.lib().mi_pixel_shuffle2_plan(B, c, H, W, in_bs, out_bs, _dtype_code(dtype), int(aligned), out), "pixel_shuffle2_plan")
+    return dict(zip(VEC_PLAN_FIELDS, out))
+
+
+def copy_rows_plan(rows: int, Ln: int, src_rs: int, dst_rs: int, dtype: torch.dtype, aligned: bool = True) -> dict:
+    """What copy_rows launches for [rows][Ln] with row strides in elements (0 = Ln) (mi_copy_rows_plan; no GPU work)."""
+    out = (L.c_i64 * 3)()
+    L.check(L.lib().mi_copy_rows_plan(rows, Ln, src_rs, dst_rs, _dtype_code(dtype), int(aligned), out), "copy_rows_plan")
+    return dict(zip(VEC_PLAN_FIELDS, out))
 
 
 def gap_fwd(x: Tensor) -> Tensor:

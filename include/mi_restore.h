@@ -776,6 +776,13 @@ int mi_glue3x3_ok(int H, int W);
 int mi_im2col3x3(const void* x, void* out, int B, int C, int H, int W, int flip, int dtype, void* stream);
 int mi_col2im3x3(const void* z, const float* bias, const void* residual, void* y, int B, int M, int H, int W, int flip,
                  int dtype, void* stream);
+/* What mi_im2col3x3 / mi_col2im3x3 launch for `planes` planes (B * C, B * M) of H x W (host-only; the launchers decide by the
+ * same code); aligned: whether every activation pointer of the call lies on a 16-byte boundary.  out[6]: fast (1 = the
+ * wave-streaming form: W in {16,32,64,128,256} and aligned; 0 = the element-wise general form), lpr (lanes per row = W / 4:
+ * 4..64; 0 in the general form), band (rows a lane group walks: 8, or 16 / 32 when that still leaves >= 4096 waves; 0 in the
+ * general form), bands per plane, blocks of the im2col grid, blocks of the col2im grid (general form: one thread per output
+ * element, capped at 65536 blocks of a grid-stride loop).  -1 on a null out, a bad dtype code, planes < 1 or H, W < 1. */
+int mi_glue3x3_plan(int64_t planes, int H, int W, int dtype, int aligned, int64_t* out);
 
 /* ------------------------------------------------------------------------
  * Dense 3x3 convolution (stride 1, zero padding 1) as an implicit GEMM (csrc/conv3x3.hip): the glue convs above and the
@@ -797,6 +804,17 @@ int mi_conv3x3_fwd(const void* pack, const void* x, int64_t x_bs, const float* b
 size_t mi_conv3x3_wgrad_workspace(int B, int M, int K, int H, int W);
 int mi_conv3x3_wgrad(const void* dy, int64_t dy_bs, const void* x, int64_t x_bs, float* dw, int accumulate, int B, int M, int K,
                      int H, int W, void* ws, void* stream);
+/* What the three kernels launch for y[B,M,H,W] = conv(x[B,K,H,W]) (host-only; the launchers decide by the same code).  out[15]:
+ *   forward / data gradient (for the data gradient pass the op's own M and K: M = planes written, K = planes read):
+ *     mt (16-row m-tiles per workgroup: 1 for M <= 16, 2 for M <= 32, else 4), twp (tile width: 16 for W <= 16, 32 for W <= 32,
+ *     else 64), tr (tile rows = 256 / twp), tiles_x, tiles_y, co_tiles (grid.y = ceil(M / (16 mt))), chunks (16-channel chunks of
+ *     K), pack_bytes (= mi_conv3x3_pack_bytes);
+ *   weight gradient: w_swap (1: x takes the 64-row role and dy the 16-column role - the choice that pads less), w_rows, w_cols
+ *     (the M and K the kernel sees after the swap), w_splits (workgroups that share the pixel tiles of one 64 x 16 block: split s
+ *     takes tiles s, s + w_splits, ... of the B * tiles_x * tiles_y), w_grid_x (= ceil(w_cols / 16)), w_grid_y (= ceil(w_rows / 64)),
+ *     w_workspace (= mi_conv3x3_wgrad_workspace).
+ * -1 on a null out, B, M, K < 1 or a plane mi_conv3x3_ok refuses. */
+int mi_conv3x3_plan(int B, int M, int K, int H, int W, int64_t* out);
 
 /* PixelShuffle(2) / PixelUnshuffle(2) of Upsample / Downsample (Restormer.py:171-189; moce_ir.py Downsample/Upsample):
  *   unshuffle == 0: in [B,4c,H,W] -> out [B,c,2H,2W], out[b][c][2y+i][2x+j] = in[b][4c+2i+j][y][x]
@@ -806,6 +824,13 @@ int mi_conv3x3_wgrad(const void* dy, int64_t dy_bs, const void* x, int64_t x_bs,
 int mi_pixel_shuffle2(const void* in, int64_t in_bs, void* out, int64_t out_bs, int B, int c, int H, int W, int unshuffle,
                       int dtype, void* stream);
 int mi_copy_rows(const void* src, int64_t src_rs, void* dst, int64_t dst_rs, int64_t rows, int64_t L, int dtype, void* stream);
+/* What the two launch (host-only; the launchers decide by the same code); strides as in the calls (0 = dense), aligned: whether
+ * both pointers lie on a 16-byte boundary.  out[3]: vector (elements per access: 16 bytes = 8 bf16 / 4 fp32 when W (L), both
+ * strides and both pointers allow it, else 1 = the element-wise form), total (work items: B c 2 H (W / vector); rows (L /
+ * vector)), blocks (ceil(total / 256), capped at 16384 blocks of a grid-stride loop).  -1 on a null out, a bad dtype code, a
+ * non-positive extent or a negative stride. */
+int mi_pixel_shuffle2_plan(int B, int c, int H, int W, int64_t in_bs, int64_t out_bs, int dtype, int aligned, int64_t* out);
+int mi_copy_rows_plan(int64_t rows, int64_t L, int64_t src_rs, int64_t dst_rs, int dtype, int aligned, int64_t* out);
 
 /* ------------------------------------------------------------------------
  * Router global average pool (moce_ir.py:703-707, RoutingFunction.gate[0]): out[b,c] = mean_n x[b,c,n] (fp32);

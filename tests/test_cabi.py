@@ -1136,3 +1136,243 @@ def test_attn_assertions_catch_five_deliberate_faults(lib):
                 T.assert_float_bwd(got, s, who)
             caught[fault] += 1
     assert min(caught.values()) >= 3, caught
+
+
+# --------------------------------------------------------------------------- the 3x3 glue (mi_conv3x3_plan, mi_glue3x3_plan, mi_pixel_shuffle2_plan, mi_copy_rows_plan)
+def _cdiv(a, b):
+    return -(-a // b)
+
+
+def _conv3x3_formulas(B, M, K, H, W):
+    """The launchers' decisions, read from csrc/conv3x3.hip."""
+    mt = 1 if M <= 16 else 2 if M <= 32 else 4
+    twp = 64 if W > 32 else 32 if W > 16 else 16
+    tr = 256 // twp
+    tx, ty, cot, ch = _cdiv(W, twp), _cdiv(H, tr), _cdiv(M, 16 * mt), _cdiv(K, 16)
+    swap = _cdiv(K, 64) * 64 * _cdiv(M, 16) * 16 < _cdiv(M, 64) * 64 * _cdiv(K, 16) * 16
+    rows, cols = (K, M) if swap else (M, K)
+    gx, gy = _cdiv(cols, 16), _cdiv(rows, 64)
+    splits = min(max(min(_cdiv(1024, gx * gy), B * tx * ty // 2), 1), 4096)
+    return {"mt": mt, "twp": twp, "tr": tr, "tiles_x": tx, "tiles_y": ty, "co_tiles": cot, "chunks": ch,
+            "pack_bytes": cot * ch * 5 * mt * 512 * 2, "w_swap": swap, "w_rows": rows, "w_cols": cols, "w_splits": splits,
+            "w_grid_x": gx, "w_grid_y": gy, "w_workspace": splits * M * K * 36}
+
+
+def test_glue_plans_from_first_principles(lib):
+    """The four plan queries against the launchers' rules written out here, over grids of shapes, against the sizing entry points
+    that existed before them, and at a few absolute figures so that this helper cannot drift with the code."""
+    from image_restoration_amd import ops
+    L = lib.lib()
+    seen = set()
+    for B in (1, 2, 3, 18):
+        for M in (1, 3, 16, 17, 32, 33, 48, 64, 65, 96, 512):
+            for K in (1, 3, 15, 16, 17, 33, 48, 64, 96, 256):
+                for H, W in ((1, 8), (15, 16), (17, 16), (8, 24), (9, 32), (4, 40), (5, 72), (7, 128), (256, 256)):
+                    p = ops.conv3x3_plan(B, M, K, H, W)
+                    assert p == _conv3x3_formulas(B, M, K, H, W), (B, M, K, H, W, p)
+                    assert p["pack_bytes"] == L.mi_conv3x3_pack_bytes(M, K) and p["w_workspace"] == L.mi_conv3x3_wgrad_workspace(B, M, K, H, W)
+                    assert p["tiles_x"] * p["twp"] >= W > (p["tiles_x"] - 1) * p["twp"] and p["tiles_y"] * p["tr"] >= H > (p["tiles_y"] - 1) * p["tr"]
+                    assert p["co_tiles"] * 16 * p["mt"] >= M and p["chunks"] * 16 >= K and {p["w_rows"], p["w_cols"]} == {M, K}
+                    assert 1 <= p["w_splits"] <= max(1, B * p["tiles_x"] * p["tiles_y"] // 2)
+                    seen.add((p["mt"], p["twp"], p["w_swap"]))
+    assert len(seen) == 18
+    # absolute figures: Restormer's patch embedding (3 -> 48 at 128 x 128, batch 2) and a Downsample body (48 -> 24)
+    assert ops.conv3x3_plan(2, 48, 3, 128, 128) == {
+        "mt": 4, "twp": 64, "tr": 4, "tiles_x": 2, "tiles_y": 32, "co_tiles": 1, "chunks": 1, "pack_bytes": 20480, "w_swap": False,
+        "w_rows": 48, "w_cols": 3, "w_splits": 64, "w_grid_x": 1, "w_grid_y": 1, "w_workspace": 64 * 48 * 3 * 36}
+    p = ops.conv3x3_plan(18, 512, 256, 1, 8)
+    assert (p["w_splits"], p["w_grid_x"], p["w_grid_y"], p["w_swap"], p["twp"], p["tr"]) == (8, 16, 8, False, 16, 16)
+    p = ops.conv3x3_plan(1, 16, 64, 8, 32)
+    assert (p["w_swap"], p["w_rows"], p["w_cols"], p["mt"], p["twp"], p["chunks"], p["w_splits"]) == (True, 64, 16, 1, 32, 4, 1)
+
+    for dt in (torch.float32, torch.bfloat16):
+        for planes in (1, 3, 9, 96, 2048, 4096):
+            for H in (1, 7, 8, 9, 17, 33, 256):
+                for W in (1, 3, 8, 16, 20, 32, 64, 128, 256, 500, 512):
+                    for aligned in (True, False):
+                        p = ops.glue3x3_plan(planes, H, W, dt, aligned)
+                        fast = aligned and W in (16, 32, 64, 128, 256)
+                        if fast:
+                            G = 64 // (W // 4)
+                            band = 32 if planes * _cdiv(H, 32) // G >= 4096 else 16 if planes * _cdiv(H, 16) // G >= 4096 else 8
+                            blocks = _cdiv(planes * _cdiv(H, band), 4 * G)
+                            want = {"fast": True, "lpr": W // 4, "band": band, "bands": _cdiv(H, band), "blocks_im2col": blocks, "blocks_col2im": blocks}
+                        else:
+                            n = planes * H * W
+                            want = {"fast": False, "lpr": 0, "band": 0, "bands": 0, "blocks_im2col": min(9 * n // 256 + 1, 65536),
+                                    "blocks_col2im": min(n // 256 + 1, 65536)}
+                        assert p == want, (planes, H, W, dt, aligned, p)
+    assert ops.glue3x3_plan(2048, 17, 256, torch.bfloat16) == {"fast": True, "lpr": 64, "band": 16, "bands": 2, "blocks_im2col": 1024, "blocks_col2im": 1024}
+    assert ops.glue3x3_plan(2048, 33, 256, torch.bfloat16)["band"] == 32 and ops.glue3x3_plan(2047, 33, 256, torch.bfloat16)["band"] == 16
+    assert ops.glue3x3_plan(6, 128, 128, torch.float32) == {"fast": True, "lpr": 32, "band": 8, "bands": 16, "blocks_im2col": 12, "blocks_col2im": 12}
+    assert ops.glue3x3_plan(8, 500, 500, torch.bfloat16) == {"fast": False, "lpr": 0, "band": 0, "bands": 0, "blocks_im2col": 65536, "blocks_col2im": 7813}
+
+    for dt, V in ((torch.float32, 4), (torch.bfloat16, 8)):
+        for W in (1, 4, 6, 8, 12, 16, 601):
+            for bs_in in (0, 4 * 3 * 5 * W + 8, 4 * 3 * 5 * W + 1):
+                for bs_out in (0, 4 * 3 * 5 * W + 16, 4 * 3 * 5 * W + 4):
+                    for aligned in (True, False):
+                        dense = 4 * 3 * 5 * W
+                        v = V if aligned and W % V == 0 and (bs_in or dense) % V == 0 and (bs_out or dense) % V == 0 else 1
+                        total = 2 * 3 * 2 * 5 * (W // v)
+                        assert ops.pixel_shuffle2_plan(2, 3, 5, W, bs_in, bs_out, dt, aligned) == \
+                            {"vector": v, "total": total, "blocks": min(_cdiv(total, 256), 16384)}, (dt, W, bs_in, bs_out, aligned)
+                        rs_in, rs_out = bs_in and bs_in // 4, bs_out and bs_out // 4          # copy_rows: rows of L = 15 W
+                        Ln = 15 * W
+                        v = V if aligned and Ln % V == 0 and (rs_in or Ln) % V == 0 and (rs_out or Ln) % V == 0 else 1
+                        assert ops.copy_rows_plan(7, Ln, rs_in, rs_out, dt, aligned) == \
+                            {"vector": v, "total": 7 * (Ln // v), "blocks": min(_cdiv(7 * (Ln // v), 256), 16384)}, (dt, Ln, rs_in, rs_out, aligned)
+    assert ops.pixel_shuffle2_plan(2, 3, 600, 601, 0, 0, torch.bfloat16) == {"vector": 1, "total": 4327200, "blocks": 16384}
+    assert ops.pixel_shuffle2_plan(32, 48, 64, 64, 0, 0, torch.bfloat16) == {"vector": 8, "total": 1572864, "blocks": 6144}
+    assert ops.copy_rows_plan(32, 96 * 128 * 128, 192 * 128 * 128, 0, torch.bfloat16) == {"vector": 8, "total": 6291456, "blocks": 16384}
+    assert ops.copy_rows_plan(2, 45, 90, 90, torch.float32) == {"vector": 1, "total": 90, "blocks": 1}
+
+
+def test_glue_plan_argument_errors(lib):
+    """Null pointers, bad dtype codes and bad shapes: -1 with their message, nothing launched."""
+    L = lib.lib()
+    o = (C.c_int64 * 16)()
+    assert L.mi_conv3x3_plan(2, 48, 3, 16, 16, None) == -1 and b"conv3x3_plan: null pointer" in L.mi_last_error()
+    for B, M, K in ((0, 48, 3), (2, 0, 3), (2, 48, 0), (-1, 48, 3)):
+        assert L.mi_conv3x3_plan(B, M, K, 16, 16, o) == -1 and b"conv3x3_plan: bad shape" in L.mi_last_error(), (B, M, K)
+    for H, W in ((0, 16), (16, 0), (16, 12), (16, 4), (-1, 16)):                 # where mi_conv3x3_ok refuses
+        assert not L.mi_conv3x3_ok(H, W, lib.MI_BF16)
+        assert L.mi_conv3x3_plan(2, 48, 3, H, W, o) == -1 and b"conv3x3_plan: plane not covered" in L.mi_last_error(), (H, W)
+    assert L.mi_conv3x3_plan(2, 48, 3, 1, 8, o) == 0 and list(o)[:7] == [4, 16, 16, 1, 1, 1, 1]
+    assert L.mi_glue3x3_plan(3, 8, 16, lib.MI_BF16, 1, None) == -1 and b"glue3x3_plan: null pointer" in L.mi_last_error()
+    assert L.mi_glue3x3_plan(3, 8, 16, 7, 1, o) == -1 and b"glue3x3_plan: bad dtype 7" in L.mi_last_error()
+    for planes, H, W in ((0, 8, 16), (3, 0, 16), (3, 8, 0), (-3, 8, 16)):
+        assert L.mi_glue3x3_plan(planes, H, W, lib.MI_F32, 1, o) == -1 and b"glue3x3_plan: bad shape" in L.mi_last_error(), (planes, H, W)
+    assert L.mi_glue3x3_plan(3, 8, 16, lib.MI_F32, 1, o) == 0 and list(o)[:6] == [1, 4, 8, 1, 1, 1]
+    assert L.mi_pixel_shuffle2_plan(2, 3, 5, 16, 0, 0, lib.MI_BF16, 1, None) == -1 and b"pixel_shuffle2_plan: null pointer" in L.mi_last_error()
+    assert L.mi_pixel_shuffle2_plan(2, 3, 5, 16, 0, 0, 9, 1, o) == -1 and b"pixel_shuffle2_plan: bad dtype 9" in L.mi_last_error()
+    for a in ((0, 3, 5, 16, 0, 0), (2, 0, 5, 16, 0, 0), (2, 3, 0, 16, 0, 0), (2, 3, 5, 0, 0, 0), (2, 3, 5, 16, -8, 0), (2, 3, 5, 16, 0, -8)):
+        assert L.mi_pixel_shuffle2_plan(*a, lib.MI_BF16, 1, o) == -1 and b"pixel_shuffle2_plan: bad shape" in L.mi_last_error(), a
+    assert L.mi_copy_rows_plan(2, 16, 0, 0, lib.MI_BF16, 1, None) == -1 and b"copy_rows_plan: null pointer" in L.mi_last_error()
+    assert L.mi_copy_rows_plan(2, 16, 0, 0, 3, 1, o) == -1 and b"copy_rows_plan: bad dtype 3" in L.mi_last_error()
+    for a in ((0, 16, 0, 0), (2, 0, 0, 0), (2, 16, -1, 0), (2, 16, 0, -1)):
+        assert L.mi_copy_rows_plan(*a, lib.MI_F32, 1, o) == -1 and b"copy_rows_plan: bad shape" in L.mi_last_error(), a
+    assert L.mi_copy_rows_plan(2, 16, 0, 0, lib.MI_F32, 1, o) == 0 and list(o)[:3] == [4, 8, 1]
+
+
+def test_glue_case_tables_reach_every_instance(lib):
+    """The tables of tests/glue_forms.py reach every instance the launchers can select and nothing unknown, each value of each
+    dimension at each instance, and every loop state; each row names its plan, so a threshold that moves is a row that lost it."""
+    from image_restoration_amd import ops
+    import glue_forms as T
+    seen = {t: {} for t in T.TABLES}
+    for t, rows in T.TABLES.items():
+        for r in rows:
+            seen[t].setdefault(T.instance(r, T.reach(ops, r)), []).append(r)
+    conv = seen["conv"]
+    assert set(conv) == T.C3_INSTANCES
+    for (mt, twp), rows in conv.items():
+        tr = 256 // twp
+        assert {r["wkind"] for r in rows} == {k for k, _ in T.C3_W[twp]} and {r["W"] for r in rows} == {w for _, w in T.C3_W[twp]}
+        assert {r["H"] for r in rows} == {1, tr - 1, tr, tr + 1, 2 * tr + 1} and {r["K"] for r in rows if not r["transpose"]} == {1, 3, 15, 16, 17, 33}
+        assert {r["M"] for r in rows} == set(T.C3_M[mt]) and {r["B"] for r in rows} == {1, 3}
+        assert {(r["bias"], r["res"]) for r in rows} == set(T.EPILOGUES)
+        assert sum(r["transpose"] and r["M"] != r["K"] for r in rows) >= 2
+    assert {r["W"] for r in conv[(4, 64)]} == {64, 40, 72, 128} and {r["W"] for r in conv[(1, 16)]} == {16, 8} and {r["W"] for r in conv[(2, 32)]} == {32, 24}
+    assert {(r["mt"], r["twp"]) for r in T.CONV_CASES if T.module_route(r)} == T.C3_INSTANCES      # the module route runs all nine too
+    wg = seen["wgrad"]
+    assert set(wg) == T.C3W_INSTANCES
+    for (twp, swap), rows in wg.items():
+        assert {r["rows"] for r in rows} >= ({17, 33, 64, 65} if swap else {1, 16, 17, 33, 64, 65}) and {r["cols"] for r in rows} >= {1, 15, 16, 17}
+        assert {(r["tiles"], r["splits"]) for r in rows} >= {(1, 1), (3, 1), (4, 2), (5, 2), (7, 3), (6, 3), (2, 1)}
+        assert any(r["loop"] == "3x2/3" and r["B"] == 3 for r in rows)                 # 3 images x 2 tiles: each split alternates images
+        assert any(r["loop"] == "past_h" and r["H"] % (256 // twp) for r in rows) and sum(r["accumulate"] for r in rows) >= 2
+    assert not any(ops.conv3x3_plan(1, c, r, 8, 16)["w_swap"] for r in (1, 16) for c in range(1, 65))   # (no swap puts <= 16 rows in the row role)
+    by_blocks = [r for r in T.WGRAD_CASES if r["loop"] == "by_blocks"]
+    assert len(by_blocks) == 1 and by_blocks[0]["splits"] == 8 < by_blocks[0]["tiles"] // 2
+    for t in ("im2col", "col2im"):
+        g = seen[t]
+        assert set(g) == T.G3_STREAM | T.G3_BANDS | {("general", "f32"), ("general", "bf16")}, t
+        for lpr in (4, 8, 16, 32, 64):
+            rows = [r for k in T.G3_STREAM if k[0] == lpr for r in g[k]]
+            assert {r["H"] for r in rows} == {1, 7, 8, 9, 17} and all(r["idle"] and r["band"] == 8 and r["W"] == 4 * lpr for r in rows)
+        assert all(r["dtype"] == "bf16" and r["device_ref"] and r["B"] * r["C"] == 2048 for k in T.G3_BANDS for r in g[k])
+        assert ops.glue3x3_plan(2047, 17, 256, torch.bfloat16)["band"] == 8                 # 2048 is the smallest plane count for both
+        gen = g[("general", "f32")] + g[("general", "bf16")]
+        assert {(r["W"], r["H"]) for r in gen} >= {(W, H) for W in (1, 3, 8, 20, 24) for H in (1, 2, 5)}
+        assert {(r["dtype"], r["x_off"], r["out_off"]) for r in gen if r["W"] == 64} == {(d, a, b) for d in T.DTYPES for a, b in ((1, 0), (0, 1))}
+        assert sum(r["trips"] == 2 for r in gen) == 1
+    assert {(r["bias"], r["res"]) for r in T.COL2IM_CASES if r["form"] == "stream"} == set(T.EPILOGUES)
+    assert {(r["bias"], r["res"]) for r in T.COL2IM_CASES if r["form"] == "general"} == set(T.EPILOGUES)
+    assert all(r["C"] > 1 for r in T.COL2IM_CASES) and any(r["B"] > 1 and r["bias"] for r in T.COL2IM_CASES)
+    sh = seen["shuffle"]
+    assert set(sh) == T.PS_INSTANCES
+    for (form, un, dt), rows in sh.items():
+        if form == "element":
+            assert {r["why"] for r in rows} == {"width", "in_ptr", "out_ptr", "stride"}
+    assert sum(r["trips"] == 2 for r in T.SHUFFLE_CASES) == 1
+    cr = seen["copy"]
+    assert set(cr) == T.CR_INSTANCES
+    assert all({r["why"] for r in rows} == {"tail", "in_ptr", "out_ptr", "stride"} for (form, dt), rows in cr.items() if form == "element")
+
+
+def _glue_calls(tables):
+    from image_restoration_amd import ops
+    import glue_forms as T
+    for t in tables:
+        for r in T.TABLES[t]:
+            if not r.get("device_ref"):
+                yield t, r, T.BUILD[t](ops, r, "cpu")
+
+
+def test_glue_rows_meet_the_integer_precondition(lib):
+    """Every expected value of every row is an integer its output dtype holds exactly (the builders assert it on the reference
+    alone; none is skipped), the operands lie inside NaN and a result equal to the reference passes the comparison and the guards.
+    The rows whose reference is computed on the device (the two tall-band cases and the grid-cap cases) are bounded by their
+    ranges: a tap of x in [-2, 2], or nine z in [-3, 3] plus a bias and a residual in [-8, 8], at most 43."""
+    import glue_forms as T
+    n, peak = 0, {}
+    for t, r, c in _glue_calls(T.TABLES):
+        T.precondition(c.ref, c.out.dtype, T.case_id(r))
+        peak[t] = max(peak.get(t, 0.0), float(c.ref.abs().max()))
+        assert bool(c.out_buf.isnan().all())
+        c.reset()
+        c.out.copy_(c.ref)
+        c.check()
+        n += 1
+    big = [r for rows in T.TABLES.values() for r in rows if r.get("device_ref")]
+    assert n + len(big) == sum(map(len, T.TABLES.values())) and len(big) == 6
+    assert all(r["dtype"] == "bf16" and 9 * 3 + 8 + 8 <= 256 for r in big)
+    assert peak["conv"] <= 256 and peak["wgrad"] < 2 ** 24 and peak["col2im"] <= 43, peak
+
+
+def test_glue_assertions_catch_deliberately_wrong_results(lib):
+    """Eight alterations of the kind these kernels can have - a halo column at a tile seam read as zero, a row-end neighbour taken
+    from the adjacent row, taps 0 and 8 exchanged, the last partial channel chunk dropped, one split's partial sum left out of dw,
+    the column phases of a shuffle exchanged, a band's halo row read as zero, the bias of another plane - applied to the reference
+    of every row where each can occur: the comparison fails each time.  And one stray write fails the guard check.
+
+    Contrast with the bar these kernels had (tests/test_gpu_conv3x3.py: one scalar, max|delta| / max|ref| < 1e-2 on random normal
+    data, at five of the nine forward instances; the layout kernels behind whole modules only): any error under a hundredth of
+    the largest output passes it, and it names no element; here one unit in one element fails, with its tile, chunk or band."""
+    import glue_forms as T
+    caught = dict.fromkeys(T.FAULTS, 0)
+    for t, r, c in _glue_calls({tb for tb, _ in T.FAULTS.values()}):
+        for name, (table, fault) in T.FAULTS.items():
+            if table != t or not T.fault_applies(name, r, c.plan):
+                continue
+            wrong = fault(c)
+            assert wrong.shape == c.ref.shape
+            c.reset()
+            c.out.copy_(wrong)
+            with pytest.raises(AssertionError, match="elements differ; first at"):
+                c.check()
+            caught[name] += 1
+    assert min(caught.values()) >= 3, caught
+    _, r, c = next(_glue_calls(["conv"]))
+    c.reset()
+    c.out.copy_(c.ref)
+    c.check()
+    c.out_buf[c.out.storage_offset() - 1] = 1.0                                # one element, in the guard channel before image 0
+    with pytest.raises(AssertionError, match="1 elements outside the output were written"):
+        c.check()
+    c.reset()
+    c.out.copy_(c.ref)
+    c.out[0, 0, 0, 0] = float("nan")
+    with pytest.raises(AssertionError, match="1 elements of the output were never written"):
+        c.check()
