@@ -236,6 +236,33 @@ class SfhLocalGrads(C.Structure):
     _fields_ = [(n, fp) for n in SFH_LOCAL_FIELDS] + [("accumulate", C.c_int)]
 
 
+class SfhMixerShape(C.Structure):
+    """mi_sfh_global_shape / mi_sfh_mixer_shape (one struct)"""
+    _fields_ = [("B", C.c_int), ("dim", C.c_int), ("H", C.c_int), ("W", C.c_int), ("dtype", C.c_int), ("training", C.c_int),
+                ("eps", C.c_float), ("momentum", C.c_float)]
+
+
+# mi_sfh_global_params / _grads and mi_sfh_mixer_params / _grads in field order (the modules' named_parameters() order)
+SFH_GLOBAL_FIELDS = ("init_w", "init_b", "fina_w", "fina_b") + FOURIER_UNIT_FIELDS
+SFH_MIXER_FIELDS = SFH_LOCAL_FIELDS + SFH_GLOBAL_FIELDS + ("cac_w", "cac_b", "ca1_w", "ca1_b", "ca2_w", "ca2_b", "conv_w", "conv_b")
+
+
+class SfhGlobalParams(C.Structure):
+    _fields_ = [(n, fp) for n in SFH_GLOBAL_FIELDS]
+
+
+class SfhGlobalGrads(C.Structure):
+    _fields_ = [(n, fp) for n in SFH_GLOBAL_FIELDS] + [("accumulate", C.c_int)]
+
+
+class SfhMixerParams(C.Structure):
+    _fields_ = [(n, fp) for n in SFH_MIXER_FIELDS]
+
+
+class SfhMixerGrads(C.Structure):
+    _fields_ = [(n, fp) for n in SFH_MIXER_FIELDS] + [("accumulate", C.c_int)]
+
+
 class EblockShape(C.Structure):
     _fields_ = DblockShape._fields_
 
@@ -467,6 +494,17 @@ SIGNATURES = {
     "mi_sfh_local_plan": (C.c_int, [C.POINTER(SfhLocalShape), C.POINTER(c_i64)]),
     "mi_sfh_local_fwd": (C.c_int, [C.POINTER(SfhLocalShape), C.POINTER(SfhLocalParams), vp, vp, vp, vp]),
     "mi_sfh_local_bwd": (C.c_int, [C.POINTER(SfhLocalShape), C.POINTER(SfhLocalParams), vp, vp, vp, C.POINTER(SfhLocalGrads), vp, vp]),
+    "mi_sfh_global_workspace": (C.c_size_t, [C.POINTER(SfhMixerShape)]),
+    "mi_sfh_global_saved_bytes": (C.c_size_t, [C.POINTER(SfhMixerShape)]),
+    "mi_sfh_global_plan": (C.c_int, [C.POINTER(SfhMixerShape), C.POINTER(c_i64)]),
+    "mi_sfh_global_fwd": (C.c_int, [C.POINTER(SfhMixerShape), C.POINTER(SfhGlobalParams), vp, vp, fp, fp, vp, vp, vp]),
+    "mi_sfh_global_bwd": (C.c_int, [C.POINTER(SfhMixerShape), C.POINTER(SfhGlobalParams), vp, vp, vp, C.POINTER(SfhGlobalGrads), vp, vp,
+                                    vp]),
+    "mi_sfh_mixer_workspace": (C.c_size_t, [C.POINTER(SfhMixerShape)]),
+    "mi_sfh_mixer_saved_bytes": (C.c_size_t, [C.POINTER(SfhMixerShape)]),
+    "mi_sfh_mixer_plan": (C.c_int, [C.POINTER(SfhMixerShape), C.POINTER(c_i64)]),
+    "mi_sfh_mixer_fwd": (C.c_int, [C.POINTER(SfhMixerShape), C.POINTER(SfhMixerParams), vp, vp, fp, fp, vp, vp, vp]),
+    "mi_sfh_mixer_bwd": (C.c_int, [C.POINTER(SfhMixerShape), C.POINTER(SfhMixerParams), vp, vp, vp, C.POINTER(SfhMixerGrads), vp, vp, vp]),
     "mi_fregate_fwd": (C.c_int, [vp, vp, fp, vp, C.c_int, C.c_int, c_i64, C.c_int, vp]),
     "mi_fregate_bwd_workspace": (C.c_size_t, [C.c_int, C.c_int, c_i64]),
     "mi_fregate_bwd": (C.c_int, [vp, vp, vp, fp, vp, vp, fp, C.c_int, C.c_int, c_i64, C.c_int, C.c_int, vp, vp]),

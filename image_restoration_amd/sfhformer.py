@@ -19,6 +19,15 @@ activations; BatchNorm with running statistics and a fixed momentum.  CPU tensor
 ``mi_sfh_local_*`` (``csrc/sfh_ffn.hip``): the channel axis in segments of ``dim / 2`` channels, each with its own depthwise stencil
 (identity, 3x3, 5x5, 7x7 and erf-GELU between two biased 1x1 products; 3x3 at dilation 1 and 2).  Limits: ``dim`` even (an odd
 ``dim`` changes the reference's chunk count: ``NotImplementedError``), 2 <= dim <= 256, any plane, fp32 or bf16 activations.
+
+``TokenMixer_For_Gloal(dim)`` (``:183-206``, keys ``conv_init.0.*``, ``conv_fina.0.*``, ``FFC.*``) and ``Mixer(dim)`` (``:209-251``, keys
+``mixer_local.*``, ``mixer_gloal.*``, ``ca_conv.0.*``, ``ca.1.*``, ``ca.3.*``, ``conv_init.0.*``) are each ONE autograd node over
+``mi_sfh_global_*`` / ``mi_sfh_mixer_*`` (``csrc/sfh_mixer.hip``): the 1x1 products, the FourierUnit and the local mixer through the
+library's own entry points, and between them the file's streaming kernels (GELU, the residual add, the GELU / pool tail that writes
+the concatenated tensor once, the channel attention folded into a per-image ``ca_conv`` weight).  ``FFC.bn`` behaves as in
+``FourierUnit.forward``.  ``Mixer`` takes the reference's default token mixers only.  Limits: ``Mixer`` even 2 <= dim <= 128,
+``TokenMixer_For_Gloal`` 1 <= dim <= 128 (the FourierUnit inside has 2 dim channels), planes of 2..512 pixels a side.  ``Block`` and
+``Backbone`` stay the reference's PyTorch modules around these.
 """
 from __future__ import annotations
 
@@ -30,7 +39,7 @@ from ._autograd import module_op
 
 Tensor = torch.Tensor
 
-__all__ = ["FFN", "FourierUnit", "TokenMixer_For_Local"]
+__all__ = ["FFN", "FourierUnit", "Mixer", "TokenMixer_For_Gloal", "TokenMixer_For_Local"]
 
 
 class _FourierUnitOp:
@@ -146,3 +155,74 @@ class TokenMixer_For_Local(nn.Module):
     def forward(self, x):
         ops._gpu(x)
         return module_op(_LocalOp(), (x,), (self.CDilated_1.weight, self.CDilated_1.bias, self.CDilated_2.weight, self.CDilated_2.bias))
+
+
+class _MixerOp:
+    """TokenMixer_For_Gloal.forward / Mixer.forward as one module op.  params: ops.sfh_global_fwd / ops.sfh_mixer_fwd; saved = [the
+    kernels' blob]; the running statistics are those of the FourierUnit inside."""
+
+    def __init__(self, fwd, bwd, bn: nn.BatchNorm2d, training: bool):
+        self.fwd, self.bwd = fwd, bwd
+        self.rm, self.rv, self.training, self.eps, self.momentum = bn.running_mean, bn.running_var, training, bn.eps, bn.momentum
+
+    def forward(self, acts, params, need):
+        out, blob = self.fwd(acts[0], params, self.rm, self.rv, self.training, need, self.eps, self.momentum)
+        return out, [blob]
+
+    def backward(self, acts, saved, dout, params, grads, acc):
+        return (self.bwd(acts[0], dout, params, saved[0], grads, acc, self.training, self.eps, self.momentum),)
+
+
+def _run_mixer(mod, fwd, bwd, bn, x):
+    if not (bn.track_running_stats and bn.affine and bn.momentum is not None and bn.running_mean is not None):
+        raise NotImplementedError("image_restoration_amd: FourierUnit's BatchNorm runs affine, with running statistics and a "
+                                  "fixed momentum (the form the kernels were built for)")
+    ops._gpu(x)
+    training = bool(bn.training)
+    out = module_op(_MixerOp(fwd, bwd, bn, training), (x,), tuple(mod.parameters()))
+    if training:
+        with torch.no_grad():
+            bn.num_batches_tracked += 1
+    return out
+
+
+class TokenMixer_For_Gloal(nn.Module):
+    """conv_fina(FFC(p) + p), p = conv_init(x): two biased 1x1 convs, each followed by GELU, around a FourierUnit(2 dim, 2 dim)."""
+
+    def __init__(self, dim):
+        super().__init__()
+        if not (isinstance(dim, int) and 1 <= dim <= ops.SFH_MIXER_MAX_DIM):
+            raise NotImplementedError(f"image_restoration_amd: TokenMixer_For_Gloal(dim={dim!r}) not covered; the kernels were built "
+                                      f"for 1 <= dim <= {ops.SFH_MIXER_MAX_DIM}")
+        self.dim = dim
+        self.conv_init = nn.Sequential(nn.Conv2d(dim, dim * 2, 1), nn.GELU())
+        self.conv_fina = nn.Sequential(nn.Conv2d(dim * 2, dim, 1), nn.GELU())
+        self.FFC = FourierUnit(dim * 2, dim * 2)
+
+    def forward(self, x):
+        return _run_mixer(self, ops.sfh_global_fwd, ops.sfh_global_bwd, self.FFC.bn, x)
+
+
+class Mixer(nn.Module):
+    """ca_conv(ca(g) g), g = gelu(cat(mixer_local(a), mixer_gloal(b))), [a, b] = conv_init(x) split in halves; ca: global average
+    pool, 1x1 to dim, ReLU, 1x1 to 2 dim, sigmoid."""
+
+    def __init__(self, dim, token_mixer_for_local=TokenMixer_For_Local, token_mixer_for_gloal=TokenMixer_For_Gloal):
+        super().__init__()
+        if token_mixer_for_local is not TokenMixer_For_Local or token_mixer_for_gloal is not TokenMixer_For_Gloal:
+            raise NotImplementedError("image_restoration_amd: Mixer runs the reference's default token mixers only "
+                                      "(TokenMixer_For_Local, TokenMixer_For_Gloal)")
+        if not (isinstance(dim, int) and 2 <= dim <= ops.SFH_MIXER_MAX_DIM and dim % 2 == 0):
+            raise NotImplementedError(f"image_restoration_amd: Mixer(dim={dim!r}) not covered; the kernels were built for even "
+                                      f"2 <= dim <= {ops.SFH_MIXER_MAX_DIM} (the FourierUnit inside has 2 dim <= 256 channels)")
+        self.dim = dim
+        self.mixer_local = token_mixer_for_local(dim=dim)
+        self.mixer_gloal = token_mixer_for_gloal(dim=dim)
+        self.ca_conv = nn.Sequential(nn.Conv2d(2 * dim, dim, 1))
+        self.ca = nn.Sequential(nn.AdaptiveAvgPool2d(1), nn.Conv2d(2 * dim, 2 * dim // 2, kernel_size=1), nn.ReLU(inplace=True),
+                                nn.Conv2d(2 * dim // 2, 2 * dim, kernel_size=1), nn.Sigmoid())
+        self.gelu = nn.GELU()
+        self.conv_init = nn.Sequential(nn.Conv2d(dim, 2 * dim, 1))
+
+    def forward(self, x):
+        return _run_mixer(self, ops.sfh_mixer_fwd, ops.sfh_mixer_bwd, self.mixer_gloal.FFC.bn, x)

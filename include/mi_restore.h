@@ -1047,6 +1047,82 @@ int mi_sfh_local_bwd(const mi_sfh_local_shape* s, const mi_sfh_local_params* p, 
                      const mi_sfh_local_grads* g, void* ws, void* stream);
 
 /* ------------------------------------------------------------------------
+ * SFHformer — TokenMixer_For_Gloal (SFHformer.py:183-206) and Mixer (:209-251) (csrc/sfh_mixer.hip), each as one launch sequence
+ * over mi_pw_gemm, mi_gram, the channel sum, mi_fourier_unit_*, mi_sfh_local_* and the file's own streaming kernels.
+ *   global  b [B,dim,H,W] -> u1 = Wi b + bi [2dim] -> p = gelu_erf(u1) -> f = FourierUnit(2dim, 2dim, groups 4)(p) -> r = f + p
+ *           -> u2 = Wf r + bf [dim] -> out = gelu_erf(u2).
+ *   mixer   x [B,dim,H,W] -> [a; b] = conv_init(x) as two dense [B,dim,H,W] tensors (one grouped product whose two groups read the
+ *           same x and write the halves apart: no slice copy) -> l = local(a),
+ *           u2 = global(b) without its last GELU -> g = gelu(cat(l, gelu(u2))) written once into one [B,2dim,H,W] tensor together
+ *           with fixed-order partial sums -> per image m = mean g, s = sigmoid(W2 relu(W1 m + b1) + b2) and the folded weight
+ *           Wc diag(s_b) [dim,2dim] (one workgroup per image) -> out = (Wc diag(s_b)) g + bc: one mi_pw_gemm with a per-image weight
+ *           (never cached: w_bs != 0); s g is never written.
+ * running_mean / running_var [4dim] are the FourierUnit's BatchNorm statistics, handled as in mi_fourier_unit_fwd (updated in
+ * place when shape.training, on the device; with saved == NULL too).
+ * saved (mi_*_saved_bytes(), sections 256-byte aligned, in this order): a, b, l [B,dim,N] (mixer only), u1, r [B,2dim,N], u2
+ * [B,dim,N], all in the activation dtype, then the FourierUnit's own blob.  p, f, q, g, m, hidden, s and the folded weights are
+ * recomputed or live in the workspace: the backward runs the forward's own tail kernels again over l and u2, so they are the
+ * forward's bit for bit.  saved == NULL in _fwd (inference, no_grad): nothing is kept.
+ * Backward (mixer): the per-image Gram P_b = dout_b g_b^T (mi_gram, sum_batch = 0); from it dWc = sum_b P_b diag(s_b),
+ * ds = sum_m Wc . P_b and the gate's backward (two small kernels: per image, then the sums over the images in order);
+ * e = (Wc diag(s_b))^T dout (transposed per-image product); one pass dl = (e + dm/N) gelu'(l), du2 = (e + dm/N) gelu'(q) gelu'(u2);
+ * mi_sfh_local_bwd; conv_fina's gradients and dr; mi_fourier_unit_bwd; du1 = (dr + dp) gelu'(u1); the global conv_init's
+ * gradients; the mixer's conv_init takes da and db as two K panels (two Grams and two bias sums into the halves of its
+ * gradient).  Gradients are added to when g->accumulate, else overwritten.  Bitwise reproducible; no allocation, no host sync.
+ * Limits: mixer dim even, 2..128; global dim 1..128; 2 <= H, W <= 512; 1 <= B <= 65535; B 2dim H W below 2^31; fp32 or bf16; and
+ * the FourierUnit's own (eps > 0, 0 <= momentum <= 1).  Anything else is refused before any launch; the sizing calls return 0.
+ * The plan calls (host-only; launchers and sizing calls read the same plan) fill out[64]: mode (0 global, 1 mixer), B, dim, 2dim,
+ * N, pool partials per plane, grid of the flat passes over [B,dim,N] and over [B,2dim,N], grid x of the tail's backward pass,
+ * threads per workgroup, own kernel launches forward / backward [10, 11], library calls forward / backward [12, 13], bytes of the
+ * backward's planes (e, dl, du2, da, db) inside the scratch section [14], 0; then (byte offset, bytes) of the 13 workspace
+ * sections [16..41]: the 1x1, Gram and channel-sum workspaces, the FourierUnit's and the local mixer's workspaces, p (backward:
+ * the FourierUnit's input gradient), f (backward: dr, then du1), g, the small fp32 vectors (m, hidden, s, dz2, dz1, dm/N), the
+ * folded weights, the per-image Gram, the pool partials, the scratch (forward without a blob: the saved planes without the FourierUnit's blob; backward: e, dl,
+ * du2, da, db); then (byte offset, bytes) of the 7 saved sections [44..57]; the workspace size [60], the saved blob's size [61].
+ * ------------------------------------------------------------------------ */
+typedef struct { int B, dim, H, W, dtype, training; float eps, momentum; } mi_sfh_global_shape;
+typedef mi_sfh_global_shape mi_sfh_mixer_shape;
+typedef struct {
+  const float* init_w; const float* init_b;   /* conv_init.0  [2dim,dim], [2dim] */
+  const float* fina_w; const float* fina_b;   /* conv_fina.0  [dim,2dim], [dim] */
+  const float* bn_w; const float* bn_b; const float* fdc_w; const float* fdc_b; const float* gate_w; const float* gate_b;
+  const float* fpe_w; const float* fpe_b;     /* FFC.*: mi_fourier_unit_params with c = 2dim, groups = 4 */
+} mi_sfh_global_params;
+typedef struct {
+  float* init_w; float* init_b; float* fina_w; float* fina_b; float* bn_w; float* bn_b; float* fdc_w; float* fdc_b; float* gate_w;
+  float* gate_b; float* fpe_w; float* fpe_b; int accumulate;
+} mi_sfh_global_grads;
+typedef struct {
+  const float* cd1_w; const float* cd1_b; const float* cd2_w; const float* cd2_b;             /* mixer_local.* */
+  const float* init_w; const float* init_b; const float* fina_w; const float* fina_b;         /* mixer_gloal.*, as above */
+  const float* bn_w; const float* bn_b; const float* fdc_w; const float* fdc_b; const float* gate_w; const float* gate_b;
+  const float* fpe_w; const float* fpe_b;
+  const float* cac_w; const float* cac_b;     /* ca_conv.0  [dim,2dim], [dim] */
+  const float* ca1_w; const float* ca1_b;     /* ca.1       [dim,2dim], [dim] */
+  const float* ca2_w; const float* ca2_b;     /* ca.3       [2dim,dim], [2dim] */
+  const float* conv_w; const float* conv_b;   /* conv_init.0 [2dim,dim], [2dim] */
+} mi_sfh_mixer_params;
+typedef struct {
+  float* cd1_w; float* cd1_b; float* cd2_w; float* cd2_b; float* init_w; float* init_b; float* fina_w; float* fina_b; float* bn_w;
+  float* bn_b; float* fdc_w; float* fdc_b; float* gate_w; float* gate_b; float* fpe_w; float* fpe_b; float* cac_w; float* cac_b;
+  float* ca1_w; float* ca1_b; float* ca2_w; float* ca2_b; float* conv_w; float* conv_b; int accumulate;
+} mi_sfh_mixer_grads;
+size_t mi_sfh_global_workspace(const mi_sfh_global_shape* s);
+size_t mi_sfh_global_saved_bytes(const mi_sfh_global_shape* s);
+int mi_sfh_global_plan(const mi_sfh_global_shape* s, int64_t* out);
+int mi_sfh_global_fwd(const mi_sfh_global_shape* s, const mi_sfh_global_params* p, const void* x, void* out, float* running_mean,
+                      float* running_var, void* saved, void* ws, void* stream);
+int mi_sfh_global_bwd(const mi_sfh_global_shape* s, const mi_sfh_global_params* p, const void* x, const void* dout, void* dx,
+                      const mi_sfh_global_grads* g, const void* saved, void* ws, void* stream);
+size_t mi_sfh_mixer_workspace(const mi_sfh_mixer_shape* s);
+size_t mi_sfh_mixer_saved_bytes(const mi_sfh_mixer_shape* s);
+int mi_sfh_mixer_plan(const mi_sfh_mixer_shape* s, int64_t* out);
+int mi_sfh_mixer_fwd(const mi_sfh_mixer_shape* s, const mi_sfh_mixer_params* p, const void* x, void* out, float* running_mean,
+                     float* running_var, void* saved, void* ws, void* stream);
+int mi_sfh_mixer_bwd(const mi_sfh_mixer_shape* s, const mi_sfh_mixer_params* p, const void* x, const void* dout, void* dx,
+                     const mi_sfh_mixer_grads* g, const void* saved, void* ws, void* stream);
+
+/* ------------------------------------------------------------------------
  * DarkIR — the encoder block (DarkIR-main/archs/arch_model.py:141-204 EBlock) and its tail (csrc/darkir.hip).
  *
  * fregate: the block's last line, y + gamma (y f), as one streaming pass.  y, f, out [B,C,N] in `dtype`, gamma [C] fp32, fp32
