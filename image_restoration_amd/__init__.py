@@ -10,7 +10,8 @@ from .darkir import DarkIR, DBlock, EBlock, FreMLP  # noqa: F401
 from .ops import reload_env  # noqa: F401
 from .restormer import (Attention, Downsample, FeedForward, LayerNorm, OverlapPatchEmbed, Restormer,  # noqa: F401
                         TransformerBlock, Upsample)
-from .sfhformer import FFN, FourierUnit, Mixer, TokenMixer_For_Gloal, TokenMixer_For_Local  # noqa: F401
+from .sfhformer import (FFN, BatchNorm2d, FourierUnit, Mixer, TokenMixer_For_Gloal, TokenMixer_For_Local,  # noqa: F401
+                        scaled_residual)
 
-__all__ = ["Attention", "DarkIR", "DBlock", "Downsample", "EBlock", "FFN", "FeedForward", "FourierUnit", "FreMLP", "LayerNorm", "Mixer", "OverlapPatchEmbed", "Restormer",
-           "TokenMixer_For_Gloal", "TokenMixer_For_Local", "TransformerBlock", "Upsample", "reload_env"]
+__all__ = ["Attention", "BatchNorm2d", "DarkIR", "DBlock", "Downsample", "EBlock", "FFN", "FeedForward", "FourierUnit", "FreMLP", "LayerNorm", "Mixer", "OverlapPatchEmbed", "Restormer",
+           "TokenMixer_For_Gloal", "TokenMixer_For_Local", "TransformerBlock", "Upsample", "reload_env", "scaled_residual"]

@@ -263,6 +263,12 @@ class SfhMixerGrads(C.Structure):
     _fields_ = [(n, fp) for n in SFH_MIXER_FIELDS] + [("accumulate", C.c_int)]
 
 
+class Bn2dShape(C.Structure):
+    """mi_bn2d_shape / mi_scale_res_shape (one struct)"""
+    _fields_ = [("B", C.c_int), ("C", C.c_int), ("H", C.c_int), ("W", C.c_int), ("dtype", C.c_int), ("training", C.c_int),
+                ("eps", C.c_float), ("momentum", C.c_float)]
+
+
 class EblockShape(C.Structure):
     _fields_ = DblockShape._fields_
 
@@ -505,6 +511,14 @@ SIGNATURES = {
     "mi_sfh_mixer_plan": (C.c_int, [C.POINTER(SfhMixerShape), C.POINTER(c_i64)]),
     "mi_sfh_mixer_fwd": (C.c_int, [C.POINTER(SfhMixerShape), C.POINTER(SfhMixerParams), vp, vp, fp, fp, vp, vp, vp]),
     "mi_sfh_mixer_bwd": (C.c_int, [C.POINTER(SfhMixerShape), C.POINTER(SfhMixerParams), vp, vp, vp, C.POINTER(SfhMixerGrads), vp, vp, vp]),
+    "mi_bn2d_workspace": (C.c_size_t, [C.POINTER(Bn2dShape)]),
+    "mi_bn2d_plan": (C.c_int, [C.POINTER(Bn2dShape), C.POINTER(c_i64)]),
+    "mi_bn2d_fwd": (C.c_int, [C.POINTER(Bn2dShape), fp, fp, vp, vp, fp, fp, fp, fp, vp, vp]),
+    "mi_bn2d_bwd": (C.c_int, [C.POINTER(Bn2dShape), fp, vp, vp, vp, vp, fp, fp, C.c_int, fp, vp, vp]),
+    "mi_scale_res_workspace": (C.c_size_t, [C.POINTER(Bn2dShape)]),
+    "mi_scale_res_plan": (C.c_int, [C.POINTER(Bn2dShape), C.POINTER(c_i64)]),
+    "mi_scale_res_fwd": (C.c_int, [C.POINTER(Bn2dShape), fp, vp, vp, vp, fp, vp]),
+    "mi_scale_res_bwd": (C.c_int, [C.POINTER(Bn2dShape), fp, vp, vp, vp, fp, C.c_int, vp, vp]),
     "mi_fregate_fwd": (C.c_int, [vp, vp, fp, vp, C.c_int, C.c_int, c_i64, C.c_int, vp]),
     "mi_fregate_bwd_workspace": (C.c_size_t, [C.c_int, C.c_int, c_i64]),
     "mi_fregate_bwd": (C.c_int, [vp, vp, vp, fp, vp, vp, fp, C.c_int, C.c_int, c_i64, C.c_int, C.c_int, vp, vp]),

@@ -1352,6 +1352,134 @@ def sfh_mixer_bwd(x: Tensor, dout: Tensor, params: Sequence[Tensor], saved: Tens
     return _sm_bwd(True, x, dout, params, saved, grads, accumulate, training, eps, momentum)
 
 
+# ----------------------------------------------------------------------------- SFHformer: the Block's BatchNorm2d and scaled residual
+BN2D_MAX_C = 4096
+_BN_PLAN_KEYS = ("B", "C", "N", "dtype", "training", "block", "chunk", "chunks_per_plane", "partials_per_channel", "vector_width",
+                 "chunks", "grid_chunks", "grid_channels", "launches_fwd", "launches_fwd_part_in", "launches_bwd")
+_BN_SECTIONS = ("partials", "stat", "bwd_means")
+
+
+def _bn_shape(B: int, Cn: int, H: int, W: int, dtype_code: int, training: bool = True, eps: float = 1e-5,
+              momentum: float = 0.1) -> L.Bn2dShape:
+    return L.Bn2dShape(B, Cn, H, W, dtype_code, int(training), eps, momentum)
+
+
+def _bn_plan(fn, shape, who: str) -> dict:
+    out = (L.c_i64 * 64)()
+    L.check(fn(C.byref(shape), out), who)
+    plan = {k: int(out[i]) for i, k in enumerate(_BN_PLAN_KEYS)}
+    plan["sections"] = {n: (int(out[16 + 2 * i]), int(out[17 + 2 * i])) for i, n in enumerate(_BN_SECTIONS)}
+    plan["workspace"], plan["stat_bytes"], plan["pair_bytes"] = int(out[60]), int(out[61]), int(out[62])
+    return plan
+
+
+def bn2d_plan(B: int, Cn: int, H: int, W: int, dtype: torch.dtype = torch.float32, training: bool = True) -> dict:
+    """What bn2d_fwd / bn2d_bwd launch for x [B, C, H, W] (mi_bn2d_plan; no GPU work): the chunk size, chunks per plane, partials per
+    channel, the vector width the shape allows, grids, launch counts; ``sections`` maps each workspace section to its (byte offset,
+    bytes); ``pair_bytes``: what ``part_in`` / ``part_out`` hold."""
+    return _bn_plan(L.lib().mi_bn2d_plan, _bn_shape(B, Cn, H, W, _dtype_code(dtype), training), "bn2d_plan")
+
+
+def scale_res_plan(B: int, Cn: int, H: int, W: int, dtype: torch.dtype = torch.float32) -> dict:
+    """The same for scale_res_fwd / scale_res_bwd (mi_scale_res_plan); its workspace holds the backward's partial sums only."""
+    return _bn_plan(L.lib().mi_scale_res_plan, _bn_shape(B, Cn, H, W, _dtype_code(dtype)), "scale_res_plan")
+
+
+def bn2d_workspace(B: int, Cn: int, H: int, W: int, dtype: torch.dtype, training: bool = True) -> int:
+    """Workspace bytes of one BatchNorm2d call; 0 for a shape the kernels refuse.  No GPU needed."""
+    s = _bn_shape(B, Cn, H, W, _dtype_code(dtype), training)
+    return int(L.lib().mi_bn2d_workspace(C.byref(s)))
+
+
+def scale_res_workspace(B: int, Cn: int, H: int, W: int, dtype: torch.dtype) -> int:
+    s = _bn_shape(B, Cn, H, W, _dtype_code(dtype))
+    return int(L.lib().mi_scale_res_workspace(C.byref(s)))
+
+
+def _bn_args(who: str, x: Tensor, per_channel: Sequence[Optional[Tensor]], sizer, training: bool, eps: float, momentum: float):
+    """The shape struct and workspace bytes for x [B, C, H, W]; ``per_channel``: fp32 tensors that must hold C values."""
+    if x.dim() != 4:
+        raise ValueError(f"{who}: x must be [B, C, H, W], got {tuple(x.shape)}")
+    B, Cn, H, W = x.shape
+    for t in per_channel:
+        if t is not None and _f32(t, f"{who} parameter / statistic").numel() != Cn:
+            raise ValueError(f"{who}: a per-channel tensor of shape {tuple(t.shape)} does not fit C = {Cn}")
+    s = _bn_shape(B, Cn, H, W, _dt(x), training, eps, momentum)
+    ws_bytes = sizer(C.byref(s))
+    if ws_bytes == 0:
+        raise NotImplementedError("image_restoration_amd: " + L.lib().mi_last_error().decode("utf-8", "replace"))
+    return s, ws_bytes
+
+
+def _same(who: str, x: Tensor, *others: Optional[Tensor]) -> None:
+    for t in others:
+        if t is not None and (t.shape != x.shape or t.dtype != x.dtype):
+            raise ValueError(f"{who}: tensors differ in shape or dtype ({tuple(t.shape)} {t.dtype} against {tuple(x.shape)} {x.dtype})")
+
+
+def bn2d_fwd(x: Tensor, weight: Tensor, bias: Tensor, running_mean: Tensor, running_var: Tensor, training: bool, need_stat: bool,
+             eps: float = 1e-5, momentum: float = 0.1, part_in: Optional[Tensor] = None):
+    """BatchNorm2d.forward over x [B, C, H, W] (see mi_restore.h).  ``running_mean`` / ``running_var`` [C] fp32 are updated in place
+    when ``training``.  ``part_in``: the (mean, M2) pairs of x as ``scale_res_fwd(..., want_part=True)`` returns them; the statistics
+    pass is skipped.  -> (y, stat); stat [2C] = (mu, r) is what bn2d_bwd needs beside x (None unless ``need_stat``)."""
+    _gpu(x, weight, bias, running_mean, running_var, part_in)
+    lib = L.lib()
+    s, ws_bytes = _bn_args("bn2d", x, (weight, bias, running_mean, running_var), lib.mi_bn2d_workspace, training, eps, momentum)
+    if part_in is not None and (part_in.dtype != torch.float32 or part_in.numel() * 4 != bn2d_plan(*x.shape, x.dtype, training)["pair_bytes"]):
+        raise ValueError("bn2d: part_in must hold the plan's fp32 (mean, M2) pairs")
+    y = torch.empty_like(x)
+    stat = torch.empty(2 * x.shape[1], dtype=torch.float32, device=x.device) if need_stat else None
+    ws = _ws(ws_bytes, x.device)
+    L.check(lib.mi_bn2d_fwd(C.byref(s), _p(weight), _p(bias), _p(x), _p(y), _p(running_mean), _p(running_var), _p(stat), _p(part_in),
+                            _p(ws), _stream()), "bn2d_fwd")
+    return y, stat
+
+
+def bn2d_bwd(x: Tensor, dy: Tensor, weight: Tensor, stat: Tensor, grads: Sequence[Tensor], accumulate: bool, training: bool,
+             eps: float = 1e-5, momentum: float = 0.1, dres: Optional[Tensor] = None) -> Tensor:
+    """Backward of bn2d_fwd: dx (``dres`` given: dx + dres, added in fp32 and rounded once); dw and db are written (accumulate: added)
+    into ``grads``."""
+    dw, db = grads
+    _gpu(x, dy, weight, stat, dw, db, dres)
+    _same("bn2d", x, dy, dres)
+    lib = L.lib()
+    s, ws_bytes = _bn_args("bn2d", x, (weight, dw, db), lib.mi_bn2d_workspace, training, eps, momentum)
+    if _f32(stat, "bn2d stat").numel() != 2 * x.shape[1]:
+        raise ValueError("bn2d: stat must hold 2C values")
+    dx = torch.empty_like(x)
+    ws = _ws(ws_bytes, x.device)
+    L.check(lib.mi_bn2d_bwd(C.byref(s), _p(weight), _p(x), _p(dy), _p(dres), _p(dx), _p(dw), _p(db), int(accumulate), _p(stat), _p(ws),
+                            _stream()), "bn2d_bwd")
+    return dx
+
+
+def scale_res_fwd(f: Tensor, x: Tensor, scale: Tensor, want_part: bool = False):
+    """out = f scale[c] + x (``scale``: C fp32 values).  ``want_part``: -> (out, part), part the BatchNorm (mean, M2) pairs of out as
+    stored, for ``bn2d_fwd(..., part_in=part)``; else -> out."""
+    _gpu(f, x, scale)
+    _same("scale_res", f, x)
+    lib = L.lib()
+    s, _ = _bn_args("scale_res", f, (scale,), lib.mi_scale_res_workspace, True, 1e-5, 0.1)
+    out = torch.empty_like(f)
+    part = torch.empty(bn2d_plan(*f.shape, f.dtype, False)["pair_bytes"] // 4, dtype=torch.float32, device=f.device) if want_part else None
+    L.check(lib.mi_scale_res_fwd(C.byref(s), _p(scale), _p(f), _p(x), _p(out), _p(part), _stream()), "scale_res_fwd")
+    return (out, part) if want_part else out
+
+
+def scale_res_bwd(f: Tensor, dout: Tensor, scale: Tensor, dscale: Tensor, accumulate: bool) -> Tensor:
+    """Backward of scale_res_fwd: df = dout scale[c]; sum f dout is written (accumulate: added) into ``dscale``.  The gradient towards
+    x is ``dout`` itself."""
+    _gpu(f, dout, scale, dscale)
+    _same("scale_res", f, dout)
+    lib = L.lib()
+    s, ws_bytes = _bn_args("scale_res", f, (scale, dscale), lib.mi_scale_res_workspace, True, 1e-5, 0.1)
+    df = torch.empty_like(f)
+    ws = _ws(ws_bytes, f.device)
+    L.check(lib.mi_scale_res_bwd(C.byref(s), _p(scale), _p(f), _p(dout), _p(df), _p(dscale), int(accumulate), _p(ws), _stream()),
+            "scale_res_bwd")
+    return df
+
+
 # ----------------------------------------------------------------------------- DarkIR: EBlock and its tail
 EBLOCK_MAX_C, EBLOCK_MIN_HW, EBLOCK_MAX_HW = 256, 2, FREMLP_MAX_HW
 _EBLOCK_PLAN_KEYS = ("x0_bytes", "xe_bytes", "x1_bytes", "g_bytes", "y_bytes", "f_bytes", "stats_bytes", "small_bytes",

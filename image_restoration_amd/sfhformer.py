@@ -1,5 +1,6 @@
-"""SFHformer on the MI355X, the pieces built so far: the spectral token mixer core ``FourierUnit``, the feed-forward ``FFN`` and the
-local token mixer ``TokenMixer_For_Local`` (below).
+"""SFHformer on the MI355X, the pieces built so far: the spectral token mixer core ``FourierUnit``, the feed-forward ``FFN``, the
+local token mixer ``TokenMixer_For_Local``, the global one and the ``Mixer``, and the Block's ``BatchNorm2d`` and ``scaled_residual``
+(below).
 
 ``FourierUnit`` (``SFHformer.py:143-180``) with the reference's constructor
 arguments and ``state_dict`` keys (``bn.*``, ``fdc.*``, ``weight.0.*``, ``fpe.*``), so a checkpoint slice loads with
@@ -26,8 +27,17 @@ activations; BatchNorm with running statistics and a fixed momentum.  CPU tensor
 library's own entry points, and between them the file's streaming kernels (GELU, the residual add, the GELU / pool tail that writes
 the concatenated tensor once, the channel attention folded into a per-image ``ca_conv`` weight).  ``FFC.bn`` behaves as in
 ``FourierUnit.forward``.  ``Mixer`` takes the reference's default token mixers only.  Limits: ``Mixer`` even 2 <= dim <= 128,
-``TokenMixer_For_Gloal`` 1 <= dim <= 128 (the FourierUnit inside has 2 dim channels), planes of 2..512 pixels a side.  ``Block`` and
-``Backbone`` stay the reference's PyTorch modules around these.
+``TokenMixer_For_Gloal`` 1 <= dim <= 128 (the FourierUnit inside has 2 dim channels), planes of 2..512 pixels a side.
+
+``BatchNorm2d(num_features)`` is ``torch.nn.BatchNorm2d`` (constructor, parameters, buffers and ``state_dict`` keys) whose ``forward``
+is ONE autograd node over ``mi_bn2d_*`` (``csrc/bn2d.hip``): training mode normalises with the batch statistics and updates the
+running ones on the device, eval mode normalises with the running ones in a single launch.  ``scaled_residual(f, x, scale)`` is the
+Block's ``f * scale + x`` with ``scale`` of shape ``(1, C, 1, 1)`` or ``(C,)``, ONE autograd node over ``mi_scale_res_*``; the gradient
+towards ``x`` is the cotangent itself.  Limits: 1 <= C <= 4096, any plane, fp32 or bf16 activations; BatchNorm affine, with running
+statistics and a fixed momentum; training needs more than one value per channel.
+
+``Block`` and ``Backbone`` stay the reference's PyTorch modules, but their norm and their residual are now available natively: the
+reference's ``Block(dim, norm_layer=BatchNorm2d)`` takes the class as it is.
 """
 from __future__ import annotations
 
@@ -39,7 +49,7 @@ from ._autograd import module_op
 
 Tensor = torch.Tensor
 
-__all__ = ["FFN", "FourierUnit", "Mixer", "TokenMixer_For_Gloal", "TokenMixer_For_Local"]
+__all__ = ["BatchNorm2d", "FFN", "FourierUnit", "Mixer", "TokenMixer_For_Gloal", "TokenMixer_For_Local", "scaled_residual"]
 
 
 class _FourierUnitOp:
@@ -226,3 +236,63 @@ class Mixer(nn.Module):
 
     def forward(self, x):
         return _run_mixer(self, ops.sfh_mixer_fwd, ops.sfh_mixer_bwd, self.mixer_gloal.FFC.bn, x)
+
+
+_BN_FORM = ("image_restoration_amd: BatchNorm2d runs affine, with running statistics and a fixed momentum (the form the kernels "
+            "were built for)")
+
+
+class _Bn2dOp:
+    """BatchNorm2d.forward as one module op.  params: weight, bias; saved = [stat = (mu, r)] beside the input."""
+
+    def __init__(self, bn: nn.BatchNorm2d, training: bool):
+        self.rm, self.rv, self.training, self.eps, self.momentum = bn.running_mean, bn.running_var, training, bn.eps, bn.momentum
+
+    def forward(self, acts, params, need):
+        y, stat = ops.bn2d_fwd(acts[0], params[0], params[1], self.rm, self.rv, self.training, need, self.eps, self.momentum)
+        return y, [stat]
+
+    def backward(self, acts, saved, dout, params, grads, acc):
+        return (ops.bn2d_bwd(acts[0], dout, params[0], saved[0], grads, acc, self.training, self.eps, self.momentum),)
+
+
+class BatchNorm2d(nn.BatchNorm2d):
+    """``torch.nn.BatchNorm2d`` on the library's kernels: y = (x - mu) / sqrt(var + eps) * weight + bias per channel."""
+
+    def __init__(self, num_features, eps=1e-5, momentum=0.1, affine=True, track_running_stats=True, device=None, dtype=None):
+        if not (affine and track_running_stats and momentum is not None):
+            raise NotImplementedError(_BN_FORM)
+        if not (isinstance(num_features, int) and 1 <= num_features <= ops.BN2D_MAX_C):
+            raise NotImplementedError(f"image_restoration_amd: BatchNorm2d(num_features={num_features!r}) not covered; the kernels were "
+                                      f"built for 1 <= num_features <= {ops.BN2D_MAX_C}")
+        super().__init__(num_features, eps, momentum, affine, track_running_stats, device=device, dtype=dtype)
+
+    def forward(self, x):
+        if not (self.track_running_stats and self.affine and self.momentum is not None and self.running_mean is not None):
+            raise NotImplementedError(_BN_FORM)
+        self._check_input_dim(x)
+        ops._gpu(x)
+        training = bool(self.training)
+        out = module_op(_Bn2dOp(self, training), (x,), (self.weight, self.bias))
+        if training:
+            with torch.no_grad():
+                self.num_batches_tracked += 1
+        return out
+
+
+class _ScaledResidualOp:
+    """f * scale + x as one module op over acts (f, x) and params (scale,); nothing is saved beyond f."""
+
+    def forward(self, acts, params, need):
+        return ops.scale_res_fwd(acts[0], acts[1], params[0]), []
+
+    def backward(self, acts, saved, dout, params, grads, acc):
+        return ops.scale_res_bwd(acts[0], dout, params[0], grads[0], acc), dout
+
+
+def scaled_residual(f: Tensor, x: Tensor, scale: Tensor) -> Tensor:
+    """``f * scale + x`` (SFHformer.py:275, :280) with a per-channel ``scale`` of shape ``(1, C, 1, 1)`` or ``(C,)``."""
+    ops._gpu(f, x, scale)
+    if f.dim() != 4 or tuple(scale.shape) not in ((1, f.shape[1], 1, 1), (f.shape[1],)):
+        raise ValueError(f"scaled_residual: scale of shape {tuple(scale.shape)} does not fit f {tuple(f.shape)}")
+    return module_op(_ScaledResidualOp(), (f, x), (scale,))

@@ -1123,6 +1123,58 @@ int mi_sfh_mixer_bwd(const mi_sfh_mixer_shape* s, const mi_sfh_mixer_params* p, 
                      const mi_sfh_mixer_grads* g, const void* saved, void* ws, void* stream);
 
 /* ------------------------------------------------------------------------
+ * SFHformer — the Block's BatchNorm2d and scaled residual (SFHformer.py:254-282; csrc/bn2d.hip).  x, y, f, out and the cotangents
+ * [B,C,H,W] in `dtype`, N = H W, n = B N; w, b, scale, running_mean, running_var, stat and every parameter gradient fp32; fp32
+ * arithmetic between load and store, one rounding to `dtype` at the store.
+ *   BatchNorm2d, training:  mu[c] = mean of x over the n values of channel c, var[c] = their biased variance,
+ *        r[c] = 1 / sqrt(var[c] + eps),  y = (x - mu[c]) (w[c] r[c]) + b[c], and in the same launch sequence, in place, on the device
+ *        running_mean <- (1 - momentum) running_mean + momentum mu,
+ *        running_var  <- (1 - momentum) running_var  + momentum var n / (n - 1)       (num_batches_tracked is the caller's).
+ *        A plane is cut into chunks of 4096 elements; one workgroup holds one chunk in registers and writes its (mean, sum of
+ *        squared deviations from that mean), so x is read once and two large sums are never differenced; one thread per channel
+ *        merges the channel's B nchunk pairs, image by image and chunk by chunk (Chan's update).  The pairs are laid out
+ *        [B][C][nchunk][2].
+ *   BatchNorm2d, eval:  mu = running_mean, r = 1 / sqrt(running_var + eps); nothing is updated; ONE launch.
+ *   stat [2C] = (mu[C], r[C]) is what the backward needs beside x; stat == NULL in _fwd (inference, no_grad): it lives in the
+ *        workspace (training mode still updates the running statistics).
+ *   part_in != NULL (training): the pairs are taken from there, in the layout above, and the statistics pass is skipped; what
+ *        mi_scale_res_fwd(..., part_out) writes for the same shape are those pairs, bit for bit.  Ignored in eval mode.
+ *   backward:  xhat = (x - mu) r;  db (+)= sum dy;  dw (+)= sum dy xhat  (`accumulate` adds, else overwrites; per-chunk partial
+ *        rows summed in the order above);  training: dx = w r ((dy - sum dy / n) - xhat (sum dy xhat) / n);  eval: dx = w r dy.
+ *        dres != NULL: dx + dres is written instead, added in fp32 and rounded once.  `stat` is the forward's.
+ *   scaled residual:  out = f scale[c] + x.   part_out != NULL: also the BatchNorm pairs of out AS STORED (after the rounding to
+ *        `dtype`), part_out [B][C][nchunk][2] floats (bytes: plan [62]).
+ *        backward, one pass over f and dout:  df = dout scale[c];  dscale[c] (+)= sum f dout.  The gradient towards x is dout
+ *        itself: nothing is written for it.  The shape's training, eps and momentum are not read.
+ * Limits: 1 <= C <= 4096; B, H, W >= 1; B C H W below 2^31; fp32 or bf16; BatchNorm: eps > 0, 0 <= momentum <= 1, and training with
+ * n = 1 is refused (no variance).  Anything else is refused before any launch (the message: mi_last_error); the sizing calls
+ * return 0.  16-byte accesses where N is a multiple of 16 / sizeof(dtype) and the pointers are 16-byte aligned, element by element
+ * otherwise, over the same assignment of elements to threads: the results do not depend on which form ran.  Bitwise reproducible
+ * (no atomics, every sum in a fixed order).  No allocation, no host synchronisation.
+ * The plan calls (host-only; the launchers and the sizing calls read the same plan) fill out[64]: B, C, N, dtype, training, threads
+ * per workgroup, chunk size, chunks per plane, partials per channel (B nchunk), elements per access the shape allows (4 / 8, or 1),
+ * chunks of work B C nchunk, grid of the per-chunk launches (capped at 2^20, the rest by a grid stride), grid of the per-channel
+ * finish launches, launches forward / forward with part_in / backward [13..15]; then (byte offset, bytes) of the workspace
+ * sections [16..21]: the partial rows (BatchNorm: pairs, forward and backward; scaled residual: the sums of f dout), stat (used
+ * when none is given), the backward's two means (scaled residual: 0, 0); the workspace size [60], the bytes of stat [61], the
+ * bytes of the pairs part_in / part_out hold [62]; 0.
+ * ------------------------------------------------------------------------ */
+typedef struct { int B, C, H, W, dtype, training; float eps, momentum; } mi_bn2d_shape;
+typedef mi_bn2d_shape mi_scale_res_shape;
+size_t mi_bn2d_workspace(const mi_bn2d_shape* s);
+int mi_bn2d_plan(const mi_bn2d_shape* s, int64_t* out);
+int mi_bn2d_fwd(const mi_bn2d_shape* s, const float* w, const float* b, const void* x, void* y, float* running_mean,
+                float* running_var, float* stat, const float* part_in, void* ws, void* stream);
+int mi_bn2d_bwd(const mi_bn2d_shape* s, const float* w, const void* x, const void* dy, const void* dres, void* dx, float* dw,
+                float* db, int accumulate, const float* stat, void* ws, void* stream);
+size_t mi_scale_res_workspace(const mi_scale_res_shape* s);
+int mi_scale_res_plan(const mi_scale_res_shape* s, int64_t* out);
+int mi_scale_res_fwd(const mi_scale_res_shape* s, const float* scale, const void* f, const void* x, void* out, float* part_out,
+                     void* stream);
+int mi_scale_res_bwd(const mi_scale_res_shape* s, const float* scale, const void* f, const void* dout, void* df, float* dscale,
+                     int accumulate, void* ws, void* stream);
+
+/* ------------------------------------------------------------------------
  * DarkIR — the encoder block (DarkIR-main/archs/arch_model.py:141-204 EBlock) and its tail (csrc/darkir.hip).
  *
  * fregate: the block's last line, y + gamma (y f), as one streaming pass.  y, f, out [B,C,N] in `dtype`, gamma [C] fp32, fp32
