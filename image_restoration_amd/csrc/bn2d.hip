@@ -319,7 +319,8 @@ struct BnPlan {
   int nchunk, parts, width;                      // chunks per plane; partials per channel (B nchunk); elements per access the shape allows
   int total, grid, grid_chan;                    // B C nchunk workgroups of work; the per-chunk launches' grid; the finish kernels' grid
   int fwd, fwd_part_in, bwd;                     // launches
-  size_t off[BS_SECTIONS], bytes[BS_SECTIONS], ws, stat_bytes;
+  Sections<BS_SECTIONS> ws;
+  size_t stat_bytes;
 };
 
 // bn: BatchNorm's own checks (eps, momentum, the count) and sections; else the scaled residual's (the three fields are not read)
@@ -346,30 +347,26 @@ int bn_check(const char* who, const mi_bn2d_shape* s, bool bn, BnPlan* p) {
   p->total = B * Cn * p->nchunk;
   p->grid = p->total < BN_MAX_GRID ? p->total : BN_MAX_GRID;
   p->grid_chan = cdiv(Cn, BN_THREADS);
-  Carver cv(nullptr);
-  auto sec = [&](int i, size_t n) { p->off[i] = cv.off; p->bytes[i] = n; cv.take(n); };
+  Sections<BS_SECTIONS>& ws = p->ws;
   if (bn) {
     p->fwd = p->training ? 3 : 1; p->fwd_part_in = p->training ? 2 : 1; p->bwd = 3;
-    sec(BS_PART, (size_t)p->total * 2 * sizeof(float));      // forward: (mean, M2); backward: (sum dy, sum dy xhat)
-    sec(BS_STAT, (size_t)2 * Cn * sizeof(float));            // (mu, r) of a forward that is given no stat
-    sec(BS_COEF, (size_t)2 * Cn * sizeof(float));            // backward: (mean dy, mean dy xhat)
+    ws.put(BS_PART, (size_t)p->total * 2 * sizeof(float));      // forward: (mean, M2); backward: (sum dy, sum dy xhat)
+    ws.put(BS_STAT, (size_t)2 * Cn * sizeof(float));            // (mu, r) of a forward that is given no stat
+    ws.put(BS_COEF, (size_t)2 * Cn * sizeof(float));            // backward: (mean dy, mean dy xhat)
   } else {
     p->fwd = 1; p->fwd_part_in = 1; p->bwd = 2;
-    sec(BS_PART, (size_t)p->total * sizeof(float));          // backward: the chunks' sums of f dout
-    sec(BS_STAT, 0); sec(BS_COEF, 0);
+    ws.put(BS_PART, (size_t)p->total * sizeof(float));          // backward: the chunks' sums of f dout
+    ws.put(BS_STAT, 0); ws.put(BS_COEF, 0);
   }
-  p->ws = cv.off;
   p->stat_bytes = (size_t)2 * Cn * sizeof(float);
   return MI_OK;
 }
 
+// 16 scalars, the BS_* sections from [16]; tail: workspace, stat and forward-partial bytes (the format: plan_report, internal.h)
 int bn_plan_out(const BnPlan& p, int64_t* out) {
-  int64_t v[64] = {p.B, p.C, p.N, p.dtype, p.training, BN_THREADS, BN_CHUNK, p.nchunk, p.parts, p.width, p.total, p.grid, p.grid_chan,
-                   p.fwd, p.fwd_part_in, p.bwd};
-  for (int i = 0; i < BS_SECTIONS; ++i) { v[16 + 2 * i] = (int64_t)p.off[i]; v[17 + 2 * i] = (int64_t)p.bytes[i]; }
-  v[60] = (int64_t)p.ws; v[61] = (int64_t)p.stat_bytes; v[62] = (int64_t)p.total * 2 * (int64_t)sizeof(float);
-  memcpy(out, v, sizeof(v));
-  return MI_OK;
+  return plan_report<16>(out, {p.B, p.C, p.N, p.dtype, p.training, BN_THREADS, BN_CHUNK, p.nchunk, p.parts, p.width, p.total, p.grid,
+                               p.grid_chan, p.fwd, p.fwd_part_in, p.bwd},
+                         p.ws, {(int64_t)p.ws.total, (int64_t)p.stat_bytes, (int64_t)p.total * 2 * (int64_t)sizeof(float)});
 }
 
 int bn_vec(const BnPlan& p, std::initializer_list<const void*> ptrs) {
@@ -387,7 +384,7 @@ using namespace mi;
 // ---------------------------------------------------------------------------------------------------------------- BatchNorm2d
 extern "C" size_t mi_bn2d_workspace(const mi_bn2d_shape* s) {
   BnPlan p;
-  return bn_check("bn2d_workspace", s, true, &p) == MI_OK ? p.ws : 0;
+  return bn_check("bn2d_workspace", s, true, &p) == MI_OK ? p.ws.total : 0;
 }
 extern "C" int mi_bn2d_plan(const mi_bn2d_shape* s, int64_t* out) {
   MI_CHECK_ARG(out, "bn2d_plan: null pointer");
@@ -402,10 +399,9 @@ extern "C" int mi_bn2d_fwd(const mi_bn2d_shape* s, const float* w, const float* 
   MI_TRY(bn_check("bn2d_fwd", s, true, &p));
   MI_CHECK_ARG(w && b && x && y && running_mean && running_var && ws, "bn2d_fwd: null pointer");
   hipStream_t st = (hipStream_t)stream;
-  char* wsp = (char*)ws;
   const int vec = bn_vec(p, {x, y});
-  float* part = (float*)(wsp + p.off[BS_PART]);
-  float* stat_use = stat ? stat : (float*)(wsp + p.off[BS_STAT]);
+  float* part = p.ws.at(ws, BS_PART);
+  float* stat_use = stat ? stat : p.ws.at(ws, BS_STAT);
   return with_dtype(p.dtype, "bn2d_fwd", [&](auto tag) -> int {
     using T = decltype(tag);
     if (p.training) {
@@ -432,10 +428,9 @@ extern "C" int mi_bn2d_bwd(const mi_bn2d_shape* s, const float* w, const void* x
   MI_CHECK_ARG(w && x && dy && dx && stat && ws, "bn2d_bwd: null pointer");
   MI_CHECK_ARG(dw && db, "bn2d_bwd: null gradient buffer");
   hipStream_t st = (hipStream_t)stream;
-  char* wsp = (char*)ws;
   const int vec = bn_vec(p, {x, dy, dres, dx});
-  float* part = (float*)(wsp + p.off[BS_PART]);
-  float* coef = (float*)(wsp + p.off[BS_COEF]);
+  float* part = p.ws.at(ws, BS_PART);
+  float* coef = p.ws.at(ws, BS_COEF);
   const float inv_n = 1.0f / (float)((int64_t)p.B * p.N);
   return with_dtype(p.dtype, "bn2d_bwd", [&](auto tag) -> int {
     using T = decltype(tag);
@@ -459,7 +454,7 @@ extern "C" int mi_bn2d_bwd(const mi_bn2d_shape* s, const float* w, const void* x
 // ---------------------------------------------------------------------------------------------------------------- scaled residual
 extern "C" size_t mi_scale_res_workspace(const mi_scale_res_shape* s) {
   BnPlan p;
-  return bn_check("scale_res_workspace", s, false, &p) == MI_OK ? p.ws : 0;
+  return bn_check("scale_res_workspace", s, false, &p) == MI_OK ? p.ws.total : 0;
 }
 extern "C" int mi_scale_res_plan(const mi_scale_res_shape* s, int64_t* out) {
   MI_CHECK_ARG(out, "scale_res_plan: null pointer");
@@ -493,7 +488,7 @@ extern "C" int mi_scale_res_bwd(const mi_scale_res_shape* s, const float* scale,
   MI_CHECK_ARG(scale && f && dout && df && ws, "scale_res_bwd: null pointer");
   MI_CHECK_ARG(dscale, "scale_res_bwd: null gradient buffer");
   hipStream_t st = (hipStream_t)stream;
-  float* part = (float*)((char*)ws + p.off[BS_PART]);
+  float* part = p.ws.at(ws, BS_PART);
   const int vec = bn_vec(p, {f, dout, df});
   return with_dtype(p.dtype, "scale_res_bwd", [&](auto tag) -> int {
     using T = decltype(tag);

@@ -36,8 +36,8 @@ struct FrePlan {
   int grid_bins, grid_hidden;                           // elementwise passes over P*H*K bins / over B*hc*H*K hidden values
   int kernels_fwd, kernels_bwd, lib_calls_fwd, lib_calls_bwd;   // own launches; mi_pw_gemm / mi_gram / channel-sum calls
   int64_t bins, hidden;
-  size_t off[FRE_SECTIONS], bytes[FRE_SECTIONS], total;
-  size_t saved_a_off, saved_bytes;                      // the blob: Z (re | im) at 0, a at saved_a_off
+  Sections<FRE_SECTIONS> ws;
+  Sections<2> saved;                                    // the blob: Z (re | im), then a
 };
 
 bool fre_plan(int B, int nc, int expand, int H, int W, FrePlan* p) {
@@ -55,19 +55,16 @@ bool fre_plan(int B, int nc, int expand, int H, int W, FrePlan* p) {
   // channel sum and W^T dY
   p->kernels_fwd = 8; p->kernels_bwd = 9; p->lib_calls_fwd = 2; p->lib_calls_bwd = 7;
   const size_t cplx = (size_t)bins * 2 * 4, real = (size_t)bins * 4;
-  size_t* sz = p->bytes;
-  for (int i = 0; i < DFT2_TABLES; ++i) { p->off[i] = p->dft.tab[i]; sz[i] = dft2_table_bytes(p->g, i); }
-  p->off[FS_T] = p->dft.t; sz[FS_T] = cplx;
-  sz[FS_U] = cplx; sz[FS_Z] = cplx; sz[FS_A] = (size_t)hidden * 4; sz[FS_M1] = real; sz[FS_M2] = real;
-  sz[FS_PW] = max_of({pw_ws_bytes(probe1x1(nc, hc, false, B, N, MI_F32)), pw_ws_bytes(probe1x1(hc, nc, false, B, N, MI_F32)),
-                      pw_ws_bytes(probe1x1(nc, hc, true, B, N, MI_F32)), pw_ws_bytes(probe1x1(hc, nc, true, B, N, MI_F32))});
-  sz[FS_GRAM] = max_of({gram_ws_bytes(probe_wgrad(nc, hc, B, N, MI_F32)), gram_ws_bytes(probe_wgrad(hc, nc, B, N, MI_F32))});
-  sz[FS_CS] = max_of({chan_sum_workspace(hc, N), chan_sum_workspace(nc, N)});
-  size_t o = p->dft.total;   // the sections after the transforms' blob
-  for (int i = FS_U; i < FRE_SECTIONS; ++i) { p->off[i] = o; o = align_up(o + sz[i], 256); }
-  p->total = o;
-  p->saved_a_off = align_up(cplx, 256);
-  p->saved_bytes = p->saved_a_off + align_up((size_t)hidden * 4, 256);
+  Sections<FRE_SECTIONS>& ws = p->ws;
+  for (int i = 0; i < DFT2_TABLES; ++i) ws.place(i, p->dft.tab[i], dft2_table_bytes(p->g, i));
+  ws.place(FS_T, p->dft.t, cplx);
+  ws.total = p->dft.total;   // FreMLP's own sections follow the transforms' blob
+  ws.put(FS_U, cplx); ws.put(FS_Z, cplx); ws.put(FS_A, (size_t)hidden * 4); ws.put(FS_M1, real); ws.put(FS_M2, real);
+  ws.put(FS_PW, max_of({pw_ws_bytes(probe1x1(nc, hc, false, B, N, MI_F32)), pw_ws_bytes(probe1x1(hc, nc, false, B, N, MI_F32)),
+                        pw_ws_bytes(probe1x1(nc, hc, true, B, N, MI_F32)), pw_ws_bytes(probe1x1(hc, nc, true, B, N, MI_F32))}));
+  ws.put(FS_GRAM, max_of({gram_ws_bytes(probe_wgrad(nc, hc, B, N, MI_F32)), gram_ws_bytes(probe_wgrad(hc, nc, B, N, MI_F32))}));
+  ws.put(FS_CS, max_of({chan_sum_workspace(hc, N), chan_sum_workspace(nc, N)}));
+  p->saved.put(0, cplx); p->saved.put(1, (size_t)hidden * 4);
   return true;
 }
 
@@ -142,11 +139,6 @@ __global__ __launch_bounds__(FL_THREADS) void fre_bwd_dz_kernel(const float* __r
   dre[i] = or_; dim[i] = oi;
 }
 
-struct FreWs {
-  const FrePlan& p; char* base;
-  float* sec(int i) const { return (float*)(base + p.off[i]); }
-};
-
 int fre_check(const char* who, const mi_fremlp_shape* s, FrePlan* p) {
   MI_CHECK_ARG(s, "%s: null shape", who);
   MI_CHECK_ARG(s->dtype == MI_F32 || s->dtype == MI_BF16, "%s: bad dtype %d", who, s->dtype);
@@ -168,32 +160,28 @@ using namespace mi;
 
 extern "C" size_t mi_fremlp_workspace(const mi_fremlp_shape* s) {
   FrePlan p;
-  return fre_check("fremlp_workspace", s, &p) == MI_OK ? p.total : 0;
+  return fre_check("fremlp_workspace", s, &p) == MI_OK ? p.ws.total : 0;
 }
 
 extern "C" size_t mi_fremlp_saved_bytes(const mi_fremlp_shape* s) {
   FrePlan p;
-  return fre_check("fremlp_saved_bytes", s, &p) == MI_OK ? p.saved_bytes : 0;
+  return fre_check("fremlp_saved_bytes", s, &p) == MI_OK ? p.saved.total : 0;
 }
 
-// out[64]: planes P, K = W/2 + 1, hidden width, tile rows (64), contraction depth per LDS stage (16), l block width, l blocks,
-// x block width, x blocks, 64-row tiles over P*H, 64-row tiles over H, grid of the table fill, of the [P*H] x K stages, of the
-// per-plane stages, of the [P*H] x W stages, of the per-bin passes, of the hidden passes, threads per workgroup, own kernel
-// launches forward / backward, library calls (1x1 product, Gram, channel sum) forward / backward [22]; then (byte offset, bytes)
-// of the 19 workspace sections, the ten DT_* tables and then the FS_* list [22..59]; the workspace size [60], the saved blob's size [61], the
-// offset of `a` in it [62] (Z sits at 0), 0 [63].
+// The 22 scalars: planes P, K = W/2 + 1, hidden width, tile rows (64), contraction depth per LDS stage (16), l block width, l
+// blocks, x block width, x blocks, 64-row tiles over P*H, 64-row tiles over H, grid of the table fill, of the [P*H] x K stages, of
+// the per-plane stages, of the [P*H] x W stages, of the per-bin passes, of the hidden passes, threads per workgroup, own kernel
+// launches forward / backward, library calls (1x1 product, Gram, channel sum) forward / backward.  The 19 sections (the ten DT_*
+// tables, then the FS_* list) from [22]; [62]: the offset of `a` in the saved blob.  The format: plan_report, internal.h.
 extern "C" int mi_fremlp_plan(const mi_fremlp_shape* s, int64_t* out) {
   MI_CHECK_ARG(out, "fremlp_plan: null pointer");
   FrePlan p;
   MI_TRY(fre_check("fremlp_plan", s, &p));
   const Dft2Geom& g = p.g;
-  int64_t v[64] = {g.P, g.K, p.hc, FL_TM, FL_KC, 16 * g.nf_l, g.l_blocks, 16 * g.nf_x, g.x_blocks, g.m_tiles_fold, g.m_tiles_plane,
-                   g.grid_tab, g.grid_fold_l, g.grid_plane, g.grid_fold_x, p.grid_bins, p.grid_hidden, FL_THREADS, p.kernels_fwd,
-                   p.kernels_bwd, p.lib_calls_fwd, p.lib_calls_bwd};
-  for (int i = 0; i < FRE_SECTIONS; ++i) { v[22 + 2 * i] = (int64_t)p.off[i]; v[23 + 2 * i] = (int64_t)p.bytes[i]; }
-  v[60] = (int64_t)p.total; v[61] = (int64_t)p.saved_bytes; v[62] = (int64_t)p.saved_a_off;
-  memcpy(out, v, sizeof(v));
-  return MI_OK;
+  return plan_report<22>(out, {g.P, g.K, p.hc, FL_TM, FL_KC, 16 * g.nf_l, g.l_blocks, 16 * g.nf_x, g.x_blocks, g.m_tiles_fold,
+                               g.m_tiles_plane, g.grid_tab, g.grid_fold_l, g.grid_plane, g.grid_fold_x, p.grid_bins, p.grid_hidden,
+                               FL_THREADS, p.kernels_fwd, p.kernels_bwd, p.lib_calls_fwd, p.lib_calls_bwd},
+                         p.ws, {(int64_t)p.ws.total, (int64_t)p.saved.total, (int64_t)p.saved.off[1]});
 }
 
 extern "C" int mi_fremlp_fwd(const mi_fremlp_shape* s, const float* w1, const float* b1, const float* w2, const float* b2,
@@ -202,25 +190,25 @@ extern "C" int mi_fremlp_fwd(const mi_fremlp_shape* s, const float* w1, const fl
   MI_TRY(fre_check("fremlp_fwd", s, &p));
   MI_CHECK_ARG(w1 && b1 && w2 && b2 && x && out && ws, "fremlp_fwd: null pointer");
   hipStream_t st = (hipStream_t)stream;
-  const FreWs w = {p, (char*)ws};
+  const Sections<FRE_SECTIONS>& w = p.ws;
   const Dft2Ws dft = dft2_blob_ws(p.dft, ws);   // the tables and T
   const int n = (int)p.bins, nh = (int)p.hidden;
   const int64_t N = (int64_t)p.g.H * p.g.K;
-  float* ure = w.sec(FS_U); float* uim = ure + n;
-  float* zre = saved ? (float*)saved : w.sec(FS_Z); float* zim = zre + n;
-  float* a = saved ? (float*)((char*)saved + p.saved_a_off) : w.sec(FS_A);
-  float* mag = w.sec(FS_M1); float* mag2 = w.sec(FS_M2);
+  float* ure = w.at(ws, FS_U); float* uim = ure + n;
+  float* zre = saved ? (float*)saved : w.at(ws, FS_Z); float* zim = zre + n;
+  float* a = saved ? p.saved.at(saved, 1) : w.at(ws, FS_A);
+  float* mag = w.at(ws, FS_M1); float* mag2 = w.at(ws, FS_M2);
 
   MI_TRY(dft2_tables(p.g, dft, st));
   MI_TRY(dft2_r2c_run(p.g, dft, x, zre, zim, s->dtype, st));
   hipLaunchKernelGGL(fre_mag_kernel, dim3(p.grid_bins), dim3(FL_THREADS), 0, st, zre, zim, mag, n);
   MI_LAUNCH_CHECK();
   const mi_pw_desc d1 = conv1x1(mag, p.nc, w1, false, p.nc, b1, nullptr, a, p.hc, p.B, N, MI_F32);
-  MI_TRY(mi_pw_gemm(&d1, w.sec(FS_PW), stream));
+  MI_TRY(mi_pw_gemm(&d1, w.at(ws, FS_PW), stream));
   hipLaunchKernelGGL(fre_leaky_kernel<false>, dim3(p.grid_hidden), dim3(FL_THREADS), 0, st, a, (const float*)nullptr, nh);
   MI_LAUNCH_CHECK();
   const mi_pw_desc d2 = conv1x1(a, p.hc, w2, false, p.hc, b2, nullptr, mag2, p.nc, p.B, N, MI_F32);
-  MI_TRY(mi_pw_gemm(&d2, w.sec(FS_PW), stream));
+  MI_TRY(mi_pw_gemm(&d2, w.at(ws, FS_PW), stream));
   hipLaunchKernelGGL(fre_compose_kernel, dim3(p.grid_bins), dim3(FL_THREADS), 0, st, zre, zim, mag2, dft.tre, dft.tim, n);
   MI_LAUNCH_CHECK();
   Dft2Ws via = dft;   // Y sits in T, which r2c is done with, so c2r passes through U
@@ -235,30 +223,30 @@ extern "C" int mi_fremlp_bwd(const mi_fremlp_shape* s, const float* w1, const fl
   MI_TRY(fre_check("fremlp_bwd", s, &p));
   MI_CHECK_ARG(w1 && w2 && b2 && dout && dx && g_w1 && g_b1 && g_w2 && g_b2 && saved && ws, "fremlp_bwd: null pointer");
   hipStream_t st = (hipStream_t)stream;
-  const FreWs w = {p, (char*)ws};
+  const Sections<FRE_SECTIONS>& w = p.ws;
   const Dft2Ws dft = dft2_blob_ws(p.dft, ws);   // the tables and T
   const int n = (int)p.bins, nh = (int)p.hidden;
   const int64_t N = (int64_t)p.g.H * p.g.K;
-  float* ure = w.sec(FS_U); float* uim = ure + n;
+  float* ure = w.at(ws, FS_U); float* uim = ure + n;
   const float* zre = (const float*)saved; const float* zim = zre + n;
-  const float* a = (const float*)((const char*)saved + p.saved_a_off);
-  float* da = w.sec(FS_A); float* m1 = w.sec(FS_M1); float* m2 = w.sec(FS_M2);
+  const float* a = p.saved.at(saved, 1);
+  float* da = w.at(ws, FS_A); float* m1 = w.at(ws, FS_M1); float* m2 = w.at(ws, FS_M2);
 
   MI_TRY(dft2_tables(p.g, dft, st));
   MI_TRY(dft2_c2r_adj(p.g, dft, dout, ure, uim, s->dtype, st));                             // G (unscaled), through GV
   const mi_pw_desc d2 = conv1x1(a, p.hc, w2, false, p.hc, b2, nullptr, m2, p.nc, p.B, N, MI_F32);   // mag' again
-  MI_TRY(mi_pw_gemm(&d2, w.sec(FS_PW), stream));
+  MI_TRY(mi_pw_gemm(&d2, w.at(ws, FS_PW), stream));
   hipLaunchKernelGGL(fre_bwd_g_kernel, dim3(p.grid_bins), dim3(FL_THREADS), 0, st, zre, zim, (const float*)m2, ure, uim, m1,
                      (float)(1.0 / ((double)p.g.H * p.g.W)), n);                                 // m1 = dmag', U = du
   MI_LAUNCH_CHECK();
-  MI_TRY(conv1x1_bwd_input(m1, p.nc, a, p.hc, w2, g_w2, g_b2, da, p.B, N, MI_F32, accumulate, w.sec(FS_GRAM), w.sec(FS_CS),
-                           w.sec(FS_PW), st, false));
+  MI_TRY(conv1x1_bwd_input(m1, p.nc, a, p.hc, w2, g_w2, g_b2, da, p.B, N, MI_F32, accumulate, w.at(ws, FS_GRAM), w.at(ws, FS_CS),
+                           w.at(ws, FS_PW), st, false));
   hipLaunchKernelGGL(fre_leaky_kernel<true>, dim3(p.grid_hidden), dim3(FL_THREADS), 0, st, da, a, nh);
   MI_LAUNCH_CHECK();
   hipLaunchKernelGGL(fre_mag_kernel, dim3(p.grid_bins), dim3(FL_THREADS), 0, st, zre, zim, m2, n);   // m2 = mag
   MI_LAUNCH_CHECK();
-  MI_TRY(conv1x1_bwd_input(da, p.hc, m2, p.nc, w1, g_w1, g_b1, m1, p.B, N, MI_F32, accumulate, w.sec(FS_GRAM), w.sec(FS_CS),
-                           w.sec(FS_PW), st, false));                                        // m1 = dmag
+  MI_TRY(conv1x1_bwd_input(da, p.hc, m2, p.nc, w1, g_w1, g_b1, m1, p.B, N, MI_F32, accumulate, w.at(ws, FS_GRAM), w.at(ws, FS_CS),
+                           w.at(ws, FS_PW), st, false));                                        // m1 = dmag
   hipLaunchKernelGGL(fre_bwd_dz_kernel, dim3(p.grid_bins), dim3(FL_THREADS), 0, st, zre, zim, (const float*)m1, ure, uim, n);
   MI_LAUNCH_CHECK();
   return dft2_r2c_adj(p.g, dft, ure, uim, dx, s->dtype, st);

@@ -193,6 +193,44 @@ static inline size_t max_of(std::initializer_list<size_t> v) {
   for (size_t x : v) m = x > m ? x : m;
   return m;
 }
+// A module's workspace (or saved blob) as N sections, each on a 256-byte boundary: the plan fills it, the launchers take their
+// pointers from it, the plan report lists it.  It starts zeroed with the plan that holds it.
+template <int N> struct Sections {
+  size_t off[N], bytes[N], total;
+  void place(int i, size_t o, size_t n) { off[i] = o; bytes[i] = n; }   // where someone else decided (total does not move)
+  void put(int i, size_t n) { place(i, total, n); total = align_up(total + n, 256); }   // at the end: Carver::take's arithmetic
+  template <typename T = float> T* at(void* base, int i) const { return reinterpret_cast<T*>(static_cast<char*>(base) + off[i]); }
+  template <typename T = float> const T* at(const void* base, int i) const {
+    return reinterpret_cast<const T*>(static_cast<const char*>(base) + off[i]);
+  }
+};
+// The plan report of the section modules (mi_fremlp_plan, mi_fourier_unit_plan, mi_sfh_ffn_plan, mi_sfh_local_plan,
+// mi_sfh_global_plan, mi_sfh_mixer_plan, mi_bn2d_plan, mi_scale_res_plan), int64_t out[64]:
+//   [0, FIRST)               the module's scalars, in the order the comment at its mi_*_plan lists them; the rest 0
+//   [FIRST, FIRST + 2N)      (byte offset, bytes) of the N workspace sections, in the order of the module's section enum
+//   [FIRST2, FIRST2 + 2M)    the same for the saved blob's sections, where the module reports them (the two mixers)
+//   [60], [61], [62]         the tail: workspace bytes, the saved blob's bytes (bn2d: the stat's), one value of the module's; [63] 0
+// Slots between the sets are 0.  The sets cannot overlap one another or the tail: the counts are checked where it is compiled.
+template <int N> static inline void report_sections(int64_t* v, int first, const Sections<N>& s) {
+  for (int i = 0; i < N; ++i) { v[first + 2 * i] = (int64_t)s.off[i]; v[first + 2 * i + 1] = (int64_t)s.bytes[i]; }
+}
+template <int FIRST, int S, int N>
+static inline int plan_report(int64_t* out, const int64_t (&scalars)[S], const Sections<N>& ws, const int64_t (&tail)[3]) {
+  static_assert(S <= FIRST && FIRST + 2 * N <= 60, "plan report: the sections overlap the scalars or reach the tail");
+  memset(out, 0, 64 * sizeof(int64_t));
+  for (int i = 0; i < S; ++i) out[i] = scalars[i];
+  report_sections(out, FIRST, ws);
+  for (int i = 0; i < 3; ++i) out[60 + i] = tail[i];
+  return MI_OK;
+}
+template <int FIRST, int FIRST2, int S, int N, int M>
+static inline int plan_report(int64_t* out, const int64_t (&scalars)[S], const Sections<N>& ws, const Sections<M>& saved,
+                              const int64_t (&tail)[3]) {
+  static_assert(FIRST + 2 * N <= FIRST2 && FIRST2 + 2 * M <= 60, "plan report: the saved sections overlap the workspace's or reach the tail");
+  plan_report<FIRST>(out, scalars, ws, tail);
+  report_sections(out, FIRST2, saved);
+  return MI_OK;
+}
 // plain 1x1 conv: y[B,M,N] = W[M,K] x[B,K,N] (+bias) (+res);  transposed: W given as [K,M] used as its transpose.
 // x_bs / y_bs: batch strides in elements where x / y are channel slices of wider tensors (0: dense, K*N / M*N).
 static inline mi_pw_desc conv1x1(const void* x, int K, const float* w, bool transposed, int w_ld, const float* bias,

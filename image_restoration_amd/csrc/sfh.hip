@@ -56,8 +56,8 @@ struct SfhPlan {
   int64_t elems, bins;                // B C2 N; B N
   int nblk, grid_elems, grid_bins, grid_chan, grid_w, grid_scatter, grid_fin;
   int kernels_fwd, kernels_bwd, lib_calls_fwd, lib_calls_bwd;
-  size_t off[SFH_SECTIONS], bytes[SFH_SECTIONS], total;
-  size_t saved_stat_off, saved_bytes;
+  Sections<SFH_SECTIONS> ws;
+  Sections<2> saved;                  // the blob: Z, then (mu, r)
   ChanMap map;
 };
 
@@ -82,23 +82,19 @@ bool sfh_plan(int B, int c, int G, int H, int W, SfhPlan* p) {
   // scatter, the r2c adjoint (2); the 1x1 product again, W'^T dpre, three Grams and a channel sum
   p->kernels_fwd = 11; p->kernels_bwd = 14; p->lib_calls_fwd = 1; p->lib_calls_bwd = 6;
   const size_t spec = (size_t)elems * 4, gate = (size_t)p->bins * G * 4;
-  size_t sz[SFH_SECTIONS] = {};
-  sz[SS_DFT] = p->dft_blob.t; sz[SS_T] = spec;   // together the transforms' blob: its tables, then its complex intermediate
-  sz[SS_Z] = spec; sz[SS_U] = spec; sz[SS_A] = spec; sz[SS_B] = spec; sz[SS_P] = spec; sz[SS_Q] = spec;
-  sz[SS_S] = gate; sz[SS_DL] = gate;
-  sz[SS_STAT] = (size_t)4 * C2 * 4;
-  sz[SS_BNP] = (size_t)C2 * p->nparts * 2 * 4;
-  sz[SS_WP] = (size_t)C2 * C2 * 4;
-  sz[SS_GT] = ((size_t)C2 * C2 + (size_t)2 * G * C2) * 4;
-  sz[SS_RP] = (size_t)C2 * p->nparts * SFH_RED * 4;
-  sz[SS_PW] = max_of({pw_ws_bytes(probe1x1(C2, C2, false, B, N, MI_F32)), pw_ws_bytes(probe1x1(C2, C2, true, B, N, MI_F32))});
-  sz[SS_GRAM] = max_of({gram_ws_bytes(probe_wgrad(C2, C2, B, N, MI_F32)), gram_ws_bytes(probe_wgrad(G, C2, B, N, MI_F32))});
-  sz[SS_CS] = chan_sum_workspace(G, N);
-  size_t o = 0;
-  for (int i = 0; i < SFH_SECTIONS; ++i) { p->off[i] = o; p->bytes[i] = sz[i]; o = align_up(o + sz[i], 256); }
-  p->total = o;
-  p->saved_stat_off = align_up(spec, 256);
-  p->saved_bytes = p->saved_stat_off + align_up((size_t)2 * C2 * 4, 256);
+  Sections<SFH_SECTIONS>& ws = p->ws;
+  ws.put(SS_DFT, p->dft_blob.t); ws.put(SS_T, spec);   // together the transforms' blob: its tables, then its complex intermediate
+  ws.put(SS_Z, spec); ws.put(SS_U, spec); ws.put(SS_A, spec); ws.put(SS_B, spec); ws.put(SS_P, spec); ws.put(SS_Q, spec);
+  ws.put(SS_S, gate); ws.put(SS_DL, gate);
+  ws.put(SS_STAT, (size_t)4 * C2 * 4);
+  ws.put(SS_BNP, (size_t)C2 * p->nparts * 2 * 4);
+  ws.put(SS_WP, (size_t)C2 * C2 * 4);
+  ws.put(SS_GT, ((size_t)C2 * C2 + (size_t)2 * G * C2) * 4);
+  ws.put(SS_RP, (size_t)C2 * p->nparts * SFH_RED * 4);
+  ws.put(SS_PW, max_of({pw_ws_bytes(probe1x1(C2, C2, false, B, N, MI_F32)), pw_ws_bytes(probe1x1(C2, C2, true, B, N, MI_F32))}));
+  ws.put(SS_GRAM, max_of({gram_ws_bytes(probe_wgrad(C2, C2, B, N, MI_F32)), gram_ws_bytes(probe_wgrad(G, C2, B, N, MI_F32))}));
+  ws.put(SS_CS, chan_sum_workspace(G, N));
+  p->saved.put(0, spec); p->saved.put(1, (size_t)2 * C2 * 4);
   return true;
 }
 
@@ -459,11 +455,6 @@ template <int G, typename... A> void launch_gate_bwd(dim3 grid, hipStream_t st, 
     case 5: CALL(5); break; case 6: CALL(6); break; case 7: CALL(7); break; default: CALL(8); break;               \
   }
 
-struct SfhWs {
-  const SfhPlan& p; char* base;
-  float* sec(int i) const { return (float*)(base + p.off[i]); }
-};
-
 int sfh_check(const char* who, const mi_fourier_unit_shape* s, SfhPlan* p) {
   MI_CHECK_ARG(s, "%s: null shape", who);
   MI_CHECK_ARG(s->dtype == MI_F32 || s->dtype == MI_BF16, "%s: bad dtype %d", who, s->dtype);
@@ -480,21 +471,21 @@ int sfh_check(const char* who, const mi_fourier_unit_shape* s, SfhPlan* p) {
 }
 
 // Z, (mu, r) -> t (SS_A), s (SS_S), ts (SS_B), W' (SS_WP), W' ts (SS_P): the forward's middle, run again by the backward
-int sfh_middle(const SfhWs& w, const mi_fourier_unit_params* pr, const float* z, const float* stat, hipStream_t st) {
-  const SfhPlan& p = w.p;
+int sfh_middle(const SfhPlan& p, void* ws, const mi_fourier_unit_params* pr, const float* z, const float* stat, hipStream_t st) {
+  const Sections<SFH_SECTIONS>& w = p.ws;
   const int bins = (int)p.bins;
-  hipLaunchKernelGGL(sfh_fold_kernel, dim3(p.grid_w), dim3(SFH_THREADS), 0, st, pr->fdc_w, p.map, p.S, w.sec(SS_WP));
+  hipLaunchKernelGGL(sfh_fold_kernel, dim3(p.grid_w), dim3(SFH_THREADS), 0, st, pr->fdc_w, p.map, p.S, w.at(ws, SS_WP));
   MI_LAUNCH_CHECK();
   hipLaunchKernelGGL(bn_fpe_kernel, dim3(p.grid_elems), dim3(SFH_THREADS), 0, st, z, p.map, stat, pr->bn_w, pr->bn_b, pr->fpe_w,
-                     pr->fpe_b, w.sec(SS_A), p.H, p.K, p.nblk);
+                     pr->fpe_b, w.at(ws, SS_A), p.H, p.K, p.nblk);
   MI_LAUNCH_CHECK();
-#define SFH_GATE(GG) launch_gate<GG>(dim3(p.grid_bins), st, (const float*)w.sec(SS_A), p.map, p.S, pr->gate_w, pr->gate_b, \
-                                     w.sec(SS_S), w.sec(SS_B), p.N, bins)
+#define SFH_GATE(GG) launch_gate<GG>(dim3(p.grid_bins), st, (const float*)w.at(ws, SS_A), p.map, p.S, pr->gate_w, pr->gate_b, \
+                                     w.at(ws, SS_S), w.at(ws, SS_B), p.N, bins)
   SFH_FOR_G(p.G, SFH_GATE)
 #undef SFH_GATE
   MI_LAUNCH_CHECK();
-  const mi_pw_desc d = conv1x1(w.sec(SS_B), p.C2, w.sec(SS_WP), false, p.C2, nullptr, nullptr, w.sec(SS_P), p.C2, p.B, p.N, MI_F32);
-  return mi_pw_gemm(&d, w.sec(SS_PW), st);
+  const mi_pw_desc d = conv1x1(w.at(ws, SS_B), p.C2, w.at(ws, SS_WP), false, p.C2, nullptr, nullptr, w.at(ws, SS_P), p.C2, p.B, p.N, MI_F32);
+  return mi_pw_gemm(&d, w.at(ws, SS_PW), st);
 }
 
 }  // namespace
@@ -504,30 +495,26 @@ using namespace mi;
 
 extern "C" size_t mi_fourier_unit_workspace(const mi_fourier_unit_shape* s) {
   SfhPlan p;
-  return sfh_check("fourier_unit_workspace", s, &p) == MI_OK ? p.total : 0;
+  return sfh_check("fourier_unit_workspace", s, &p) == MI_OK ? p.ws.total : 0;
 }
 
 extern "C" size_t mi_fourier_unit_saved_bytes(const mi_fourier_unit_shape* s) {
   SfhPlan p;
-  return sfh_check("fourier_unit_saved_bytes", s, &p) == MI_OK ? p.saved_bytes : 0;
+  return sfh_check("fourier_unit_saved_bytes", s, &p) == MI_OK ? p.saved.total : 0;
 }
 
-// out[64]: planes B c, K, 2c, groups, channels per group, elements B 2c H K, bins B H K, threads per workgroup, bins per BatchNorm
-// chunk, chunks per plane, partials per channel, grid of the per-element passes (1024 bins of one plane per workgroup), of the gate
-// passes (64 bins per workgroup), own kernel launches
-// forward / backward, library calls (1x1 product, Gram, channel sum) forward / backward [17], 0; then (byte offset, bytes) of the 18
-// workspace sections in the order of the SS_* list [18..53]; the workspace size [60], the saved blob's size [61], the offset of
-// (mu, r) in it [62] (Z sits at 0), 0 [63].
+// The 17 scalars: planes B c, K, 2c, groups, channels per group, elements B 2c H K, bins B H K, threads per workgroup, bins per
+// BatchNorm chunk, chunks per plane, partials per channel, grid of the per-element passes (1024 bins of one plane per workgroup),
+// of the gate passes (64 bins per workgroup), own kernel launches forward / backward, library calls (1x1 product, Gram, channel
+// sum) forward / backward.  The 18 SS_* sections from [18]; [62]: the offset of (mu, r) in the saved blob.  The format:
+// plan_report, internal.h.
 extern "C" int mi_fourier_unit_plan(const mi_fourier_unit_shape* s, int64_t* out) {
   MI_CHECK_ARG(out, "fourier_unit_plan: null pointer");
   SfhPlan p;
   MI_TRY(sfh_check("fourier_unit_plan", s, &p));
-  int64_t v[64] = {(int64_t)p.B * p.c, p.K, p.C2, p.G, p.S, p.elems, p.bins, SFH_THREADS, SFH_CHUNK, p.nchunk, p.nparts,
-                   p.grid_elems, p.grid_bins, p.kernels_fwd, p.kernels_bwd, p.lib_calls_fwd, p.lib_calls_bwd};
-  for (int i = 0; i < SFH_SECTIONS; ++i) { v[18 + 2 * i] = (int64_t)p.off[i]; v[19 + 2 * i] = (int64_t)p.bytes[i]; }
-  v[60] = (int64_t)p.total; v[61] = (int64_t)p.saved_bytes; v[62] = (int64_t)p.saved_stat_off;
-  memcpy(out, v, sizeof(v));
-  return MI_OK;
+  return plan_report<18>(out, {(int64_t)p.B * p.c, p.K, p.C2, p.G, p.S, p.elems, p.bins, SFH_THREADS, SFH_CHUNK, p.nchunk, p.nparts,
+                               p.grid_elems, p.grid_bins, p.kernels_fwd, p.kernels_bwd, p.lib_calls_fwd, p.lib_calls_bwd},
+                         p.ws, {(int64_t)p.ws.total, (int64_t)p.saved.total, (int64_t)p.saved.off[1]});
 }
 
 extern "C" int mi_fourier_unit_fwd(const mi_fourier_unit_shape* s, const mi_fourier_unit_params* pr, const void* x, void* out,
@@ -537,26 +524,26 @@ extern "C" int mi_fourier_unit_fwd(const mi_fourier_unit_shape* s, const mi_four
   MI_CHECK_ARG(pr && pr->bn_w && pr->bn_b && pr->fdc_w && pr->fdc_b && pr->gate_w && pr->gate_b && pr->fpe_w && pr->fpe_b && x &&
                out && running_mean && running_var && ws, "fourier_unit_fwd: null pointer");
   hipStream_t st = (hipStream_t)stream;
-  const SfhWs w = {p, (char*)ws};
-  const Dft2Ws dft = dft2_blob_ws(p.dft_blob, w.sec(SS_DFT));
-  float* z = saved ? (float*)saved : w.sec(SS_Z);
-  float* stat = saved ? (float*)((char*)saved + p.saved_stat_off) : w.sec(SS_STAT);
-  float* o = w.sec(SS_U);
+  const Sections<SFH_SECTIONS>& w = p.ws;
+  const Dft2Ws dft = dft2_blob_ws(p.dft_blob, w.at(ws, SS_DFT));
+  float* z = saved ? (float*)saved : w.at(ws, SS_Z);
+  float* stat = saved ? p.saved.at(saved, 1) : w.at(ws, SS_STAT);
+  float* o = w.at(ws, SS_U);
   const int64_t half = (int64_t)p.B * p.c * p.N;
   const double hw = (double)p.H * p.W;
   MI_TRY(dft2_tables(p.dft, dft, st));
   MI_TRY(dft2_r2c_run(p.dft, dft, x, z, z + half, s->dtype, st));
   if (s->training) {
     hipLaunchKernelGGL(bn_partial_kernel, dim3(p.nparts, p.C2), dim3(SFH_THREADS), 0, st, (const float*)z, p.map, p.N, p.nchunk,
-                       w.sec(SS_BNP));
+                       w.at(ws, SS_BNP));
     MI_LAUNCH_CHECK();
   }
-  hipLaunchKernelGGL(bn_finish_kernel, dim3(p.grid_chan), dim3(SFH_THREADS), 0, st, (const float*)w.sec(SS_BNP), p.map, p.N, p.nchunk,
+  hipLaunchKernelGGL(bn_finish_kernel, dim3(p.grid_chan), dim3(SFH_THREADS), 0, st, (const float*)w.at(ws, SS_BNP), p.map, p.N, p.nchunk,
                      p.nparts, (float)(1.0 / sqrt(hw)), s->eps, s->momentum, s->training, running_mean, running_var, stat);
   MI_LAUNCH_CHECK();
-  MI_TRY(sfh_middle(w, pr, z, stat, st));
-  hipLaunchKernelGGL(sfh_gelu_kernel, dim3(p.grid_elems), dim3(SFH_THREADS), 0, st, (const float*)w.sec(SS_P),
-                     (const float*)w.sec(SS_S), pr->fdc_b, p.map, p.G, o, (float)sqrt(hw), p.N, p.nblk);
+  MI_TRY(sfh_middle(p, ws, pr, z, stat, st));
+  hipLaunchKernelGGL(sfh_gelu_kernel, dim3(p.grid_elems), dim3(SFH_THREADS), 0, st, (const float*)w.at(ws, SS_P),
+                     (const float*)w.at(ws, SS_S), pr->fdc_b, p.map, p.G, o, (float)sqrt(hw), p.N, p.nblk);
   MI_LAUNCH_CHECK();
   return dft2_c2r_run(p.dft, dft, o, o + half, out, s->dtype, st);
 }
@@ -569,41 +556,41 @@ extern "C" int mi_fourier_unit_bwd(const mi_fourier_unit_shape* s, const mi_four
                dx && g && g->bn_w && g->bn_b && g->fdc_w && g->fdc_b && g->gate_w && g->gate_b && g->fpe_w && g->fpe_b && saved && ws,
                "fourier_unit_bwd: null pointer");
   hipStream_t st = (hipStream_t)stream;
-  const SfhWs w = {p, (char*)ws};
-  const Dft2Ws dft = dft2_blob_ws(p.dft_blob, w.sec(SS_DFT));
+  const Sections<SFH_SECTIONS>& w = p.ws;
+  const Dft2Ws dft = dft2_blob_ws(p.dft_blob, w.at(ws, SS_DFT));
   const int bins = (int)p.bins, acc = g->accumulate ? 1 : 0;
   const float* z = (const float*)saved;
-  const float* stat = (const float*)((const char*)saved + p.saved_stat_off);
-  float* u = w.sec(SS_U);
+  const float* stat = p.saved.at(saved, 1);
+  float* u = w.at(ws, SS_U);
   const int64_t half = (int64_t)p.B * p.c * p.N;
   const double hw = (double)p.H * p.W;
-  float* t = w.sec(SS_A); float* ts = w.sec(SS_B); float* dpre = w.sec(SS_P); float* q = w.sec(SS_Q);
-  float* sg = w.sec(SS_S); float* dl = w.sec(SS_DL); float* tmp = w.sec(SS_GT); float* means = w.sec(SS_STAT) + 2 * p.C2;
+  float* t = w.at(ws, SS_A); float* ts = w.at(ws, SS_B); float* dpre = w.at(ws, SS_P); float* q = w.at(ws, SS_Q);
+  float* sg = w.at(ws, SS_S); float* dl = w.at(ws, SS_DL); float* tmp = w.at(ws, SS_GT); float* means = w.at(ws, SS_STAT) + 2 * p.C2;
   float* tmp_b = tmp + (size_t)p.C2 * p.C2; float* tmp_w = tmp_b + (size_t)p.G * p.C2;
 
   MI_TRY(dft2_tables(p.dft, dft, st));
   MI_TRY(dft2_c2r_adj(p.dft, dft, dout, u, u + half, s->dtype, st));    // H W x the adjoint
-  MI_TRY(sfh_middle(w, pr, z, stat, st));
+  MI_TRY(sfh_middle(p, ws, pr, z, stat, st));
   hipLaunchKernelGGL(sfh_gelu_bwd_kernel, dim3(p.grid_elems), dim3(SFH_THREADS), 0, st, dpre, (const float*)sg, pr->fdc_b, p.map, p.G,
                      (const float*)u, (float)(1.0 / sqrt(hw)), p.N, p.nblk);
   MI_LAUNCH_CHECK();
-  MI_TRY(conv1x1_bwd_input(dpre, p.C2, ts, p.C2, w.sec(SS_WP), tmp, nullptr, q, p.B, p.N, MI_F32, 0, w.sec(SS_GRAM), w.sec(SS_CS),
-                           w.sec(SS_PW), st, false));
+  MI_TRY(conv1x1_bwd_input(dpre, p.C2, ts, p.C2, w.at(ws, SS_WP), tmp, nullptr, q, p.B, p.N, MI_F32, 0, w.at(ws, SS_GRAM), w.at(ws, SS_CS),
+                           w.at(ws, SS_PW), st, false));
   const mi_gram_desc gb = wgrad_gram(sg, p.G, dpre, p.C2, p.B, p.N, MI_F32, tmp_b, 0);
-  MI_TRY(mi_gram(&gb, w.sec(SS_GRAM), st));
+  MI_TRY(mi_gram(&gb, w.at(ws, SS_GRAM), st));
 #define SFH_GATE_BWD(GG) launch_gate_bwd<GG>(dim3(p.grid_bins), st, (const float*)t, q, (const float*)dpre, (const float*)sg, p.map, \
                                              p.S, pr->gate_w, pr->fdc_b, dl, p.N, bins)
   SFH_FOR_G(p.G, SFH_GATE_BWD)
 #undef SFH_GATE_BWD
   MI_LAUNCH_CHECK();
   const mi_gram_desc gw = wgrad_gram(dl, p.G, t, p.C2, p.B, p.N, MI_F32, tmp_w, 0);
-  MI_TRY(mi_gram(&gw, w.sec(SS_GRAM), st));
-  MI_TRY(launch_chan_sum(dl, g->gate_b, p.B, p.G, p.N, MI_F32, acc, w.sec(SS_CS), st));
+  MI_TRY(mi_gram(&gw, w.at(ws, SS_GRAM), st));
+  MI_TRY(launch_chan_sum(dl, g->gate_b, p.B, p.G, p.N, MI_F32, acc, w.at(ws, SS_CS), st));
   float* dt1 = ts;   // ts is dead: the Gram above was its last reader
   hipLaunchKernelGGL(fpe_bn_bwd_partial_kernel, dim3(p.nparts, p.C2), dim3(SFH_THREADS), 0, st, (const float*)q, z, p.map, stat,
-                     pr->bn_w, pr->bn_b, pr->fpe_w, dt1, w.sec(SS_RP), p.H, p.K, p.nchunk);
+                     pr->bn_w, pr->bn_b, pr->fpe_w, dt1, w.at(ws, SS_RP), p.H, p.K, p.nchunk);
   MI_LAUNCH_CHECK();
-  hipLaunchKernelGGL(fpe_bn_bwd_finish_kernel, dim3(p.grid_fin), dim3(SFH_THREADS), 0, st, (const float*)w.sec(SS_RP), p.map, p.nparts,
+  hipLaunchKernelGGL(fpe_bn_bwd_finish_kernel, dim3(p.grid_fin), dim3(SFH_THREADS), 0, st, (const float*)w.at(ws, SS_RP), p.map, p.nparts,
                      (float)(1.0 / (double)p.bins), acc, g->fpe_w, g->fpe_b, g->bn_w, g->bn_b, means);
   MI_LAUNCH_CHECK();
   hipLaunchKernelGGL(bn_bwd_dz_kernel, dim3(p.grid_elems), dim3(SFH_THREADS), 0, st, (const float*)dt1, z, p.map, stat,

@@ -307,7 +307,8 @@ struct SfPlan {
   int tiles_x, tiles_y, ntiles, splits;
   int64_t N, rows, part_cols, part_off[SF_MAX_SEG];   // partial rows B splits; columns in all; float offset of segment k's rows
   int kernels_fwd, kernels_bwd, lib_fwd, lib_bwd;
-  size_t off[SF_SECTIONS], bytes[SF_SECTIONS], total, saved_bytes, saved_u_off;
+  Sections<SF_SECTIONS> ws;
+  Sections<2> saved;                                  // the FFN's blob: h, then u
 };
 
 int sf_check(const char* who, int mode, const void* shape, int B, int dim, int H, int W, int dtype, SfPlan* p) {
@@ -335,31 +336,25 @@ int sf_check(const char* who, int mode, const void* shape, int B, int dim, int H
     p->part_off[k] = p->rows * p->part_cols;
     if (p->ks[k] > 1) p->part_cols += (int64_t)p->s * (p->ks[k] * p->ks[k] + 1);
   }
-  Carver cv(nullptr);
-  auto sec = [&](int i, size_t n) { p->off[i] = cv.off; p->bytes[i] = n; cv.take(n); };
+  Sections<SF_SECTIONS>& ws = p->ws;
   if (mode == SF_FFN) {
     const int C = p->C, dt = dtype;
     const int64_t N = p->N;
-    sec(SS_PW, max_of({pw_ws_bytes(probe1x1(dim, C, false, B, N, dt)), pw_ws_bytes(probe1x1(C, dim, false, B, N, dt)),
-                       pw_ws_bytes(probe1x1(dim, C, true, B, N, dt)), pw_ws_bytes(probe1x1(C, dim, true, B, N, dt))}));
-    sec(SS_GRAM, max_of({gram_ws_bytes(probe_wgrad(dim, C, B, N, dt)), gram_ws_bytes(probe_wgrad(C, dim, B, N, dt))}));
-    sec(SS_CS, chan_sum_workspace(C, N));
-    sec(SS_PART, (size_t)(p->rows * p->part_cols) * sizeof(float));
+    ws.put(SS_PW, max_of({pw_ws_bytes(probe1x1(dim, C, false, B, N, dt)), pw_ws_bytes(probe1x1(C, dim, false, B, N, dt)),
+                          pw_ws_bytes(probe1x1(dim, C, true, B, N, dt)), pw_ws_bytes(probe1x1(C, dim, true, B, N, dt))}));
+    ws.put(SS_GRAM, max_of({gram_ws_bytes(probe_wgrad(dim, C, B, N, dt)), gram_ws_bytes(probe_wgrad(C, dim, B, N, dt))}));
+    ws.put(SS_CS, chan_sum_workspace(C, N));
+    ws.put(SS_PART, (size_t)(p->rows * p->part_cols) * sizeof(float));
     const size_t plane = (size_t)B * C * N * dtype_size(dt);
-    sec(SS_G, plane);
-    sec(SS_DG, plane);                                       // inference: h
-    sec(SS_DH, plane);
-    Carver sv(nullptr);
-    sv.take(plane);
-    p->saved_u_off = sv.off;
-    sv.take(plane);
-    p->saved_bytes = sv.off;
+    ws.put(SS_G, plane);
+    ws.put(SS_DG, plane);                                    // inference: h
+    ws.put(SS_DH, plane);
+    p->saved.put(0, plane); p->saved.put(1, plane);
     p->kernels_fwd = 1; p->kernels_bwd = 7; p->lib_fwd = 2; p->lib_bwd = 6;
   } else {
-    sec(SS_PART, (size_t)(p->rows * p->part_cols) * sizeof(float));
+    ws.put(SS_PART, (size_t)(p->rows * p->part_cols) * sizeof(float));
     p->kernels_fwd = 1; p->kernels_bwd = 3;
   }
-  p->total = cv.off;
   return MI_OK;
 }
 int sf_check(const char* who, const mi_sfh_ffn_shape* s, SfPlan* p) {
@@ -369,14 +364,13 @@ int sf_check(const char* who, const mi_sfh_local_shape* s, SfPlan* p) {
   return sf_check(who, SF_LOCAL, s, s ? s->B : 0, s ? s->dim : 0, s ? s->H : 0, s ? s->W : 0, s ? s->dtype : 0, p);
 }
 
+// 23 scalars (tile, segments, halos, tiles, partial rows, launch counts, LDS bytes forward / backward, threads), the SS_* sections
+// from [24]; [62]: the offset of u in the saved blob (the format: plan_report, internal.h)
 int sf_plan_out(const SfPlan& p, int64_t* out) {
-  int64_t v[64] = {SF_TW, SF_TH, p.S, p.s, p.halo[0], p.halo[1], p.halo[2], p.halo[3], p.tiles_x, p.tiles_y, p.ntiles, p.C, p.B,
-                   p.splits, p.rows, p.part_cols, p.kernels_fwd, p.kernels_bwd, p.lib_fwd, p.lib_bwd,
-                   (int64_t)(SF_MAXLT * sizeof(float)), (int64_t)((2 * SF_MAXLT + 4 * 50) * sizeof(float)), SF_THREADS};
-  for (int i = 0; i < SF_SECTIONS; ++i) { v[24 + 2 * i] = (int64_t)p.off[i]; v[25 + 2 * i] = (int64_t)p.bytes[i]; }
-  v[60] = (int64_t)p.total; v[61] = (int64_t)p.saved_bytes; v[62] = (int64_t)p.saved_u_off;
-  memcpy(out, v, sizeof(v));
-  return MI_OK;
+  return plan_report<24>(out, {SF_TW, SF_TH, p.S, p.s, p.halo[0], p.halo[1], p.halo[2], p.halo[3], p.tiles_x, p.tiles_y, p.ntiles, p.C,
+                               p.B, p.splits, p.rows, p.part_cols, p.kernels_fwd, p.kernels_bwd, p.lib_fwd, p.lib_bwd,
+                               (int64_t)(SF_MAXLT * sizeof(float)), (int64_t)((2 * SF_MAXLT + 4 * 50) * sizeof(float)), SF_THREADS},
+                         p.ws, {(int64_t)p.ws.total, (int64_t)p.saved.total, (int64_t)p.saved.off[1]});
 }
 
 // rows are 4 wide where every row of every plane starts on a 16-byte boundary of its dtype's 4-element chunk
@@ -439,11 +433,11 @@ using namespace mi;
 // ------------------------------------------------------------------ FFN
 extern "C" size_t mi_sfh_ffn_workspace(const mi_sfh_ffn_shape* s) {
   SfPlan p;
-  return sf_check("sfh_ffn_workspace", s, &p) == MI_OK ? p.total : 0;
+  return sf_check("sfh_ffn_workspace", s, &p) == MI_OK ? p.ws.total : 0;
 }
 extern "C" size_t mi_sfh_ffn_saved_bytes(const mi_sfh_ffn_shape* s) {
   SfPlan p;
-  return sf_check("sfh_ffn_saved_bytes", s, &p) == MI_OK ? p.saved_bytes : 0;
+  return sf_check("sfh_ffn_saved_bytes", s, &p) == MI_OK ? p.saved.total : 0;
 }
 extern "C" int mi_sfh_ffn_plan(const mi_sfh_ffn_shape* s, int64_t* out) {
   MI_CHECK_ARG(out, "sfh_ffn_plan: null pointer");
@@ -465,15 +459,15 @@ extern "C" int mi_sfh_ffn_fwd(const mi_sfh_ffn_shape* s, const mi_sfh_ffn_params
   MI_TRY(sf_check("sfh_ffn_fwd", s, &p));
   MI_CHECK_ARG(ffn_params_ok(pr) && x && out && ws, "sfh_ffn_fwd: null pointer");
   hipStream_t st = (hipStream_t)stream;
-  char* w = (char*)ws;
-  void* h = saved ? saved : (void*)(w + p.off[SS_DG]);
-  void* u = saved ? (void*)((char*)saved + p.saved_u_off) : nullptr;
-  void* g = w + p.off[SS_G];
+  const Sections<SF_SECTIONS>& w = p.ws;
+  void* h = saved ? saved : w.at<void>(ws, SS_DG);
+  void* u = saved ? p.saved.at<void>(saved, 1) : nullptr;
+  void* g = w.at(ws, SS_G);
   const mi_pw_desc d1 = conv1x1(x, p.dim, pr->init_w, false, p.dim, pr->init_b, nullptr, h, p.C, p.B, p.N, p.dtype);      // SFHformer.py:109
-  MI_TRY(mi_pw_gemm(&d1, w + p.off[SS_PW], st));
+  MI_TRY(mi_pw_gemm(&d1, w.at(ws, SS_PW), st));
   MI_TRY(sf_fwd(p, h, ffn_seg(pr), u, g, st));                                                                              // :110-115
   const mi_pw_desc d2 = conv1x1(g, p.C, pr->fina_w, false, p.C, pr->fina_b, nullptr, out, p.dim, p.B, p.N, p.dtype);       // :116
-  return mi_pw_gemm(&d2, w + p.off[SS_PW], st);
+  return mi_pw_gemm(&d2, w.at(ws, SS_PW), st);
 }
 
 extern "C" int mi_sfh_ffn_bwd(const mi_sfh_ffn_shape* s, const mi_sfh_ffn_params* pr, const void* x, const void* dout, void* dx,
@@ -484,30 +478,30 @@ extern "C" int mi_sfh_ffn_bwd(const mi_sfh_ffn_shape* s, const mi_sfh_ffn_params
   MI_CHECK_ARG(gr->init_w && gr->init_b && gr->c1_w && gr->c1_b && gr->c2_w && gr->c2_b && gr->c3_w && gr->c3_b && gr->fina_w &&
                gr->fina_b, "sfh_ffn_bwd: null gradient buffer");
   hipStream_t st = (hipStream_t)stream;
-  char* w = (char*)ws;
+  const Sections<SF_SECTIONS>& w = p.ws;
   const int acc = gr->accumulate ? 1 : 0;
   const void* h = saved;
-  const void* u = (const char*)saved + p.saved_u_off;
-  void* g = w + p.off[SS_G];
-  void* dg = w + p.off[SS_DG];
-  void* dh = w + p.off[SS_DH];
-  float* part = (float*)(w + p.off[SS_PART]);
-  MI_TRY(launch_chan_sum(dout, gr->fina_b, p.B, p.dim, p.N, p.dtype, acc, w + p.off[SS_CS], st));
+  const void* u = p.saved.at<void>(saved, 1);
+  void* g = w.at(ws, SS_G);
+  void* dg = w.at(ws, SS_DG);
+  void* dh = w.at(ws, SS_DH);
+  float* part = w.at(ws, SS_PART);
+  MI_TRY(launch_chan_sum(dout, gr->fina_b, p.B, p.dim, p.N, p.dtype, acc, w.at(ws, SS_CS), st));
   const mi_pw_desc d2 = conv1x1(dout, p.dim, pr->fina_w, true, p.C, nullptr, nullptr, dg, p.C, p.B, p.N, p.dtype);
-  MI_TRY(mi_pw_gemm(&d2, w + p.off[SS_PW], st));
+  MI_TRY(mi_pw_gemm(&d2, w.at(ws, SS_PW), st));
   float* const gw[SF_MAX_SEG] = {nullptr, gr->c1_w, gr->c2_w, gr->c3_w};
   float* const gb[SF_MAX_SEG] = {nullptr, gr->c1_b, gr->c2_b, gr->c3_b};
   MI_TRY(sf_bwd(p, dg, u, h, ffn_seg(pr), g, dh, part, gw, gb, acc, st));
   const mi_gram_desc g2 = wgrad_gram(dout, p.dim, g, p.C, p.B, p.N, p.dtype, gr->fina_w, acc);
-  MI_TRY(mi_gram(&g2, w + p.off[SS_GRAM], st));
-  return conv1x1_bwd_input(dh, p.C, x, p.dim, pr->init_w, gr->init_w, gr->init_b, dx, p.B, p.N, p.dtype, acc, w + p.off[SS_GRAM],
-                           w + p.off[SS_CS], w + p.off[SS_PW], st, false);
+  MI_TRY(mi_gram(&g2, w.at(ws, SS_GRAM), st));
+  return conv1x1_bwd_input(dh, p.C, x, p.dim, pr->init_w, gr->init_w, gr->init_b, dx, p.B, p.N, p.dtype, acc, w.at(ws, SS_GRAM),
+                           w.at(ws, SS_CS), w.at(ws, SS_PW), st, false);
 }
 
 // ------------------------------------------------------------------ TokenMixer_For_Local
 extern "C" size_t mi_sfh_local_workspace(const mi_sfh_local_shape* s) {
   SfPlan p;
-  return sf_check("sfh_local_workspace", s, &p) == MI_OK ? p.total : 0;
+  return sf_check("sfh_local_workspace", s, &p) == MI_OK ? p.ws.total : 0;
 }
 extern "C" int mi_sfh_local_plan(const mi_sfh_local_shape* s, int64_t* out) {
   MI_CHECK_ARG(out, "sfh_local_plan: null pointer");
@@ -535,6 +529,6 @@ extern "C" int mi_sfh_local_bwd(const mi_sfh_local_shape* s, const mi_sfh_local_
   const SegPtrs sp = {{pr->cd1_w, pr->cd2_w, nullptr, nullptr}, {pr->cd1_b, pr->cd2_b, nullptr, nullptr}};
   float* const gw[SF_MAX_SEG] = {gr->cd1_w, gr->cd2_w, nullptr, nullptr};
   float* const gb[SF_MAX_SEG] = {gr->cd1_b, gr->cd2_b, nullptr, nullptr};
-  return sf_bwd(p, dout, nullptr, x, sp, nullptr, dx, (float*)((char*)ws + p.off[SS_PART]), gw, gb, gr->accumulate ? 1 : 0,
+  return sf_bwd(p, dout, nullptr, x, sp, nullptr, dx, p.ws.at(ws, SS_PART), gw, gb, gr->accumulate ? 1 : 0,
                 (hipStream_t)stream);
 }

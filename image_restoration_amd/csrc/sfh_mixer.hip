@@ -258,9 +258,9 @@ struct SmPlan {
   int kernels_fwd, kernels_bwd, lib_fwd, lib_bwd;
   mi_fourier_unit_shape fu;
   mi_sfh_local_shape loc;
-  size_t off[MS_SECTIONS], bytes[MS_SECTIONS], total;
-  size_t sv_off[SV_SECTIONS], sv_bytes[SV_SECTIONS], saved_bytes;
-  size_t bw_off[BW_SECTIONS], bw_bytes;          // the backward's planes, overlaid on the inference copy of the saved planes
+  Sections<MS_SECTIONS> ws;
+  Sections<SV_SECTIONS> saved;
+  Sections<BW_SECTIONS> bw;                      // the backward's planes, overlaid on the inference copy of the saved planes
   size_t small_off[SMALL_COUNT];                 // float offsets inside MS_SMALL
 };
 
@@ -307,67 +307,60 @@ int sm_check(const char* who, int mode, const S* s, SmPlan* p) {
   const int64_t N = p->N;
   const bool mix = mode == SM_MIXER;
   const size_t pl1 = (size_t)p->elems1 * dtype_size(dt), pl2 = 2 * pl1;
-  Carver sv(nullptr);
-  auto keep = [&](int i, size_t n) { p->sv_off[i] = sv.off; p->sv_bytes[i] = n; sv.take(n); };
-  keep(SV_A, mix ? pl1 : 0); keep(SV_B, mix ? pl1 : 0); keep(SV_L, mix ? pl1 : 0);
-  keep(SV_U1, pl2); keep(SV_R, pl2); keep(SV_U2, pl1); keep(SV_FU, fu_saved);
-  p->saved_bytes = sv.off;
-  Carver bw(nullptr);
-  auto tmp = [&](int i, size_t n) { p->bw_off[i] = bw.off; bw.take(n); };
-  tmp(BW_E, mix ? pl2 : 0); tmp(BW_DL, mix ? pl1 : 0); tmp(BW_DU2, pl1); tmp(BW_DA, mix ? pl1 : 0); tmp(BW_DB, mix ? pl1 : 0);
-  p->bw_bytes = bw.off;
+  Sections<SV_SECTIONS>& sv = p->saved;
+  sv.put(SV_A, mix ? pl1 : 0); sv.put(SV_B, mix ? pl1 : 0); sv.put(SV_L, mix ? pl1 : 0);
+  sv.put(SV_U1, pl2); sv.put(SV_R, pl2); sv.put(SV_U2, pl1); sv.put(SV_FU, fu_saved);
+  Sections<BW_SECTIONS>& bw = p->bw;
+  bw.put(BW_E, mix ? pl2 : 0); bw.put(BW_DL, mix ? pl1 : 0); bw.put(BW_DU2, pl1);
+  bw.put(BW_DA, mix ? pl1 : 0); bw.put(BW_DB, mix ? pl1 : 0);
 
-  Carver cv(nullptr);
-  auto sec = [&](int i, size_t n) { p->off[i] = cv.off; p->bytes[i] = n; cv.take(n); };
+  Sections<MS_SECTIONS>& ws = p->ws;
   mi_pw_desc ca = per_image(probe1x1(C2, dim, false, B, N, dt)), cat = per_image(probe1x1(dim, C2, true, B, N, dt));
   mi_pw_desc dx2 = probe1x1(dim, dim, true, B, N, dt);
   dx2.x2 = PROBE_PTR; dx2.x2_bs = dx2.x1_bs; dx2.k2 = dim;
-  sec(MS_PW, max_of({pw_ws_bytes(probe1x1(dim, C2, false, B, N, dt)), pw_ws_bytes(probe1x1(C2, dim, false, B, N, dt)),
+  ws.put(MS_PW, max_of({pw_ws_bytes(probe1x1(dim, C2, false, B, N, dt)), pw_ws_bytes(probe1x1(C2, dim, false, B, N, dt)),
                      pw_ws_bytes(probe1x1(dim, C2, true, B, N, dt)), pw_ws_bytes(probe1x1(C2, dim, true, B, N, dt)),
                      mix ? pw_ws_bytes(init_desc(PROBE_PTR, (const float*)PROBE_PTR, (const float*)PROBE_PTR, PROBE_PTR,
-                                                 (int64_t)((p->sv_off[SV_B] - p->sv_off[SV_A]) / dtype_size(dt)), dim, B, N, dt)) : 0,
+                                                 (int64_t)((sv.off[SV_B] - sv.off[SV_A]) / dtype_size(dt)), dim, B, N, dt)) : 0,
                      mix ? pw_ws_bytes(ca) : 0, mix ? pw_ws_bytes(cat) : 0,
                      mix ? pw_ws_bytes(dx2) : 0}));
-  sec(MS_GRAM, max_of({gram_ws_bytes(probe_wgrad(dim, C2, B, N, dt)), gram_ws_bytes(probe_wgrad(C2, dim, B, N, dt)),
+  ws.put(MS_GRAM, max_of({gram_ws_bytes(probe_wgrad(dim, C2, B, N, dt)), gram_ws_bytes(probe_wgrad(C2, dim, B, N, dt)),
                        mix ? gram_ws_bytes(probe_wgrad(dim, dim, B, N, dt)) : 0, mix ? gram_ws_bytes(probe_wgrad(dim, C2, B, N, dt, 0)) : 0}));
-  sec(MS_CS, chan_sum_workspace(C2, N));
-  sec(MS_FU, fu_ws);
-  sec(MS_LOCAL, mix ? mi_sfh_local_workspace(&p->loc) : 0);
-  sec(MS_P, pl2);                                            // p; backward: the FourierUnit's input gradient
-  sec(MS_F, pl2);                                            // f; backward: dr, then du1 in place
-  sec(MS_G, mix ? pl2 : 0);
+  ws.put(MS_CS, chan_sum_workspace(C2, N));
+  ws.put(MS_FU, fu_ws);
+  ws.put(MS_LOCAL, mix ? mi_sfh_local_workspace(&p->loc) : 0);
+  ws.put(MS_P, pl2);                                            // p; backward: the FourierUnit's input gradient
+  ws.put(MS_F, pl2);                                            // f; backward: dr, then du1 in place
+  ws.put(MS_G, mix ? pl2 : 0);
   size_t so = 0;
   const size_t small_n[SMALL_COUNT] = {(size_t)B * C2, (size_t)B * dim, (size_t)B * C2, (size_t)B * C2, (size_t)B * dim, (size_t)B * C2};
   for (int i = 0; i < SMALL_COUNT; ++i) { p->small_off[i] = so; so += align_up(small_n[i], 64); }
-  sec(MS_SMALL, mix ? so * sizeof(float) : 0);
-  sec(MS_FOLD, mix ? (size_t)B * dim * C2 * sizeof(float) : 0);
-  sec(MS_PGRAM, mix ? (size_t)B * dim * C2 * sizeof(float) : 0);
-  sec(MS_PART, mix ? (size_t)B * C2 * p->pool * sizeof(float) : 0);
+  ws.put(MS_SMALL, mix ? so * sizeof(float) : 0);
+  ws.put(MS_FOLD, mix ? (size_t)B * dim * C2 * sizeof(float) : 0);
+  ws.put(MS_PGRAM, mix ? (size_t)B * dim * C2 * sizeof(float) : 0);
+  ws.put(MS_PART, mix ? (size_t)B * C2 * p->pool * sizeof(float) : 0);
   // forward without a blob: the saved planes (the FourierUnit's blob is never written then); backward: e, dl, du2, da, db
-  sec(MS_SCRATCH, max_of({p->sv_off[SV_FU], p->bw_bytes}));
-  p->total = cv.off;
+  ws.put(MS_SCRATCH, max_of({sv.off[SV_FU], bw.total}));
   if (mix) { p->kernels_fwd = 4; p->kernels_bwd = 6; p->lib_fwd = 6; p->lib_bwd = 12; }
   else { p->kernels_fwd = 3; p->kernels_bwd = 2; p->lib_fwd = 3; p->lib_bwd = 3; }
   return MI_OK;
 }
 
+// 15 scalars (mode, B, dim, 2dim, N, pool, three grids, threads, launch counts, the backward overlay's bytes), the MS_* sections
+// from [16], the SV_* sections of the saved blob from [44] (the format: plan_report, internal.h)
 int sm_plan_out(const SmPlan& p, int64_t* out) {
-  int64_t v[64] = {p.mode, p.B, p.dim, p.C2, p.N, p.pool, p.ew_grid1, p.ew_grid2, p.tail_grid, SM_THREADS, p.kernels_fwd, p.kernels_bwd,
-                   p.lib_fwd, p.lib_bwd, (int64_t)p.bw_bytes, 0};
-  for (int i = 0; i < MS_SECTIONS; ++i) { v[16 + 2 * i] = (int64_t)p.off[i]; v[17 + 2 * i] = (int64_t)p.bytes[i]; }
-  for (int i = 0; i < SV_SECTIONS; ++i) { v[44 + 2 * i] = (int64_t)p.sv_off[i]; v[45 + 2 * i] = (int64_t)p.sv_bytes[i]; }
-  v[60] = (int64_t)p.total; v[61] = (int64_t)p.saved_bytes;
-  memcpy(out, v, sizeof(v));
-  return MI_OK;
+  return plan_report<16, 44>(out, {p.mode, p.B, p.dim, p.C2, p.N, p.pool, p.ew_grid1, p.ew_grid2, p.tail_grid, SM_THREADS, p.kernels_fwd,
+                                   p.kernels_bwd, p.lib_fwd, p.lib_bwd, (int64_t)p.bw.total},
+                             p.ws, p.saved, {(int64_t)p.ws.total, (int64_t)p.saved.total, 0});
 }
 
 struct GloParams { const float* init_w; const float* init_b; const float* fina_w; const float* fina_b; mi_fourier_unit_params fu; };
 struct GloGrads { float* init_w; float* init_b; float* fina_w; float* fina_b; mi_fourier_unit_grads fu; };
 struct Saved { void* a; void* b; void* l; void* u1; void* r; void* u2; void* fu; };
 Saved sm_saved(const SmPlan& p, void* base) {
-  char* c = (char*)base;
-  return Saved{c + p.sv_off[SV_A], c + p.sv_off[SV_B], c + p.sv_off[SV_L], c + p.sv_off[SV_U1], c + p.sv_off[SV_R], c + p.sv_off[SV_U2],
-               c + p.sv_off[SV_FU]};
+  const Sections<SV_SECTIONS>& s = p.saved;
+  return Saved{s.at(base, SV_A), s.at(base, SV_B), s.at(base, SV_L), s.at(base, SV_U1),
+               s.at(base, SV_R), s.at(base, SV_U2), s.at(base, SV_FU)};
 }
 
 bool sm_vec(int64_t n, std::initializer_list<const void*> ptrs) {
@@ -388,45 +381,45 @@ int sm_ew_launch(const SmPlan& p, const void* a, const void* b, const void* u, v
 }
 
 // b -> u2 (:201-204 without conv_fina's GELU).  keep_fu: the FourierUnit's blob or NULL.
-int glo_fwd(const SmPlan& p, const GloParams& g, const void* bin, const Saved& s, void* keep_fu, float* rm, float* rv, char* w, hipStream_t st) {
-  void* P = w + p.off[MS_P];
-  void* F = w + p.off[MS_F];
+int glo_fwd(const SmPlan& p, const GloParams& g, const void* bin, const Saved& s, void* keep_fu, float* rm, float* rv, void* ws, hipStream_t st) {
+  void* P = p.ws.at(ws, MS_P);
+  void* F = p.ws.at(ws, MS_F);
   const mi_pw_desc d1 = conv1x1(bin, p.dim, g.init_w, false, p.dim, g.init_b, nullptr, s.u1, p.C2, p.B, p.N, p.dtype);
-  MI_TRY(mi_pw_gemm(&d1, w + p.off[MS_PW], st));
+  MI_TRY(mi_pw_gemm(&d1, p.ws.at(ws, MS_PW), st));
   MI_TRY(sm_ew_launch<EW_GELU>(p, s.u1, nullptr, nullptr, P, p.elems2, p.ew_grid2, st));
-  MI_TRY(mi_fourier_unit_fwd(&p.fu, &g.fu, P, F, rm, rv, keep_fu, w + p.off[MS_FU], st));
+  MI_TRY(mi_fourier_unit_fwd(&p.fu, &g.fu, P, F, rm, rv, keep_fu, p.ws.at(ws, MS_FU), st));
   MI_TRY(sm_ew_launch<EW_ADD>(p, F, P, nullptr, s.r, p.elems2, p.ew_grid2, st));
   const mi_pw_desc d2 = conv1x1(s.r, p.C2, g.fina_w, false, p.C2, g.fina_b, nullptr, s.u2, p.dim, p.B, p.N, p.dtype);
-  return mi_pw_gemm(&d2, w + p.off[MS_PW], st);
+  return mi_pw_gemm(&d2, p.ws.at(ws, MS_PW), st);
 }
 
 // du2 -> db (the gradient at the branch's input) and the twelve parameter gradients
-int glo_bwd(const SmPlan& p, const GloParams& g, const GloGrads& gr, const void* bin, const void* du2, void* db, const Saved& s, char* w,
+int glo_bwd(const SmPlan& p, const GloParams& g, const GloGrads& gr, const void* bin, const void* du2, void* db, const Saved& s, void* ws,
             hipStream_t st) {
   const int acc = gr.fu.accumulate;
-  void* dpf = w + p.off[MS_P];
-  void* dr = w + p.off[MS_F];
-  MI_TRY(conv1x1_bwd_input(du2, p.dim, s.r, p.C2, g.fina_w, gr.fina_w, gr.fina_b, dr, p.B, p.N, p.dtype, acc, w + p.off[MS_GRAM],
-                           w + p.off[MS_CS], w + p.off[MS_PW], st, false));
-  MI_TRY(mi_fourier_unit_bwd(&p.fu, &g.fu, dr, dpf, &gr.fu, s.fu, w + p.off[MS_FU], st));
+  void* dpf = p.ws.at(ws, MS_P);
+  void* dr = p.ws.at(ws, MS_F);
+  MI_TRY(conv1x1_bwd_input(du2, p.dim, s.r, p.C2, g.fina_w, gr.fina_w, gr.fina_b, dr, p.B, p.N, p.dtype, acc, p.ws.at(ws, MS_GRAM),
+                           p.ws.at(ws, MS_CS), p.ws.at(ws, MS_PW), st, false));
+  MI_TRY(mi_fourier_unit_bwd(&p.fu, &g.fu, dr, dpf, &gr.fu, s.fu, p.ws.at(ws, MS_FU), st));
   MI_TRY(sm_ew_launch<EW_ADD_DGELU>(p, dr, dpf, s.u1, dr, p.elems2, p.ew_grid2, st));
-  return conv1x1_bwd_input(dr, p.C2, bin, p.dim, g.init_w, gr.init_w, gr.init_b, db, p.B, p.N, p.dtype, acc, w + p.off[MS_GRAM],
-                           w + p.off[MS_CS], w + p.off[MS_PW], st, false);
+  return conv1x1_bwd_input(dr, p.C2, bin, p.dim, g.init_w, gr.init_w, gr.init_b, db, p.B, p.N, p.dtype, acc, p.ws.at(ws, MS_GRAM),
+                           p.ws.at(ws, MS_CS), p.ws.at(ws, MS_PW), st, false);
 }
 
-int tail_in(const SmPlan& p, const void* l, const void* u2, char* w, hipStream_t st) {
-  void* g = w + p.off[MS_G];
-  float* part = (float*)(w + p.off[MS_PART]);
+int tail_in(const SmPlan& p, const void* l, const void* u2, void* ws, hipStream_t st) {
+  void* g = p.ws.at(ws, MS_G);
+  float* part = p.ws.at(ws, MS_PART);
   const int vec = sm_vec(p.N, {l, u2, g});
   return with_dtype(p.dtype, "sfh_mixer_tail_in", [&](auto tag) {
     using T = decltype(tag);
     hipLaunchKernelGGL((sm_tail_in<T>), dim3(p.pool, p.C2, p.B), dim3(SM_THREADS), 0, st, (const T*)l, (const T*)u2, (T*)g, part, p.dim, p.N, vec);
   });
 }
-int chan_attn(const SmPlan& p, const float* w1, const float* b1, const float* w2, const float* b2, const float* wc, char* w, hipStream_t st) {
-  float* sm = (float*)(w + p.off[MS_SMALL]);
-  hipLaunchKernelGGL(sm_ca_kernel, dim3(p.B), dim3(SM_THREADS), 0, st, (const float*)(w + p.off[MS_PART]), w1, b1, w2, b2, wc,
-                     sm + p.small_off[SMALL_M], sm + p.small_off[SMALL_HID], sm + p.small_off[SMALL_S], (float*)(w + p.off[MS_FOLD]), p.dim,
+int chan_attn(const SmPlan& p, const float* w1, const float* b1, const float* w2, const float* b2, const float* wc, void* ws, hipStream_t st) {
+  float* sm = p.ws.at(ws, MS_SMALL);
+  hipLaunchKernelGGL(sm_ca_kernel, dim3(p.B), dim3(SM_THREADS), 0, st, (const float*)p.ws.at(ws, MS_PART), w1, b1, w2, b2, wc,
+                     sm + p.small_off[SMALL_M], sm + p.small_off[SMALL_HID], sm + p.small_off[SMALL_S], p.ws.at(ws, MS_FOLD), p.dim,
                      p.pool, 1.0f / (float)p.N);
   MI_LAUNCH_CHECK();
   return MI_OK;
@@ -461,11 +454,11 @@ using namespace mi;
 // ------------------------------------------------------------------ TokenMixer_For_Gloal
 extern "C" size_t mi_sfh_global_workspace(const mi_sfh_global_shape* s) {
   SmPlan p;
-  return sm_check("sfh_global_workspace", SM_GLOBAL, s, &p) == MI_OK ? p.total : 0;
+  return sm_check("sfh_global_workspace", SM_GLOBAL, s, &p) == MI_OK ? p.ws.total : 0;
 }
 extern "C" size_t mi_sfh_global_saved_bytes(const mi_sfh_global_shape* s) {
   SmPlan p;
-  return sm_check("sfh_global_saved_bytes", SM_GLOBAL, s, &p) == MI_OK ? p.saved_bytes : 0;
+  return sm_check("sfh_global_saved_bytes", SM_GLOBAL, s, &p) == MI_OK ? p.saved.total : 0;
 }
 extern "C" int mi_sfh_global_plan(const mi_sfh_global_shape* s, int64_t* out) {
   MI_CHECK_ARG(out, "sfh_global_plan: null pointer");
@@ -480,9 +473,8 @@ extern "C" int mi_sfh_global_fwd(const mi_sfh_global_shape* s, const mi_sfh_glob
   MI_TRY(sm_check("sfh_global_fwd", SM_GLOBAL, s, &p));
   MI_CHECK_ARG(glo_ok(pr) && x && out && running_mean && running_var && ws, "sfh_global_fwd: null pointer");
   hipStream_t st = (hipStream_t)stream;
-  char* w = (char*)ws;
-  const Saved sv = sm_saved(p, saved ? saved : (void*)(w + p.off[MS_SCRATCH]));
-  MI_TRY(glo_fwd(p, glo_params(pr), x, sv, saved ? sv.fu : nullptr, running_mean, running_var, w, st));                  // :201-204
+  const Saved sv = sm_saved(p, saved ? saved : p.ws.at<void>(ws, MS_SCRATCH));
+  MI_TRY(glo_fwd(p, glo_params(pr), x, sv, saved ? sv.fu : nullptr, running_mean, running_var, ws, st));                  // :201-204
   return sm_ew_launch<EW_GELU>(p, sv.u2, nullptr, nullptr, out, p.elems1, p.ew_grid1, st);
 }
 
@@ -493,21 +485,20 @@ extern "C" int mi_sfh_global_bwd(const mi_sfh_global_shape* s, const mi_sfh_glob
   MI_CHECK_ARG(glo_ok(pr) && x && dout && dx && gr && saved && ws, "sfh_global_bwd: null pointer");
   MI_CHECK_ARG(glo_ok(gr), "sfh_global_bwd: null gradient buffer");
   hipStream_t st = (hipStream_t)stream;
-  char* w = (char*)ws;
   const Saved sv = sm_saved(p, const_cast<void*>(saved));
-  void* du2 = w + p.off[MS_SCRATCH] + p.bw_off[BW_DU2];
+  void* du2 = p.bw.at(p.ws.at(ws, MS_SCRATCH), BW_DU2);
   MI_TRY(sm_ew_launch<EW_DGELU>(p, dout, nullptr, sv.u2, du2, p.elems1, p.ew_grid1, st));
-  return glo_bwd(p, glo_params(pr), glo_grads(gr), x, du2, dx, sv, w, st);
+  return glo_bwd(p, glo_params(pr), glo_grads(gr), x, du2, dx, sv, ws, st);
 }
 
 // ------------------------------------------------------------------ Mixer
 extern "C" size_t mi_sfh_mixer_workspace(const mi_sfh_mixer_shape* s) {
   SmPlan p;
-  return sm_check("sfh_mixer_workspace", SM_MIXER, s, &p) == MI_OK ? p.total : 0;
+  return sm_check("sfh_mixer_workspace", SM_MIXER, s, &p) == MI_OK ? p.ws.total : 0;
 }
 extern "C" size_t mi_sfh_mixer_saved_bytes(const mi_sfh_mixer_shape* s) {
   SmPlan p;
-  return sm_check("sfh_mixer_saved_bytes", SM_MIXER, s, &p) == MI_OK ? p.saved_bytes : 0;
+  return sm_check("sfh_mixer_saved_bytes", SM_MIXER, s, &p) == MI_OK ? p.saved.total : 0;
 }
 extern "C" int mi_sfh_mixer_plan(const mi_sfh_mixer_shape* s, int64_t* out) {
   MI_CHECK_ARG(out, "sfh_mixer_plan: null pointer");
@@ -522,20 +513,19 @@ extern "C" int mi_sfh_mixer_fwd(const mi_sfh_mixer_shape* s, const mi_sfh_mixer_
   MI_TRY(sm_check("sfh_mixer_fwd", SM_MIXER, s, &p));
   MI_CHECK_ARG(glo_ok(pr) && mix_ok(pr) && x && out && running_mean && running_var && ws, "sfh_mixer_fwd: null pointer");
   hipStream_t st = (hipStream_t)stream;
-  char* w = (char*)ws;
   const int dim = p.dim, C2 = p.C2;
-  const Saved sv = sm_saved(p, saved ? saved : (void*)(w + p.off[MS_SCRATCH]));
-  const mi_pw_desc di = init_desc(x, pr->conv_w, pr->conv_b, sv.a, (int64_t)((p.sv_off[SV_B] - p.sv_off[SV_A]) / dtype_size(p.dtype)), dim,
-                                  p.B, p.N, p.dtype);
-  MI_TRY(mi_pw_gemm(&di, w + p.off[MS_PW], st));                                                                            // :240-241
+  const Saved sv = sm_saved(p, saved ? saved : p.ws.at<void>(ws, MS_SCRATCH));
+  const mi_pw_desc di = init_desc(x, pr->conv_w, pr->conv_b, sv.a,
+                                  (int64_t)((p.saved.off[SV_B] - p.saved.off[SV_A]) / dtype_size(p.dtype)), dim, p.B, p.N, p.dtype);
+  MI_TRY(mi_pw_gemm(&di, p.ws.at(ws, MS_PW), st));                                                                            // :240-241
   const mi_sfh_local_params lp = {pr->cd1_w, pr->cd1_b, pr->cd2_w, pr->cd2_b};
-  MI_TRY(mi_sfh_local_fwd(&p.loc, &lp, sv.a, sv.l, w + p.off[MS_LOCAL], st));                                              // :242
-  MI_TRY(glo_fwd(p, glo_params(pr), sv.b, sv, saved ? sv.fu : nullptr, running_mean, running_var, w, st));                 // :243
-  MI_TRY(tail_in(p, sv.l, sv.u2, w, st));                                                                                   // :244-245
-  MI_TRY(chan_attn(p, pr->ca1_w, pr->ca1_b, pr->ca2_w, pr->ca2_b, pr->cac_w, w, st));                                       // :246
-  const mi_pw_desc dc = per_image(conv1x1(w + p.off[MS_G], C2, (const float*)(w + p.off[MS_FOLD]), false, C2, pr->cac_b, nullptr, out, dim,
+  MI_TRY(mi_sfh_local_fwd(&p.loc, &lp, sv.a, sv.l, p.ws.at(ws, MS_LOCAL), st));                                              // :242
+  MI_TRY(glo_fwd(p, glo_params(pr), sv.b, sv, saved ? sv.fu : nullptr, running_mean, running_var, ws, st));                 // :243
+  MI_TRY(tail_in(p, sv.l, sv.u2, ws, st));                                                                                   // :244-245
+  MI_TRY(chan_attn(p, pr->ca1_w, pr->ca1_b, pr->ca2_w, pr->ca2_b, pr->cac_w, ws, st));                                       // :246
+  const mi_pw_desc dc = per_image(conv1x1(p.ws.at(ws, MS_G), C2, (const float*)p.ws.at(ws, MS_FOLD), false, C2, pr->cac_b, nullptr, out, dim,
                                           p.B, p.N, p.dtype));
-  return mi_pw_gemm(&dc, w + p.off[MS_PW], st);                                                                             // :247
+  return mi_pw_gemm(&dc, p.ws.at(ws, MS_PW), st);                                                                             // :247
 }
 
 extern "C" int mi_sfh_mixer_bwd(const mi_sfh_mixer_shape* s, const mi_sfh_mixer_params* pr, const void* x, const void* dout, void* dx,
@@ -545,25 +535,24 @@ extern "C" int mi_sfh_mixer_bwd(const mi_sfh_mixer_shape* s, const mi_sfh_mixer_
   MI_CHECK_ARG(glo_ok(pr) && mix_ok(pr) && x && dout && dx && gr && saved && ws, "sfh_mixer_bwd: null pointer");
   MI_CHECK_ARG(glo_ok(gr) && mix_ok(gr), "sfh_mixer_bwd: null gradient buffer");
   hipStream_t st = (hipStream_t)stream;
-  char* w = (char*)ws;
   const int dim = p.dim, C2 = p.C2, acc = gr->accumulate ? 1 : 0, dt = p.dtype;
   const Saved sv = sm_saved(p, const_cast<void*>(saved));
-  char* bw = w + p.off[MS_SCRATCH];
-  void* e = bw + p.bw_off[BW_E];
-  void* dl = bw + p.bw_off[BW_DL];
-  void* du2 = bw + p.bw_off[BW_DU2];
-  void* dA = bw + p.bw_off[BW_DA];
-  void* dB = bw + p.bw_off[BW_DB];
-  void* g = w + p.off[MS_G];
-  float* sm = (float*)(w + p.off[MS_SMALL]);
-  float* fold = (float*)(w + p.off[MS_FOLD]);
-  float* P = (float*)(w + p.off[MS_PGRAM]);
+  void* bw = p.ws.at(ws, MS_SCRATCH);
+  void* e = p.bw.at(bw, BW_E);
+  void* dl = p.bw.at(bw, BW_DL);
+  void* du2 = p.bw.at(bw, BW_DU2);
+  void* dA = p.bw.at(bw, BW_DA);
+  void* dB = p.bw.at(bw, BW_DB);
+  void* g = p.ws.at(ws, MS_G);
+  float* sm = p.ws.at(ws, MS_SMALL);
+  float* fold = p.ws.at(ws, MS_FOLD);
+  float* P = p.ws.at(ws, MS_PGRAM);
   // g, m, hidden, s and the folded weights again, by the forward's own kernels (bit for bit the forward's)
-  MI_TRY(tail_in(p, sv.l, sv.u2, w, st));
-  MI_TRY(chan_attn(p, pr->ca1_w, pr->ca1_b, pr->ca2_w, pr->ca2_b, pr->cac_w, w, st));
-  MI_TRY(launch_chan_sum(dout, gr->cac_b, p.B, dim, p.N, dt, acc, w + p.off[MS_CS], st));
+  MI_TRY(tail_in(p, sv.l, sv.u2, ws, st));
+  MI_TRY(chan_attn(p, pr->ca1_w, pr->ca1_b, pr->ca2_w, pr->ca2_b, pr->cac_w, ws, st));
+  MI_TRY(launch_chan_sum(dout, gr->cac_b, p.B, dim, p.N, dt, acc, p.ws.at(ws, MS_CS), st));
   const mi_gram_desc pg = wgrad_gram(dout, dim, g, C2, p.B, p.N, dt, P, 0, 0);
-  MI_TRY(mi_gram(&pg, w + p.off[MS_GRAM], st));
+  MI_TRY(mi_gram(&pg, p.ws.at(ws, MS_GRAM), st));
   hipLaunchKernelGGL(sm_gate_bwd, dim3(p.B), dim3(SM_THREADS), 0, st, (const float*)P, pr->cac_w, pr->ca1_w, pr->ca2_w,
                      (const float*)(sm + p.small_off[SMALL_HID]), (const float*)(sm + p.small_off[SMALL_S]), sm + p.small_off[SMALL_DZ2],
                      sm + p.small_off[SMALL_DZ1], sm + p.small_off[SMALL_DMN], dim, 1.0f / (float)p.N);
@@ -574,7 +563,7 @@ extern "C" int mi_sfh_mixer_bwd(const mi_sfh_mixer_shape* s, const mi_sfh_mixer_
                      (const float*)(sm + p.small_off[SMALL_DZ1]), gr->cac_w, gr->ca1_w, gr->ca1_b, gr->ca2_w, gr->ca2_b, p.B, dim, acc);
   MI_LAUNCH_CHECK();
   const mi_pw_desc de = per_image(conv1x1(dout, dim, fold, true, C2, nullptr, nullptr, e, C2, p.B, p.N, dt));
-  MI_TRY(mi_pw_gemm(&de, w + p.off[MS_PW], st));
+  MI_TRY(mi_pw_gemm(&de, p.ws.at(ws, MS_PW), st));
   const int vec = sm_vec(p.N, {e, sv.l, sv.u2, dl, du2});
   MI_TRY(with_dtype(dt, "sfh_mixer_tail_back", [&](auto tag) {
     using T = decltype(tag);
@@ -583,16 +572,16 @@ extern "C" int mi_sfh_mixer_bwd(const mi_sfh_mixer_shape* s, const mi_sfh_mixer_
   }));
   const mi_sfh_local_params lp = {pr->cd1_w, pr->cd1_b, pr->cd2_w, pr->cd2_b};
   const mi_sfh_local_grads lg = {gr->cd1_w, gr->cd1_b, gr->cd2_w, gr->cd2_b, acc};
-  MI_TRY(mi_sfh_local_bwd(&p.loc, &lp, sv.a, dl, dA, &lg, w + p.off[MS_LOCAL], st));
-  MI_TRY(glo_bwd(p, glo_params(pr), glo_grads(gr), sv.b, du2, dB, sv, w, st));
+  MI_TRY(mi_sfh_local_bwd(&p.loc, &lp, sv.a, dl, dA, &lg, p.ws.at(ws, MS_LOCAL), st));
+  MI_TRY(glo_bwd(p, glo_params(pr), glo_grads(gr), sv.b, du2, dB, sv, ws, st));
   // conv_init: the two halves of its gradient stay apart (two Grams, two bias sums); dx takes them as the two K panels
   const mi_gram_desc ga = wgrad_gram(dA, dim, x, dim, p.B, p.N, dt, gr->conv_w, acc);
-  MI_TRY(mi_gram(&ga, w + p.off[MS_GRAM], st));
+  MI_TRY(mi_gram(&ga, p.ws.at(ws, MS_GRAM), st));
   const mi_gram_desc gb = wgrad_gram(dB, dim, x, dim, p.B, p.N, dt, gr->conv_w + (size_t)dim * dim, acc);
-  MI_TRY(mi_gram(&gb, w + p.off[MS_GRAM], st));
-  MI_TRY(launch_chan_sum(dA, gr->conv_b, p.B, dim, p.N, dt, acc, w + p.off[MS_CS], st));
-  MI_TRY(launch_chan_sum(dB, gr->conv_b + dim, p.B, dim, p.N, dt, acc, w + p.off[MS_CS], st));
+  MI_TRY(mi_gram(&gb, p.ws.at(ws, MS_GRAM), st));
+  MI_TRY(launch_chan_sum(dA, gr->conv_b, p.B, dim, p.N, dt, acc, p.ws.at(ws, MS_CS), st));
+  MI_TRY(launch_chan_sum(dB, gr->conv_b + dim, p.B, dim, p.N, dt, acc, p.ws.at(ws, MS_CS), st));
   mi_pw_desc dxd = conv1x1(dA, dim, pr->conv_w, true, dim, nullptr, nullptr, dx, dim, p.B, p.N, dt);
   dxd.x2 = dB; dxd.x2_bs = dxd.x1_bs; dxd.k2 = dim;
-  return mi_pw_gemm(&dxd, w + p.off[MS_PW], st);
+  return mi_pw_gemm(&dxd, p.ws.at(ws, MS_PW), st);
 }

@@ -121,6 +121,53 @@ def _ws(nbytes: int, device) -> Tensor:
     return buf
 
 
+# ----------------------------------------------------------------------------- what the module wrappers share
+def _covered(sizer, shape) -> int:
+    """Workspace bytes of ``shape``; a shape the kernels do not cover raises NotImplementedError with the library's reason."""
+    ws_bytes = sizer(C.byref(shape))
+    if ws_bytes == 0:
+        raise NotImplementedError("image_restoration_amd: " + L.lib().mi_last_error().decode("utf-8", "replace"))
+    return ws_bytes
+
+
+def _sizes(saved_fn, ws_fn, shape) -> Tuple[int, int]:
+    """(saved bytes, workspace bytes) as the library's two sizing calls answer: (0, 0) for a shape the kernels do not cover."""
+    return int(saved_fn(C.byref(shape))), int(ws_fn(C.byref(shape)))
+
+
+def _out_saved_ws(x: Tensor, shape, saved_fn, need_saved: bool, ws_bytes: int):
+    """What a module forward allocates: (out like x, the saved blob or None, the workspace)."""
+    out = torch.empty_like(x)
+    saved = _blob(saved_fn(C.byref(shape)), x.device) if need_saved else None
+    return out, saved, _ws(ws_bytes, x.device)
+
+
+def _out_ws(x: Tensor, ws_bytes: int):
+    """What a module backward, or a forward that saves nothing, allocates: (dx / out like x, the workspace)."""
+    return torch.empty_like(x), _ws(ws_bytes, x.device)
+
+
+def _plan_report(fn, shape, who: str, keys: Sequence[str], first: int, sections: Sequence[str], saved=None,
+                 tail: Sequence[str] = ("workspace", "saved_bytes")) -> dict:
+    """Decodes the out[64] report of a module's mi_*_plan (the wire format: plan_report in csrc/internal.h): the scalars named by
+    ``keys`` from slot 0, ``sections`` as (byte offset, bytes) pairs from slot ``first``, the saved blob's sections
+    (``saved`` = (first slot, names)) where the module reports them, and the values from slot 60 on named by ``tail``."""
+    out = (L.c_i64 * 64)()
+    L.check(fn(C.byref(shape), out), who)
+    return _decode_report(out, keys, first, sections, saved, tail, 60)
+
+
+def _decode_report(out, keys, first, sections, saved, tail, tail_at) -> dict:
+    def pairs(at, names):
+        return {n: (int(out[at + 2 * i]), int(out[at + 2 * i + 1])) for i, n in enumerate(names)}
+    plan = {k: int(out[i]) for i, k in enumerate(keys)}
+    plan["sections"] = pairs(first, sections)
+    if saved is not None:
+        plan["saved_sections"] = pairs(*saved)
+    plan.update((k, int(out[tail_at + i])) for i, k in enumerate(tail))
+    return plan
+
+
 # ----------------------------------------------------------------------------- LayerNorm
 def ln_fwd(x: Tensor, w: Tensor, b: Optional[Tensor], with_bias: bool, want_stats: bool = True):
     _gpu(x, w, b)
@@ -694,8 +741,7 @@ def _tksa_shape(x: Tensor, heads: int, topk: Sequence[int]) -> L.TksaShape:
 def tksa_sizes(B: int, Cc: int, heads: int, H: int, W: int, dtype: torch.dtype, topk: Sequence[int]) -> Tuple[int, int]:
     """(saved bytes, workspace bytes) of one TKSA call; (0, 0) for a shape the kernels do not cover.  No GPU needed."""
     s = L.TksaShape(B, Cc, heads, H, W, _dtype_code(dtype), *[int(k) for k in topk])
-    lib = L.lib()
-    return int(lib.mi_tksa_saved_bytes(C.byref(s))), int(lib.mi_tksa_workspace(C.byref(s)))
+    return _sizes(L.lib().mi_tksa_saved_bytes, L.lib().mi_tksa_workspace, s)
 
 
 def tksa_fwd(x: Tensor, residual: Optional[Tensor], params: Sequence[Optional[Tensor]], heads: int, topk: Sequence[int],
@@ -709,9 +755,7 @@ def tksa_fwd(x: Tensor, residual: Optional[Tensor], params: Sequence[Optional[Te
     ws_bytes = lib.mi_tksa_workspace(C.byref(s))
     if ws_bytes == 0:
         L.check(-1, "tksa_workspace")
-    out = torch.empty_like(x)
-    saved = _blob(lib.mi_tksa_saved_bytes(C.byref(s)), x.device) if need_saved else None
-    ws = _ws(ws_bytes, x.device)
+    out, saved, ws = _out_saved_ws(x, s, lib.mi_tksa_saved_bytes, need_saved, ws_bytes)
     c = x.shape[1] // heads
     scores = torch.empty((x.shape[0], heads, c, c), dtype=torch.float32, device=x.device) if want_scores else None
     pp = _mdta_params(params[:7])
@@ -727,12 +771,11 @@ def tksa_bwd(x: Tensor, dout: Tensor, params: Sequence[Optional[Tensor]], heads:
     _gpu(x, dout, saved, *params, *grads)
     s = _tksa_shape(x, heads, topk)
     lib = L.lib()
-    dx = torch.empty_like(x)
+    dx, ws = _out_ws(x, lib.mi_tksa_workspace(C.byref(s)))
     pp = _mdta_params(params[:7])
     tp = _f32_struct(L.TksaParams, params[7:11], "TKSA parameter")
     gg = _f32_struct(L.MdtaGrads, grads[:7], "TKSA gradient", int(accumulate))
     tg = _f32_struct(L.TksaGrads, grads[7:11], "TKSA gradient")
-    ws = _ws(lib.mi_tksa_workspace(C.byref(s)), x.device)
     L.check(lib.mi_tksa_bwd(C.byref(s), C.byref(pp), C.byref(tp), _p(x), _p(dout), _p(dx), C.byref(gg), C.byref(tg), _p(saved),
                             _p(ws), _stream()), "tksa_bwd")
     return dx
@@ -749,9 +792,7 @@ def msfn_fwd(x: Tensor, residual: Optional[Tensor], params: Sequence[Optional[Te
     _gpu(x, residual, *params)
     s = _msfn_shape(x, params[6].shape[0])
     lib = L.lib()
-    out = torch.empty_like(x)
-    saved = _blob(lib.mi_msfn_saved_bytes(C.byref(s)), x.device) if need_saved else None
-    ws = _ws(lib.mi_msfn_workspace(C.byref(s)), x.device)
+    out, saved, ws = _out_saved_ws(x, s, lib.mi_msfn_saved_bytes, need_saved, lib.mi_msfn_workspace(C.byref(s)))
     pp = _f32_struct(L.MsfnParams, params, "MSFN parameter")
     L.check(lib.mi_msfn_fwd(C.byref(s), C.byref(pp), _p(x), _p(residual), _p(out), _p(saved), _p(ws), _stream()), "msfn_fwd")
     return out, saved
@@ -773,10 +814,9 @@ def msfn_bwd(x: Tensor, dout: Tensor, params: Sequence[Optional[Tensor]], saved:
     _gpu(x, dout, saved, *params, *grads)
     s = _msfn_shape(x, params[6].shape[0])
     lib = L.lib()
-    dx = torch.empty_like(x)
+    dx, ws = _out_ws(x, lib.mi_msfn_workspace(C.byref(s)))
     pp = _f32_struct(L.MsfnParams, params, "MSFN parameter")
     gg = _f32_struct(L.MsfnGrads, grads, "MSFN gradient", int(accumulate))
-    ws = _ws(lib.mi_msfn_workspace(C.byref(s)), x.device)
     L.check(lib.mi_msfn_bwd(C.byref(s), C.byref(pp), _p(x), _p(dout), _p(dx), C.byref(gg), _p(saved), _p(ws), _stream()),
             "msfn_bwd")
     return dx
@@ -911,8 +951,7 @@ _dblock_shape = functools.partial(_block_shape, L.DblockShape)
 def dblock_sizes(B: int, Cc: int, H: int, W: int, dtype: torch.dtype, dilations: Sequence[int], extra: bool) -> Tuple[int, int]:
     """(saved bytes, workspace bytes) of one DBlock; (0, 0) for a shape the kernels do not cover.  No GPU needed."""
     s = _dblock_shape(B, Cc, H, W, _dtype_code(dtype), dilations, extra)
-    lib = L.lib()
-    return int(lib.mi_dblock_saved_bytes(C.byref(s))), int(lib.mi_dblock_workspace(C.byref(s)))
+    return _sizes(L.lib().mi_dblock_saved_bytes, L.lib().mi_dblock_workspace, s)
 
 
 # mi_dblock_params / mi_dblock_grads from the flat list: norm1 (2), conv1 (2), extra_conv (2, None without it), the branches'
@@ -929,9 +968,7 @@ def dblock_fwd(x: Tensor, params: Sequence[Optional[Tensor]], dilations: Sequenc
     ws_bytes = lib.mi_dblock_workspace(C.byref(s))
     if ws_bytes == 0:
         L.check(-1, "dblock_workspace")
-    out = torch.empty_like(x)
-    saved = _blob(lib.mi_dblock_saved_bytes(C.byref(s)), x.device) if need_saved else None
-    ws = _ws(ws_bytes, x.device)
+    out, saved, ws = _out_saved_ws(x, s, lib.mi_dblock_saved_bytes, need_saved, ws_bytes)
     pp = _dblock_struct(L.DblockParams, params, len(dilations), "DBlock parameter")
     L.check(lib.mi_dblock_fwd(C.byref(s), C.byref(pp), _p(x), _p(out), _p(saved), _p(ws), _stream()), "dblock_fwd")
     return out, saved
@@ -944,10 +981,9 @@ def dblock_bwd(x: Tensor, dout: Tensor, params: Sequence[Optional[Tensor]], dila
     B, Cc, H, W = x.shape
     s = _dblock_shape(B, Cc, H, W, _dt(x), dilations, extra)
     lib = L.lib()
-    dx = torch.empty_like(x)
+    dx, ws = _out_ws(x, lib.mi_dblock_workspace(C.byref(s)))
     pp = _dblock_struct(L.DblockParams, params, len(dilations), "DBlock parameter")
     gg = _dblock_struct(L.DblockGrads, grads, len(dilations), "DBlock gradient", int(accumulate))
-    ws = _ws(lib.mi_dblock_workspace(C.byref(s)), x.device)
     L.check(lib.mi_dblock_bwd(C.byref(s), C.byref(pp), _p(x), _p(dout), _p(dx), C.byref(gg), _p(saved), _p(ws), _stream()), "dblock_bwd")
     return dx
 
@@ -959,6 +995,7 @@ _FREMLP_PLAN_KEYS = ("planes", "K", "hidden", "tile_m", "tile_k", "l_block", "l_
                      "kernels_fwd", "kernels_bwd", "lib_calls_fwd", "lib_calls_bwd")
 _FREMLP_SECTIONS = ("cos_w", "sin_w", "cos_wt", "sin_wt", "wcos_w", "wsin_w", "wcos_wt", "wsin_wt", "cos_h", "sin_h", "T", "U", "Z",
                     "hidden", "m1", "m2", "pw_ws", "gram_ws", "chan_sum_ws")
+_FREMLP_PLAN = dict(keys=_FREMLP_PLAN_KEYS, first=22, sections=_FREMLP_SECTIONS, tail=("workspace", "saved_bytes", "saved_hidden_offset"))
 
 
 def _fremlp_shape(B: int, nc: int, expand: int, H: int, W: int, dtype_code: int) -> L.FremlpShape:
@@ -968,19 +1005,13 @@ def _fremlp_shape(B: int, nc: int, expand: int, H: int, W: int, dtype_code: int)
 def fremlp_plan(B: int, nc: int, expand: int, H: int, W: int, dtype: torch.dtype = torch.float32) -> dict:
     """What fremlp_fwd / fremlp_bwd launch for x [B, nc, H, W] (mi_fremlp_plan: the plan the launchers follow; no GPU work).
     ``sections`` maps each workspace section to its (byte offset, bytes)."""
-    out = (L.c_i64 * 64)()
-    s = _fremlp_shape(B, nc, expand, H, W, _dtype_code(dtype))
-    L.check(L.lib().mi_fremlp_plan(C.byref(s), out), "fremlp_plan")
-    plan = {k: int(out[i]) for i, k in enumerate(_FREMLP_PLAN_KEYS)}
-    plan["sections"] = {n: (int(out[22 + 2 * i]), int(out[23 + 2 * i])) for i, n in enumerate(_FREMLP_SECTIONS)}
-    plan["workspace"], plan["saved_bytes"], plan["saved_hidden_offset"] = int(out[60]), int(out[61]), int(out[62])
-    return plan
+    return _plan_report(L.lib().mi_fremlp_plan, _fremlp_shape(B, nc, expand, H, W, _dtype_code(dtype)), "fremlp_plan", **_FREMLP_PLAN)
 
 
 def fremlp_sizes(B: int, nc: int, expand: int, H: int, W: int, dtype: torch.dtype) -> Tuple[int, int]:
     """(saved bytes, workspace bytes) of one FreMLP; (0, 0) for a shape the kernels do not cover.  No GPU needed."""
     s = _fremlp_shape(B, nc, expand, H, W, _dtype_code(dtype))
-    return int(L.lib().mi_fremlp_saved_bytes(C.byref(s))), int(L.lib().mi_fremlp_workspace(C.byref(s)))
+    return _sizes(L.lib().mi_fremlp_saved_bytes, L.lib().mi_fremlp_workspace, s)
 
 
 def _fremlp_args(x: Tensor, params: Sequence[Tensor]):
@@ -993,10 +1024,7 @@ def _fremlp_args(x: Tensor, params: Sequence[Tensor]):
         raise ValueError(f"fremlp: parameters {tuple(w1.shape)}, {tuple(b1.shape)}, {tuple(w2.shape)}, {tuple(b2.shape)} do not "
                          f"fit nc = {nc}")
     s = _fremlp_shape(B, nc, hc // nc, H, W, _dt(x))
-    ws_bytes = L.lib().mi_fremlp_workspace(C.byref(s))
-    if ws_bytes == 0:
-        raise NotImplementedError("image_restoration_amd: " + L.lib().mi_last_error().decode("utf-8", "replace"))
-    return s, ws_bytes
+    return s, _covered(L.lib().mi_fremlp_workspace, s)
 
 
 def fremlp_fwd(x: Tensor, params: Sequence[Tensor], need_saved: bool):
@@ -1007,9 +1035,7 @@ def fremlp_fwd(x: Tensor, params: Sequence[Tensor], need_saved: bool):
         _f32(t, "FreMLP parameter")
     s, ws_bytes = _fremlp_args(x, params)
     lib = L.lib()
-    out = torch.empty_like(x)
-    saved = _blob(lib.mi_fremlp_saved_bytes(C.byref(s)), x.device) if need_saved else None
-    ws = _ws(ws_bytes, x.device)
+    out, saved, ws = _out_saved_ws(x, s, lib.mi_fremlp_saved_bytes, need_saved, ws_bytes)
     w1, b1, w2, b2 = params
     L.check(lib.mi_fremlp_fwd(C.byref(s), _p(w1), _p(b1), _p(w2), _p(b2), _p(x), _p(out), _p(saved), _p(ws), _stream()), "fremlp_fwd")
     return out, saved
@@ -1022,8 +1048,7 @@ def fremlp_bwd(dout: Tensor, params: Sequence[Tensor], saved: Tensor, grads: Seq
         _f32(t, "FreMLP parameter / gradient")
     s, ws_bytes = _fremlp_args(dout, params)
     lib = L.lib()
-    dx = torch.empty_like(dout)
-    ws = _ws(ws_bytes, dout.device)
+    dx, ws = _out_ws(dout, ws_bytes)
     w1, _, w2, b2 = params
     L.check(lib.mi_fremlp_bwd(C.byref(s), _p(w1), _p(w2), _p(b2), _p(dout), _p(dx), *[_p(g) for g in grads], int(accumulate),
                               _p(saved), _p(ws), _stream()), "fremlp_bwd")
@@ -1036,6 +1061,7 @@ _FU_PLAN_KEYS = ("planes", "K", "channels", "groups", "group_width", "elements",
                  "partials_per_channel", "grid_elements", "grid_bins", "kernels_fwd", "kernels_bwd", "lib_calls_fwd", "lib_calls_bwd")
 _FU_SECTIONS = ("dft_tables", "dft_T", "Z", "U", "t", "ts", "pre", "q", "s", "dlogit", "stat", "bn_partials", "w_fold", "grad_tmp", "bwd_partials",
                 "pw_ws", "gram_ws", "chan_sum_ws")
+_FU_PLAN = dict(keys=_FU_PLAN_KEYS, first=18, sections=_FU_SECTIONS, tail=("workspace", "saved_bytes", "saved_stat_offset"))
 
 
 def _fu_shape(B: int, c: int, groups: int, H: int, W: int, dtype_code: int, training: bool = True, eps: float = 1e-5,
@@ -1046,19 +1072,13 @@ def _fu_shape(B: int, c: int, groups: int, H: int, W: int, dtype_code: int, trai
 def fourier_unit_plan(B: int, c: int, groups: int, H: int, W: int, dtype: torch.dtype = torch.float32) -> dict:
     """What fourier_unit_fwd / fourier_unit_bwd launch for x [B, c, H, W] (mi_fourier_unit_plan; no GPU work).  ``sections`` maps
     each workspace section to its (byte offset, bytes)."""
-    out = (L.c_i64 * 64)()
-    s = _fu_shape(B, c, groups, H, W, _dtype_code(dtype))
-    L.check(L.lib().mi_fourier_unit_plan(C.byref(s), out), "fourier_unit_plan")
-    plan = {k: int(out[i]) for i, k in enumerate(_FU_PLAN_KEYS)}
-    plan["sections"] = {n: (int(out[18 + 2 * i]), int(out[19 + 2 * i])) for i, n in enumerate(_FU_SECTIONS)}
-    plan["workspace"], plan["saved_bytes"], plan["saved_stat_offset"] = int(out[60]), int(out[61]), int(out[62])
-    return plan
+    return _plan_report(L.lib().mi_fourier_unit_plan, _fu_shape(B, c, groups, H, W, _dtype_code(dtype)), "fourier_unit_plan", **_FU_PLAN)
 
 
 def fourier_unit_sizes(B: int, c: int, groups: int, H: int, W: int, dtype: torch.dtype) -> Tuple[int, int]:
     """(saved bytes, workspace bytes) of one FourierUnit; (0, 0) for a shape the kernels do not cover.  No GPU needed."""
     s = _fu_shape(B, c, groups, H, W, _dtype_code(dtype))
-    return int(L.lib().mi_fourier_unit_saved_bytes(C.byref(s))), int(L.lib().mi_fourier_unit_workspace(C.byref(s)))
+    return _sizes(L.lib().mi_fourier_unit_saved_bytes, L.lib().mi_fourier_unit_workspace, s)
 
 
 def _fu_args(x: Tensor, params: Sequence[Tensor], training: bool, eps: float, momentum: float):
@@ -1072,10 +1092,7 @@ def _fu_args(x: Tensor, params: Sequence[Tensor], training: bool, eps: float, mo
             tuple(fdc_w.shape[:2]) != (G * C2, C2 // G) or gate_w.numel() != G * C2 or fpe_w.numel() != 9 * C2:
         raise ValueError(f"fourier_unit: parameters {[tuple(p.shape) for p in params]} do not fit c = {c}")
     s = _fu_shape(B, c, G, H, W, _dt(x), training, eps, momentum)
-    ws_bytes = L.lib().mi_fourier_unit_workspace(C.byref(s))
-    if ws_bytes == 0:
-        raise NotImplementedError("image_restoration_amd: " + L.lib().mi_last_error().decode("utf-8", "replace"))
-    return s, ws_bytes
+    return s, _covered(L.lib().mi_fourier_unit_workspace, s)
 
 
 def fourier_unit_fwd(x: Tensor, params: Sequence[Tensor], running_mean: Tensor, running_var: Tensor, training: bool,
@@ -1089,9 +1106,7 @@ def fourier_unit_fwd(x: Tensor, params: Sequence[Tensor], running_mean: Tensor, 
     if running_mean.numel() != 2 * x.shape[1] or running_var.numel() != 2 * x.shape[1]:
         raise ValueError("fourier_unit: the running statistics must hold 2c values")
     lib = L.lib()
-    out = torch.empty_like(x)
-    saved = _blob(lib.mi_fourier_unit_saved_bytes(C.byref(s)), x.device) if need_saved else None
-    ws = _ws(ws_bytes, x.device)
+    out, saved, ws = _out_saved_ws(x, s, lib.mi_fourier_unit_saved_bytes, need_saved, ws_bytes)
     pp = _f32_struct(L.FourierUnitParams, params, "FourierUnit parameter")
     L.check(lib.mi_fourier_unit_fwd(C.byref(s), C.byref(pp), _p(x), _p(out), _p(running_mean), _p(running_var), _p(saved), _p(ws),
                                     _stream()), "fourier_unit_fwd")
@@ -1104,8 +1119,7 @@ def fourier_unit_bwd(dout: Tensor, params: Sequence[Tensor], saved: Tensor, grad
     _gpu(dout, saved, *params, *grads)
     s, ws_bytes = _fu_args(dout, params, training, eps, momentum)
     lib = L.lib()
-    dx = torch.empty_like(dout)
-    ws = _ws(ws_bytes, dout.device)
+    dx, ws = _out_ws(dout, ws_bytes)
     pp = _f32_struct(L.FourierUnitParams, params, "FourierUnit parameter")
     gg = _f32_struct(L.FourierUnitGrads, grads, "FourierUnit gradient", int(accumulate))
     L.check(lib.mi_fourier_unit_bwd(C.byref(s), C.byref(pp), _p(dout), _p(dx), C.byref(gg), _p(saved), _p(ws), _stream()),
@@ -1119,16 +1133,16 @@ _SF_PLAN_KEYS = ("tile_w", "tile_h", "segments", "segment_width", "halo0", "halo
                  "grid_y", "grid_z", "splits", "partial_rows", "partial_cols", "kernels_fwd", "kernels_bwd", "lib_calls_fwd",
                  "lib_calls_bwd", "lds_fwd", "lds_bwd", "block")
 _SF_SECTIONS = ("pw_ws", "gram_ws", "chan_sum_ws", "partials", "g", "dg", "dh")
+_SF_PLAN = dict(keys=_SF_PLAN_KEYS, first=24, sections=_SF_SECTIONS, tail=("workspace", "saved_bytes", "saved_u_offset"))
 
 
 def _sf_plan(fn, shape, who: str) -> dict:
-    out = (L.c_i64 * 64)()
-    L.check(fn(C.byref(shape), out), who)
-    plan = {k: int(out[i]) for i, k in enumerate(_SF_PLAN_KEYS)}
-    plan["halo"] = tuple(plan.pop(f"halo{k}") for k in range(4))[:plan["segments"]]
-    plan["sections"] = {n: (int(out[24 + 2 * i]), int(out[25 + 2 * i])) for i, n in enumerate(_SF_SECTIONS)}
-    plan["workspace"], plan["saved_bytes"], plan["saved_u_offset"] = int(out[60]), int(out[61]), int(out[62])
-    return plan
+    """The report with the four halo scalars folded into one ``halo`` tuple, one entry per segment, after the other scalars."""
+    plan = _plan_report(fn, shape, who, **_SF_PLAN)
+    halo = tuple(plan.pop(f"halo{k}") for k in range(4))[:plan["segments"]]
+    items = list(plan.items())
+    at = list(plan).index("sections")
+    return dict(items[:at] + [("halo", halo)] + items[at:])
 
 
 def sfh_ffn_plan(B: int, dim: int, H: int, W: int, dtype: torch.dtype = torch.float32) -> dict:
@@ -1145,7 +1159,7 @@ def sfh_local_plan(B: int, dim: int, H: int, W: int, dtype: torch.dtype = torch.
 def sfh_ffn_sizes(B: int, dim: int, H: int, W: int, dtype: torch.dtype) -> Tuple[int, int]:
     """(saved bytes, workspace bytes) of one SFHformer FFN; (0, 0) for a shape the kernels do not cover.  No GPU needed."""
     s = L.SfhFfnShape(B, dim, H, W, _dtype_code(dtype))
-    return int(L.lib().mi_sfh_ffn_saved_bytes(C.byref(s))), int(L.lib().mi_sfh_ffn_workspace(C.byref(s)))
+    return _sizes(L.lib().mi_sfh_ffn_saved_bytes, L.lib().mi_sfh_ffn_workspace, s)
 
 
 def _sf_args(x: Tensor, params: Sequence[Tensor], local: bool):
@@ -1161,10 +1175,7 @@ def _sf_args(x: Tensor, params: Sequence[Tensor], local: bool):
         raise ValueError(f"sfh: parameters {[tuple(p.shape) for p in params]} do not fit dim = {dim}")
     lib = L.lib()
     shape = (L.SfhLocalShape if local else L.SfhFfnShape)(B, dim, H, W, _dt(x))
-    ws_bytes = (lib.mi_sfh_local_workspace if local else lib.mi_sfh_ffn_workspace)(C.byref(shape))
-    if ws_bytes == 0:
-        raise NotImplementedError("image_restoration_amd: " + lib.mi_last_error().decode("utf-8", "replace"))
-    return shape, ws_bytes
+    return shape, _covered(lib.mi_sfh_local_workspace if local else lib.mi_sfh_ffn_workspace, shape)
 
 
 def sfh_ffn_fwd(x: Tensor, params: Sequence[Tensor], need_saved: bool):
@@ -1173,9 +1184,7 @@ def sfh_ffn_fwd(x: Tensor, params: Sequence[Tensor], need_saved: bool):
     _gpu(x, *params)
     s, ws_bytes = _sf_args(x, params, False)
     lib = L.lib()
-    out = torch.empty_like(x)
-    saved = _blob(lib.mi_sfh_ffn_saved_bytes(C.byref(s)), x.device) if need_saved else None
-    ws = _ws(ws_bytes, x.device)
+    out, saved, ws = _out_saved_ws(x, s, lib.mi_sfh_ffn_saved_bytes, need_saved, ws_bytes)
     pp = _f32_struct(L.SfhFfnParams, params, "SFHformer FFN parameter")
     L.check(lib.mi_sfh_ffn_fwd(C.byref(s), C.byref(pp), _p(x), _p(out), _p(saved), _p(ws), _stream()), "sfh_ffn_fwd")
     return out, saved
@@ -1186,8 +1195,7 @@ def sfh_ffn_bwd(x: Tensor, dout: Tensor, params: Sequence[Tensor], saved: Tensor
     _gpu(x, dout, saved, *params, *grads)
     s, ws_bytes = _sf_args(x, params, False)
     lib = L.lib()
-    dx = torch.empty_like(x)
-    ws = _ws(ws_bytes, x.device)
+    dx, ws = _out_ws(x, ws_bytes)
     pp = _f32_struct(L.SfhFfnParams, params, "SFHformer FFN parameter")
     gg = _f32_struct(L.SfhFfnGrads, grads, "SFHformer FFN gradient", int(accumulate))
     L.check(lib.mi_sfh_ffn_bwd(C.byref(s), C.byref(pp), _p(x), _p(dout), _p(dx), C.byref(gg), _p(saved), _p(ws), _stream()),
@@ -1199,8 +1207,7 @@ def sfh_local_fwd(x: Tensor, params: Sequence[Tensor]) -> Tensor:
     """SFHformer TokenMixer_For_Local.forward.  params: CDilated_1 and CDilated_2 weights and biases.  Saves nothing but x."""
     _gpu(x, *params)
     s, ws_bytes = _sf_args(x, params, True)
-    out = torch.empty_like(x)
-    ws = _ws(ws_bytes, x.device)
+    out, ws = _out_ws(x, ws_bytes)
     pp = _f32_struct(L.SfhLocalParams, params, "SFHformer local mixer parameter")
     L.check(L.lib().mi_sfh_local_fwd(C.byref(s), C.byref(pp), _p(x), _p(out), _p(ws), _stream()), "sfh_local_fwd")
     return out
@@ -1210,8 +1217,7 @@ def sfh_local_bwd(x: Tensor, dout: Tensor, params: Sequence[Tensor], grads: Sequ
     """Backward of sfh_local_fwd: dx; the four parameter gradients are written (accumulate: added) into ``grads``."""
     _gpu(x, dout, *params, *grads)
     s, ws_bytes = _sf_args(x, params, True)
-    dx = torch.empty_like(x)
-    ws = _ws(ws_bytes, x.device)
+    dx, ws = _out_ws(x, ws_bytes)
     pp = _f32_struct(L.SfhLocalParams, params, "SFHformer local mixer parameter")
     gg = _f32_struct(L.SfhLocalGrads, grads, "SFHformer local mixer gradient", int(accumulate))
     L.check(L.lib().mi_sfh_local_bwd(C.byref(s), C.byref(pp), _p(x), _p(dout), _p(dx), C.byref(gg), _p(ws), _stream()),
@@ -1226,6 +1232,7 @@ _SM_PLAN_KEYS = ("mode", "B", "dim", "channels", "N", "pool", "grid_flat_dim", "
 _SM_SECTIONS = ("pw_ws", "gram_ws", "chan_sum_ws", "fu_ws", "local_ws", "p", "f", "g", "small", "fold", "gram_out", "pool_partials",
                 "scratch")
 _SM_SAVED = ("a", "b", "l", "u1", "r", "u2", "fu_blob")
+_SM_PLAN = dict(keys=_SM_PLAN_KEYS, first=16, sections=_SM_SECTIONS, saved=(44, _SM_SAVED))
 
 
 def _sm_shape(B: int, dim: int, H: int, W: int, dtype_code: int, training: bool = True, eps: float = 1e-5,
@@ -1233,37 +1240,27 @@ def _sm_shape(B: int, dim: int, H: int, W: int, dtype_code: int, training: bool 
     return L.SfhMixerShape(B, dim, H, W, dtype_code, int(training), eps, momentum)
 
 
-def _sm_plan(fn, shape, who: str) -> dict:
-    out = (L.c_i64 * 64)()
-    L.check(fn(C.byref(shape), out), who)
-    plan = {k: int(out[i]) for i, k in enumerate(_SM_PLAN_KEYS)}
-    plan["sections"] = {n: (int(out[16 + 2 * i]), int(out[17 + 2 * i])) for i, n in enumerate(_SM_SECTIONS)}
-    plan["saved_sections"] = {n: (int(out[44 + 2 * i]), int(out[45 + 2 * i])) for i, n in enumerate(_SM_SAVED)}
-    plan["workspace"], plan["saved_bytes"] = int(out[60]), int(out[61])
-    return plan
-
-
 def sfh_global_plan(B: int, dim: int, H: int, W: int, dtype: torch.dtype = torch.float32) -> dict:
     """What sfh_global_fwd / sfh_global_bwd launch for x [B, dim, H, W] (mi_sfh_global_plan; no GPU work): grids, launch counts,
     ``sections`` (workspace) and ``saved_sections`` (the blob), each name -> (byte offset, bytes)."""
-    return _sm_plan(L.lib().mi_sfh_global_plan, _sm_shape(B, dim, H, W, _dtype_code(dtype)), "sfh_global_plan")
+    return _plan_report(L.lib().mi_sfh_global_plan, _sm_shape(B, dim, H, W, _dtype_code(dtype)), "sfh_global_plan", **_SM_PLAN)
 
 
 def sfh_mixer_plan(B: int, dim: int, H: int, W: int, dtype: torch.dtype = torch.float32) -> dict:
     """The same for sfh_mixer_fwd / sfh_mixer_bwd (mi_sfh_mixer_plan)."""
-    return _sm_plan(L.lib().mi_sfh_mixer_plan, _sm_shape(B, dim, H, W, _dtype_code(dtype)), "sfh_mixer_plan")
+    return _plan_report(L.lib().mi_sfh_mixer_plan, _sm_shape(B, dim, H, W, _dtype_code(dtype)), "sfh_mixer_plan", **_SM_PLAN)
 
 
 def sfh_global_sizes(B: int, dim: int, H: int, W: int, dtype: torch.dtype) -> Tuple[int, int]:
     """(saved bytes, workspace bytes) of one TokenMixer_For_Gloal; (0, 0) for a shape the kernels do not cover.  No GPU needed."""
     s = _sm_shape(B, dim, H, W, _dtype_code(dtype))
-    return int(L.lib().mi_sfh_global_saved_bytes(C.byref(s))), int(L.lib().mi_sfh_global_workspace(C.byref(s)))
+    return _sizes(L.lib().mi_sfh_global_saved_bytes, L.lib().mi_sfh_global_workspace, s)
 
 
 def sfh_mixer_sizes(B: int, dim: int, H: int, W: int, dtype: torch.dtype) -> Tuple[int, int]:
     """(saved bytes, workspace bytes) of one Mixer; (0, 0) for a shape the kernels do not cover.  No GPU needed."""
     s = _sm_shape(B, dim, H, W, _dtype_code(dtype))
-    return int(L.lib().mi_sfh_mixer_saved_bytes(C.byref(s))), int(L.lib().mi_sfh_mixer_workspace(C.byref(s)))
+    return _sizes(L.lib().mi_sfh_mixer_saved_bytes, L.lib().mi_sfh_mixer_workspace, s)
 
 
 def _sm_global_shapes(dim: int):
@@ -1288,10 +1285,7 @@ def _sm_args(x: Tensor, params: Sequence[Tensor], mixer: bool, training: bool, e
         raise ValueError(f"sfh: parameters {[tuple(p.shape) for p in params]} do not fit dim = {dim}")
     lib = L.lib()
     shape = _sm_shape(B, dim, H, W, _dt(x), training, eps, momentum)
-    ws_bytes = (lib.mi_sfh_mixer_workspace if mixer else lib.mi_sfh_global_workspace)(C.byref(shape))
-    if ws_bytes == 0:
-        raise NotImplementedError("image_restoration_amd: " + lib.mi_last_error().decode("utf-8", "replace"))
-    return shape, ws_bytes
+    return shape, _covered(lib.mi_sfh_mixer_workspace if mixer else lib.mi_sfh_global_workspace, shape)
 
 
 def _sm_fwd(mixer: bool, x, params, running_mean, running_var, training, need_saved, eps, momentum):
@@ -1301,11 +1295,9 @@ def _sm_fwd(mixer: bool, x, params, running_mean, running_var, training, need_sa
     if running_mean.numel() != 4 * x.shape[1] or running_var.numel() != 4 * x.shape[1]:
         raise ValueError("sfh: the running statistics must hold 4 dim values")
     lib = L.lib()
-    out = torch.empty_like(x)
     sized, fwd, cls, who = ((lib.mi_sfh_mixer_saved_bytes, lib.mi_sfh_mixer_fwd, L.SfhMixerParams, "sfh_mixer_fwd") if mixer else
                             (lib.mi_sfh_global_saved_bytes, lib.mi_sfh_global_fwd, L.SfhGlobalParams, "sfh_global_fwd"))
-    saved = _blob(sized(C.byref(s)), x.device) if need_saved else None
-    ws = _ws(ws_bytes, x.device)
+    out, saved, ws = _out_saved_ws(x, s, sized, need_saved, ws_bytes)
     pp = _f32_struct(cls, params, "SFHformer mixer parameter")
     L.check(fwd(C.byref(s), C.byref(pp), _p(x), _p(out), _p(running_mean), _p(running_var), _p(saved), _p(ws), _stream()), who)
     return out, saved
@@ -1315,8 +1307,7 @@ def _sm_bwd(mixer: bool, x, dout, params, saved, grads, accumulate, training, ep
     _gpu(x, dout, saved, *params, *grads)
     s, ws_bytes = _sm_args(x, params, mixer, training, eps, momentum)
     lib = L.lib()
-    dx = torch.empty_like(x)
-    ws = _ws(ws_bytes, x.device)
+    dx, ws = _out_ws(x, ws_bytes)
     bwd, pcls, gcls, who = ((lib.mi_sfh_mixer_bwd, L.SfhMixerParams, L.SfhMixerGrads, "sfh_mixer_bwd") if mixer else
                             (lib.mi_sfh_global_bwd, L.SfhGlobalParams, L.SfhGlobalGrads, "sfh_global_bwd"))
     pp = _f32_struct(pcls, params, "SFHformer mixer parameter")
@@ -1357,6 +1348,7 @@ BN2D_MAX_C = 4096
 _BN_PLAN_KEYS = ("B", "C", "N", "dtype", "training", "block", "chunk", "chunks_per_plane", "partials_per_channel", "vector_width",
                  "chunks", "grid_chunks", "grid_channels", "launches_fwd", "launches_fwd_part_in", "launches_bwd")
 _BN_SECTIONS = ("partials", "stat", "bwd_means")
+_BN_PLAN = dict(keys=_BN_PLAN_KEYS, first=16, sections=_BN_SECTIONS, tail=("workspace", "stat_bytes", "pair_bytes"))
 
 
 def _bn_shape(B: int, Cn: int, H: int, W: int, dtype_code: int, training: bool = True, eps: float = 1e-5,
@@ -1364,25 +1356,16 @@ def _bn_shape(B: int, Cn: int, H: int, W: int, dtype_code: int, training: bool =
     return L.Bn2dShape(B, Cn, H, W, dtype_code, int(training), eps, momentum)
 
 
-def _bn_plan(fn, shape, who: str) -> dict:
-    out = (L.c_i64 * 64)()
-    L.check(fn(C.byref(shape), out), who)
-    plan = {k: int(out[i]) for i, k in enumerate(_BN_PLAN_KEYS)}
-    plan["sections"] = {n: (int(out[16 + 2 * i]), int(out[17 + 2 * i])) for i, n in enumerate(_BN_SECTIONS)}
-    plan["workspace"], plan["stat_bytes"], plan["pair_bytes"] = int(out[60]), int(out[61]), int(out[62])
-    return plan
-
-
 def bn2d_plan(B: int, Cn: int, H: int, W: int, dtype: torch.dtype = torch.float32, training: bool = True) -> dict:
     """What bn2d_fwd / bn2d_bwd launch for x [B, C, H, W] (mi_bn2d_plan; no GPU work): the chunk size, chunks per plane, partials per
     channel, the vector width the shape allows, grids, launch counts; ``sections`` maps each workspace section to its (byte offset,
     bytes); ``pair_bytes``: what ``part_in`` / ``part_out`` hold."""
-    return _bn_plan(L.lib().mi_bn2d_plan, _bn_shape(B, Cn, H, W, _dtype_code(dtype), training), "bn2d_plan")
+    return _plan_report(L.lib().mi_bn2d_plan, _bn_shape(B, Cn, H, W, _dtype_code(dtype), training), "bn2d_plan", **_BN_PLAN)
 
 
 def scale_res_plan(B: int, Cn: int, H: int, W: int, dtype: torch.dtype = torch.float32) -> dict:
     """The same for scale_res_fwd / scale_res_bwd (mi_scale_res_plan); its workspace holds the backward's partial sums only."""
-    return _bn_plan(L.lib().mi_scale_res_plan, _bn_shape(B, Cn, H, W, _dtype_code(dtype)), "scale_res_plan")
+    return _plan_report(L.lib().mi_scale_res_plan, _bn_shape(B, Cn, H, W, _dtype_code(dtype)), "scale_res_plan", **_BN_PLAN)
 
 
 def bn2d_workspace(B: int, Cn: int, H: int, W: int, dtype: torch.dtype, training: bool = True) -> int:
@@ -1405,10 +1388,7 @@ def _bn_args(who: str, x: Tensor, per_channel: Sequence[Optional[Tensor]], sizer
         if t is not None and _f32(t, f"{who} parameter / statistic").numel() != Cn:
             raise ValueError(f"{who}: a per-channel tensor of shape {tuple(t.shape)} does not fit C = {Cn}")
     s = _bn_shape(B, Cn, H, W, _dt(x), training, eps, momentum)
-    ws_bytes = sizer(C.byref(s))
-    if ws_bytes == 0:
-        raise NotImplementedError("image_restoration_amd: " + L.lib().mi_last_error().decode("utf-8", "replace"))
-    return s, ws_bytes
+    return s, _covered(sizer, s)
 
 
 def _same(who: str, x: Tensor, *others: Optional[Tensor]) -> None:
@@ -1446,8 +1426,7 @@ def bn2d_bwd(x: Tensor, dy: Tensor, weight: Tensor, stat: Tensor, grads: Sequenc
     s, ws_bytes = _bn_args("bn2d", x, (weight, dw, db), lib.mi_bn2d_workspace, training, eps, momentum)
     if _f32(stat, "bn2d stat").numel() != 2 * x.shape[1]:
         raise ValueError("bn2d: stat must hold 2C values")
-    dx = torch.empty_like(x)
-    ws = _ws(ws_bytes, x.device)
+    dx, ws = _out_ws(x, ws_bytes)
     L.check(lib.mi_bn2d_bwd(C.byref(s), _p(weight), _p(x), _p(dy), _p(dres), _p(dx), _p(dw), _p(db), int(accumulate), _p(stat), _p(ws),
                             _stream()), "bn2d_bwd")
     return dx
@@ -1530,8 +1509,7 @@ _eblock_shape = functools.partial(_block_shape, L.EblockShape)
 def eblock_sizes(B: int, Cc: int, H: int, W: int, dtype: torch.dtype, dilations: Sequence[int], extra: bool) -> Tuple[int, int]:
     """(saved bytes, workspace bytes) of one EBlock; (0, 0) for a shape the kernels do not cover.  No GPU needed."""
     s = _eblock_shape(B, Cc, H, W, _dtype_code(dtype), dilations, extra)
-    lib = L.lib()
-    return int(lib.mi_eblock_saved_bytes(C.byref(s))), int(lib.mi_eblock_workspace(C.byref(s)))
+    return _sizes(L.lib().mi_eblock_saved_bytes, L.lib().mi_eblock_workspace, s)
 
 
 def eblock_plan(B: int, Cc: int, H: int, W: int, dtype: torch.dtype, dilations: Sequence[int], extra: bool) -> dict:
@@ -1552,10 +1530,7 @@ def _eblock_args(x: Tensor, dilations: Sequence[int], extra: bool):
         raise ValueError(f"eblock: x must be [B, c, H, W], got {tuple(x.shape)}")
     B, Cc, H, W = x.shape
     s = _eblock_shape(B, Cc, H, W, _dt(x), dilations, extra)
-    ws_bytes = L.lib().mi_eblock_workspace(C.byref(s))
-    if ws_bytes == 0:
-        raise NotImplementedError("image_restoration_amd: " + L.lib().mi_last_error().decode("utf-8", "replace"))
-    return s, ws_bytes
+    return s, _covered(L.lib().mi_eblock_workspace, s)
 
 
 def eblock_fwd(x: Tensor, params: Sequence[Optional[Tensor]], dilations: Sequence[int], extra: bool, need_saved: bool):
@@ -1563,9 +1538,7 @@ def eblock_fwd(x: Tensor, params: Sequence[Optional[Tensor]], dilations: Sequenc
     _gpu(x, *params)
     s, ws_bytes = _eblock_args(x, dilations, extra)
     lib = L.lib()
-    out = torch.empty_like(x)
-    saved = _blob(lib.mi_eblock_saved_bytes(C.byref(s)), x.device) if need_saved else None
-    ws = _ws(ws_bytes, x.device)
+    out, saved, ws = _out_saved_ws(x, s, lib.mi_eblock_saved_bytes, need_saved, ws_bytes)
     pp = _eblock_struct(L.EblockParams, params, len(dilations), "EBlock parameter")
     L.check(lib.mi_eblock_fwd(C.byref(s), C.byref(pp), _p(x), _p(out), _p(saved), _p(ws), _stream()), "eblock_fwd")
     return out, saved
@@ -1577,10 +1550,9 @@ def eblock_bwd(x: Tensor, dout: Tensor, params: Sequence[Optional[Tensor]], dila
     _gpu(x, dout, saved, *params, *grads)
     s, ws_bytes = _eblock_args(x, dilations, extra)
     lib = L.lib()
-    dx = torch.empty_like(x)
+    dx, ws = _out_ws(x, ws_bytes)
     pp = _eblock_struct(L.EblockParams, params, len(dilations), "EBlock parameter")
     gg = _eblock_struct(L.EblockGrads, grads, len(dilations), "EBlock gradient", int(accumulate))
-    ws = _ws(ws_bytes, x.device)
     L.check(lib.mi_eblock_bwd(C.byref(s), C.byref(pp), _p(x), _p(dout), _p(dx), C.byref(gg), _p(saved), _p(ws), _stream()), "eblock_bwd")
     return dx
 
@@ -2417,10 +2389,7 @@ def fft_l1_plan(B: int, C: int, H: int, W: int, dtype: torch.dtype = torch.float
     keys = ("planes", "K", "tile_m", "tile_k", "l_block", "l_blocks", "x_block", "x_blocks", "m_tiles_folded", "m_tiles_plane",
             "grid_tables", "grid_stage1", "grid_stage2", "grid_stage3", "grid_stage4", "block", "partials", "reduce_launches",
             "launches")
-    plan = {k: int(out[i]) for i, k in enumerate(keys)}
-    plan["sections"] = {n: (int(out[19 + 2 * i]), int(out[20 + 2 * i])) for i, n in enumerate(_FFT_L1_SECTIONS)}
-    plan["workspace"] = int(out[39])
-    return plan
+    return _decode_report(out, keys, 19, _FFT_L1_SECTIONS, None, ("workspace",), 39)      # (its own report: out[40], one tail value)
 
 
 def fft_l1_loss(pred: Tensor, target: Tensor, loss_weight: float = 1.0, want_grad: bool = True):

@@ -14,6 +14,7 @@ sys.path.insert(0, HERE)
 sys.path.insert(0, ROOT)
 
 import bn2d_ref as R  # noqa: E402
+from plan_checks import sections_tile, up256 as up  # noqa: E402
 from test_sfh_fu_cabi import _exported  # noqa: E402  (the ELF dynamic-symbol reader)
 
 SYMBOLS = {p: tuple(f"mi_{p}_{n}" for n in ("workspace", "plan", "fwd", "bwd")) for p in ("bn2d", "scale_res")}
@@ -63,7 +64,6 @@ def test_plans_are_consistent_with_the_sizing_calls(lib, dtype):
     from image_restoration_amd import ops
     assert ops.BN2D_MAX_C == 4096
     V = R.vec_width(dtype)
-    up = lambda n: -(-n // 256) * 256   # noqa: E731
     for B, Cn, H, W in SWEEP:
         N = H * W
         nchunk = -(-N // R.CHUNK)
@@ -77,12 +77,10 @@ def test_plans_are_consistent_with_the_sizing_calls(lib, dtype):
             assert (p["launches_fwd"], p["launches_fwd_part_in"], p["launches_bwd"]) == ((3, 2, 3) if training else (1, 1, 3))
             assert p["workspace"] == ops.bn2d_workspace(B, Cn, H, W, dtype, training) > 0
             assert p["stat_bytes"] == 8 * Cn and p["pair_bytes"] == 8 * B * Cn * nchunk
-            sec, end = p["sections"], 0
+            sec = p["sections"]
             assert list(sec) == list(ops._BN_SECTIONS)
-            for name, (off, nbytes) in sec.items():
-                assert off % 256 == 0 and off >= end, name
-                end = off + nbytes
-            assert up(end) == p["workspace"] == sum(up(n) for _, n in sec.values())
+            end, total = sections_tile(sec)
+            assert up(end) == p["workspace"] == total
             assert [n for _, n in sec.values()] == [p["pair_bytes"], 8 * Cn, 8 * Cn]
         q = ops.scale_res_plan(B, Cn, H, W, dtype)
         assert all(q[k] == p[k] for k in ("B", "C", "N", "block", "chunk", "chunks_per_plane", "partials_per_channel", "vector_width", "chunks",

@@ -14,6 +14,7 @@ sys.path.insert(0, HERE)
 sys.path.insert(0, ROOT)
 
 import fremlp_ref as R  # noqa: E402
+from plan_checks import sections_tile  # noqa: E402
 from oracle.fixtures import load  # noqa: E402
 
 SYMBOLS = ("mi_fremlp_workspace", "mi_fremlp_saved_bytes", "mi_fremlp_plan", "mi_fremlp_fwd", "mi_fremlp_bwd", "mi_dft2_workspace",
@@ -68,11 +69,8 @@ def test_plan_is_consistent_with_the_sizing_calls(lib, dtype):
         assert p["saved_hidden_offset"] >= 8 * bins and saved >= p["saved_hidden_offset"] + 4 * expand * bins
         assert saved < (2 + expand) * 4 * bins + 512
         # sections lie in order, 256-byte aligned, inside the workspace, and hold what the launcher puts there
-        sec, end = p["sections"], 0
-        for name, (off, nbytes) in sec.items():
-            assert off % 256 == 0 and off >= end, name
-            end = off + nbytes
-        assert end <= ws
+        sec = p["sections"]
+        assert sections_tile(sec)[0] <= ws
         for name in ("cos_w", "sin_w", "cos_wt", "sin_wt", "wcos_w", "wsin_w", "wcos_wt", "wsin_wt"):
             assert sec[name][1] == 4 * W * K
         assert sec["cos_h"][1] == sec["sin_h"][1] == 4 * H * H

@@ -14,6 +14,8 @@ ROOT = os.path.dirname(HERE)
 sys.path.insert(0, HERE)
 sys.path.insert(0, ROOT)
 
+from plan_checks import sections_tile  # noqa: E402
+
 SYMBOLS = ("mi_fourier_unit_workspace", "mi_fourier_unit_saved_bytes", "mi_fourier_unit_plan", "mi_fourier_unit_fwd",
            "mi_fourier_unit_bwd")
 
@@ -92,11 +94,8 @@ def test_plan_is_consistent_with_the_sizing_calls(lib, dtype):
         assert (p["kernels_fwd"], p["kernels_bwd"], p["lib_calls_fwd"], p["lib_calls_bwd"]) == (11, 14, 1, 6)
         # the blob: Z (two floats per bin and channel), then (mu, r) per spectral channel; nothing else
         assert p["saved_stat_offset"] >= 4 * elems and saved >= p["saved_stat_offset"] + 8 * C2 and saved < 4 * elems + 8 * C2 + 512
-        sec, end = p["sections"], 0
-        for name, (off, nbytes) in sec.items():
-            assert off % 256 == 0 and off >= end, name
-            end = off + nbytes
-        assert end <= ws
+        sec = p["sections"]
+        assert sections_tile(sec)[0] <= ws
         # the transforms' blob: its tables, then its one complex intermediate, contiguous
         assert sec["dft_T"][0] == sec["dft_tables"][0] + sec["dft_tables"][1]
         assert sec["Z"][0] - sec["dft_tables"][0] == lib.lib().mi_dft2_workspace(B, c, H, W)

@@ -15,6 +15,7 @@ sys.path.insert(0, HERE)
 sys.path.insert(0, ROOT)
 
 import sfh_mixer_ref as R  # noqa: E402
+from plan_checks import sections_tile  # noqa: E402
 from test_sfh_fu_cabi import _exported  # noqa: E402  (the ELF dynamic-symbol reader)
 
 KINDS = ("global", "mixer")
@@ -78,11 +79,9 @@ def test_plans_are_consistent_with_the_sizing_calls(lib, dtype):
             assert (p["kernels_fwd"], p["kernels_bwd"], p["lib_calls_fwd"], p["lib_calls_bwd"]) == ((4, 6, 6, 12) if mix else (3, 2, 3, 3))
             assert (p["saved_bytes"], p["workspace"]) == sizes(B, dim, H, W, dtype) and p["workspace"] > 0
             # the workspace: aligned, in order, not overlapping
-            sec, end = p["sections"], 0
+            sec = p["sections"]
             assert list(sec) == list(ops._SM_SECTIONS)
-            for name, (off, nbytes) in sec.items():
-                assert off % 256 == 0 and off >= end, name
-                end = off + nbytes
+            end, _ = sections_tile(sec)
             assert end <= p["workspace"] < end + 256
             plane = B * dim * N * el
             for name, k in WS_PLANES.items():
@@ -96,14 +95,11 @@ def test_plans_are_consistent_with_the_sizing_calls(lib, dtype):
             assert sec["fu_ws"][1] == fu_ws
             assert sec["local_ws"][1] == (ops.sfh_local_plan(B, dim, H, W, dtype)["workspace"] if mix else 0)
             # saved: the documented planes in the activation dtype, then the FourierUnit's blob; the sum of the sections
-            sv, end, total = p["saved_sections"], 0, 0
+            sv = p["saved_sections"]
             assert list(sv) == list(ops._SM_SAVED)
-            for name, (off, nbytes) in sv.items():
-                assert off % 256 == 0 and off >= end, name
-                want = fu_saved if name == "fu_blob" else SAVED_PLANES[kind][name] * plane
-                assert nbytes == want, (kind, name)
-                end, total = off + nbytes, total + -(-nbytes // 256) * 256
-            assert p["saved_bytes"] == total
+            for name, (_, nbytes) in sv.items():
+                assert nbytes == (fu_saved if name == "fu_blob" else SAVED_PLANES[kind][name] * plane), (kind, name)
+            assert p["saved_bytes"] == sections_tile(sv)[1]
             # the scratch holds the inference copy of the saved planes (not of the FourierUnit's blob, which a forward without a
             # blob never writes) or the backward's planes (e, dl, du2, da, db), whichever is larger
             bwd = sum(-(-k * plane // 256) * 256 for k in ((2, 1, 1, 1, 1) if mix else (1,)))
