@@ -10,8 +10,9 @@ from .darkir import DarkIR, DBlock, EBlock, FreMLP  # noqa: F401
 from .ops import reload_env  # noqa: F401
 from .restormer import (Attention, Downsample, FeedForward, LayerNorm, OverlapPatchEmbed, Restormer,  # noqa: F401
                         TransformerBlock, Upsample)
-from .sfhformer import (FFN, BatchNorm2d, FourierUnit, Mixer, TokenMixer_For_Gloal, TokenMixer_For_Local,  # noqa: F401
-                        scaled_residual)
+from .sfhformer import (FFN, BatchNorm2d, FourierUnit, Mixer, SFHformer_l, SFHformer_m, SFHformer_s, SFHformer_t,  # noqa: F401
+                        TokenMixer_For_Gloal, TokenMixer_For_Local, scaled_residual)
 
 __all__ = ["Attention", "BatchNorm2d", "DarkIR", "DBlock", "Downsample", "EBlock", "FFN", "FeedForward", "FourierUnit", "FreMLP", "LayerNorm", "Mixer", "OverlapPatchEmbed", "Restormer",
-           "TokenMixer_For_Gloal", "TokenMixer_For_Local", "TransformerBlock", "Upsample", "reload_env", "scaled_residual"]
+           "SFHformer_l", "SFHformer_m", "SFHformer_s", "SFHformer_t", "TokenMixer_For_Gloal", "TokenMixer_For_Local", "TransformerBlock",
+           "Upsample", "reload_env", "scaled_residual"]

@@ -269,6 +269,22 @@ class Bn2dShape(C.Structure):
                 ("eps", C.c_float), ("momentum", C.c_float)]
 
 
+# mi_sfh_block_params / _grads: norm1, the Mixer's struct, beta, norm2, the FFN's struct, gamma (the Block's named_parameters()
+# order is beta, gamma, norm1, norm2, mixer, ffn: ops._sb_struct places them)
+class SfhBlockParams(C.Structure):
+    _fields_ = [("bn1_w", fp), ("bn1_b", fp), ("mixer", SfhMixerParams), ("beta", fp), ("bn2_w", fp), ("bn2_b", fp), ("ffn", SfhFfnParams),
+                ("gamma", fp)]
+
+
+class SfhBlockGrads(C.Structure):
+    _fields_ = [("bn1_w", fp), ("bn1_b", fp), ("mixer", SfhMixerGrads), ("beta", fp), ("bn2_w", fp), ("bn2_b", fp), ("ffn", SfhFfnGrads),
+                ("gamma", fp), ("accumulate", C.c_int)]
+
+
+class SfhBlockStats(C.Structure):
+    _fields_ = [(n, fp) for n in ("mean1", "var1", "mean2", "var2", "mean_fu", "var_fu")]
+
+
 class EblockShape(C.Structure):
     _fields_ = DblockShape._fields_
 
@@ -519,6 +535,11 @@ SIGNATURES = {
     "mi_scale_res_plan": (C.c_int, [C.POINTER(Bn2dShape), C.POINTER(c_i64)]),
     "mi_scale_res_fwd": (C.c_int, [C.POINTER(Bn2dShape), fp, vp, vp, vp, fp, vp]),
     "mi_scale_res_bwd": (C.c_int, [C.POINTER(Bn2dShape), fp, vp, vp, vp, fp, C.c_int, vp, vp]),
+    "mi_sfh_block_workspace": (C.c_size_t, [C.POINTER(SfhMixerShape)]),
+    "mi_sfh_block_saved_bytes": (C.c_size_t, [C.POINTER(SfhMixerShape)]),
+    "mi_sfh_block_plan": (C.c_int, [C.POINTER(SfhMixerShape), C.POINTER(c_i64)]),
+    "mi_sfh_block_fwd": (C.c_int, [C.POINTER(SfhMixerShape), C.POINTER(SfhBlockParams), vp, vp, C.POINTER(SfhBlockStats), fp, fp, vp, vp, vp]),
+    "mi_sfh_block_bwd": (C.c_int, [C.POINTER(SfhMixerShape), C.POINTER(SfhBlockParams), vp, vp, vp, C.POINTER(SfhBlockGrads), vp, vp, vp]),
     "mi_fregate_fwd": (C.c_int, [vp, vp, fp, vp, C.c_int, C.c_int, c_i64, C.c_int, vp]),
     "mi_fregate_bwd_workspace": (C.c_size_t, [C.c_int, C.c_int, c_i64]),
     "mi_fregate_bwd": (C.c_int, [vp, vp, vp, fp, vp, vp, fp, C.c_int, C.c_int, c_i64, C.c_int, C.c_int, vp, vp]),

@@ -1459,6 +1459,101 @@ def scale_res_bwd(f: Tensor, dout: Tensor, scale: Tensor, dscale: Tensor, accumu
     return df
 
 
+# ----------------------------------------------------------------------------- SFHformer: Block
+SFH_BLOCK_MAX_DIM, SFH_BLOCK_MIN_HW, SFH_BLOCK_MAX_HW = SFH_MIXER_MAX_DIM, SFH_MIXER_MIN_HW, SFH_MIXER_MAX_HW
+SFH_BLOCK_PARAMS = 40                                         # beta, gamma, norm1, norm2 (weight, bias), the Mixer's 24, the FFN's 10
+_SB_PLAN_KEYS = ("B", "dim", "N", "chunks_per_plane", "lib_calls_fwd", "lib_calls_fwd_part_in", "lib_calls_bwd", "kernels_fwd",
+                 "kernels_fwd_part_in", "kernels_bwd", "sub_lib_calls_fwd", "sub_lib_calls_bwd")
+_SB_SECTIONS = ("sub_ws", "p1", "d0", "d1", "d2", "scratch")
+_SB_SAVED = ("y1", "m", "x1", "y2", "f", "stat1", "stat2", "mixer_blob", "ffn_blob")
+_SB_PLAN = dict(keys=_SB_PLAN_KEYS, first=16, sections=_SB_SECTIONS, saved=(32, _SB_SAVED), tail=("workspace", "saved_bytes", "pair_bytes"))
+
+
+def sfh_block_plan(B: int, dim: int, H: int, W: int, dtype: torch.dtype = torch.float32, training: bool = True) -> dict:
+    """What sfh_block_fwd / sfh_block_bwd run for x [B, dim, H, W] (mi_sfh_block_plan; no GPU work): library calls, the kernel launches
+    summed from the parts' plans, ``sections`` (workspace) and ``saved_sections`` (the blob), each name -> (byte offset, bytes);
+    ``pair_bytes``: what ``part_in`` / ``part_out`` hold."""
+    return _plan_report(L.lib().mi_sfh_block_plan, _sm_shape(B, dim, H, W, _dtype_code(dtype), training), "sfh_block_plan", **_SB_PLAN)
+
+
+def sfh_block_sizes(B: int, dim: int, H: int, W: int, dtype: torch.dtype, training: bool = True) -> Tuple[int, int]:
+    """(saved bytes, workspace bytes) of one Block; (0, 0) for a shape the kernels do not cover.  No GPU needed."""
+    s = _sm_shape(B, dim, H, W, _dtype_code(dtype), training)
+    return _sizes(L.lib().mi_sfh_block_saved_bytes, L.lib().mi_sfh_block_workspace, s)
+
+
+@functools.lru_cache(maxsize=None)
+def _sb_pairs(B: int, dim: int, H: int, W: int, dtype: torch.dtype) -> int:
+    """fp32 values in the pair buffer of x [B, dim, H, W] (a property of the shape: asked once)."""
+    return sfh_block_plan(B, dim, H, W, dtype, True)["pair_bytes"] // 4
+
+
+def _sb_struct(cls, ts: Sequence[Tensor], what: str, *tail):
+    """mi_sfh_block_params / _grads from the 40 tensors in the Block's named_parameters() order."""
+    beta, gamma, n1w, n1b, n2w, n2b = ts[:6]
+    mixer, ffn = ts[6:30], ts[30:40]
+    grads = cls is L.SfhBlockGrads
+    mx = _f32_struct(L.SfhMixerGrads if grads else L.SfhMixerParams, mixer, what, *tail)
+    ff = _f32_struct(L.SfhFfnGrads if grads else L.SfhFfnParams, ffn, what, *tail)
+    for t in ts[:6]:
+        _f32(t, what)
+    return cls(_p(n1w), _p(n1b), mx, _p(beta), _p(n2w), _p(n2b), ff, _p(gamma), *tail)
+
+
+def _sb_args(x: Tensor, params: Sequence[Tensor], training: bool, eps: float, momentum: float):
+    if x.dim() != 4:
+        raise ValueError(f"sfh_block: x must be [B, dim, H, W], got {tuple(x.shape)}")
+    B, dim, H, W = x.shape
+    s = dim // 2
+    want = ([(1, dim, 1, 1)] * 2 + [(dim,)] * 4 + [(s, 1, 3, 3), (s,), (s, 1, 3, 3), (s,)] + _sm_global_shapes(dim) +
+            [(dim, 2 * dim, 1, 1), (dim,), (dim, 2 * dim, 1, 1), (dim,), (2 * dim, dim, 1, 1), (2 * dim,), (2 * dim, dim, 1, 1), (2 * dim,)] +
+            [(2 * dim, dim, 1, 1), (2 * dim,), (s, 1, 3, 3), (s,), (s, 1, 5, 5), (s,), (s, 1, 7, 7), (s,), (dim, 2 * dim, 1, 1), (dim,)])
+    if len(params) != SFH_BLOCK_PARAMS or (dim % 2 == 0 and [tuple(p.shape) for p in params] != want):
+        raise ValueError(f"sfh_block: parameters {[tuple(p.shape) for p in params]} do not fit dim = {dim}")
+    shape = _sm_shape(B, dim, H, W, _dt(x), training, eps, momentum)
+    return shape, _covered(L.lib().mi_sfh_block_workspace, shape)
+
+
+def sfh_block_fwd(x: Tensor, params: Sequence[Tensor], stats: Sequence[Tensor], training: bool, need_saved: bool, eps: float = 1e-5,
+                  momentum: float = 0.1, part_in: Optional[Tensor] = None, want_part: bool = False):
+    """SFHformer Block.forward (see mi_restore.h).  params: the 40 of the module's named_parameters() order (beta, gamma, norm1,
+    norm2, mixer, ffn); ``stats``: running mean and var of norm1, of norm2 [dim] and of mixer.mixer_gloal.FFC.bn [4 dim], fp32,
+    updated in place when ``training``.  ``part_in``: the (mean, M2) pairs of x from a producer; ``want_part``: also return those of
+    out (training mode only: eval mode uses neither).  -> (out, saved, part_out)."""
+    _gpu(x, part_in, *params, *stats)
+    s, ws_bytes = _sb_args(x, params, training, eps, momentum)
+    dim = x.shape[1]
+    if len(stats) != 6 or [_f32(t, "sfh_block running statistic").numel() for t in stats] != [dim] * 4 + [4 * dim] * 2:
+        raise ValueError("sfh_block: the running statistics must hold dim, dim, dim, dim, 4 dim, 4 dim values")
+    lib = L.lib()
+    pairs = _sb_pairs(*x.shape, x.dtype) if training and (want_part or part_in is not None) else 0
+    if part_in is not None and training and (part_in.dtype != torch.float32 or part_in.numel() != pairs):
+        raise ValueError("sfh_block: part_in must hold the plan's fp32 (mean, M2) pairs")
+    out, saved, ws = _out_saved_ws(x, s, lib.mi_sfh_block_saved_bytes, need_saved, ws_bytes)
+    part_out = torch.empty(pairs, dtype=torch.float32, device=x.device) if training and want_part else None
+    pp = _sb_struct(L.SfhBlockParams, params, "SFHformer Block parameter")
+    st = L.SfhBlockStats(*[_p(t) for t in stats])
+    L.check(lib.mi_sfh_block_fwd(C.byref(s), C.byref(pp), _p(x), _p(out), C.byref(st), _p(part_in) if training else None, _p(part_out),
+                                 _p(saved), _p(ws), _stream()), "sfh_block_fwd")
+    return out, saved, part_out
+
+
+def sfh_block_bwd(x: Tensor, dout: Tensor, params: Sequence[Tensor], saved: Tensor, grads: Sequence[Tensor], accumulate: bool,
+                  training: bool, eps: float = 1e-5, momentum: float = 0.1) -> Tensor:
+    """Backward of sfh_block_fwd: dx; the 40 parameter gradients are written (accumulate: added) into ``grads``."""
+    _gpu(x, dout, saved, *params, *grads)
+    _same("sfh_block", x, dout)
+    s, ws_bytes = _sb_args(x, params, training, eps, momentum)
+    if len(grads) != SFH_BLOCK_PARAMS:
+        raise ValueError("sfh_block: 40 gradient buffers expected")
+    dx, ws = _out_ws(x, ws_bytes)
+    pp = _sb_struct(L.SfhBlockParams, params, "SFHformer Block parameter")
+    gg = _sb_struct(L.SfhBlockGrads, grads, "SFHformer Block gradient", int(accumulate))
+    L.check(L.lib().mi_sfh_block_bwd(C.byref(s), C.byref(pp), _p(x), _p(dout), _p(dx), C.byref(gg), _p(saved), _p(ws), _stream()),
+            "sfh_block_bwd")
+    return dx
+
+
 # ----------------------------------------------------------------------------- DarkIR: EBlock and its tail
 EBLOCK_MAX_C, EBLOCK_MIN_HW, EBLOCK_MAX_HW = 256, 2, FREMLP_MAX_HW
 _EBLOCK_PLAN_KEYS = ("x0_bytes", "xe_bytes", "x1_bytes", "g_bytes", "y_bytes", "f_bytes", "stats_bytes", "small_bytes",

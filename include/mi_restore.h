@@ -1175,6 +1175,55 @@ int mi_scale_res_bwd(const mi_scale_res_shape* s, const float* scale, const void
                      int accumulate, void* ws, void* stream);
 
 /* ------------------------------------------------------------------------
+ * SFHformer — Block (SFHformer.py:254-282; csrc/sfh_block.hip) as one launch sequence forward and one backward over the entry
+ * points above; the file has no kernel and no arithmetic of its own.
+ *   forward   y1 = mi_bn2d_fwd(x; part_in)        m = mi_sfh_mixer_fwd(y1)     x1 = mi_scale_res_fwd(m, x, beta; part_out = p1)
+ *             y2 = mi_bn2d_fwd(x1; part_in = p1)  f = mi_sfh_ffn_fwd(y2)       out = mi_scale_res_fwd(f, x1, gamma; part_out)
+ *   backward  df, dgamma = mi_scale_res_bwd(f, dout)     dy2 = mi_sfh_ffn_bwd(y2, df)       dx1 = mi_bn2d_bwd(x1, dy2; dres = dout)
+ *             dm, dbeta  = mi_scale_res_bwd(m, dx1)      dy1 = mi_sfh_mixer_bwd(y1, dm)     dx  = mi_bn2d_bwd(x, dy1; dres = dx1)
+ * The results are those of the six calls made one by one, bit for bit.  One eps / momentum pair serves norm1, norm2 and the
+ * Mixer's FFC.bn.  part_in: the (mean, M2) pairs of x (mi_bn2d_fwd's part_in) or NULL; part_out: where the pairs of out go, or
+ * NULL (a following Block's part_in); p1 lives in the workspace.  Eval mode (shape.training == 0) reads and writes no pairs: both
+ * are ignored.  stats: the running statistics of norm1, norm2 [dim] and of the Mixer's FFC.bn [4 dim], updated in place in
+ * training mode.
+ * saved (mi_sfh_block_saved_bytes(), sections 256-byte aligned, in this order): y1, m, x1, y2, f [B,dim,N] in the activation
+ * dtype, stat1, stat2 [2 dim] fp32, the Mixer's blob, the FFN's blob.  saved == NULL in _fwd (inference, no_grad): nothing is
+ * kept, the five planes live in the workspace and the Mixer and the FFN run with their own saved == NULL.
+ * Gradients are added to when g->accumulate, else overwritten (the `accumulate` fields of the embedded structs are not read).
+ * Limits, the intersection of the parts': dim even, 2..128; 2 <= H, W <= 512; 1 <= B <= 65535; fp32 or bf16; eps > 0,
+ * 0 <= momentum <= 1; the parts' size limits (B 4dim H W below 2^31 among them).  Anything else is refused before any launch; the
+ * sizing calls return 0.  Bitwise reproducible; no allocation, no host synchronisation.
+ * mi_sfh_block_plan (host-only; launchers and sizing calls read the same plan) fills out[64]: B, dim, N, chunks per plane of the
+ * BatchNorm kernels, library calls forward / forward with part_in / backward [4..6], kernel launches of those calls' own
+ * forward / forward with part_in / backward [7..9] (summed from the parts' plans), library calls the Mixer and the FFN make in
+ * turn forward / backward [10, 11]; then (byte offset, bytes) of the 6 workspace sections [16..27]: the region the parts'
+ * workspaces share (the calls are sequential on one stream), the pairs p1 (eval: 0 bytes), the backward's three planes (df then
+ * dm; dy2 then dy1; dx1), the scratch of a forward without a blob; then of the 9 saved sections [32..49]; the workspace size
+ * [60], the saved blob's size [61], the bytes part_in / part_out hold [62] (mi_bn2d_plan's).
+ * ------------------------------------------------------------------------ */
+typedef mi_sfh_mixer_shape mi_sfh_block_shape;
+typedef struct {
+  const float* bn1_w; const float* bn1_b;     /* norm1 [dim] */
+  mi_sfh_mixer_params mixer;                  /* mixer.* */
+  const float* beta;                          /* [1,dim,1,1] */
+  const float* bn2_w; const float* bn2_b;     /* norm2 [dim] */
+  mi_sfh_ffn_params ffn;                      /* ffn.* */
+  const float* gamma;                         /* [1,dim,1,1] */
+} mi_sfh_block_params;
+typedef struct {
+  float* bn1_w; float* bn1_b; mi_sfh_mixer_grads mixer; float* beta; float* bn2_w; float* bn2_b; mi_sfh_ffn_grads ffn; float* gamma;
+  int accumulate;
+} mi_sfh_block_grads;
+typedef struct { float* mean1; float* var1; float* mean2; float* var2; float* mean_fu; float* var_fu; } mi_sfh_block_stats;
+size_t mi_sfh_block_workspace(const mi_sfh_block_shape* s);
+size_t mi_sfh_block_saved_bytes(const mi_sfh_block_shape* s);
+int mi_sfh_block_plan(const mi_sfh_block_shape* s, int64_t* out);
+int mi_sfh_block_fwd(const mi_sfh_block_shape* s, const mi_sfh_block_params* p, const void* x, void* out,
+                     const mi_sfh_block_stats* stats, const float* part_in, float* part_out, void* saved, void* ws, void* stream);
+int mi_sfh_block_bwd(const mi_sfh_block_shape* s, const mi_sfh_block_params* p, const void* x, const void* dout, void* dx,
+                     const mi_sfh_block_grads* g, const void* saved, void* ws, void* stream);
+
+/* ------------------------------------------------------------------------
  * DarkIR — the encoder block (DarkIR-main/archs/arch_model.py:141-204 EBlock) and its tail (csrc/darkir.hip).
  *
  * fregate: the block's last line, y + gamma (y f), as one streaming pass.  y, f, out [B,C,N] in `dtype`, gamma [C] fp32, fp32
